@@ -12,9 +12,14 @@ the 96-byte result records with RCCL.  Synthetic data, seeded (riv-slam_amd/scen
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Timing protocol: W warm-up steps, then the region "exactly K steps, barrier + device synchronise on both
-sides, MAX over ranks" is repeated R times (--repeats, default 20); `value` / `ms_per_step` are the MEDIAN repetition,
-p10 / p90 / mean / the first repetition are printed beside it, and each repetition is also timed with HIP events
-recorded on the handles' own streams (`timing.event_ms_per_step`).  Rank 0 prints ONE JSON line.
+sides, MAX over ranks" is repeated R times (--repeats; default 1, so a plain run times exactly K steps, and 20 with
+--full); `value` / `ms_per_step` are the MEDIAN repetition, p10 / p90 / mean / the first repetition are printed beside
+it, and each repetition is also timed with HIP events recorded on the handles' own streams (`timing.event_ms_per_step`).
+Rank 0 prints ONE JSON line.
+
+A plain run measures the headline only.  --full adds the legs that take runs of their own (one GPU): single-pair
+latency, the executed-flops and brute-force diagnostics, the pooled LM loop batch, the dense C5 pair and the CPU
+baseline with its parity check.  --dump-outputs DIR writes the records of the last timed step, one .npy per field.
 """
 from __future__ import annotations
 
@@ -48,7 +53,12 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=20, help="repetitions of the timed K-step region (median / p10 / p90 are reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed K-step region (median / p10 / p90 are reported); default 1, 20 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline (one GPU): single-pair latency, diagnostics, LM loop batch, C5, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the records of the last timed step to DIR/<field>.npy (float32 / float64, one file per record field)")
     ap.add_argument("--pairs-per-gpu", type=int, default=32)
     ap.add_argument("--points", type=int, default=N_PTS)
     ap.add_argument("--kind", default="odometry", choices=("odometry", "loop"), help="scene.make_pair kind of the synthetic pairs")
@@ -58,9 +68,9 @@ def parse_args():
     ap.add_argument("--handles", type=int, default=0, help="batch handles = steps kept in flight (0: 4; 1: one handle with three pair groups)")
     ap.add_argument("--depth", type=int, default=1, help="steps in flight PER handle (Gauss-Newton only; a handle alternates between two record buffers, so 1 or 2)")
     ap.add_argument("--groups", type=int, default=1, help="pair groups (HIP streams) per handle when several handles are in flight")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (rank 0, N=1 only)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the cpu_baseline leg (--full; rank 0, N=1 only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-diagnostics", action="store_true", help="skip the untimed executed-flops / brute-force legs")
+    ap.add_argument("--no-diagnostics", action="store_true", help="with --full: skip the untimed executed-flops / brute-force legs")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even for one rank (self-test of the N>1 path)")
     ap.add_argument("--ranks-share-gpu", action="store_true",
                     help="every rank uses GPU 0: exercises the N > 1 loop (late gather, barrier, MAX over ranks) on a one-GPU box; needs "
@@ -384,7 +394,7 @@ def main():
         torch.cuda.synchronize()
 
     run_steps(args.warmup)
-    R = max(1, args.repeats)
+    R = max(1, args.repeats if args.repeats is not None else (20 if args.full else 1))
     host_s, event_ms = [], []
     ev0 = [torch.cuda.Event(enable_timing=True) for _ in range(R)]
     ev1 = [[torch.cuda.Event(enable_timing=True) for _ in range(H + 1)] for _ in range(R)]
@@ -432,6 +442,13 @@ def main():
     if rank == 0:
         recs = sharded.records_from_bytes(gathered)
         assert len(recs) == total_pairs and (lm or int(recs["n_linearize"].min()) == GN_ITERS)
+        if args.dump_outputs:
+            # what a caller of the step receives: the records of all pairs, field by field (T: fp32 column-major 4x4 per pair,
+            # final_cost fp64, the integer counters and flags as fp64)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name in recs.dtype.names:
+                a = recs[name]
+                np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
         nn_mode = os.environ.get("APDGICP_NN_MODE", "pruned")
         # ---- roofline of the dominant kernel, the nearest-neighbour search: ALGORITHMIC HBM bytes per launch = per pair
         # 16(N+M) (both sorted clouds) + 16N (warm-start hints) + 8N (result), SURVEY 8d / DESIGN 3, over the kernel's own
@@ -603,7 +620,7 @@ def main():
                                   "note": "whole step: B_reg x pairs / ms_per_step; B_reg = 40(N+M) + L(108N+16M) + E 56N with the run's mean L, E"},
         }
 
-        if world == 1 and not args.no_diagnostics and not lm:
+        if world == 1 and args.full and not args.no_diagnostics and not lm:
             # ---- outside the timed region: what the pruned kernel really executes, and the brute-force kernel on the same data
             def one_step(env):
                 old = {k_: os.environ.get(k_) for k_ in env}
@@ -652,7 +669,7 @@ def main():
                                                   "~0.4 of the FMA-based spec peak (profiles/r01_ubench_valu.txt)"}
             del bf
 
-        if world == 1:
+        if world == 1 and args.full:
             # ---- single-pair latency (configs[1] exactly): one handle, one registration at a time
             s, t, g = h_pairs[0]
             one = reg.FastAPDGICP(params, device=local_rank)

@@ -1,5 +1,7 @@
 """CPU tests (-m "not gpu"): the two oracle restatements against the committed golden vectors and
 against each other.  The reference holds no fixture for FastAPDGICP (parity unpinned)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -72,19 +74,31 @@ def _nanoflann_cases(golden):
     return cases
 
 
-@pytest.mark.skipif(R.nanoflann_lib() is None, reason="/root/reference (nanoflann.hpp of the ScanContext module) is not present on this box")
+NANOFLANN_KS, NANOFLANN_LEAVES, NANOFLANN_QUERIES = (1, 20), (10, 15), 256
+
+
 def test_kdtree_against_the_reference_trees_own_nanoflann(golden):
     """VERDICT r05 item 6.  The reference tree holds ONE exact nearest-neighbour implementation that compiles in this image:
     radar_graph_slam/include/scan_context/nanoflann.hpp with L2_Simple_Adaptor<float> (:423-446) -- FLANN's L2_Simple accumulation
     order.  The oracle's kd-tree (the piece SURVEY 7 hard-part 2 calls the parity risk) must return the same fp32 distances BIT FOR
     BIT for 1-NN and 20-NN, and the same indices wherever the distance is unique among the cloud's points (ties: FLANN's order is
-    unspecified, the oracle's is the lowest index).  It is ScanContext's tree, not the path's FLANN: the cap "parity unpinned" stays."""
+    unspecified, the oracle's is the lowest index).  It is ScanContext's tree, not the path's FLANN: the cap "parity unpinned" stays.
+    nanoflann's answers are stored vectors (tests/golden/nanoflann_knn.npz, tests/golden/make_nanoflann_golden.py): a seeded sample of
+    NANOFLANN_QUERIES queries per case, the target clouds regenerated here and checked against the stored hashes."""
+    import hashlib
+    nf = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "nanoflann_knn.npz"))
     for name, tgt, q in _nanoflann_cases(golden):
+        key = name.replace("/", "_")
+        sel = nf[f"{key}__sel"]
+        q = np.ascontiguousarray(q[sel], dtype=np.float32)
+        assert np.array_equal(q.view(np.uint32), nf[f"{key}__q"].view(np.uint32)), name      # the same queries ...
+        sha = hashlib.sha256(np.ascontiguousarray(tgt, dtype=np.float32).tobytes()).digest()
+        assert sha == nf[f"{key}__tgt_sha"].tobytes(), name                                 # ... against the same cloud
         r = R.RefAPDGICP()
         r.setInputTarget(tgt)
-        for k in (1, 20):
-            for leaf in (10, 15):   # nanoflann's default leaf size and the one PCL's FLANN index is built with: exact either way
-                ni, nd = R.nanoflann_knn(tgt, q, k, leaf)
+        for k in NANOFLANN_KS:
+            for leaf in NANOFLANN_LEAVES:   # nanoflann's default leaf size and the one PCL's FLANN index is built with: exact either way
+                ni, nd = nf[f"{key}__idx_k{k}_l{leaf}"], nf[f"{key}__d_k{k}_l{leaf}"]
                 oi, od = r.knn_kdtree_batch("target", q, k)
                 assert np.array_equal(nd.view(np.uint32), od.view(np.uint32)), (name, k, leaf)
                 # a distance is unique for its query when its neighbours in the sorted list differ and nothing BEHIND the list equals the last entry

@@ -79,16 +79,27 @@ def test_sharded_aligner_over_the_hip_batch_and_rccl_world_size_1(tmp_path):
 
 
 @pytest.mark.gpu
-def test_bench_force_dist_prints_world_size_and_rccl_version():
+def test_bench_force_dist_prints_world_size_and_rccl_version(tmp_path):
+    import importlib
     import json
+    import numpy as np
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "3", "--warmup", "2", "--repeats", "3", "--pairs-per-gpu", "8",
-                        "--points", "2048", "--no-cpu-baseline", "--no-diagnostics"], capture_output=True, text=True, timeout=600)
+                        "--points", "2048", "--no-cpu-baseline", "--no-diagnostics", "--dump-outputs", str(tmp_path / "out"),
+                        "--dump-records", str(tmp_path / "records.npy")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads(lines[0])
     assert d["world_size"] == 1 and d["rccl_version"] and d["n_gpus"] == 1 and d["timing"]["repeats"] == 3
     assert 0 < d["roofline"]["frac"] <= 1 and d["roofline"]["bound"] == "hbm"
+    assert "single_pair" not in d and "cpu_baseline" not in d        # a plain run (no --full) measures the headline only
+    # --dump-outputs: every record field of the last timed step, fp32 / fp64, equal to the records themselves
+    reg = importlib.import_module("riv-slam_amd.registration")
+    recs = np.frombuffer(np.load(tmp_path / "records.npy").tobytes(), dtype=reg.RESULT_DTYPE)
+    assert len(recs) == 8
+    for name in reg.RESULT_DTYPE.names:
+        a = np.load(tmp_path / "out" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, recs[name].astype(a.dtype)), name
 
 
 CHILD2 = textwrap.dedent("""

@@ -8,6 +8,6 @@ trap 'cp riv-slam_amd/_keep.bin riv-slam_amd/libapdgicp_hip.so; rm -f riv-slam_a
 for v in "$@"; do
   cp riv-slam_amd/_$v.bin riv-slam_amd/libapdgicp_hip.so
   for h in $hs; do
-    echo -n "$v handles $h: "; timeout 300 python bench.py --handles $h --no-cpu-baseline --no-diagnostics --repeats 8 | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['timing']['step_latency_ms']['median'])"
+    echo -n "$v handles $h: "; timeout 300 python bench.py --full --handles $h --no-cpu-baseline --no-diagnostics --repeats 8 | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'], d['timing']['step_latency_ms']['median'])"
   done
 done

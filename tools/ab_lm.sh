@@ -8,6 +8,6 @@ trap 'cp riv-slam_amd/_keep.bin riv-slam_amd/libapdgicp_hip.so; rm -f riv-slam_a
 for i in $(seq $rounds); do
   for v in "$@"; do
     cp riv-slam_amd/_$v.bin riv-slam_amd/libapdgicp_hip.so
-    echo -n "$v "; timeout 300 python bench.py --kind loop --optimizer lm --no-cpu-baseline --no-diagnostics | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'])"
+    echo -n "$v "; timeout 300 python bench.py --full --kind loop --optimizer lm --no-cpu-baseline --no-diagnostics | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['ms_per_step'])"
   done
 done

@@ -2,7 +2,7 @@
 # Regenerates the judged evidence on the GPU box into gpurun_out/ev/ (about 45 minutes); afterwards, HERE, `bash tools/refresh_evidence.sh --collect rNN`
 # copies the summaries into profiles/ (named per round; pmc_nn_latest.json / pmc_lm_loop.json under their fixed names).
 #   usage: gpurun --timeout 2400 -- 'bash tools/refresh_evidence.sh r04'
-#   kernel_stats.md      rocprofv3 --kernel-trace --stats of the DRIVER's command (python3 bench.py --gpus 1 --steps 20 --warmup 5)
+#   kernel_stats.md      rocprofv3 --kernel-trace --stats of the DRIVER's command (python3 bench.py --full --gpus 1 --steps 20 --warmup 5)
 #   bench_profiled.json  the JSON line printed by that same profiled run (its roofline.avg_launch_ms must agree with the table)
 #   pmc_*.md             separate --pmc passes (never combined with other trace domains): HBM bytes and the issue-side SQ counters
 #   pmc_nn_latest.json   per-launch PMC numbers of the batch's nearest-neighbour launches (bench.py's roofline.traffic / roofline_issue)
@@ -22,9 +22,9 @@ fi
 tag=${1:-r04}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 ev=gpurun_out/ev; rm -rf $ev; mkdir -p $ev
-DRV="python3 bench.py --gpus 1 --steps 20 --warmup 5"
-PMC="python3 bench.py --gpus 1 --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-diagnostics"
-LMC="python3 bench.py --kind loop --optimizer lm --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-diagnostics"
+DRV="python3 bench.py --full --gpus 1 --steps 20 --warmup 5"
+PMC="python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-diagnostics"
+LMC="python3 bench.py --full --kind loop --optimizer lm --steps 20 --warmup 5 --repeats 2 --no-cpu-baseline --no-diagnostics"
 # (APDGICP_PROFILE_STRIDE=1: bench.py's own timing brackets EVERY search launch in this run, like the trace does, so the two
 # averages cover the same launches; the default run samples one tick in ten)
 export APDGICP_PROFILE_STRIDE=1
@@ -57,17 +57,17 @@ python3 tools/pmc_lm_json.py $ev/pmc_lm_loop.json 8192 $dbs > /dev/null && cp $e
 bash tools/c5_profile.sh ev > /dev/null 2>&1
 for f in kernel_stats.md ticks.txt ticks_pmc.txt prune_stats.txt pmc_insts.md pmc_busy.md pmc_fetch.md pmc_write.md order_ab.txt; do [ -s gpurun_out/c5_ev_$f ] && cp gpurun_out/c5_ev_$f $ev/c5_$f; done
 [ -s gpurun_out/c5_ev_pmc_c5.json ] && cp gpurun_out/c5_ev_pmc_c5.json $ev/pmc_c5.json   # (and profiles/pmc_c5.json, written by c5_profile.sh: bench.py below reads it)
-timeout 900 python3 bench.py > $ev/bench.json 2> $ev/bench.err
-timeout 300 python3 bench.py --host-clouds --no-cpu-baseline --no-diagnostics > $ev/bench_host_clouds.json 2> /dev/null   # the PCIe-inclusive rate
+timeout 900 python3 bench.py --full > $ev/bench.json 2> $ev/bench.err
+timeout 300 python3 bench.py --full --host-clouds --no-cpu-baseline --no-diagnostics > $ev/bench_host_clouds.json 2> /dev/null   # the PCIe-inclusive rate
 # the reference's optimiser on the C4 shard (bench.py --kind loop --optimizer lm): the JSON line, its kernel table, its streams
-timeout 600 python3 bench.py --kind loop --optimizer lm --no-cpu-baseline > $ev/bench_lm_loop.json 2> $ev/bench_lm.err
-timeout 600 rocprofv3 --kernel-trace --stats -d $ev/ks_lm -o k -- python3 bench.py --kind loop --optimizer lm --no-cpu-baseline --repeats 3 > /dev/null 2> $ev/ks_lm.err
-python3 tools/rocpd_summary.py $(find $ev/ks_lm -name "*.db" | head -1) "$tag: 'python3 bench.py --kind loop --optimizer lm' under rocprofv3 --kernel-trace --stats" > $ev/kernel_stats_lm_loop.md
+timeout 600 python3 bench.py --full --kind loop --optimizer lm --no-cpu-baseline > $ev/bench_lm_loop.json 2> $ev/bench_lm.err
+timeout 600 rocprofv3 --kernel-trace --stats -d $ev/ks_lm -o k -- python3 bench.py --full --kind loop --optimizer lm --no-cpu-baseline --repeats 3 > /dev/null 2> $ev/ks_lm.err
+python3 tools/rocpd_summary.py $(find $ev/ks_lm -name "*.db" | head -1) "$tag: 'python3 bench.py --full --kind loop --optimizer lm' under rocprofv3 --kernel-trace --stats" > $ev/kernel_stats_lm_loop.md
 # stream occupancy of the pool in steady state: the continuous loop of tools/lm_loop_bench.py (bench.py drains the pool between repetitions)
 bash tools/lm_trace.sh ev > /dev/null 2>&1; cp gpurun_out/lt_ev.streams.txt $ev/lm_pool_streams.txt
 find $ev/ks_lm -type f ! -name "*.db" -delete
 # bench.py's own N > 1 loop with two ranks on the one GPU (gloo): a self-test of that code path, not a scaling point
-timeout 600 python3 bench.py --gpus 2 --ranks-share-gpu --dist-backend gloo --no-cpu-baseline --no-diagnostics > $ev/bench_2ranks_gloo.json 2> $ev/bench_2ranks.err
+timeout 600 python3 bench.py --full --gpus 2 --ranks-share-gpu --dist-backend gloo --no-cpu-baseline --no-diagnostics > $ev/bench_2ranks_gloo.json 2> $ev/bench_2ranks.err
 # the other BASELINE configs, the odometry protocol through the C++ adapter, the C++ multi-device path against the Python one
 timeout 900 python3 tests/measure/bench_configs.py > $ev/other_configs.json 2> $ev/other_configs.err
 timeout 600 python3 tests/measure/odometry_protocol.py > $ev/odometry_protocol.json 2> $ev/odometry.err
