@@ -1041,7 +1041,10 @@ class Engine {
     work.blk_cost = nullptr, work.blk_order = nullptr;
     const int nn_blocks = (nmax_src + 63) / 64;
     if (blk_order_on && nn_pruned && npairs == 1 && nn_blocks > 1280 && nn_blocks <= ORDER_MAX && nmax_tgt > SORT_LDS_MAX_N) {
+      const size_t old_cap = b_blkcost.cap;
       APD_TRY(b_blkcost.ensure((size_t)nn_blocks * 4));
+      // (fresh memory: a block whose search returned early, every point kept, writes no cost -- k_block_order must not sort garbage)
+      if (b_blkcost.cap != old_cap) APD_HIP(hipMemsetAsync(b_blkcost.p, 0, b_blkcost.cap, stream));
       APD_TRY(b_blkorder.ensure((size_t)nn_blocks * 4));
       work.blk_cost = b_blkcost.as<unsigned>();
     }

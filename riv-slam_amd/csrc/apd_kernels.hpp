@@ -1233,9 +1233,9 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
   static_assert(GB_BATCH == kSuperGroups, "one batch of group boxes per super box");
   const bool use_super = M > SORT_LDS_MAX_N;
   const int nsuper = (ngroups + GB_BATCH - 1) / GB_BATCH;
-  float rad0 = bestR[0];
+  float rad0 = bestR[0], bestR0[S];  // bestR0: the start radii, for the per-point refinement of every chunk of super boxes
 #pragma unroll
-  for (int s = 1; s < S; s++) rad0 = fmaxf(rad0, bestR[s]);
+  for (int s = 0; s < S; s++) rad0 = fmaxf(rad0, bestR[s]), bestR0[s] = bestR[s];
   rad0 = wave_max_uniform(rad0);
   for (int sb0 = 0; sb0 < nsuper; sb0 += 64) {
   unsigned long long smask = nsuper - sb0 >= 64 ? ~0ull : (1ull << (nsuper - sb0)) - 1ull;
@@ -1247,13 +1247,16 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
     // in the 100k x 500k registration ONE such block tested 2 100 group boxes where its points need nine groups, three times the
     // duration of the median block and as long as the whole launch.  When more than eight super boxes pass the wave's box, every point
     // is looked at on its own (lane = super box, the points broadcast in turn, each with ITS radius): what no point needs is left out.
-    // Uniform over the block's waves like the test above: points and start radii are the same in all of them.
+    // Uniform over the block's waves like the test above: points and START radii (bestR0) are the same in all of them.  Not the live
+    // bestR: from the second chunk on (more than 64 super boxes, targets beyond 524 288 points) each wave has scanned only its own
+    // groups (index = wid mod W) and holds radii of its own -- different masks, different barrier counts below.  Radii only shrink,
+    // so what passes against a start radius is a superset of what the point needs: exact, only less pruning in later chunks.
     if (!GIVEN && __popcll(smask) > 8) {  // (not in the throughput kernel of scan-sized clouds: its registers are spoken for)
       unsigned long long fine = 0;
 #pragma unroll 1
       for (int l = 0; l < 64; l++) {
 #pragma unroll
-        for (int s = 0; s < S; s++) fine |= __ballot(lb_point_box(sbx, readlane_f(px[s], l), readlane_f(py[s], l), readlane_f(pz[s], l)) <= readlane_f(bestR[s], l));
+        for (int s = 0; s < S; s++) fine |= __ballot(lb_point_box(sbx, readlane_f(px[s], l), readlane_f(py[s], l), readlane_f(pz[s], l)) <= readlane_f(bestR0[s], l));
       }
       smask &= fine;
     }
@@ -1305,6 +1308,8 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
       unsigned long long pre = nb < 64 ? (1ull << nb) - 1ull : ~0ull;
       if (rad < inf) pre &= __ballot(lb_box_box(wbox, lds_box(boxes, min(lane, nb - 1))) <= rad);
       if (!GIVEN && use_super && S == 1 && __popcll(pre) > 16) {
+        // (per wave with the LIVE radii, unlike the super-box refinement above: it only narrows this wave's own `pre`, and no barrier
+        // depends on that mask)
         // ... and the same one level down: most of a batch's groups pass the wave's box although only a few of the wave's points reach into the
         // batch's super box at all -- those points are tested against the 64 group boxes (lane = group) instead of every group against all points
         // (the batch's super box through a uniform load: kept in a register per lane from the test above it cost the kernel a wave per SIMD)
@@ -1396,7 +1401,8 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
   if (wid == 0) nn_finish<S>(tgt, w, pair, lane, skin_on, k_mul, k_add, px, py, pz, best, bestc, pidx, kept, g1, g2);
   if (tstat) { const long long t = clock64(); tcy[2] += t - tm, tm = t; }
   // what this block's search cost (wave 0's share stands for the block: the W waves split the same groups): the order of the NEXT launches
-  if (w.blk_cost && wid == 0 && lane == 0) w.blk_cost[base / (64 * S)] = 16u * n_cscan + 2u * n_ctest + 8u * n_groups + 4u * n_batches + 32u;
+  // (not from k_nn_compact: it calls with base = 0 for every block, and its blocks are not the ones k_block_order orders)
+  if (!GIVEN && w.blk_cost && wid == 0 && lane == 0) w.blk_cost[base / (64 * S)] = 16u * n_cscan + 2u * n_ctest + 8u * n_groups + 4u * n_batches + 32u;
   if (w.stats && lane == 0) {  // (W > 1: every wave of the block scanned its own share of the groups, reports it and counts as a wave)
     atomicAdd(w.stats + 0, (unsigned long long)n_groups), atomicAdd(w.stats + 1, (unsigned long long)n_ctest);
     atomicAdd(w.stats + 2, (unsigned long long)n_cscan), atomicAdd(w.stats + 3, 1ull), atomicAdd(w.stats + 5, (unsigned long long)n_batches);

@@ -167,6 +167,31 @@ def test_large_submap_properties(mods, scene):
 
 
 @pytest.mark.gpu
+def test_assemble_past_4m_points_vs_oracle(mods, scene):
+    """5 x 860k = 4.3M points: more than 2^22 sort keys, so the head counts of the 4096-key blocks (2048 of them) are scanned by
+    k_scan_bsum in two passes of 1024 with a running total carried from the first into the second.  A 0.1 m leaf over 120 m x 120 m
+    keeps most voxels small, so tens of thousands of output rows start behind key 4 194 304: against the oracle row by row (both emit
+    the voxels in ascending index), a wrong carry would shift or overwrite exactly those rows."""
+    reg, sub = mods
+    rng = np.random.default_rng(4_194_305)
+    n = 860_000
+    clouds = [np.concatenate([rng.uniform(-60, 60, (n, 2)), rng.uniform(0, 0.3, (n, 1)), rng.uniform(0, 40, (n, 1))], 1).astype(np.float32)
+              for _ in range(5)]
+    poses = [scene.make_transform([0.3 * f, -0.2 * f, 0.0], np.deg2rad(0.5 * f)) for f in range(5)]
+    leaf = 0.1
+    exp, idx, cnt = R.submap_assemble(clouds, poses, leaf)
+    first_key = np.cumsum(cnt) - cnt                     # sorted position of every voxel's first point
+    assert cnt.sum() == 5 * n > 2 ** 22 and (first_key >= 2 ** 22).sum() > 10_000
+    a = sub.SubmapAssembler()
+    assert a.assemble(clouds, poses, leaf) == exp.shape[0]
+    got = a.to_numpy()
+    assert got.shape == exp.shape
+    single = cnt == 1
+    assert single[first_key >= 2 ** 22].any() and np.array_equal(got[single], exp[single])
+    assert centroids_close(got, exp, cnt)
+
+
+@pytest.mark.gpu
 def test_update_submap_target_feeds_the_registration(mods, scene):
     """the :606-618 block end to end: the device-resident submap as target gives the same registration as its host copy"""
     reg, sub = mods
