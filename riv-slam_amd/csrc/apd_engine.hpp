@@ -162,10 +162,6 @@ struct CachedTable {
   CachedTable() = default;
   CachedTable(const CachedTable&) = delete;
   CachedTable& operator=(const CachedTable&) = delete;
-  void swap(CachedTable& o) {
-    std::swap(dev, o.dev), host.swap(o.host), std::swap(cur, o.cur);
-    for (int i = 0; i < 2; i++) std::swap(pin[i], o.pin[i]), std::swap(pin_cap[i], o.pin_cap[i]), std::swap(ev[i], o.ev[i]);
-  }
 };
 
 class Engine {
@@ -178,7 +174,6 @@ class Engine {
     bool sorted = false;
     bool cov_valid = false;
     uint64_t token = 0;
-    int prep_lane = -1;  // the cloud stream (pool: cloud lane) the last operation on this cloud was enqueued on; -1: known to be complete
     // a host cloud of the tiled-sort size class stays in this pinned buffer until the sort has read it (TileJob::staged)
     char* stage_p = nullptr;
     char* stage_dev = nullptr;
@@ -396,12 +391,6 @@ class Engine {
                       &pool.nnpt, &pool.nnaux, &pool.sqd, &pool.maha, &pool.blkpart, &pool.errpart})
       b->release();
     for (Pool::List& li : pool.L) li.active.release(), li.nactive.release();
-    if (pool.cstream2) e = hipStreamSynchronize(pool.cstream2), e = hipStreamDestroy(pool.cstream2);
-    if (pool.ev_cross) e = hipEventDestroy(pool.ev_cross);
-    for (CachedTable* t : {&lane2.desc, &lane2.ids, &lane2.packjobs, &lane2.sortjobs, &lane2.tilejobs[0], &lane2.tilejobs[1], &lane2.tilejobs[2]}) t->dev.release();
-    lane2.tkeys.release(), lane2.bulk_dev.release();
-    if (lane2.bulk_host) e = hipHostFree(lane2.bulk_host);
-    if (lane2.bulk_ev) e = hipEventDestroy(lane2.bulk_ev);
     if (pool.host) e = hipHostFree(pool.host);
     if (pool.cstream) e = hipStreamDestroy(pool.cstream);
     for (HostStage& hs : h_stage) {
@@ -460,7 +449,6 @@ class Engine {
     APD_HIP(hipEventRecord(ev_producer, (hipStream_t)producer));
     APD_HIP(hipStreamWaitEvent(stream, ev_producer, 0));
     if (cstream != stream) APD_HIP(hipStreamWaitEvent(cstream, ev_producer, 0));
-    if (pool.on && pool.cstream2) APD_HIP(hipStreamWaitEvent(pool.cstream2, ev_producer, 0));
     return 0;
   }
 
@@ -482,13 +470,8 @@ class Engine {
     roctx_range rr("apdgicp:pack");
     if ((int)clouds.size() <= slot) clouds.resize(slot + 1);
     Cloud& c = clouds[slot];
-    lane_touch(c);
-    APD_TRY(lane_order());
     // the previous contents may still be in use by queued kernels on this stream; stream order protects us
-    if ((size_t)n * 16 > c.opts.cap) {
-      APD_HIP(hipStreamSynchronize(cstream));
-      if (pool.on && pool.cstream2) APD_HIP(hipStreamSynchronize(pool.cstream2));
-    }
+    if ((size_t)n * 16 > c.opts.cap) APD_HIP(hipStreamSynchronize(cstream));
     APD_TRY(c.opts.ensure((size_t)n * 16));
     const char* raw = (const char*)xyz;
     c.staged = false;
@@ -616,13 +599,8 @@ class Engine {
       if (!xyz[q] || ns[q] <= 0 || ns[q] > (1 << 30)) return fail(APDGICP_ERR_INVALID_ARG, "cloud is null, empty or too large");
       grew |= (size_t)ns[q] * 16 > clouds[first + q].opts.cap;
       nmax = std::max<int>(nmax, (int)ns[q]);
-      lane_touch(clouds[first + q]);
     }
-    APD_TRY(lane_order());
-    if (grew) {  // a buffer about to be re-allocated may still be in use
-      APD_HIP(hipStreamSynchronize(cstream));
-      if (pool.on && pool.cstream2) APD_HIP(hipStreamSynchronize(pool.cstream2));
-    }
+    if (grew) APD_HIP(hipStreamSynchronize(cstream));  // a buffer about to be re-allocated may still be in use
     std::vector<PackJob> jobs(count);
     for (int q = 0; q < count; q++) {
       Cloud& c = clouds[first + q];
@@ -668,14 +646,9 @@ class Engine {
       any = true;
       const size_t n = c.n, nch = (n + 15) / 16, ngr = (n + kGroupPts - 1) / kGroupPts, nsup = (ngr + kSuperGroups - 1) / kSuperGroups;
       grew |= n * 16 > c.pts.cap || n * 4 > c.perm.cap || nch * sizeof(Box) > c.cbox.cap || (ngr + nsup) * sizeof(Box) > c.gbox.cap;
-      lane_touch(c);
     }
     if (!any) return 0;
-    APD_TRY(lane_order());
-    if (grew) {  // old buffers may still be read by queued kernels
-      APD_HIP(hipStreamSynchronize(cstream));
-      if (pool.on && pool.cstream2) APD_HIP(hipStreamSynchronize(pool.cstream2));
-    }
+    if (grew) APD_HIP(hipStreamSynchronize(cstream));  // old buffers may still be read by queued kernels
     roctx_range rr("apdgicp:sort");
     for (size_t i = 0; i < clouds.size(); i++) {
       Cloud& c = clouds[i];
@@ -745,7 +718,6 @@ class Engine {
       int np2 = VOX_TILE;
       while (np2 < n) np2 <<= 1;
       APD_HIP(hipStreamSynchronize(cstream));
-      if (pool.on && pool.cstream2) APD_HIP(hipStreamSynchronize(pool.cstream2));  // (d_keys / d_box6 are shared by the lanes)
       APD_TRY(d_keys.ensure((size_t)np2 * 8));
       APD_TRY(d_box6.ensure(6 * sizeof(int)));
       const int init[6] = {0x7f800000, 0x7f800000, 0x7f800000, (int)0x807fffff, (int)0x807fffff, (int)0x807fffff};  // +inf x3, -inf x3 (ordered-int)
@@ -777,14 +749,7 @@ class Engine {
 
   int upload_desc() {
     APD_TRY(sort_clouds());
-    if (!desc_dirty) {
-      const int ln = pool.on ? pool.clane : 0;
-      if (pool.nclanes > 1 && pool.desc_gen_lane[ln] != desc_gen) {  // this lane's device table is an older generation
-        APD_TRY(d_desc.upload(h_desc.data(), h_desc.size() * sizeof(CloudDesc), cstream));
-        pool.desc_gen_lane[ln] = desc_gen;
-      }
-      return 0;
-    }
+    if (!desc_dirty) return 0;
     std::vector<CloudDesc>& h = h_desc;
     h.resize(clouds.size());
     for (size_t i = 0; i < clouds.size(); i++) {
@@ -800,8 +765,6 @@ class Engine {
     }
     APD_TRY(d_desc.upload(h.data(), h.size() * sizeof(CloudDesc), cstream));
     desc_dirty = false;
-    desc_gen++;
-    pool.desc_gen_lane[pool.on ? pool.clane : 0] = desc_gen;
     return 0;
   }
 
@@ -869,10 +832,6 @@ class Engine {
   // one covariance launch for the clouds ids[0..count) (device copy of the list: d_list) on stream `st`
   int launch_knn(const int* ids, const int* d_list, int count, hipStream_t st) {
     if (count <= 0) return 0;
-    if (st == cstream) {
-      for (int i = 0; i < count; i++) lane_touch(clouds[ids[i]]);
-      APD_TRY(lane_order());
-    }
     roctx_range rr("apdgicp:knn_cov");
     int nmax = 0;
     long long total = 0;
@@ -1472,7 +1431,7 @@ class Engine {
   // (see k_pool_poll in apd_kernels.hpp for the device side)  A batch handle whose optimiser is LM keeps the pairs of up to
   // `lanes` batches in one pool of pair slots; enqueue prepares the batch's clouds on the cloud stream, hands its pair
   // descriptors and guesses to the lane and returns; the ticks -- every launch over the device-side list of running pairs --
-  // are enqueued in chunks of a few, always `depth` chunks ahead of the header the host has seen, by whichever call of the
+  // are enqueued in chunks (a poll and one tick), one chunk per list ahead of the header the host has seen, by whichever call of the
   // handle is running (enqueue tops up, collect pumps until its batch is done).  A cloud slot referenced by a batch in flight
   // must not be replaced: set_cloud on such a slot first waits for that batch.
   struct PoolJob {
@@ -1511,8 +1470,8 @@ class Engine {
     // streams that forked behind every poll and joined in front of the next -- 13 % of the time no kernel ran at all.  Two pooled
     // handles on two host threads showed what independence is worth, tools/lm_threads.py: 1.03 -> 0.96 ms per batch of 32 loop
     // pairs with sixteen batches in flight, 0.91 with thirty-two.)
-    static constexpr int kMaxLists = 4;
-    int nlists = 2;  // APDGICP_POOL_LISTS (1 .. 4), read when the pool is first entered
+    // (round 6, docs/experiments.md, C4 shard: 1 / 2 / 3 / 4 lists -> 0.930 / 0.851 / 0.961 / 0.966 ms per batch)
+    static constexpr int kLists = 2;
     struct List {
       DevBuf active, nactive;          // the device-side list of running pairs and its length
       hipStream_t st = nullptr;        // list 0: the engine's stream; list 1: gstreams[0]
@@ -1521,21 +1480,11 @@ class Engine {
       int adm[kPoolRing] = {};
       int ub = 0;                      // upper bound of the device's list length behind the last ENQUEUED poll
       int kill_mask = 0;
-    } L[kMaxLists];
+    } L[kLists];
     int cur = 0;                       // the list whose ticks are being launched (t_work)
-    // TWO cloud lanes (round 6): the preparation of consecutive batches -- pack, sort, covariances -- alternates between two streams, each
-    // with its own job tables (descriptor table, id list, pack / sort / tile jobs, tile keys, bulk staging), so that the chain of batch
-    // n + 1 (five launches of which four leave most of the GPU empty) runs beside the covariance launch of batch n.  The engine's
-    // d_desc / d_ids / ... members always are those of the CURRENT lane; pool_swap_cloud_lane() exchanges them with the parked set.
-    int nclanes = 1;                   // APDGICP_POOL_CLOUD_STREAMS (1 or 2)
-    int clane = 0;                     // the current lane
-    hipStream_t cstream2 = nullptr;    // the parked lane's stream
-    hipEvent_t ev_cross = nullptr;     // orders one lane behind the other when a batch touches a cloud the other lane prepared
-    uint64_t desc_gen_lane[2] = {0, 0};
-    int ticks_per_chunk = 1;  // APDGICP_POOL_TICKS
-    // measured (tools/pool_sweep.sh, docs/experiments.md): chunks two deep, the list cut into two slices from 24 pairs on
+    // measured (docs/experiments.md, round 3: the list cut into 1 / 2 / 3 slices -> 1.38 / 1.33 / 1.54 ms per batch, 8 in flight): a list that
+    // ticks alone is cut into two slices from 24 pairs on
     static constexpr int groups = 2, group_min = 24;
-    int depth = 1;  // APDGICP_POOL_DEPTH: chunks enqueued ahead of the last header seen, per list
     int last_lane = -1;
     long long n_chunks = 0, n_ticks = 0, n_pair_ticks = 0;  // statistics (apdgicp_batch_last_ticks)
     std::vector<int> cloud_busy;
@@ -1563,43 +1512,6 @@ class Engine {
   // batches of one handle that may be in flight at once (round 4, two lists: 8 / 16 / 24 / 32 in flight: 1.08 / 0.91 / 0.87 / 0.86 ms per 32 loop
   // pairs; round 3, one list: 8 / 12 / 16 / 24 / 32: 1.27 / 1.13 / 1.07 / 1.03 / 1.01)
   static int pool_lanes_cfg() { return std::max(1, std::min(kPoolLanes, env_int("APDGICP_POOL_LANES", 24))); }
-  // the parked cloud lane's tables (the current lane's are the engine's own members)
-  struct ParkedLane {
-    CachedTable desc, ids, packjobs, sortjobs, tilejobs[3];
-    DevBuf tkeys, bulk_dev;
-    char* bulk_host = nullptr;
-    size_t bulk_cap = 0;
-    hipEvent_t bulk_ev = nullptr;
-  } lane2;
-  uint64_t desc_gen = 0;  // counts the rebuilds of h_desc: a lane's device table is current when it has uploaded this generation
-  void pool_swap_cloud_lane() {
-    if (pool.nclanes < 2 || !pool.on) return;
-    d_desc.swap(lane2.desc), d_ids.swap(lane2.ids), d_packjobs.swap(lane2.packjobs), d_sortjobs.swap(lane2.sortjobs);
-    for (int i = 0; i < 3; i++) d_tilejobs[i].swap(lane2.tilejobs[i]);
-    std::swap(d_tkeys, lane2.tkeys), std::swap(bulk_dev, lane2.bulk_dev);
-    std::swap(bulk_host, lane2.bulk_host), std::swap(bulk_cap, lane2.bulk_cap), std::swap(bulk_ev, lane2.bulk_ev);
-    std::swap(pool.cstream, pool.cstream2);
-    cstream = pool.cstream;
-    pool.clane ^= 1;
-  }
-  // In front of operations on clouds on the current cloud stream: `touch` every cloud involved, then `lane_order`.  A cloud whose last
-  // operation went to the OTHER lane (and is not known to be complete) puts the current lane behind everything the other lane holds.
-  bool lane_cross = false;
-  void lane_touch(Cloud& c) {
-    if (pool.on && pool.nclanes > 1) {
-      if (c.prep_lane >= 0 && c.prep_lane != pool.clane) lane_cross = true;
-      c.prep_lane = pool.clane;
-    } else {
-      c.prep_lane = -1;  // (one cloud stream: stream order)
-    }
-  }
-  int lane_order() {
-    if (!lane_cross) return 0;
-    lane_cross = false;
-    APD_HIP(hipEventRecord(pool.ev_cross, pool.cstream2));
-    APD_HIP(hipStreamWaitEvent(pool.cstream, pool.ev_cross, 0));
-    return 0;
-  }
   PoolHdr* pool_hdr(int l, uint64_t seq) const { return (PoolHdr*)(pool.host + (size_t)pool.cap * sizeof(ResultRec)) + (size_t)l * kPoolRing + seq % kPoolRing; }
   bool pool_busy() const {
     for (const PoolJob& j : pool.jobs)
@@ -1611,51 +1523,19 @@ class Engine {
     if (pool.on) return 0;
     APD_HIP(hipStreamSynchronize(stream));  // whatever the clouds went through on the main stream so far
     if (!pool.cstream) {
-      // experiments (round 6, docs/experiments.md): the cloud stream at the lowest stream priority and / or confined to a share of the CUs,
-      // so that the tick launches -- the chain the pool's throughput hangs on (their streams are 96 % busy, the cloud stream 77 %) -- get
-      // the GPU first.  APDGICP_POOL_CLOUD_PRIO=1, APDGICP_POOL_CLOUD_CUS=<CUs of 256>; default: neither
-      auto make_cloud_stream = [&](hipStream_t* out) -> int {
-        const int cus = std::max(0, std::min(256, env_int("APDGICP_POOL_CLOUD_CUS", 0)));
-        if (cus > 0) {
-          uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-          for (int b = 0; b < cus; b++) mask[b >> 5] |= 1u << (b & 31);
-          APD_HIP(hipExtStreamCreateWithCUMask(out, 8, mask));
-          return 0;
-        }
-        if (env_int("APDGICP_POOL_CLOUD_PRIO", 0)) {
-          int least = 0, greatest = 0;
-          APD_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-          APD_HIP(hipStreamCreateWithPriority(out, hipStreamNonBlocking, least));
-          return 0;
-        }
-        APD_HIP(hipStreamCreateWithFlags(out, hipStreamNonBlocking));
-        return 0;
-      };
-      APD_TRY(make_cloud_stream(&pool.cstream));
+      // one cloud stream at the default priority on every CU (round 6, docs/experiments.md, C4 shard: a second cloud stream 0.892 against
+      // 0.851 ms per batch; the lowest priority 0.852, confined to 192 / 128 / 96 CUs 0.859 / 0.907 / 1.031 against 0.846)
+      APD_HIP(hipStreamCreateWithFlags(&pool.cstream, hipStreamNonBlocking));
       for (Pool::List& li : pool.L)
         for (int i = 0; i < kPoolRing; i++) APD_HIP(hipEventCreateWithFlags(&li.ev[i], hipEventDisableTiming));
-      // measured (round 6, docs/experiments.md): lists 2 / 3 / 4 and cloud streams 1 / 2 on the C4 shard
-      pool.nlists = std::max(1, std::min(Pool::kMaxLists, env_int("APDGICP_POOL_LISTS", 2)));
-      pool.nclanes = std::max(1, std::min(2, env_int("APDGICP_POOL_CLOUD_STREAMS", 1)));
-      if (pool.nclanes > 1) {
-        APD_TRY(make_cloud_stream(&pool.cstream2));
-        APD_HIP(hipEventCreateWithFlags(&pool.ev_cross, hipEventDisableTiming));
-      }
-      APD_TRY(ensure_group_streams(pool.nlists + 1));  // gstreams[l - 1]: list l; gstreams[nlists - 1]: the slice stream of a list that ticks alone
+      APD_TRY(ensure_group_streams(Pool::kLists + 1));  // gstreams[l - 1]: list l; gstreams[kLists - 1]: the slice stream of a list that ticks alone
       pool.L[0].st = stream;
-      for (int l = 1; l < pool.nlists; l++) pool.L[l].st = gstreams[l - 1];
+      for (int l = 1; l < Pool::kLists; l++) pool.L[l].st = gstreams[l - 1];
       for (PoolJob& j : pool.jobs) APD_HIP(hipEventCreateWithFlags(&j.ev_pro, hipEventDisableTiming));
-      // measured on the two-list pool (docs/experiments.md, round 4): ticks per chunk 1 / 2 / 3 / 4 -> 0.931 / 0.962 / 1.018 / 1.065 ms per batch of
-      // 32 loop pairs (16 in flight, two chunks ahead); chunks ahead 1 / 2 / 3 / 4 -> 0.906 / 0.933 / 0.951 / 0.970 (one tick per chunk): a poll
-      // is a bubble on its own list's stream only, and every tick enqueued past a pair's last one is three empty launches
-      pool.ticks_per_chunk = std::max(1, std::min(16, env_int("APDGICP_POOL_TICKS", 1)));
-      pool.depth = std::max(1, std::min(kPoolRing - 2, env_int("APDGICP_POOL_DEPTH", 1)));
       profile_stride = std::max(1, env_int("APDGICP_PROFILE_STRIDE", 10));
-
     }
     cstream = pool.cstream;
     pool.on = true;
-    for (Cloud& c : clouds) c.prep_lane = -1;  // (the main stream was synchronised above)
     return 0;
   }
   // back to one stream: every other entry point (Gauss-Newton batches, fitness, probes) prepares clouds and ticks in stream order
@@ -1663,9 +1543,6 @@ class Engine {
     if (!pool.on) return 0;
     APD_TRY(pool_drain());
     APD_HIP(hipStreamSynchronize(pool.cstream));
-    if (pool.cstream2) APD_HIP(hipStreamSynchronize(pool.cstream2));
-    if (pool.clane != 0) pool_swap_cloud_lane();  // (the engine's own tables are lane 0's again)
-    for (Cloud& c : clouds) c.prep_lane = -1;
     for (Pool::List& li : pool.L)
       if (li.st) APD_HIP(hipStreamSynchronize(li.st));
     APD_HIP(hipStreamSynchronize(stream));
@@ -1710,7 +1587,7 @@ class Engine {
     APD_TRY(pool.maha.ensure((size_t)cap * 6 * ns * 8));
     APD_TRY(pool.blkpart.ensure((size_t)cap * nblk * kRed * 8));
     APD_TRY(pool.errpart.ensure((size_t)cap * nblk * 8));
-    const size_t host_bytes = (size_t)cap * sizeof(ResultRec) + (size_t)Pool::kMaxLists * kPoolRing * sizeof(PoolHdr);
+    const size_t host_bytes = (size_t)cap * sizeof(ResultRec) + (size_t)Pool::kLists * kPoolRing * sizeof(PoolHdr);
     if (host_bytes > pool.host_cap) {
       if (pool.host) APD_HIP(hipHostFree(pool.host));
       pool.host = pool.host_dev = nullptr, pool.host_cap = 0;
@@ -1759,15 +1636,13 @@ class Engine {
 
   void pool_job_finished(PoolJob& j) {
     j.state = PoolJob::DONE;
-    for (int id : j.cloud_ids) {
+    for (int id : j.cloud_ids)
       if (id < (int)pool.cloud_busy.size() && pool.cloud_busy[id] > 0) pool.cloud_busy[id]--;
-      // (its ticks ran behind the event behind its clouds' preparation: whatever lane that was on, it is complete -- unless the cloud has
-      // not been given covariances yet by a LATER enqueue, which cannot be: a cloud a batch in flight reads is never replaced)
-      if (id < (int)clouds.size() && clouds[id].cov_valid && clouds[id].sorted) clouds[id].prep_lane = -1;
-    }
   }
 
-  // one chunk of list l: the poll (completions of everything enqueued before, admissions) and ticks_per_chunk ticks over the list
+  // one chunk of list l: the poll (completions of everything enqueued before, admissions) and ONE tick over the list (measured on the
+  // two-list pool, docs/experiments.md, round 4: ticks per chunk 1 / 2 / 3 / 4 -> 0.931 / 0.962 / 1.018 / 1.065 ms per batch of 32 loop
+  // pairs, 16 in flight: every tick enqueued past a pair's last one is three empty launches)
   int pool_enqueue_chunk(int l) {
     Pool::List& li = pool.L[l];
     PoolAdmit adm{};
@@ -1812,10 +1687,10 @@ class Engine {
       // between its polls, like the one list of round 3: its head holds few pairs with many iterations to go, a latency-bound
       // chain of small launches, its tail the young wide ones.  With both lists busy every list is one stream of its own.
       int other = 0;
-      for (int o = 0; o < pool.nlists; o++)
+      for (int o = 0; o < Pool::kLists; o++)
         if (o != l) other += pool.L[o].ub;
-      const int G = other == 0 && li.ub >= pool.group_min ? std::max(1, std::min(pool.groups, env_int("APDGICP_POOL_GROUPS", pool.groups))) : 1;
-      hipStream_t slice = gstreams[pool.nlists - 1];
+      const int G = other == 0 && li.ub >= pool.group_min ? pool.groups : 1;
+      hipStream_t slice = gstreams[Pool::kLists - 1];
       if (G > 1) {
         APD_HIP(hipEventRecord(ev_main, li.st));
         APD_HIP(hipStreamWaitEvent(slice, ev_main, 0));
@@ -1823,34 +1698,30 @@ class Engine {
       for (int g = 0; g < G; g++) {
         const int p0 = (int)((long long)li.ub * g / G), p1 = (int)((long long)li.ub * (g + 1) / G);
         if (p1 <= p0) continue;
-        const int nt = pool.ticks_per_chunk;
         cur_active = p1 - p0;
-        for (int t = 0; t < nt; t++) {
-          pool.cur_timed = nullptr;
-          // (which tick of the chunk: in turn -- the first one alone would over-represent the cold searches of pairs just admitted)
-          if (profile_nn && (int)(seq % (uint64_t)profile_stride) == 0 && t == (int)((seq / (uint64_t)profile_stride) % (uint64_t)nt)) {
-            Pool::Timed* slot = nullptr;
-            for (Pool::Timed& c : pool.timed)
-              if (!c.busy) slot = &c;
-            if (!slot && pool.timed.size() < 64) {
-              pool.timed.emplace_back();
-              slot = &pool.timed.back();
-              APD_HIP(hipEventCreate(&slot->e0));
-              APD_HIP(hipEventCreate(&slot->e1));
-            }
-            if (slot) slot->busy = true, slot->list = l, slot->seq = seq, slot->p0 = p0, slot->p1 = p1, slot->n_active = -1, pool.cur_timed = slot;
+        pool.cur_timed = nullptr;
+        if (profile_nn && (int)(seq % (uint64_t)profile_stride) == 0) {
+          Pool::Timed* slot = nullptr;
+          for (Pool::Timed& c : pool.timed)
+            if (!c.busy) slot = &c;
+          if (!slot && pool.timed.size() < 64) {
+            pool.timed.emplace_back();
+            slot = &pool.timed.back();
+            APD_HIP(hipEventCreate(&slot->e0));
+            APD_HIP(hipEventCreate(&slot->e1));
           }
-          const int rc_t = launch_tick(Span{p0, p1 - p0, g == 0 ? li.st : slice});
-          pool.cur_timed = nullptr;
-          APD_TRY(rc_t);
+          if (slot) slot->busy = true, slot->list = l, slot->seq = seq, slot->p0 = p0, slot->p1 = p1, slot->n_active = -1, pool.cur_timed = slot;
         }
-        pool.n_pair_ticks += (long long)nt * (p1 - p0);
+        const int rc_t = launch_tick(Span{p0, p1 - p0, g == 0 ? li.st : slice});
+        pool.cur_timed = nullptr;
+        APD_TRY(rc_t);
+        pool.n_pair_ticks += p1 - p0;
       }
       if (G > 1) {
-        APD_HIP(hipEventRecord(gevents[pool.nlists - 1], slice));
-        APD_HIP(hipStreamWaitEvent(li.st, gevents[pool.nlists - 1], 0));
+        APD_HIP(hipEventRecord(gevents[Pool::kLists - 1], slice));
+        APD_HIP(hipStreamWaitEvent(li.st, gevents[Pool::kLists - 1], 0));
       }
-      pool.n_ticks += pool.ticks_per_chunk;
+      pool.n_ticks++;
     }
     APD_HIP(hipGetLastError());
     return 0;
@@ -1895,12 +1766,14 @@ class Engine {
     return 0;
   }
 
+  // one chunk in flight per list (measured, docs/experiments.md, round 4: chunks ahead 1 / 2 / 3 / 4 -> 0.906 / 0.933 / 0.951 / 0.970 ms per
+  // batch: a poll is a bubble on its own list's stream only)
   int pool_topup() {
     for (;;) {
       bool any = false;
-      for (int l = 0; l < pool.nlists; l++) {
+      for (int l = 0; l < Pool::kLists; l++) {
         Pool::List& li = pool.L[l];
-        if ((int)(li.seq_enq - li.seq_seen) >= pool.depth) continue;
+        if (li.seq_enq != li.seq_seen) continue;
         bool pending = li.kill_mask != 0;
         for (const PoolJob& j : pool.jobs) pending |= j.state == PoolJob::PENDING && j.list == l;
         if (li.ub <= 0 && !pending) continue;
@@ -1911,13 +1784,13 @@ class Engine {
     }
   }
 
-  // serves the pool: reads the headers that have arrived, keeps `depth` chunks enqueued per list; block: waits for one more header
+  // serves the pool: reads the headers that have arrived, keeps a chunk enqueued per list; block: waits for one more header
   int pool_pump(bool block) {
     if (!pool.layout_valid) return block ? fail(APDGICP_ERR_INTERNAL, "pool: nothing in flight") : 0;
     APD_HIP(hipSetDevice(device));
     auto arrived = [&]() -> int {  // processes every header that is there; > 0 when there was one
       int n = 0;
-      for (int l = 0; l < pool.nlists; l++) {
+      for (int l = 0; l < Pool::kLists; l++) {
         Pool::List& li = pool.L[l];
         while (li.seq_seen < li.seq_enq && *(volatile int*)&pool_hdr(l, li.seq_seen + 1)->seq == (int)(li.seq_seen + 1)) {
           const int rc = pool_process(l, li.seq_seen + 1);
@@ -1939,7 +1812,7 @@ class Engine {
         st += " [" + std::to_string(ln) + ": state " + std::to_string((int)pool.jobs[ln].state) + " list " + std::to_string(pool.jobs[ln].list) + " ticket " +
               std::to_string(pool.jobs[ln].ticket) + " np " + std::to_string(pool.jobs[ln].np) + " admitted at " + std::to_string(pool.jobs[ln].admit_seq) + "]";
       std::string ls;
-      for (int l = 0; l < pool.nlists; l++) ls += " [list " + std::to_string(l) + ": chunks " + std::to_string(pool.L[l].seq_enq) + ", bound " + std::to_string(pool.L[l].ub) + "]";
+      for (int l = 0; l < Pool::kLists; l++) ls += " [list " + std::to_string(l) + ": chunks " + std::to_string(pool.L[l].seq_enq) + ", bound " + std::to_string(pool.L[l].ub) + "]";
       return fail(APDGICP_ERR_INTERNAL, "pool: nothing in flight to wait for (" + ls + ";" + st + ")");
     }
     {
@@ -1953,7 +1826,7 @@ class Engine {
       if (got < 0) return got;
       if (got == 0) {  // a GPU that takes this long gets the sleeping wait: the older outstanding poll of the two lists
         int l = 0;
-        while (l + 1 < pool.nlists && !(pool.L[l].seq_seen < pool.L[l].seq_enq)) l++;
+        while (l + 1 < Pool::kLists && !(pool.L[l].seq_seen < pool.L[l].seq_enq)) l++;
         const uint64_t want = pool.L[l].seq_seen + 1;
         APD_HIP(hipEventSynchronize(pool.L[l].ev[want % kPoolRing]));
         if (*(volatile int*)&pool_hdr(l, want)->seq != (int)want) return fail(APDGICP_ERR_INTERNAL, "pool: a poll finished without posting its header");
@@ -2001,21 +1874,17 @@ class Engine {
       if (rank < best_rank || (rank == best_rank && c.ticket < best_ticket)) lane = l, best_rank = rank, best_ticket = c.ticket;
     }
     // the pair list the batch joins: the one with fewer pairs pending or running
-    int load[Pool::kMaxLists] = {0, 0, 0, 0};
+    int load[Pool::kLists] = {};
     for (const PoolJob& c : pool.jobs)
       if (c.state == PoolJob::PENDING || c.state == PoolJob::RUNNING) load[c.list] += c.np;
     int list = 0;
-    for (int l = 1; l < pool.nlists; l++)
+    for (int l = 1; l < Pool::kLists; l++)
       if (load[l] < load[list]) list = l;
     while (pool.jobs[lane].state == PoolJob::PENDING || pool.jobs[lane].state == PoolJob::RUNNING) APD_TRY(pool_pump(true));  // (the oldest batch: its lane is next)
     PoolJob& j = pool.jobs[lane];
     // the clouds of this batch, on the cloud stream: sort, covariances of those that lack them, descriptor table
     std::vector<int> ids;
     APD_TRY(filter_cov_ids(need, false, ids));
-    // every cloud the batch reads: one the other lane prepared (a keyframe shared with the previous batch) puts this lane behind it, so
-    // that the event below covers it
-    for (int id : need) lane_touch(clouds[id]);
-    APD_TRY(lane_order());
     APD_TRY(upload_desc());
     if (!ids.empty()) {
       APD_TRY(d_ids.upload(ids.data(), ids.size() * sizeof(int), cstream));
@@ -2058,7 +1927,6 @@ class Engine {
     j.layout_gen = pool.layout_gen;
     pool.last_lane = lane;
     *ticket = j.ticket;
-    pool_swap_cloud_lane();  // the next batch's clouds are prepared on the other cloud stream
     return pool_pump(false);
   }
 

@@ -982,7 +982,6 @@ int apdgicp_batch_synchronize(apdgicp_batch* b) {
   return guarded([&]() -> int {
     if (b->eng.pool.on) APD_TRY(b->eng.pool_drain());  // (pooled LM batches: every batch in flight runs to its end)
     if (b->eng.cstream != b->eng.stream) APD_HIP(hipStreamSynchronize(b->eng.cstream));
-    if (b->eng.pool.on && b->eng.pool.cstream2) APD_HIP(hipStreamSynchronize(b->eng.pool.cstream2));
     APD_HIP(hipStreamSynchronize(b->eng.stream));
     return 0;
   });

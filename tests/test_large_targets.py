@@ -336,6 +336,8 @@ def test_registration_against_1_2m_points_is_the_oracles(reg, scene, clouds):
             assert info_of(h) == [int(o.converged), o.nr_iterations, o.n_linearize, o.n_compute_error], (len(src), kw is GN6)
 
 
+@pytest.mark.skipif(os.environ.get("APDGICP_NN_MODE") == "brute",
+                    reason="tools/knob_matrix.sh row with the brute-force search: it visits no group boxes for the counters to count")
 @pytest.mark.parametrize("m", (600_000, BIG))
 def test_the_host_model_of_the_layout_is_the_devices(reg, clouds, m):
     """The diverging wave is built on a host model of the device's layout (Layout: the curve order of the generic sort, the group
