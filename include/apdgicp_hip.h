@@ -36,7 +36,8 @@ extern "C" {
                                    4: T*p is summed pairwise by default (Eigen >= 3.3), APDGICP_FLAG_XF_LINEAR_CHAIN selects the former order;
                                    5: the three fp32 angles of the sensor model (A:168,172-173) through glibc's atan2f algorithm (apd_atan2f.h) instead of the
                                       device library's; + source_stamp, set_trace / get_trace, debug_atan2f;
-                                   6: + APDGICP_FLAG_ALGEBRAIC_APD, build_flags, nearest_neighbours_of, get_trace_step_norms */
+                                   6: + APDGICP_FLAG_ALGEBRAIC_APD, build_flags, nearest_neighbours_of, get_trace_step_norms;
+                                      still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -382,6 +383,66 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
 int apdgicp_submap_points(apdgicp_submap* s, const float** device_xyzi, int64_t* n);
 /* copies the last assembled cloud ({x, y, z, intensity} per point) into caller memory */
 int apdgicp_submap_copy(apdgicp_submap* s, float* dst_xyzi, int64_t capacity_points, int dst_on_device);
+
+/* ------------------------------------------------------------------ scan preprocessing
+ * What PreprocessingNodelet::cloud_callback does to every scan before it is published and becomes a registration source
+ * (radar_graph_slam/apps/preprocessing_nodelet.cpp:812-815), in the reference's order, on the device:
+ *   1. distance_filter (:881-889), when use_distance_filter: a point stays iff  d > near && d < far && z < z_high && z > z_low  with
+ *      d = the fp32 norm sqrtf((x*x + y*y) + z*z) and z, both widened to double; a non-finite point fails; input order is kept.
+ *      (Eigen's own summation order for a 3-vector norm is not pinned here; it can matter only within 1 ulp of a threshold.)
+ *   2. downsample (:850-866): leaf[0] > 0: pcl::VoxelGrid ("VOXELGRID", :137-144) through the kernels of apdgicp_submap_assemble --
+ *      one point per occupied voxel in ascending voxel index, a leaf too small for the extent returns the cloud unfiltered with the
+ *      same warning (non-finite points are dropped from it here, in input order); leaf[0] <= 0: pcl::removeNaNFromPointCloud (:852-857),
+ *      order kept.  APPROX_VOXELGRID is not offered.
+ *   3. outlier_removal (:868-879) on the cloud of step 2, whose order the output keeps.  d2 = the fp32 squared distance in FLANN
+ *      L2_Simple order, neighbours in rank order, the first one the point itself (or a duplicate) at 0:
+ *        STATISTICAL (:167-175, pcl::StatisticalOutlierRemoval): k = mean_k + 1; score = (float)(sum_{r=1..mean_k} (double)sqrtf(d2[r]) / mean_k)
+ *          added in rank order; sum = sum of the scores, sq = sum of (double)(score * score) (fp32 product); mean = sum / n,
+ *          var = (sq - sum * sum / n) / (n - 1), thr = mean + stddev_mul * sqrt(var); a point stays iff (double)score <= thr.  The device
+ *          adds sum / sq in a fixed tree (PCL: point after point): the same bits on every run, mean / thr may differ from PCL's in the last bits.
+ *        RADIUS (:176-184, pcl::RadiusOutlierRemoval, dense branch): k = min_neighbors + 1; a point stays iff (double)d2[k - 1] <= radius * radius.
+ *        NONE: the cloud of step 2.
+ *      mean_k / min_neighbors up to 31 (the exact pruned k-NN of the covariances serves them; APDGICP_KNN_MODE=brute: the brute-force one);
+ *      above: APDGICP_ERR_UNSUPPORTED.  A step-2 cloud with fewer than k points: APDGICP_ERR_TOO_FEW_POINTS; an empty one: n_out = 0, status 0.
+ * PCL is not part of the reference tree: "as published" (PCL 1.10), like the voxel grid.  The power filter, the ego-velocity RANSAC,
+ * underfloor_filter, tf and ROS are not part of this object. */
+typedef enum { APDGICP_OUTLIER_NONE = 0, APDGICP_OUTLIER_STATISTICAL = 1, APDGICP_OUTLIER_RADIUS = 2 } apdgicp_outlier_method;
+typedef struct {
+  int32_t use_distance_filter;   /* "use_distance_filter", :201 ; default 1 */
+  int32_t outlier_method;        /* apdgicp_outlier_method, "outlier_removal_method", :166 ; default STATISTICAL */
+  int32_t mean_k;                /* "statistical_mean_k", :168 ; default 20 */
+  int32_t min_neighbors;         /* "radius_min_neighbors", :178 ; default 2 */
+  double near;                   /* "distance_near_thresh", :202 ; default 1.0 */
+  double far;                    /* "distance_far_thresh", :203 ; default 100.0 */
+  double z_low;                  /* "z_low_thresh", :204 ; default -5.0 */
+  double z_high;                 /* "z_high_thresh", :205 ; default 20.0 */
+  double stddev_mul;             /* "statistical_stddev", :169 ; default 1.0 */
+  double radius;                 /* "radius_radius", :177 ; default 0.8 */
+  float leaf[3];                 /* "downsample_resolution", :138 ; default 0.1 each; leaf[0] <= 0: "downsample_method" NONE */
+  int32_t reserved;              /* 0 */
+} apdgicp_scan_filter_params;
+typedef struct apdgicp_scan_filter apdgicp_scan_filter;
+void apdgicp_scan_filter_default_params(apdgicp_scan_filter_params* p);                       /* the nodelet's defaults, :137-205 */
+/* PreprocessingNodelet::initialize_params (:136-206).  `stream` may be NULL (the object creates its own) or a hipStream_t of the caller */
+int apdgicp_scan_filter_create(const apdgicp_scan_filter_params* p, int device, void* stream, apdgicp_scan_filter** out);
+int apdgicp_scan_filter_destroy(apdgicp_scan_filter* f);
+int apdgicp_scan_filter_set_params(apdgicp_scan_filter* f, const apdgicp_scan_filter_params* p);
+/* distance_filter -> downsample -> outlier_removal (:812-815) of one scan: xyz / n / stride_bytes / intensity_offset_bytes / on_device as in
+ * apdgicp_submap_assemble (intensity is carried through: the centroid's in a voxel, the point's own otherwise).  The call waits for
+ * the size of the cloud of step 2 (the launches of step 3 are sized by it) and for n_out. */
+int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device,
+                            int64_t* n_out);
+/* device pointer to the filtered scan: n points of {x, y, z, intensity} floats (16-byte stride), valid until the next run; what
+ * apdgicp_set_source(..., on_device = 1) and apdgicp_batch_set_cloud accept -- the cloud points_pub publishes (:826) never leaves the device */
+int apdgicp_scan_filter_points(apdgicp_scan_filter* f, const float** device_xyzi, int64_t* n);
+/* copies the filtered scan ({x, y, z, intensity} per point) into caller memory */
+int apdgicp_scan_filter_copy(apdgicp_scan_filter* f, float* dst_xyzi, int64_t capacity_points, int dst_on_device);
+/* sizes of the last run: counts[0] the input, [1] behind distance_filter, [2] behind downsample, [3] the output */
+int apdgicp_scan_filter_stage_counts(apdgicp_scan_filter* f, int64_t counts[4]);
+/* What step 3 of the last run decided on, in the order of the cloud of step 2 (counts[2] entries; 0 entries for NONE): stat = the score
+ * (STATISTICAL) or d2[k - 1] (RADIUS), kept = 1 / 0; mean / stddev / thr: STATISTICAL's, RADIUS: 0, 0, radius * radius.  Any pointer may
+ * be NULL; host memory.  For tests and for tuning the two thresholds. */
+int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kept, int64_t capacity, double* mean, double* stddev, double* thr);
 
 #ifdef __cplusplus
 }

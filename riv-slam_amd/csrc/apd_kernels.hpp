@@ -1846,9 +1846,17 @@ __device__ __forceinline__ unsigned long long group_or_u64(unsigned long long v)
 #endif
 // The work of ONE wave: the 64 / L queries starting at bx * (64 / L) of cloud c; knn_smem: the wave's own knn_coop_lds_bytes(64 / L)
 // bytes of LDS.  (k_knn_cov_coop: one wave per block; k_knn_and_search: eight.)
-template <int L>
+// EPI selects what phase C leaves behind (apd_filter.hpp uses 1 and 2: no gather, no moments, no Jacobi):
+//   KNN_EPI_COV      the covariance of the k neighbours (calculate_covariances, the text above);
+//   KNN_EPI_MEANDIST stat_out[original index] = (float)(sum over ranks 1 .. k-1 of (double)sqrtf(d2[rank]) / (k - 1)), added in rank order
+//                    in fp64: pcl::StatisticalOutlierRemoval's mean distance to the mean_k = k - 1 nearest neighbours;
+//   KNN_EPI_KTH      stat_out[original index] = d2[k - 1]: what pcl::RadiusOutlierRemoval's dense branch compares with the squared radius.
+// The rank-ordered keys of the merge carry the fp32 squared distance in their high word, so both come out of the rounds themselves.
+constexpr int KNN_EPI_COV = 0, KNN_EPI_MEANDIST = 1, KNN_EPI_KTH = 2;
+template <int L, int EPI = KNN_EPI_COV>
 __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned bx, int lane, unsigned long long* knn_smem, int k, int reg, int* err_flag,
-                                                  unsigned long long* stats, int raw /* 1: store the population covariance, k_regularize_covs follows */) {
+                                                  unsigned long long* stats, int raw /* 1: store the population covariance, k_regularize_covs follows */,
+                                                  float* stat_out = nullptr /* EPI != KNN_EPI_COV: one float per point, original index order */) {
   constexpr int QPW = 64 / L, NCL = KNN_NC / L, KQ_CAP = knn_coop_cap(L), KQ_STRIDE = KQ_CAP + 1, EPL = KQ_CAP / L;  // queries per wave, classes and list entries per lane
   static_assert(L == 4 || L == 8 || L == 16, "L lanes per query");
   static_assert(KQ_CAP % L == 0 && KQ_CAP <= 64 && KQ_WIN % KNN_NC == 0, "layout");
@@ -2264,6 +2272,8 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   int mysel[KNN_NC / L];  // the neighbours of rank sub, sub + L, ...: the ones this lane gathers
 #pragma unroll
   for (int t = 0; t < KNN_NC / L; t++) mysel[t] = i;
+  double stat_sum = 0.0;   // EPI == KNN_EPI_MEANDIST
+  float stat_last = 0.f;   // EPI == KNN_EPI_KTH
   {
     unsigned long long head = e[0], next = e[1];
     int cpos = 1;  // position of `next` in this lane's list
@@ -2277,7 +2287,13 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
             atomicExch(err_flag, 2);
             bk = (unsigned long long)(unsigned)i;  // keeps the gathers in range
           }
-          if (sub == u) mysel[t] = (int)(unsigned)bk;
+          if constexpr (EPI == KNN_EPI_COV) {
+            if (sub == u) mysel[t] = (int)(unsigned)bk;
+          } else if constexpr (EPI == KNN_EPI_MEANDIST) {  // (every lane of the query adds the same numbers in the same order)
+            if (t * L + u >= 1) stat_sum += (double)sqrtf(__uint_as_float((unsigned)(bk >> 32)));
+          } else {
+            stat_last = __uint_as_float((unsigned)(bk >> 32));
+          }
           if (head == bk) {  // keys are unique: one lane of the query
             head = next;
             cpos++;
@@ -2288,6 +2304,13 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
     }
   }
 #endif  // APD_ABL_KNN_SKIP_C
+#ifndef APD_ABL_KNN_SKIP_C
+  if constexpr (EPI != KNN_EPI_COV) {
+    const float v = EPI == KNN_EPI_MEANDIST ? (float)(stat_sum / (double)(k - 1)) : stat_last;
+    if (sub == 0) GW(stat_out)[G(c.perm)[i]] = v;
+    return;
+  }
+#endif
   // gathers: lane sub fetches the neighbours of rank sub, sub+L, ... -- all loads in flight together
   float4 nbv[KNN_NC / L];
 #pragma unroll

@@ -1,11 +1,14 @@
 // libapdgicp_hip.so -- the C ABI declared in include/apdgicp_hip.h, on top of apd::Engine.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -shared -fPIC (see build.py)
 #include <cstddef>
+#include <cmath>
 #include <limits>
+#include <memory>
 #include <new>
 
 #include "apd_engine.hpp"
 #include "apd_voxel.hpp"
+#include "apd_filter.hpp"
 
 using namespace apd;
 
@@ -36,6 +39,29 @@ struct apdgicp_submap {
   ~apdgicp_submap() {
     if (h_scal) (void)hipHostFree(h_scal);
     for (DevBuf* b : {&stage, &cat, &keys, &pos, &bsum, &out, &scal, &jobs.dev}) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_scan_filter {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  apdgicp_scan_filter_params prm;
+  apdgicp_submap* vox = nullptr;  // step 2 with a leaf: the voxel grid of the submap target, on this object's stream
+  Engine* eng = nullptr;          // step 3: packs, sorts and boxes the cloud of step 2 like a registration cloud (created when first needed)
+  DevBuf stage, gated, dense, stat, kept, out, bsum, scal;  // scal: int counts[4] {gate, compaction, output, -}, double {mean, stddev, thr}
+  char* h_scal = nullptr;         // pinned mirror of scal + the engine's error flag
+  const float* result = nullptr;
+  int64_t counts[4] = {0, 0, 0, 0};
+  int64_t n_stat = 0;
+  double mean = 0, stddev = 0, thr = 0;
+  ~apdgicp_scan_filter() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete eng;
+    delete vox;
+    if (h_scal) (void)hipHostFree(h_scal);
+    for (DevBuf* b : {&stage, &gated, &dense, &stat, &kept, &out, &bsum, &scal}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -84,6 +110,18 @@ int guarded(F&& f) {
   } catch (...) {
     return fail(APDGICP_ERR_INTERNAL, "unexpected C++ exception");
   }
+}
+
+// order-preserving compaction of src[0..n): count, scan of the block counts (total -> *d_total), scatter
+template <int PRED>
+int scan_filter_compact(apdgicp_scan_filter* f, const float4* src, const float* stat, double thr, const double* thr_ptr, int n, float4* dst,
+                               unsigned char* kept, int* d_total) {
+  const int nb = (n + FLT_BLK - 1) / FLT_BLK;
+  hipLaunchKernelGGL(k_flt_count<PRED>, dim3(nb), dim3(FLT_BLK), 0, f->stream, src, stat, thr, thr_ptr, n, f->bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, f->stream, f->bsum.as<int>(), nb, d_total);
+  hipLaunchKernelGGL(k_flt_scatter<PRED>, dim3(nb), dim3(FLT_BLK), 0, f->stream, src, stat, thr, thr_ptr, n, f->bsum.as<int>(), dst, n, kept);
+  APD_HIP(hipGetLastError());
+  return 0;
 }
 
 }  // namespace
@@ -1244,6 +1282,252 @@ int apdgicp_submap_copy(apdgicp_submap* s, float* dst_xyzi, int64_t capacity_poi
     const float* src = s->last_is_cat ? s->cat.as<float>() : s->out.as<float>();
     APD_HIP(hipMemcpyAsync(dst_xyzi, src, (size_t)s->n_last * 16, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s->stream));
     APD_HIP(hipStreamSynchronize(s->stream));
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------ scan preprocessing (apd_filter.hpp)
+void apdgicp_scan_filter_default_params(apdgicp_scan_filter_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->use_distance_filter = 1, p->near = 1.0, p->far = 100.0, p->z_low = -5.0, p->z_high = 20.0;  // preprocessing_nodelet.cpp:201-205
+  p->leaf[0] = p->leaf[1] = p->leaf[2] = 0.1f;                                                   // :137-144
+  p->outlier_method = APDGICP_OUTLIER_STATISTICAL, p->mean_k = 20, p->stddev_mul = 1.0;          // :166-175
+  p->radius = 0.8, p->min_neighbors = 2;                                                         // :176-184
+}
+
+static int scan_filter_check_params(const apdgicp_scan_filter_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
+  if (p->leaf[0] > 0.f && (!(p->leaf[1] > 0.f) || !(p->leaf[2] > 0.f))) return fail(APDGICP_ERR_INVALID_ARG, "leaf sizes must be positive");
+  if (p->outlier_method == APDGICP_OUTLIER_STATISTICAL) {
+    if (p->mean_k < 1) return fail(APDGICP_ERR_INVALID_ARG, "mean_k must be >= 1");
+    if (p->mean_k + 1 > KNN_NC) return fail(APDGICP_ERR_UNSUPPORTED, "mean_k above 31");
+    if (!std::isfinite(p->stddev_mul)) return fail(APDGICP_ERR_INVALID_ARG, "stddev_mul is not finite");
+  } else if (p->outlier_method == APDGICP_OUTLIER_RADIUS) {
+    if (p->min_neighbors < 0) return fail(APDGICP_ERR_INVALID_ARG, "min_neighbors must be >= 0");
+    if (p->min_neighbors + 1 > KNN_NC) return fail(APDGICP_ERR_UNSUPPORTED, "min_neighbors above 31");
+    if (!(p->radius > 0.0)) return fail(APDGICP_ERR_INVALID_ARG, "radius must be positive");
+  } else if (p->outlier_method != APDGICP_OUTLIER_NONE) {
+    return fail(APDGICP_ERR_UNSUPPORTED, "unknown outlier removal method");
+  }
+  return 0;
+}
+
+int apdgicp_scan_filter_create(const apdgicp_scan_filter_params* p, int device, void* stream, apdgicp_scan_filter** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_scan_filter_params dflt;
+    apdgicp_scan_filter_default_params(&dflt);
+    if (!p) p = &dflt;
+    APD_TRY(scan_filter_check_params(p));
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_scan_filter> f(new apdgicp_scan_filter);
+    f->device = device, f->prm = *p;
+    if (stream) {
+      f->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+      f->own_stream = true;
+    }
+    APD_HIP(hipHostMalloc((void**)&f->h_scal, 64, hipHostMallocDefault));
+    APD_TRY(f->scal.ensure(64));
+    APD_TRY(apdgicp_submap_create(device, f->stream, &f->vox));
+    *out = f.release();
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_destroy(apdgicp_scan_filter* f) {
+  return guarded([&]() -> int {
+    if (f) (void)hipSetDevice(f->device);
+    delete f;
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_set_params(apdgicp_scan_filter* f, const apdgicp_scan_filter_params* p) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(scan_filter_check_params(p));
+    f->prm = *p;
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device,
+                            int64_t* n_out) {
+  return guarded([&]() -> int {
+    if (!f || !n_out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *n_out = 0;
+    f->result = nullptr, f->n_stat = 0, f->mean = f->stddev = f->thr = 0;
+    f->counts[0] = f->counts[1] = f->counts[2] = f->counts[3] = 0;
+    if (n < 0 || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity offset outside the point");
+    if (n > (1ll << 27)) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^27 points");
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    const apdgicp_scan_filter_params& P = f->prm;
+    const int ni = (int)n;
+    f->counts[0] = n;
+    // ---- input: device pointers are read in place, a host scan goes through the staging buffer
+    const float* d_in = xyz;
+    if (!on_device) {
+      APD_HIP(hipStreamSynchronize(f->stream));  // the staging buffer may still be read by the previous run
+      APD_TRY(f->stage.ensure((size_t)n * stride_bytes));
+      const size_t used = std::max<int64_t>(12, intensity_offset_bytes >= 0 ? intensity_offset_bytes + 4 : 12);
+      APD_HIP(hipMemcpyAsync(f->stage.p, xyz, (size_t)(n - 1) * stride_bytes + used, hipMemcpyHostToDevice, f->stream));
+      d_in = f->stage.as<float>();
+    }
+    int* d_counts = f->scal.as<int>();
+    double* d_thr = (double*)(f->scal.as<char>() + 16);
+    int* h_counts = (int*)f->h_scal;
+    APD_TRY(f->gated.ensure((size_t)n * 16));
+    APD_TRY(f->bsum.ensure((size_t)((n + FLT_BLK - 1) / FLT_BLK) * 4));
+    APD_HIP(hipMemsetAsync(f->scal.p, 0, 64, f->stream));
+    // ---- 1. distance_filter (:881-889)
+    GateParams g;
+    g.near_ = P.near, g.far_ = P.far, g.z_low = P.z_low, g.z_high = P.z_high, g.on = P.use_distance_filter ? 1 : 0, g.pad_ = 0;
+    hipLaunchKernelGGL(k_flt_gate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, f->stream, d_in, (long long)n, (int)(stride_bytes / 4),
+                       intensity_offset_bytes >= 0 ? (int)(intensity_offset_bytes / 4) : -1, g, f->gated.as<float4>(), d_counts);
+    APD_HIP(hipGetLastError());
+    // ---- 2. downsample (:850-866)
+    const float4* step2 = nullptr;
+    int n2 = -1;  // < 0: still on the device (d_counts[1])
+    if (P.leaf[0] > 0.f) {
+      const void* src = f->gated.p;
+      int64_t nn = n, nv = 0;
+      APD_TRY(apdgicp_submap_assemble(f->vox, 1, &src, &nn, 16, 12, 1, nullptr, P.leaf, &nv));
+      if (!f->vox->last_is_cat) step2 = f->vox->out.as<float4>(), n2 = (int)nv;  // (else: leaf too small, PCL returns its input: compacted below)
+    }
+    if (!step2) {  // removeNaNFromPointCloud (:852-857) / what the range gate left, in input order
+      APD_TRY(f->dense.ensure((size_t)n * 16));
+      APD_TRY((scan_filter_compact<0>(f, f->gated.as<float4>(), nullptr, 0.0, nullptr, ni, f->dense.as<float4>(), nullptr, d_counts + 1)));
+      step2 = f->dense.as<float4>();
+    }
+    auto read_back = [&](bool with_engine_flag) -> int {
+      APD_HIP(hipMemcpyAsync(f->h_scal, f->scal.p, 40, hipMemcpyDeviceToHost, f->stream));
+      if (with_engine_flag) APD_HIP(hipMemcpyAsync(f->h_scal + 40, f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+      APD_HIP(hipStreamSynchronize(f->stream));
+      return 0;
+    };
+    if (n2 < 0 || P.outlier_method == APDGICP_OUTLIER_NONE) {
+      APD_TRY(read_back(false));
+      if (n2 < 0) n2 = h_counts[1];
+    }
+    f->counts[2] = n2;
+    if (P.outlier_method == APDGICP_OUTLIER_NONE || n2 == 0) {
+      if (P.outlier_method != APDGICP_OUTLIER_NONE && P.leaf[0] > 0.f && !f->vox->last_is_cat) APD_TRY(read_back(false));  // (the gate's count)
+      f->counts[1] = h_counts[0], f->counts[3] = n2;
+      f->result = n2 ? (const float*)step2 : nullptr;
+      *n_out = n2;
+      return 0;
+    }
+    // ---- 3. outlier_removal (:868-879)
+    const bool statistical = P.outlier_method == APDGICP_OUTLIER_STATISTICAL;
+    const int k = statistical ? P.mean_k + 1 : P.min_neighbors + 1;
+    if (n2 < k) return fail(APDGICP_ERR_TOO_FEW_POINTS, "the downsampled scan has fewer points than the outlier filter's k");
+    apdgicp_params ep;
+    apdgicp_default_params(&ep);
+    ep.k_correspondences = k;
+    if (!f->eng) {
+      std::unique_ptr<Engine> e(new Engine);
+      APD_TRY(e->init(&ep, f->device, f->stream));
+      f->eng = e.release();
+    } else {
+      APD_TRY(f->eng->set_params(&ep));
+    }
+    Engine& E = *f->eng;
+    APD_TRY(E.set_cloud(0, (const float*)step2, n2, 16, 1, 0));  // pack, and (upload_desc) curve sort + 16 / 128 / 8192-point boxes
+    APD_TRY(E.upload_desc());
+    const int id0 = 0;
+    APD_TRY(E.d_ids.upload(&id0, sizeof(int), f->stream));
+    APD_TRY(f->stat.ensure((size_t)n2 * 4));
+    APD_TRY(f->kept.ensure((size_t)n2));
+    APD_TRY(f->out.ensure((size_t)n2 * 16));
+    const CloudDesc* desc = E.d_desc.as<CloudDesc>();
+    const int* ids = E.d_ids.as<int>();
+    int* eflag = E.d_errflag.as<int>();
+    float* stat = f->stat.as<float>();
+    if (E.knn_pruned) {
+      const dim3 grid((unsigned)((n2 + 3) / 4), 1u);
+      if (statistical)
+        hipLaunchKernelGGL(k_knn_stat_coop<KNN_EPI_MEANDIST>, grid, dim3(64), knn_coop_lds_bytes(4), f->stream, desc, ids, k, eflag, E.d_stats.as<unsigned long long>(), stat);
+      else
+        hipLaunchKernelGGL(k_knn_stat_coop<KNN_EPI_KTH>, grid, dim3(64), knn_coop_lds_bytes(4), f->stream, desc, ids, k, eflag, E.d_stats.as<unsigned long long>(), stat);
+    } else {
+      const dim3 grid((unsigned)((n2 + STAT_BRUTE_BLK - 1) / STAT_BRUTE_BLK), 1u);
+      if (statistical) hipLaunchKernelGGL(k_knn_stat_brute<KNN_EPI_MEANDIST>, grid, dim3(STAT_BRUTE_BLK), 0, f->stream, desc, ids, k, eflag, stat);
+      else hipLaunchKernelGGL(k_knn_stat_brute<KNN_EPI_KTH>, grid, dim3(STAT_BRUTE_BLK), 0, f->stream, desc, ids, k, eflag, stat);
+    }
+    APD_HIP(hipGetLastError());
+    const double r2 = P.radius * P.radius;
+    if (statistical) hipLaunchKernelGGL(k_flt_threshold, dim3(1), dim3(FLT_BLK), 0, f->stream, stat, n2, P.stddev_mul, d_thr);
+    APD_TRY((scan_filter_compact<1>(f, step2, stat, r2, statistical ? d_thr + 2 : nullptr, n2, f->out.as<float4>(), f->kept.as<unsigned char>(), d_counts + 2)));
+    APD_TRY(read_back(true));
+    const int flag = *(int*)(f->h_scal + 40);
+    if (flag) {
+      APD_HIP(hipMemsetAsync(E.d_errflag.p, 0, sizeof(int), f->stream));
+      return fail(APDGICP_ERR_INTERNAL, "outlier filter k-NN: " + Engine::errflag_text(flag));
+    }
+    const double* h_thr = (const double*)(f->h_scal + 16);
+    f->n_stat = n2;
+    if (statistical) f->mean = h_thr[0], f->stddev = h_thr[1], f->thr = h_thr[2];
+    else f->thr = r2;
+    f->counts[1] = h_counts[0], f->counts[3] = h_counts[2];
+    f->result = h_counts[2] ? f->out.as<float>() : nullptr;
+    *n_out = h_counts[2];
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_points(apdgicp_scan_filter* f, const float** device_xyzi, int64_t* n) {
+  return guarded([&]() -> int {
+    if (!f || !device_xyzi || !n) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *device_xyzi = f->result;
+    *n = f->result ? f->counts[3] : 0;
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_copy(apdgicp_scan_filter* f, float* dst_xyzi, int64_t capacity_points, int dst_on_device) {
+  return guarded([&]() -> int {
+    if (!f || (!dst_xyzi && capacity_points > 0)) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t n = f->result ? f->counts[3] : 0;
+    if (capacity_points < n) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer points than the filtered scan");
+    if (!n) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    APD_HIP(hipMemcpyAsync(dst_xyzi, f->result, (size_t)n * 16, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_stage_counts(apdgicp_scan_filter* f, int64_t counts[4]) {
+  return guarded([&]() -> int {
+    if (!f || !counts) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    for (int q = 0; q < 4; q++) counts[q] = f->counts[q];
+    return 0;
+  });
+}
+
+int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kept, int64_t capacity, double* mean, double* stddev, double* thr) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if ((stat || kept) && capacity < f->n_stat) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer entries than the cloud behind downsample");
+    if (mean) *mean = f->mean;
+    if (stddev) *stddev = f->stddev;
+    if (thr) *thr = f->thr;
+    if (!f->n_stat || (!stat && !kept)) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    if (stat) APD_HIP(hipMemcpyAsync(stat, f->stat.p, (size_t)f->n_stat * 4, hipMemcpyDeviceToHost, f->stream));
+    if (kept) APD_HIP(hipMemcpyAsync(kept, f->kept.p, (size_t)f->n_stat, hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));
     return 0;
   });
 }

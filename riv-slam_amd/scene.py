@@ -181,6 +181,34 @@ def make_keyframe_set(n_src: int, n_tgt: int, n_keyframes: int, seed: int):
     return source, targets, truths, guesses
 
 
+def raw_scan(n: int, seed: int, outlier_share: float = 0.05) -> np.ndarray:
+    """A scan as the radar driver hands it to preprocessing, BEFORE the range gate, the voxel grid and the outlier filter
+    (preprocessing_nodelet.cpp:812-815): [n, 4] float32 {x, y, z, intensity}, shuffled.  Of the n points ~3 % lie inside 2 m (returns
+    from the vehicle itself), ~2 % beyond 100 m, `outlier_share` are isolated clutter spread over the whole frustum volume, five
+    (n >= 100) have a NaN or an infinite coordinate; the rest is the structured scene of make_pair seen from the origin."""
+    rng = np.random.default_rng(seed)
+    scene = Scene(rng)
+    n_bad = 5 if n >= 100 else 0
+    n_near, n_far, n_clutter = int(0.03 * n), int(0.02 * n), int(outlier_share * n)
+    n_scene = n - n_bad - n_near - n_far - n_clutter
+
+    def polar(r, az, el):
+        ce = np.cos(el)
+        return np.stack([r * ce * np.cos(az), r * ce * np.sin(az), r * np.sin(el)], axis=1)
+
+    parts = [_observe(rng, scene, np.eye(4), n_scene).astype(np.float64)]
+    parts.append(polar(rng.uniform(0.05, 2.0, n_near), rng.uniform(-np.pi, np.pi, n_near), rng.uniform(-0.5, 0.5, n_near)))
+    parts.append(polar(rng.uniform(100.0, 180.0, n_far), rng.uniform(-AZ_MAX, AZ_MAX, n_far), rng.uniform(-EL_MAX, EL_MAX, n_far)))
+    parts.append(polar(rng.uniform(R_MIN, R_MAX, n_clutter), rng.uniform(-AZ_MAX, AZ_MAX, n_clutter), rng.uniform(-EL_MAX, EL_MAX, n_clutter)))
+    bad = rng.uniform(-10.0, 10.0, (n_bad, 3))
+    for q, v in enumerate((np.nan, np.inf, -np.inf, np.nan, np.nan)[:n_bad]):
+        bad[q, q % 3] = v
+    parts.append(bad)
+    xyz = np.concatenate(parts, axis=0)
+    out = np.concatenate([xyz, rng.uniform(0.0, 40.0, (n, 1))], axis=1).astype(np.float32)
+    return np.ascontiguousarray(out[rng.permutation(n)])
+
+
 def pose_error(T_ref: np.ndarray, T_est: np.ndarray):
     """(t_err [m], r_err [rad]) of delta = T_ref^-1 * T_est; metric of
     fast_apdgicp/src/test/gicp_test.cpp:73-78."""
