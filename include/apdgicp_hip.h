@@ -37,7 +37,8 @@ extern "C" {
                                    5: the three fp32 angles of the sensor model (A:168,172-173) through glibc's atan2f algorithm (apd_atan2f.h) instead of the
                                       device library's; + source_stamp, set_trace / get_trace, debug_atan2f;
                                    6: + APDGICP_FLAG_ALGEBRAIC_APD, build_flags, nearest_neighbours_of, get_trace_step_norms;
-                                      still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal) */
+                                      still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal);
+                                      still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -443,6 +444,114 @@ int apdgicp_scan_filter_stage_counts(apdgicp_scan_filter* f, int64_t counts[4]);
  * (STATISTICAL) or d2[k - 1] (RADIUS), kept = 1 / 0; mean / stddev / thr: STATISTICAL's, RADIUS: 0, 0, radius * radius.  Any pointer may
  * be NULL; host memory.  For tests and for tuning the two thresholds. */
 int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kept, int64_t capacity, double* mean, double* stddev, double* thr);
+
+/* ------------------------------------------------------------------ Doppler ego velocity and moving-point removal
+ * rio::RadarEgoVelocityEstimator::estimate ("E:" = radar_graph_slam/src/radar_ego_velocity_estimator.cpp, "EH:" =
+ * radar_graph_slam/include/radar_ego_velocity_estimator.h), the step PreprocessingNodelet::cloud_callback runs on the raw
+ * {x, y, z, intensity, doppler} scan right before the filters above (preprocessing_nodelet.cpp:708-741); its inlier cloud replaces the
+ * raw scan as src_cloud when enable_dynamic_object_removal is set (:775-786).  On the device, in the reference's order:
+ *   1. E:75-91, per point (input order kept):  xd, yd, zd = the coordinates widened to double;  r = sqrt((xd*xd + yd*yd) + zd*zd)
+ *      (Eigen's own order for Vector3d::norm() is not pinned here; it can matter only within 1 ulp of min_dist / max_dist);
+ *      az = (double)atan2f(y, x),  el = (double)atan2f(sqrtf(x*x + y*y), z) - M_PI_2  (fp32 products and sum each rounded on their own;
+ *      atan2f is glibc's, apd_atan2f.h);  valid = r > min_dist && r < max_dist && intensity > min_db (fp32) && fabs(az) < az_thr &&
+ *      fabs(el) < el_thr, *_thr = (double)deg * M_PI / 180.0 (angles::from_degrees), a NaN fails;  v = (-doppler) * factor in fp32;
+ *      row = {xd/r, yd/r, zd/r, (double)v}.  m = the number of valid rows; m <= 2: no estimate (success = 0).
+ *   2. E:99-118, zero velocity:  n0 = (size_t)((double)m * (1.0 - (double)allowed_outlier_percentage)), clamped to m - 1 (the reference
+ *      reads one past the end at 0 %);  the n0-th smallest |v| (exact: a radix selection on the fp32 bits) < thresh_zero_velocity:
+ *      v = 0, sigma = sigma_zero_velocity_*, the inliers are the rows with |v| < thresh in order, no outliers.
+ *   3. E:190-199, K hypotheses of S = N_ransac_points rows each.  The reference draws from std::random_device (E:187-194), which nobody
+ *      can reproduce; the CALLER supplies K * S uint32 words, and sample i of hypothesis k is  c = words[k * S + i] % (m - i)  among the
+ *      rows this hypothesis has not picked yet (for every earlier pick t in ascending order: t <= c moves c up by one): the stand-in for
+ *      std::shuffle, S distinct rows.  m < S: no hypotheses, success = 0.  The solve (E:257-273): H^T H (6 sums) and H^T y (3 sums)
+ *      added row after row in sample order, then an UNPIVOTED 3x3 LDL^T:  d0 = a00, l10 = a01/d0, l20 = a02/d0, d1 = a11 - l10*a01,
+ *      t = a12 - l20*a01, l21 = t/d1, d2 = (a22 - l20*a02) - l21*t;  z0 = b0, z1 = b1 - l10*z0, z2 = (b2 - l20*z0) - l21*z1;
+ *      w = z / d;  v2 = w2, v1 = w1 - l21*v2, v0 = (w0 - l10*v1) - l20*v2.  (Eigen's ldlt() pivots: a deviation, like the 6x6 solve of
+ *      the registration.)  use_cholesky_instead_of_bdcsvd = 0 (bdcSvd): APDGICP_ERR_UNSUPPORTED.
+ *   4. E:203-214, every hypothesis against every row in one pass:  inlier = fabs(y - ((h0*v0 + h1*v1) + h2*v2)) < (double)inlier_thresh.
+ *   5. E:215-233, the reference's bookkeeping, quirks included:  n_out = m - n_in;  (double)((float)n_out / (float)m) > 0.05: the
+ *      hypothesis's outliers are appended behind its inliers and it counts as n_in = m, n_out = 0;  best_in = the lowest k with the
+ *      largest such n_in, best_out = the lowest k with the largest such n_out if any is above 0 (it may be ANOTHER hypothesis).
+ *   6. E:239-247, 257-293, the fit on best_in's list in list order:  H^T H, H^T y, then e^T e (e = H v - y) as fixed-tree fp64 sums
+ *      (Eigen: its own order; the same bits on every run, the last bits may differ from Eigen's), the LDL^T of 3,
+ *      C = e^T e * inv(H^T H) / (rows - 3) with the inverse by cofactors, sigma = sqrt(diag C) + sigma_offset_radar_*.  The reference
+ *      returns true on every path (E:302): success = 1 whenever the inlier list is not empty; sigma_in_bounds says whether
+ *      diag C >= 0 and sigma < max_sigma_* held (if diag C < 0, sigma holds diag C as in the reference).
+ *   use_ransac = 0 (E:138-142): every valid row is an inlier, step 6 alone.
+ * Not part of this object: deskewing (:792), bdcSvd, the DBSCAN / radius filter on the outlier cloud (:766-774). */
+typedef struct {
+  float min_dist;                             /* EH:32 ; default 0.1 */
+  float max_dist;                             /* EH:33 ; default 400 */
+  float min_db;                               /* EH:34 ; default 5 */
+  float elevation_thresh_deg;                 /* EH:35 ; default 60 */
+  float azimuth_thresh_deg;                   /* EH:36 ; default 120 */
+  float doppler_velocity_correction_factor;   /* EH:37 ; default 1 */
+  float thresh_zero_velocity;                 /* EH:39 ; default 0.05 */
+  float allowed_outlier_percentage;           /* EH:40 ; default 0.30 */
+  float sigma_zero_velocity_x;                /* EH:41 ; default 1.0e-3 */
+  float sigma_zero_velocity_y;                /* EH:42 ; default 3.2e-3 */
+  float sigma_zero_velocity_z;                /* EH:43 ; default 1.0e-2 */
+  float sigma_offset_radar_x;                 /* EH:45 ; default 0 */
+  float sigma_offset_radar_y;                 /* EH:46 ; default 0 */
+  float sigma_offset_radar_z;                 /* EH:47 ; default 0 */
+  float max_sigma_x;                          /* EH:49 ; default 0.2 */
+  float max_sigma_y;                          /* EH:50 ; default 0.2 */
+  float max_sigma_z;                          /* EH:51 ; default 0.2 */
+  float max_r_cond;                           /* EH:52 ; never read by the reference (E:269) nor here; default 1000 */
+  float outlier_prob;                         /* EH:56 ; default 0.05 */
+  float success_prob;                         /* EH:57 ; default 0.995 */
+  float inlier_thresh;                        /* EH:59 ; default 0.5 */
+  int32_t use_cholesky_instead_of_bdcsvd;     /* EH:53 ; default 1 ; 0: APDGICP_ERR_UNSUPPORTED */
+  int32_t use_ransac;                         /* EH:55 ; default 1 */
+  int32_t N_ransac_points;                    /* EH:58 (a float there) ; default 5 ; 3 .. 8 */
+  int32_t n_hypotheses;                       /* 0 (default): setRansacIter's formula, EH:138-143 (3 at the defaults); else 1 .. 1024 */
+  int32_t reserved;                           /* 0 */
+} apdgicp_ego_velocity_params;
+/* What estimate() reports (E:52-170) and how it got there.  best_in / best_out: -1 when there is none. */
+typedef struct {
+  double v[3];                /* v_r */
+  double sigma[3];            /* sigma_v_r */
+  int32_t success;            /* estimate()'s return value */
+  int32_t zero_velocity;      /* the branch of E:108 was taken */
+  int32_t sigma_in_bounds;    /* E:284-292 */
+  int32_t m;                  /* valid rows (E:74-91) */
+  int32_t n_inlier;           /* points of the inlier cloud */
+  int32_t n_outlier;          /* points of the outlier cloud */
+  int32_t best_in;
+  int32_t best_out;
+  int32_t K;                  /* hypotheses of this run (ransac_iter_) */
+  int32_t reserved;
+} apdgicp_ego_velocity_result;
+typedef struct apdgicp_ego_velocity apdgicp_ego_velocity;
+void apdgicp_ego_velocity_default_params(apdgicp_ego_velocity_params* p);                     /* RadarEgoVelocityEstimatorConfig's defaults, EH:30-60 */
+/* RadarEgoVelocityEstimator() + configure() (EH:86-88, 152-188).  `stream` may be NULL (the object creates its own) or a hipStream_t of the caller */
+int apdgicp_ego_velocity_create(const apdgicp_ego_velocity_params* p, int device, void* stream, apdgicp_ego_velocity** out);
+int apdgicp_ego_velocity_destroy(apdgicp_ego_velocity* e);
+int apdgicp_ego_velocity_set_params(apdgicp_ego_velocity* e, const apdgicp_ego_velocity_params* p);   /* configure(), EH:152-188 */
+/* the number of hypotheses a run with these parameters scores: n_hypotheses, or setRansacIter's (EH:138-143)
+ * uint(log(1.0 - success_prob) / log(1.0 - pow(1.0 - outlier_prob, N_ransac_points))) ; needs no device */
+int apdgicp_ego_velocity_hypothesis_count(const apdgicp_ego_velocity_params* p, int32_t* K);
+/* estimate() (E:60-170) of one scan: `pts` is the address of the first x, points `stride_bytes` apart, intensity (snr_db) and doppler
+ * floats at the given byte offsets inside a point; on_device as everywhere.  `words`: HOST memory, n_words >= K * N_ransac_points
+ * uint32 (fewer: APDGICP_ERR_INVALID_ARG; unused without RANSAC, may be NULL then).  n = 0: status 0, success = 0.  The call waits once,
+ * for the result record (a host scan is staged by a copy on the object's stream, without a wait); the clouds stay on the device. */
+int apdgicp_ego_velocity_run(apdgicp_ego_velocity* e, const float* pts, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes,
+                             int64_t doppler_offset_bytes, int on_device, const uint32_t* words, int64_t n_words, apdgicp_ego_velocity_result* result);
+/* The inlier (static) / outlier (moving) cloud of the last run in device memory, valid until the next run: n points of {x, y, z, intensity}
+ * floats, 16 bytes apart -- what apdgicp_scan_filter_run(..., on_device = 1) and apdgicp_set_source accept --, beside it one float doppler
+ * per point (toRadarPointCloudType, E:41-50: -v) and the point's index in the input scan.  Any pointer but e may be NULL. */
+int apdgicp_ego_velocity_inliers(apdgicp_ego_velocity* e, const float** device_xyzi, const float** device_doppler, const int32_t** device_index, int64_t* n);
+int apdgicp_ego_velocity_outliers(apdgicp_ego_velocity* e, const float** device_xyzi, const float** device_doppler, const int32_t** device_index, int64_t* n);
+/* copies one of the two clouds to HOST memory: which = 0 inliers, 1 outliers; xyzi [4 * capacity], doppler / index / row [capacity]
+ * (row: the point's index among the valid rows, i.e. the reference's inlier_idx_best / outlier_idx_best); any destination may be NULL */
+int apdgicp_ego_velocity_copy(apdgicp_ego_velocity* e, int which, float* xyzi, float* doppler, int32_t* index, int32_t* row, int64_t capacity);
+/* every hypothesis of the last run: v_k [3 * capacity] doubles and n_in [capacity] (before the 5 % rule); host memory; for tests and tuning */
+int apdgicp_ego_velocity_hypotheses(apdgicp_ego_velocity* e, double* v_k, int32_t* n_in, int64_t capacity);
+/* The intermediate results of the last run, host memory, any pointer may be NULL (for tests): valid [n] 0 / 1 per input point
+ * (valid_capacity >= n entries); rows [4 * m] doubles (rows_capacity >= m rows); samples [K * N_ransac_points] row indices
+ * (samples_capacity >= that many entries; RANSAC runs only, else untouched); selected_abs_v: the n0-th smallest |v|.  A destination that
+ * is too small: APDGICP_ERR_INVALID_ARG, nothing is written. */
+int apdgicp_ego_velocity_debug(apdgicp_ego_velocity* e, uint8_t* valid, int64_t valid_capacity, double* rows, int64_t rows_capacity, int32_t* samples,
+                               int64_t samples_capacity, float* selected_abs_v);
 
 #ifdef __cplusplus
 }

@@ -9,6 +9,7 @@
 #include "apd_engine.hpp"
 #include "apd_voxel.hpp"
 #include "apd_filter.hpp"
+#include "apd_ego.hpp"
 
 using namespace apd;
 
@@ -62,6 +63,28 @@ struct apdgicp_scan_filter {
     delete vox;
     if (h_scal) (void)hipHostFree(h_scal);
     for (DevBuf* b : {&stage, &gated, &dense, &stat, &kept, &out, &bsum, &scal}) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_ego_velocity {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  apdgicp_ego_velocity_params prm;
+  DevBuf stage, rows_all, valid, rows, src, bsum, words, vk, n_in, samples, rec;
+  DevBuf in_row, in_xyzi, in_dop, in_src, out_row, out_xyzi, out_dop, out_src;
+  EgoRecord* h_rec = nullptr;  // pinned mirror of rec
+  int64_t n_last = 0;
+  int K_last = 0, S_last = 0;
+  bool ran = false;
+  std::vector<DevBuf*> bufs() {
+    return {&stage, &rows_all, &valid, &rows, &src, &bsum, &words, &vk, &n_in, &samples, &rec, &in_row, &in_xyzi, &in_dop, &in_src, &out_row, &out_xyzi, &out_dop, &out_src};
+  }
+  ~apdgicp_ego_velocity() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (h_rec) (void)hipHostFree(h_rec);
+    for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -1528,6 +1551,252 @@ int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kep
     if (stat) APD_HIP(hipMemcpyAsync(stat, f->stat.p, (size_t)f->n_stat * 4, hipMemcpyDeviceToHost, f->stream));
     if (kept) APD_HIP(hipMemcpyAsync(kept, f->kept.p, (size_t)f->n_stat, hipMemcpyDeviceToHost, f->stream));
     APD_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------ Doppler ego velocity (apd_ego.hpp)
+static_assert(sizeof(apdgicp_ego_velocity_result) == 88 && offsetof(EgoRecord, mode) == sizeof(apdgicp_ego_velocity_result), "EgoRecord starts with the result");
+
+void apdgicp_ego_velocity_default_params(apdgicp_ego_velocity_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->min_dist = 0.1f, p->max_dist = 400.f, p->min_db = 5.f, p->elevation_thresh_deg = 60.f, p->azimuth_thresh_deg = 120.f;  // EH:32-36
+  p->doppler_velocity_correction_factor = 1.f;                                                                          // EH:37
+  p->thresh_zero_velocity = 0.05f, p->allowed_outlier_percentage = 0.30f;                                               // EH:39-40
+  p->sigma_zero_velocity_x = 1.0e-03f, p->sigma_zero_velocity_y = 3.2e-03f, p->sigma_zero_velocity_z = 1.0e-02f;        // EH:41-43
+  p->max_sigma_x = p->max_sigma_y = p->max_sigma_z = 0.2f;                                                              // EH:49-51
+  p->max_r_cond = 1000.f;                                                                                               // EH:52 (uninitialised there)
+  p->use_cholesky_instead_of_bdcsvd = 1, p->use_ransac = 1;                                                             // EH:53, 55
+  p->outlier_prob = 0.05f, p->success_prob = 0.995f, p->N_ransac_points = 5, p->inlier_thresh = 0.5f;                   // EH:56-59
+}
+
+int apdgicp_ego_velocity_hypothesis_count(const apdgicp_ego_velocity_params* p, int32_t* K) {
+  if (!p || !K) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *K = 0;
+  if (p->n_hypotheses < 0 || p->n_hypotheses > EGO_MAX_K) return fail(APDGICP_ERR_INVALID_ARG, "n_hypotheses must be 0 .. 1024");
+  if (p->n_hypotheses) {
+    *K = p->n_hypotheses;
+    return 0;
+  }
+  // setRansacIter, EH:138-143: the float fields widened to double, the quotient truncated to uint
+  const double it = std::log(1.0 - (double)p->success_prob) / std::log(1.0 - std::pow(1.0 - (double)p->outlier_prob, (double)(float)p->N_ransac_points));
+  if (!(it >= 0.0)) return fail(APDGICP_ERR_INVALID_ARG, "success_prob / outlier_prob give no number of RANSAC iterations");
+  if (it >= (double)EGO_MAX_K + 1.0) return fail(APDGICP_ERR_UNSUPPORTED, "setRansacIter's formula gives more than 1024 hypotheses: set n_hypotheses");
+  *K = (int32_t)it;
+  return 0;
+}
+
+static int ego_check_params(const apdgicp_ego_velocity_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
+  if (!p->use_cholesky_instead_of_bdcsvd) return fail(APDGICP_ERR_UNSUPPORTED, "use_cholesky_instead_of_bdcsvd = false (bdcSvd) is not offered");
+  if (p->N_ransac_points < 3 || p->N_ransac_points > EGO_MAX_S) return fail(APDGICP_ERR_INVALID_ARG, "N_ransac_points must be 3 .. 8");
+  if (!(p->allowed_outlier_percentage >= 0.f && p->allowed_outlier_percentage <= 1.f)) return fail(APDGICP_ERR_INVALID_ARG, "allowed_outlier_percentage must be 0 .. 1");
+  int32_t K = 0;
+  if (p->use_ransac) APD_TRY(apdgicp_ego_velocity_hypothesis_count(p, &K));
+  return 0;
+}
+
+int apdgicp_ego_velocity_create(const apdgicp_ego_velocity_params* p, int device, void* stream, apdgicp_ego_velocity** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_ego_velocity_params dflt;
+    apdgicp_ego_velocity_default_params(&dflt);
+    if (!p) p = &dflt;
+    APD_TRY(ego_check_params(p));
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_ego_velocity> e(new apdgicp_ego_velocity);
+    e->device = device, e->prm = *p;
+    if (stream) {
+      e->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+      e->own_stream = true;
+    }
+    APD_HIP(hipHostMalloc((void**)&e->h_rec, sizeof(EgoRecord), hipHostMallocDefault));
+    memset(e->h_rec, 0, sizeof(EgoRecord));
+    APD_TRY(e->rec.ensure(sizeof(EgoRecord)));
+    APD_TRY(e->vk.ensure((size_t)EGO_MAX_K * 3 * sizeof(double)));
+    APD_TRY(e->n_in.ensure((size_t)EGO_MAX_K * sizeof(int)));
+    APD_TRY(e->samples.ensure((size_t)EGO_MAX_K * EGO_MAX_S * sizeof(int)));
+    APD_TRY(e->words.ensure((size_t)EGO_MAX_K * EGO_MAX_S * sizeof(unsigned)));
+    *out = e.release();
+    return 0;
+  });
+}
+
+int apdgicp_ego_velocity_destroy(apdgicp_ego_velocity* e) {
+  return guarded([&]() -> int {
+    if (e) (void)hipSetDevice(e->device);
+    delete e;
+    return 0;
+  });
+}
+
+int apdgicp_ego_velocity_set_params(apdgicp_ego_velocity* e, const apdgicp_ego_velocity_params* p) {
+  return guarded([&]() -> int {
+    if (!e) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(ego_check_params(p));
+    e->prm = *p;
+    return 0;
+  });
+}
+
+int apdgicp_ego_velocity_run(apdgicp_ego_velocity* e, const float* pts, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes,
+                             int64_t doppler_offset_bytes, int on_device, const uint32_t* words, int64_t n_words, apdgicp_ego_velocity_result* result) {
+  return guarded([&]() -> int {
+    if (!e || !result) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    memset(result, 0, sizeof(*result));
+    result->best_in = result->best_out = -1;
+    e->ran = false, e->n_last = 0;
+    memset(e->h_rec, 0, sizeof(EgoRecord));
+    if (n < 0 || (n > 0 && !pts)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
+    if (stride_bytes < 20 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 20");
+    for (int64_t off : {intensity_offset_bytes, doppler_offset_bytes})
+      if (off < 12 || off % 4 || off + 4 > stride_bytes) return fail(APDGICP_ERR_INVALID_ARG, "intensity / doppler offset outside the point");
+    if (n > (1ll << 24)) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    const apdgicp_ego_velocity_params& P = e->prm;
+    int32_t K = 0;
+    if (P.use_ransac) APD_TRY(apdgicp_ego_velocity_hypothesis_count(&P, &K));
+    const int S = P.N_ransac_points;
+    if (K > 0 && (n_words < (int64_t)K * S || !words)) return fail(APDGICP_ERR_INVALID_ARG, "fewer random words than hypotheses x N_ransac_points");
+    result->K = K;
+    e->K_last = K, e->S_last = S;
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(e->device));
+    const int ni = (int)n, nb = (ni + EGO_BLK - 1) / EGO_BLK;
+    const float* d_in = pts;
+    if (!on_device) {
+      // (no wait: the copy below is ordered behind the previous run's kernels by the stream; a buffer that grows is freed by hipFree, which waits)
+      APD_TRY(e->stage.ensure((size_t)n * stride_bytes));
+      const size_t used = (size_t)std::max<int64_t>(12, std::max(intensity_offset_bytes, doppler_offset_bytes) + 4);
+      APD_HIP(hipMemcpyAsync(e->stage.p, pts, (size_t)(n - 1) * stride_bytes + used, hipMemcpyHostToDevice, e->stream));
+      d_in = e->stage.as<float>();
+    }
+    APD_TRY(e->rows_all.ensure((size_t)n * 32));
+    APD_TRY(e->rows.ensure((size_t)n * 32));
+    APD_TRY(e->valid.ensure((size_t)n));
+    APD_TRY(e->bsum.ensure((size_t)nb * 3 * sizeof(int)));
+    for (DevBuf* b : {&e->src, &e->in_row, &e->in_dop, &e->in_src, &e->out_row, &e->out_dop, &e->out_src}) APD_TRY(b->ensure((size_t)n * 4));
+    APD_TRY(e->in_xyzi.ensure((size_t)n * 16));
+    APD_TRY(e->out_xyzi.ensure((size_t)n * 16));
+    EgoParams D;
+    memset(&D, 0, sizeof(D));
+    D.min_dist = (double)P.min_dist, D.max_dist = (double)P.max_dist, D.min_db = P.min_db;
+    D.az_thr = (double)P.azimuth_thresh_deg * M_PI / 180.0, D.el_thr = (double)P.elevation_thresh_deg * M_PI / 180.0;  // angles::from_degrees
+    D.factor = P.doppler_velocity_correction_factor, D.thresh_zero = P.thresh_zero_velocity;
+    D.allowed_outlier_percentage = (double)P.allowed_outlier_percentage, D.inlier_thresh = (double)P.inlier_thresh;
+    D.sigma_zero[0] = P.sigma_zero_velocity_x, D.sigma_zero[1] = P.sigma_zero_velocity_y, D.sigma_zero[2] = P.sigma_zero_velocity_z;
+    D.sigma_offset[0] = P.sigma_offset_radar_x, D.sigma_offset[1] = P.sigma_offset_radar_y, D.sigma_offset[2] = P.sigma_offset_radar_z;
+    D.max_sigma[0] = P.max_sigma_x, D.max_sigma[1] = P.max_sigma_y, D.max_sigma[2] = P.max_sigma_z;
+    D.use_ransac = P.use_ransac ? 1 : 0, D.S = S, D.K = K;
+    EgoRecord* rec = e->rec.as<EgoRecord>();
+    int* bsum = e->bsum.as<int>();
+    const int stride = (int)(stride_bytes / 4), ioff = (int)(intensity_offset_bytes / 4), doff = (int)(doppler_offset_bytes / 4);
+    double4* rows = e->rows.as<double4>();
+    double* vk = e->vk.as<double>();
+    APD_HIP(hipMemsetAsync(e->rec.p, 0, sizeof(EgoRecord), e->stream));
+    if (K > 0) {
+      APD_HIP(hipMemcpyAsync(e->words.p, words, (size_t)K * S * sizeof(uint32_t), hipMemcpyHostToDevice, e->stream));
+      APD_HIP(hipMemsetAsync(e->n_in.p, 0, (size_t)EGO_MAX_K * sizeof(int), e->stream));
+      APD_HIP(hipMemsetAsync(e->vk.p, 0, (size_t)EGO_MAX_K * 3 * sizeof(double), e->stream));
+    }
+    // 1. features + in-order compaction (m -> the record)
+    hipLaunchKernelGGL(k_ego_features, dim3(nb), dim3(EGO_BLK), 0, e->stream, d_in, ni, stride, ioff, doff, D, e->rows_all.as<double4>(), e->valid.as<unsigned char>(), bsum);
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e->stream, bsum, nb, &rec->m);
+    hipLaunchKernelGGL(k_ego_compact, dim3(nb), dim3(EGO_BLK), 0, e->stream, e->rows_all.as<double4>(), e->valid.as<unsigned char>(), ni, bsum, rows, e->src.as<int>());
+    // 2. zero velocity; decides the mode of everything below
+    hipLaunchKernelGGL(k_ego_zero_velocity, dim3(1), dim3(EGO_BLK), 0, e->stream, rows, D, rec);
+    // 3. - 5. hypotheses, scores, the two best
+    if (K > 0) {
+      hipLaunchKernelGGL(k_ego_hypotheses, dim3((K + 63) / 64), dim3(64), 0, e->stream, rows, e->words.as<unsigned>(), D, rec, vk, e->samples.as<int>());
+      hipLaunchKernelGGL(k_ego_score, dim3((ni + EGO_TILE - 1) / EGO_TILE, (K + EGO_GROUP - 1) / EGO_GROUP), dim3(EGO_TILE), 0, e->stream, rows, vk, D, rec, e->n_in.as<int>());
+      hipLaunchKernelGGL(k_ego_select, dim3(1), dim3(EGO_BLK), 0, e->stream, e->n_in.as<int>(), D, rec);
+    }
+    // the lists and the clouds, then 6. the fit
+    hipLaunchKernelGGL(k_ego_emit_count, dim3(nb), dim3(EGO_BLK), 0, e->stream, rows, vk, D, rec, bsum + nb, bsum + 2 * nb);
+    hipLaunchKernelGGL(k_ego_emit_scan, dim3(1), dim3(SCAN_BLK), 0, e->stream, bsum + nb, bsum + 2 * nb, nb, rec);
+    hipLaunchKernelGGL(k_ego_emit_scatter, dim3(nb), dim3(EGO_BLK), 0, e->stream, rows, e->src.as<int>(), vk, D, rec, bsum + nb, bsum + 2 * nb, d_in, stride, ioff,
+                       e->in_row.as<int>(), e->in_xyzi.as<float4>(), e->in_dop.as<float>(), e->in_src.as<int>(), e->out_row.as<int>(), e->out_xyzi.as<float4>(),
+                       e->out_dop.as<float>(), e->out_src.as<int>());
+    hipLaunchKernelGGL(k_ego_lsq, dim3(1), dim3(EGO_BLK), 0, e->stream, rows, e->in_row.as<int>(), D, rec);
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(e->h_rec, e->rec.p, sizeof(EgoRecord), hipMemcpyDeviceToHost, e->stream));
+    APD_HIP(hipStreamSynchronize(e->stream));  // the one wait of the call
+    memcpy(result, e->h_rec, sizeof(*result));
+    if (e->h_rec->mode != EGO_MODE_RANSAC) result->best_in = result->best_out = -1;
+    result->K = K;
+    e->n_last = n, e->ran = true;
+    return 0;
+  });
+}
+
+static int ego_cloud(apdgicp_ego_velocity* e, int which, const float** xyzi, const float** dop, const int32_t** index, int64_t* n) {
+  if (!e || which < 0 || which > 1) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+  const int64_t cnt = e->ran ? (which ? e->h_rec->n_outlier : e->h_rec->n_inlier) : 0;
+  if (xyzi) *xyzi = cnt ? (which ? e->out_xyzi : e->in_xyzi).as<float>() : nullptr;
+  if (dop) *dop = cnt ? (which ? e->out_dop : e->in_dop).as<float>() : nullptr;
+  if (index) *index = cnt ? (which ? e->out_src : e->in_src).as<int32_t>() : nullptr;
+  if (n) *n = cnt;
+  return 0;
+}
+int apdgicp_ego_velocity_inliers(apdgicp_ego_velocity* e, const float** device_xyzi, const float** device_doppler, const int32_t** device_index, int64_t* n) {
+  return guarded([&]() -> int { return ego_cloud(e, 0, device_xyzi, device_doppler, device_index, n); });
+}
+int apdgicp_ego_velocity_outliers(apdgicp_ego_velocity* e, const float** device_xyzi, const float** device_doppler, const int32_t** device_index, int64_t* n) {
+  return guarded([&]() -> int { return ego_cloud(e, 1, device_xyzi, device_doppler, device_index, n); });
+}
+
+int apdgicp_ego_velocity_copy(apdgicp_ego_velocity* e, int which, float* xyzi, float* doppler, int32_t* index, int32_t* row, int64_t capacity) {
+  return guarded([&]() -> int {
+    int64_t n = 0;
+    APD_TRY(ego_cloud(e, which, nullptr, nullptr, nullptr, &n));
+    if (capacity < n) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer points than the cloud");
+    if (!n) return 0;
+    APD_HIP(hipSetDevice(e->device));
+    if (xyzi) APD_HIP(hipMemcpyAsync(xyzi, (which ? e->out_xyzi : e->in_xyzi).p, (size_t)n * 16, hipMemcpyDeviceToHost, e->stream));
+    if (doppler) APD_HIP(hipMemcpyAsync(doppler, (which ? e->out_dop : e->in_dop).p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (index) APD_HIP(hipMemcpyAsync(index, (which ? e->out_src : e->in_src).p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    if (row) APD_HIP(hipMemcpyAsync(row, (which ? e->out_row : e->in_row).p, (size_t)n * 4, hipMemcpyDeviceToHost, e->stream));
+    APD_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+  });
+}
+
+int apdgicp_ego_velocity_hypotheses(apdgicp_ego_velocity* e, double* v_k, int32_t* n_in, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!e) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int K = e->ran ? e->K_last : 0;
+    if ((v_k || n_in) && capacity < K) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer entries than hypotheses");
+    if (!K) return 0;
+    APD_HIP(hipSetDevice(e->device));
+    if (v_k) APD_HIP(hipMemcpyAsync(v_k, e->vk.p, (size_t)K * 3 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (n_in) APD_HIP(hipMemcpyAsync(n_in, e->n_in.p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    APD_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+  });
+}
+
+int apdgicp_ego_velocity_debug(apdgicp_ego_velocity* e, uint8_t* valid, int64_t valid_capacity, double* rows, int64_t rows_capacity, int32_t* samples,
+                               int64_t samples_capacity, float* selected_abs_v) {
+  return guarded([&]() -> int {
+    if (!e) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int m = e->ran ? e->h_rec->m : 0;
+    if (e->ran && ((valid && valid_capacity < e->n_last) || (rows && rows_capacity < m) ||
+                   (samples && e->h_rec->mode == EGO_MODE_RANSAC && samples_capacity < (int64_t)e->K_last * e->S_last)))
+      return fail(APDGICP_ERR_INVALID_ARG, "a destination holds fewer entries than the last run produced");
+    if (selected_abs_v) memcpy(selected_abs_v, &e->h_rec->sel_bits, 4);
+    if (!e->ran) return 0;
+    APD_HIP(hipSetDevice(e->device));
+    if (valid) APD_HIP(hipMemcpyAsync(valid, e->valid.p, (size_t)e->n_last, hipMemcpyDeviceToHost, e->stream));
+    if (rows && m) APD_HIP(hipMemcpyAsync(rows, e->rows.p, (size_t)m * 32, hipMemcpyDeviceToHost, e->stream));
+    if (samples && e->h_rec->mode == EGO_MODE_RANSAC)
+      APD_HIP(hipMemcpyAsync(samples, e->samples.p, (size_t)e->K_last * e->S_last * sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    APD_HIP(hipStreamSynchronize(e->stream));
     return 0;
   });
 }

@@ -98,6 +98,9 @@ SYMBOLS = [
     "apdgicp_submap_create", "apdgicp_submap_destroy", "apdgicp_submap_assemble", "apdgicp_submap_points", "apdgicp_submap_copy",
     "apdgicp_scan_filter_default_params", "apdgicp_scan_filter_create", "apdgicp_scan_filter_destroy", "apdgicp_scan_filter_set_params",
     "apdgicp_scan_filter_run", "apdgicp_scan_filter_points", "apdgicp_scan_filter_copy", "apdgicp_scan_filter_stage_counts", "apdgicp_scan_filter_scores",
+    "apdgicp_ego_velocity_default_params", "apdgicp_ego_velocity_create", "apdgicp_ego_velocity_destroy", "apdgicp_ego_velocity_set_params",
+    "apdgicp_ego_velocity_hypothesis_count", "apdgicp_ego_velocity_run", "apdgicp_ego_velocity_inliers", "apdgicp_ego_velocity_outliers",
+    "apdgicp_ego_velocity_copy", "apdgicp_ego_velocity_hypotheses", "apdgicp_ego_velocity_debug",
 ]
 
 _lib = None
@@ -219,6 +222,18 @@ def load_library(path: str | None = None):
     L.apdgicp_scan_filter_copy.argtypes = [vp, vp, i64, i32]
     L.apdgicp_scan_filter_stage_counts.argtypes = [vp, vp]
     L.apdgicp_scan_filter_scores.argtypes = [vp, vp, vp, i64, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
+    L.apdgicp_ego_velocity_default_params.argtypes = [vp]
+    L.apdgicp_ego_velocity_default_params.restype = None
+    L.apdgicp_ego_velocity_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.apdgicp_ego_velocity_destroy.argtypes = [vp]
+    L.apdgicp_ego_velocity_set_params.argtypes = [vp, vp]
+    L.apdgicp_ego_velocity_hypothesis_count.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apdgicp_ego_velocity_run.argtypes = [vp, vp, i64, i64, i64, i64, i32, vp, i64, vp]
+    for f in (L.apdgicp_ego_velocity_inliers, L.apdgicp_ego_velocity_outliers):
+        f.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_ego_velocity_copy.argtypes = [vp, i32, vp, vp, vp, vp, i64]
+    L.apdgicp_ego_velocity_hypotheses.argtypes = [vp, vp, vp, i64]
+    L.apdgicp_ego_velocity_debug.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
     if path is None:
         _lib = L
     return L

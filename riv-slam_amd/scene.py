@@ -209,6 +209,29 @@ def raw_scan(n: int, seed: int, outlier_share: float = 0.05) -> np.ndarray:
     return np.ascontiguousarray(out[rng.permutation(n)])
 
 
+def raw_doppler_scan(n: int, seed: int, v_sensor=(2.0, 0.3, -0.1), moving_share: float = 0.02, doppler_noise: float = 0.02, outlier_share: float = 0.02) -> np.ndarray:
+    """raw_scan plus the column the radar driver delivers beside it: [n, 5] float32 {x, y, z, intensity, doppler}, the input of
+    rio::RadarEgoVelocityEstimator::estimate (radar_ego_velocity_estimator.cpp:60-91).  A static point seen from a sensor moving with
+    `v_sensor` (sensor frame, m/s) has doppler = -(unit direction . v_sensor) (+ gaussian noise of `doppler_noise` m/s); `moving_share`
+    of the points belong to objects with a velocity of their own (|v| 3 .. 12 m/s added to the sensor's).  Rows with a non-finite
+    coordinate or at the origin carry doppler 0."""
+    base = raw_scan(n, seed, outlier_share)
+    rng = np.random.default_rng([seed, 0xD0])
+    xyz = base[:, :3].astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        r = np.sqrt((xyz * xyz).sum(axis=1))
+        u = xyz / r[:, None]
+    v = np.broadcast_to(np.asarray(v_sensor, dtype=np.float64), (n, 3)).copy()
+    movers = rng.random(n) < moving_share
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    v[movers] += d[movers] * rng.uniform(3.0, 12.0, (int(movers.sum()), 1))
+    with np.errstate(invalid="ignore"):
+        doppler = -(u * v).sum(axis=1) + rng.normal(0.0, doppler_noise, n)
+    doppler[~np.isfinite(doppler)] = 0.0
+    return np.ascontiguousarray(np.concatenate([base, doppler[:, None].astype(np.float32)], axis=1))
+
+
 def pose_error(T_ref: np.ndarray, T_est: np.ndarray):
     """(t_err [m], r_err [rad]) of delta = T_ref^-1 * T_est; metric of
     fast_apdgicp/src/test/gicp_test.cpp:73-78."""
