@@ -38,7 +38,8 @@ extern "C" {
                                       device library's; + source_stamp, set_trace / get_trace, debug_atan2f;
                                    6: + APDGICP_FLAG_ALGEBRAIC_APD, build_flags, nearest_neighbours_of, get_trace_step_norms;
                                       still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal);
-                                      still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal) */
+                                      still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal);
+                                      still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -552,6 +553,111 @@ int apdgicp_ego_velocity_hypotheses(apdgicp_ego_velocity* e, double* v_k, int32_
  * is too small: APDGICP_ERR_INVALID_ARG, nothing is written. */
 int apdgicp_ego_velocity_debug(apdgicp_ego_velocity* e, uint8_t* valid, int64_t valid_capacity, double* rows, int64_t rows_capacity, int32_t* samples,
                                int64_t samples_capacity, float* selected_abs_v);
+
+/* ------------------------------------------------------------------ floor plane detection and under-floor removal
+ * radar_graph_slam::FloorDetectionNodelet ("F:" = radar_graph_slam/apps/floor_detection_nodelet.cpp), which runs on every raw scan
+ * (radar_graph_slam.launch:13-14): its coefficients become the ground-plane factor of every keyframe, its under-floor-clipped cloud is
+ * published for the rest of the chain.  PCL is not part of the reference tree: the steps below follow its published algorithm, and every
+ * operation order that is PCL's or Eigen's (not pinned by the reference, like T*p above) is the one written here.  On the device:
+ *   1. F:156-163, per point (input order kept):  t = R p with R = R_y(tilt_deg) in fp32 -- angle = (float)(tilt_deg * M_PI / 180.0),
+ *      c / s = its cosine / sine evaluated in double and rounded to fp32, R = {c, 0, s; 0, (1 - c) + c, 0; -s, 0, c}, a coordinate is
+ *      (r0 x + r1 y) + r2 z (every fp32 operation rounded on its own; the zero translation is not added).  A plane distance is
+ *      ((a x + b y) + c z) + d everywhere (PlaneClipper3D::getDistance).  The point stays iff the distance to (0, 0, 1,
+ *      (float)(sensor_height + height_clip_range)) is >= 0 and the distance to (0, 0, 1, (float)(sensor_height - height_clip_range)) is
+ *      not.  n_clipped points.
+ *   2. F:280-307 (use_normal_filtering): per clipped point the normal_k nearest clipped points, itself included (the exact k-NN of the
+ *      registration, keys = fp32 squared distance, then index); their population covariance in fp64 (the sums of
+ *      apdgicp_compute_covariances, no regularisation), its eigenvectors by the Jacobi sweeps of the registration; u = the eigenvector of
+ *      the smallest eigenvalue; stat = (float)(|u_z| / |u|); the point stays iff (double)stat > cos(normal_filter_thresh * M_PI / 180.0).
+ *      Deviations: PCL forms the covariance in fp32 and uses eigen33; the viewpoint flip (F:289) cannot change an absolute value and is
+ *      not evaluated.  n_clipped < normal_k: PCL's normals are NaN, nothing stays (no search is launched).
+ *      Then the inverse tilt (F:169): the fp32 TRANSPOSE of R (Eigen's 4x4 inverse divides by c c + s s, 1 within an ulp).  n_filtered points.
+ *   3. F:177: n_filtered < floor_pts_thresh: no floor.  Else K = n_hypotheses three-point hypotheses.  PCL's sampler cannot be
+ *      reproduced: the CALLER supplies K * 3 uint32 words and row i of hypothesis k is drawn as in apdgicp_ego_velocity_run (step 3 there).
+ *      SampleConsensusModelPlane::computeModelCoefficients:  a = p1 - p0, b = p2 - p0;  the sample is BAD (collinear) iff
+ *      ax/bx == ay/by && az/bz == ay/by;  n = a x b = {ay bz - az by, az bx - ax bz, ax by - ay bx};  n /= sqrtf((nx nx + ny ny) + nz nz);
+ *      d = -((nx x0 + ny y0) + nz z0).
+ *   4. countWithinDistance, every hypothesis against every filtered point in one pass:
+ *      inlier = (double)fabsf(((a x + b y) + c z) + d) < distance_threshold.
+ *   5. RandomSampleConsensus::computeModel replayed over hypotheses 0, 1, ...:  while (iterations < k && skipped < 10 * max_iterations):
+ *      a bad sample: ++skipped; else: strictly more inliers than the best so far replaces it and k = log(1 - probability) /
+ *      log(p), p = 1 - (w w) w clamped to [eps, 1 - eps], w = n_best * (1.0 / n_filtered); ++iterations; stop when iterations >
+ *      max_iterations.  table_exhausted = 1 when the K hypotheses ran out before that loop stopped (supply more words).
+ *   6. F:192-213: no model or n_inliers < floor_pts_thresh: no floor;  |(a r0 + b r1) + c r2| < cos(floor_normal_thresh * M_PI / 180.0)
+ *      with r = tilt^-1 e_z = (-s, 0, c): no floor;  c < 0: the four coefficients times -1.
+ *   7. F:100-134, the callback's memory, kept on the device: a detected floor becomes prev_coeffs and is published; without one the
+ *      published coefficients are prev_coeffs after a first detection, (0, 0, 1, 0) before.  Under-floor removal keeps an input point iff
+ *      ((a x + b y) + c z) + (float)((double)d + floor_tolerance) >= 0 with prev_coeffs, initially (0, 0, 0, (float)(sensor_height -
+ *      height_clip_range)).
+ * The call waits once for the result record; with use_normal_filtering it waits once more before that, for n_clipped (the search is
+ * sized on the host, like apdgicp_scan_filter_run's).  Not part of this object: the ROS plumbing, the marker, optimizeModelCoefficients
+ * (the nodelet never calls it). */
+typedef struct {
+  double tilt_deg;              /* F:63 ; default 0 */
+  double sensor_height;         /* F:64 ; default 2 */
+  double height_clip_range;     /* F:65 ; default 1 ; > 0 */
+  double floor_normal_thresh;   /* F:67 ; default 10 [deg] ; > 0 */
+  double normal_filter_thresh;  /* F:69 ; default 20 [deg] ; > 0 */
+  double floor_tolerance;       /* F:70 ; default 0.1 */
+  double distance_threshold;    /* F:185 ; default 0.06 ; > 0 */
+  double probability;           /* pcl::SampleConsensus::probability_ ; default 0.99 ; inside (0, 1) */
+  int32_t floor_pts_thresh;     /* F:66 ; default 50 ; >= 0 */
+  int32_t use_normal_filtering; /* F:68 ; default 1 */
+  int32_t max_iterations;       /* pcl::SampleConsensus::max_iterations_ ; default 1000 ; >= 1 */
+  int32_t normal_k;             /* F:288 ; default 10 ; 3 .. 64, above 32: APDGICP_ERR_UNSUPPORTED */
+  int32_t n_hypotheses;         /* K ; default 64 ; 1 .. 1024 */
+  int32_t reserved[3];          /* 0 */
+} apdgicp_floor_params;
+typedef enum { APDGICP_FLOOR_OK = 0, APDGICP_FLOOR_FEW_POINTS = 1, APDGICP_FLOOR_NO_MODEL = 2, APDGICP_FLOOR_FEW_INLIERS = 3, APDGICP_FLOOR_NOT_HORIZONTAL = 4 } apdgicp_floor_reject;
+typedef struct {
+  float coeffs[4];              /* what floor_pub publishes (F:100-130) */
+  float raw_coeffs[4];          /* the winning model as RANSAC left it, before the upward flip; zeros without a model */
+  int32_t detected;             /* detect() returned coefficients */
+  int32_t ground_initialized;   /* F:110, after this scan */
+  int32_t reject_reason;        /* apdgicp_floor_reject */
+  int32_t n_input;
+  int32_t n_clipped;            /* behind the height clip (F:162-163) */
+  int32_t n_filtered;           /* behind normal_filtering (F:165-169): RANSAC's cloud */
+  int32_t n_inliers;            /* inliers of the winning model (0 without one); the inlier LIST exists for a detected floor only */
+  int32_t n_under_floor;        /* points of the under-floor-filtered cloud (F:132-134) */
+  int32_t iterations;           /* iterations_ of computeModel */
+  int32_t skipped;              /* skipped_count of computeModel */
+  int32_t winner;               /* index of the winning hypothesis, -1: none */
+  int32_t table_exhausted;      /* the hypotheses ran out before computeModel's loop would have stopped */
+  int32_t K;                    /* hypotheses of this run */
+  int32_t reserved[3];
+} apdgicp_floor_result;
+typedef struct apdgicp_floor apdgicp_floor;
+void apdgicp_floor_default_params(apdgicp_floor_params* p);   /* initialize_params (F:62-70), F:185, pcl::SampleConsensus's defaults */
+/* FloorDetectionNodelet::onInit (F:36-56).  `stream` may be NULL (the object creates its own).  Parameter errors need no device; without a
+ * device: APDGICP_ERR_UNSUPPORTED */
+int apdgicp_floor_create(const apdgicp_floor_params* p, int device, void* stream, apdgicp_floor** out);
+int apdgicp_floor_destroy(apdgicp_floor* f);
+/* initialize_params (F:62-70) again; the callback's memory (prev_coeffs, ground_intialized) is kept: apdgicp_floor_reset restores it */
+int apdgicp_floor_set_params(apdgicp_floor* f, const apdgicp_floor_params* p);
+int apdgicp_floor_reset(apdgicp_floor* f);                    /* F:75-80 */
+/* cloud_callback (F:88-137) of one scan: `xyz` is the address of the first x, points `stride_bytes` apart, the intensity float at
+ * `intensity_offset_bytes` inside a point (< 0: none, 0 is carried), on_device as everywhere.  `words`: HOST memory, n_words >= 3 * K
+ * uint32 (fewer: APDGICP_ERR_INVALID_ARG).  n = 0: the callback returns before anything (F:92-94): status 0, a zero record, no change. */
+int apdgicp_floor_run(apdgicp_floor* f, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device,
+                      const uint32_t* words, int64_t n_words, apdgicp_floor_result* result);
+/* floor_points (F:215-222) of the last run in device memory, valid until the next run: n points of {x, y, z, intensity}, 16 bytes apart,
+ * in input order, beside them each point's index in the input scan; n = 0 unless a floor was detected.  Any pointer but f may be NULL. */
+int apdgicp_floor_inliers(apdgicp_floor* f, const float** device_xyzi, const int32_t** device_index, int64_t* n);
+/* /underfloor_filtered_points (F:132-137) of the last run in device memory, like apdgicp_floor_inliers: what
+ * apdgicp_scan_filter_run(..., on_device = 1) and apdgicp_set_source accept, without a host round trip */
+int apdgicp_floor_under_floor_filtered(apdgicp_floor* f, const float** device_xyzi, const int32_t** device_index, int64_t* n);
+/* copies one cloud of the last run to HOST memory: which = 0 the height-clipped cloud (tilted frame, F:162-163), 1 the filtered cloud
+ * RANSAC ran on (F:169, floor_filtered_points), 2 the inliers, 3 the under-floor-filtered cloud; xyzi [4 * capacity], index [capacity]
+ * (into the input scan); any destination may be NULL; a capacity below the cloud's size: APDGICP_ERR_INVALID_ARG */
+int apdgicp_floor_copy(apdgicp_floor* f, int which, float* xyzi, int32_t* index, int64_t capacity);
+/* every hypothesis of the last run (computeModelCoefficients / countWithinDistance): coeffs [4 * capacity] floats, bad [capacity] 0 / 1,
+ * n_in [capacity]; host memory, any may be NULL; all zero when RANSAC did not run (F:177) */
+int apdgicp_floor_hypotheses(apdgicp_floor* f, float* coeffs, uint8_t* bad, int32_t* n_in, int64_t capacity);
+/* intermediate results of the last run, host memory, any pointer may be NULL (for tests): clip_mask [n] 0 / 1 per input point (F:162-163),
+ * normal_stat [n_clipped] floats (step 2; untouched unless the search ran), samples [3 * K] row indices of the filtered cloud (untouched
+ * when RANSAC did not run).  A destination that is too small: APDGICP_ERR_INVALID_ARG, nothing is written. */
+int apdgicp_floor_debug(apdgicp_floor* f, uint8_t* clip_mask, int64_t mask_capacity, float* normal_stat, int64_t stat_capacity, int32_t* samples, int64_t samples_capacity);
 
 #ifdef __cplusplus
 }

@@ -1852,7 +1852,9 @@ __device__ __forceinline__ unsigned long long group_or_u64(unsigned long long v)
 //                    in fp64: pcl::StatisticalOutlierRemoval's mean distance to the mean_k = k - 1 nearest neighbours;
 //   KNN_EPI_KTH      stat_out[original index] = d2[k - 1]: what pcl::RadiusOutlierRemoval's dense branch compares with the squared radius.
 // The rank-ordered keys of the merge carry the fp32 squared distance in their high word, so both come out of the rounds themselves.
-constexpr int KNN_EPI_COV = 0, KNN_EPI_MEANDIST = 1, KNN_EPI_KTH = 2;
+//   KNN_EPI_NORMALZ  stat_out[original index] = (float)(|u_z| / |u|), u = the eigenvector of the smallest eigenvalue (sym3_eig) of the
+//                    unregularised covariance KNN_EPI_COV forms: the verticality of the point's surface normal (apd_floor.hpp).
+constexpr int KNN_EPI_COV = 0, KNN_EPI_MEANDIST = 1, KNN_EPI_KTH = 2, KNN_EPI_NORMALZ = 3;
 template <int L, int EPI = KNN_EPI_COV>
 __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned bx, int lane, unsigned long long* knn_smem, int k, int reg, int* err_flag,
                                                   unsigned long long* stats, int raw /* 1: store the population covariance, k_regularize_covs follows */,
@@ -2287,7 +2289,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
             atomicExch(err_flag, 2);
             bk = (unsigned long long)(unsigned)i;  // keeps the gathers in range
           }
-          if constexpr (EPI == KNN_EPI_COV) {
+          if constexpr (EPI == KNN_EPI_COV || EPI == KNN_EPI_NORMALZ) {
             if (sub == u) mysel[t] = (int)(unsigned)bk;
           } else if constexpr (EPI == KNN_EPI_MEANDIST) {  // (every lane of the query adds the same numbers in the same order)
             if (t * L + u >= 1) stat_sum += (double)sqrtf(__uint_as_float((unsigned)(bk >> 32)));
@@ -2305,7 +2307,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   }
 #endif  // APD_ABL_KNN_SKIP_C
 #ifndef APD_ABL_KNN_SKIP_C
-  if constexpr (EPI != KNN_EPI_COV) {
+  if constexpr (EPI == KNN_EPI_MEANDIST || EPI == KNN_EPI_KTH) {
     const float v = EPI == KNN_EPI_MEANDIST ? (float)(stat_sum / (double)(k - 1)) : stat_last;
     if (sub == 0) GW(stat_out)[G(c.perm)[i]] = v;
     return;
@@ -2342,6 +2344,12 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   Sym3 pc;
   pc.xx = sxx * ik - mx * mx, pc.xy = sxy * ik - mx * my, pc.xz = sxz * ik - mx * mz;
   pc.yy = syy * ik - my * my, pc.yz = syz * ik - my * mz, pc.zz = szz * ik - mz * mz;
+  if constexpr (EPI == KNN_EPI_NORMALZ) {
+    double w[3], u[9];
+    sym3_eig(pc, w, u);  // eigenvalues descending: column 2 belongs to the smallest
+    GW(stat_out)[G(c.perm)[i]] = (float)(fabs(u[8]) / sqrt((u[2] * u[2] + u[5] * u[5]) + u[8] * u[8]));
+    return;
+  }
   // Throughput launches (L lanes per query, so only one lane in L would work here -- and the Jacobi sweeps are a quarter of
   // this kernel's fp64-weighted instructions) leave the regularisation to k_regularize_covs, one lane per point.
   Sym3 out = pc;

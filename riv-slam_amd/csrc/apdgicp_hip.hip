@@ -10,6 +10,7 @@
 #include "apd_voxel.hpp"
 #include "apd_filter.hpp"
 #include "apd_ego.hpp"
+#include "apd_floor.hpp"
 
 using namespace apd;
 
@@ -83,6 +84,32 @@ struct apdgicp_ego_velocity {
   }
   ~apdgicp_ego_velocity() {
     if (stream) (void)hipStreamSynchronize(stream);
+    if (h_rec) (void)hipHostFree(h_rec);
+    for (DevBuf* b : bufs()) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_floor {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  apdgicp_floor_params prm;
+  Engine* eng = nullptr;  // the normal filter: packs, sorts and boxes the clipped cloud like a registration cloud (created when first needed)
+  DevBuf stage, tilted, mask, clip, clip_src, stat, filt, filt_src, bsum, words, coef, bad, n_in, samples, rec, state;
+  DevBuf in_xyzi, in_src, in_row, under_xyzi, under_src;
+  char* h_rec = nullptr;  // pinned mirror of rec + the engine's error flag
+  int64_t n_last = 0;
+  int K_last = 0;
+  bool ran = false, stat_valid = false;
+  FloorRecord* record() { return (FloorRecord*)h_rec; }
+  std::vector<DevBuf*> bufs() {
+    return {&stage, &tilted, &mask, &clip, &clip_src, &stat, &filt, &filt_src, &bsum, &words, &coef, &bad, &n_in, &samples, &rec, &state,
+            &in_xyzi, &in_src, &in_row, &under_xyzi, &under_src};
+  }
+  ~apdgicp_floor() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    delete eng;
     if (h_rec) (void)hipHostFree(h_rec);
     for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -1797,6 +1824,291 @@ int apdgicp_ego_velocity_debug(apdgicp_ego_velocity* e, uint8_t* valid, int64_t 
     if (samples && e->h_rec->mode == EGO_MODE_RANSAC)
       APD_HIP(hipMemcpyAsync(samples, e->samples.p, (size_t)e->K_last * e->S_last * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     APD_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+  });
+}
+
+// ------------------------------------------------------------------ floor detection and under-floor removal (apd_floor.hpp)
+static_assert(sizeof(apdgicp_floor_result) == 96 && sizeof(FloorRecord) == sizeof(apdgicp_floor_result) && offsetof(FloorRecord, n_inlier_list) == offsetof(apdgicp_floor_result, reserved),
+              "FloorRecord is the result (n_inlier_list in its first reserved word)");
+static_assert(sizeof(apdgicp_floor_params) == 96, "apdgicp_floor_params layout");
+
+void apdgicp_floor_default_params(apdgicp_floor_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->tilt_deg = 0.0, p->sensor_height = 2.0, p->height_clip_range = 1.0, p->floor_pts_thresh = 50;                         // F:63-66
+  p->floor_normal_thresh = 10.0, p->use_normal_filtering = 1, p->normal_filter_thresh = 20.0, p->floor_tolerance = 0.1;  // F:67-70
+  p->distance_threshold = 0.06;                                                                                          // F:185
+  p->probability = 0.99, p->max_iterations = 1000;                                                                       // pcl::SampleConsensus
+  p->normal_k = 10;                                                                                                      // F:288
+  p->n_hypotheses = 64;
+}
+
+static int floor_check_params(const apdgicp_floor_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
+  if (p->normal_k < 3 || p->normal_k > 64) return fail(APDGICP_ERR_INVALID_ARG, "normal_k must be 3 .. 64");
+  if (p->n_hypotheses < 1 || p->n_hypotheses > FLOOR_MAX_K) return fail(APDGICP_ERR_INVALID_ARG, "n_hypotheses must be 1 .. 1024");
+  if (!(p->distance_threshold > 0.0) || !(p->floor_normal_thresh > 0.0) || !(p->normal_filter_thresh > 0.0) || !(p->height_clip_range > 0.0))
+    return fail(APDGICP_ERR_INVALID_ARG, "distance_threshold, floor_normal_thresh, normal_filter_thresh and height_clip_range must be positive");
+  if (!(p->probability > 0.0 && p->probability < 1.0)) return fail(APDGICP_ERR_INVALID_ARG, "probability must lie inside (0, 1)");
+  if (p->max_iterations < 1 || p->floor_pts_thresh < 0) return fail(APDGICP_ERR_INVALID_ARG, "max_iterations must be >= 1 and floor_pts_thresh >= 0");
+  if (!std::isfinite(p->tilt_deg) || !std::isfinite(p->sensor_height) || !std::isfinite(p->floor_tolerance)) return fail(APDGICP_ERR_INVALID_ARG, "a parameter is not finite");
+  if (p->use_normal_filtering && p->normal_k > KNN_NC) return fail(APDGICP_ERR_UNSUPPORTED, "normal_k above 32");
+  return 0;
+}
+
+static float floor_initial_d(const apdgicp_floor_params& P) { return (float)(P.sensor_height - P.height_clip_range); }  // F:80
+
+int apdgicp_floor_create(const apdgicp_floor_params* p, int device, void* stream, apdgicp_floor** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_floor_params dflt;
+    apdgicp_floor_default_params(&dflt);
+    if (!p) p = &dflt;
+    APD_TRY(floor_check_params(p));
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(APDGICP_ERR_UNSUPPORTED, "no HIP device: floor detection has no CPU path");
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_floor> f(new apdgicp_floor);
+    f->device = device, f->prm = *p;
+    if (stream) {
+      f->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+      f->own_stream = true;
+    }
+    APD_HIP(hipHostMalloc((void**)&f->h_rec, sizeof(FloorRecord) + 16, hipHostMallocDefault));
+    memset(f->h_rec, 0, sizeof(FloorRecord) + 16);
+    APD_TRY(f->rec.ensure(sizeof(FloorRecord)));
+    APD_TRY(f->state.ensure(sizeof(FloorState)));
+    APD_TRY(f->coef.ensure((size_t)FLOOR_MAX_K * sizeof(float4)));
+    APD_TRY(f->bad.ensure((size_t)FLOOR_MAX_K));
+    APD_TRY(f->n_in.ensure((size_t)FLOOR_MAX_K * sizeof(int)));
+    APD_TRY(f->samples.ensure((size_t)FLOOR_MAX_K * 3 * sizeof(int)));
+    APD_TRY(f->words.ensure((size_t)FLOOR_MAX_K * 3 * sizeof(unsigned)));
+    hipLaunchKernelGGL(k_floor_reset, dim3(1), dim3(64), 0, f->stream, f->state.as<FloorState>(), floor_initial_d(f->prm));
+    APD_HIP(hipGetLastError());
+    *out = f.release();
+    return 0;
+  });
+}
+
+int apdgicp_floor_destroy(apdgicp_floor* f) {
+  return guarded([&]() -> int {
+    if (f) (void)hipSetDevice(f->device);
+    delete f;
+    return 0;
+  });
+}
+
+int apdgicp_floor_set_params(apdgicp_floor* f, const apdgicp_floor_params* p) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(floor_check_params(p));
+    f->prm = *p;
+    return 0;
+  });
+}
+
+int apdgicp_floor_reset(apdgicp_floor* f) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(f->device));
+    hipLaunchKernelGGL(k_floor_reset, dim3(1), dim3(64), 0, f->stream, f->state.as<FloorState>(), floor_initial_d(f->prm));
+    APD_HIP(hipGetLastError());
+    return 0;
+  });
+}
+
+int apdgicp_floor_run(apdgicp_floor* f, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device, const uint32_t* words,
+                      int64_t n_words, apdgicp_floor_result* result) {
+  return guarded([&]() -> int {
+    if (!f || !result) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    memset(result, 0, sizeof(*result));
+    result->winner = -1;
+    f->ran = false, f->stat_valid = false, f->n_last = 0;
+    memset(f->h_rec, 0, sizeof(FloorRecord) + 16);
+    if (n < 0 || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity offset outside the point");
+    if (n > (1ll << 24)) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    const apdgicp_floor_params& P = f->prm;
+    const int K = P.n_hypotheses;
+    if (!words || n_words < (int64_t)K * 3) return fail(APDGICP_ERR_INVALID_ARG, "fewer random words than 3 x n_hypotheses");
+    result->K = K;
+    f->K_last = K;
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    const int ni = (int)n, nb = (ni + FLOOR_BLK - 1) / FLOOR_BLK;
+    const float* d_in = xyz;
+    if (!on_device) {
+      // (no wait: the copy is ordered behind the previous run's kernels by the stream; a buffer that grows is freed by hipFree, which waits)
+      APD_TRY(f->stage.ensure((size_t)n * stride_bytes));
+      const size_t used = (size_t)std::max<int64_t>(12, intensity_offset_bytes >= 0 ? intensity_offset_bytes + 4 : 12);
+      APD_HIP(hipMemcpyAsync(f->stage.p, xyz, (size_t)(n - 1) * stride_bytes + used, hipMemcpyHostToDevice, f->stream));
+      d_in = f->stage.as<float>();
+    }
+    for (DevBuf* b : {&f->tilted, &f->clip, &f->filt, &f->in_xyzi, &f->under_xyzi}) APD_TRY(b->ensure((size_t)n * 16));
+    for (DevBuf* b : {&f->clip_src, &f->stat, &f->filt_src, &f->in_src, &f->in_row, &f->under_src}) APD_TRY(b->ensure((size_t)n * 4));
+    APD_TRY(f->mask.ensure((size_t)n));
+    APD_TRY(f->bsum.ensure((size_t)nb * 4 * sizeof(int)));
+    FloorParams D;
+    memset(&D, 0, sizeof(D));
+    {
+      const float angle = (float)(P.tilt_deg * M_PI / 180.0f);  // F:157
+      const float c = (float)std::cos((double)angle), s = (float)std::sin((double)angle);
+      const float R[9] = {c, 0.f, s, 0.f, (1.f - c) + c, 0.f, -s, 0.f, c};
+      for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 3; q++) D.R[3 * r + q] = R[3 * r + q], D.Ri[3 * q + r] = R[3 * r + q];
+      D.ref[0] = D.Ri[2], D.ref[1] = D.Ri[5], D.ref[2] = D.Ri[8];  // tilt^-1 * e_z: the third column of the inverse
+    }
+    D.d_hi = (float)(P.sensor_height + P.height_clip_range), D.d_lo = (float)(P.sensor_height - P.height_clip_range);
+    D.cos_nf = std::cos(P.normal_filter_thresh * M_PI / 180.0), D.cos_fn = std::cos(P.floor_normal_thresh * M_PI / 180.0);
+    D.dist_thr = P.distance_threshold, D.log_prob = std::log(1.0 - P.probability), D.floor_tol = P.floor_tolerance;
+    D.pts_thresh = P.floor_pts_thresh, D.max_iter = P.max_iterations, D.K = K, D.nf_mode = FLOOR_NF_OFF;
+    FloorRecord* rec = f->rec.as<FloorRecord>();
+    FloorState* st = f->state.as<FloorState>();
+    int* bsum = f->bsum.as<int>();
+    const int stride = (int)(stride_bytes / 4), ioff = intensity_offset_bytes >= 0 ? (int)(intensity_offset_bytes / 4) : -1;
+    float4 *clip = f->clip.as<float4>(), *filt = f->filt.as<float4>(), *coef = f->coef.as<float4>();
+    unsigned char* bad = f->bad.as<unsigned char>();
+    APD_HIP(hipMemsetAsync(f->rec.p, 0, sizeof(FloorRecord), f->stream));
+    APD_HIP(hipMemcpyAsync(f->words.p, words, (size_t)K * 3 * sizeof(uint32_t), hipMemcpyHostToDevice, f->stream));
+    APD_HIP(hipMemsetAsync(f->n_in.p, 0, (size_t)FLOOR_MAX_K * sizeof(int), f->stream));
+    APD_HIP(hipMemsetAsync(f->coef.p, 0, (size_t)FLOOR_MAX_K * sizeof(float4), f->stream));
+    APD_HIP(hipMemsetAsync(f->bad.p, 0, (size_t)FLOOR_MAX_K, f->stream));
+    // 1. tilt + height clip, in-order compaction (n_clipped -> the record)
+    hipLaunchKernelGGL(k_floor_clip, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, d_in, ni, stride, ioff, D, f->tilted.as<float4>(), f->mask.as<unsigned char>(), bsum);
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, f->stream, bsum, nb, &rec->n_clipped);
+    hipLaunchKernelGGL(k_floor_compact, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, f->tilted.as<float4>(), f->mask.as<unsigned char>(), ni, bsum, clip, f->clip_src.as<int>());
+    APD_HIP(hipGetLastError());
+    // 2. the normal filter: the exact k-NN of the registration over the clipped cloud, whose size the host has to know
+    bool searched = false;
+    if (P.use_normal_filtering) {
+      APD_HIP(hipMemcpyAsync(f->h_rec, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
+      APD_HIP(hipStreamSynchronize(f->stream));
+      const int nc = f->record()->n_clipped;
+      D.nf_mode = nc >= P.normal_k ? FLOOR_NF_STAT : FLOOR_NF_NONE;
+      if (nc >= P.normal_k) {
+        apdgicp_params ep;
+        apdgicp_default_params(&ep);
+        ep.k_correspondences = P.normal_k;
+        if (!f->eng) {
+          std::unique_ptr<Engine> e(new Engine);
+          APD_TRY(e->init(&ep, f->device, f->stream));
+          f->eng = e.release();
+        } else {
+          APD_TRY(f->eng->set_params(&ep));
+        }
+        Engine& E = *f->eng;
+        if (!E.knn_pruned) return fail(APDGICP_ERR_UNSUPPORTED, "floor detection needs the pruned k-NN (APDGICP_KNN_MODE)");
+        APD_TRY(E.set_cloud(0, (const float*)clip, nc, 16, 1, 0));
+        APD_TRY(E.upload_desc());
+        const int id0 = 0;
+        APD_TRY(E.d_ids.upload(&id0, sizeof(int), f->stream));
+        hipLaunchKernelGGL(k_knn_stat_coop<KNN_EPI_NORMALZ>, dim3((unsigned)((nc + 3) / 4), 1u), dim3(64), knn_coop_lds_bytes(4), f->stream, E.d_desc.as<CloudDesc>(),
+                           E.d_ids.as<int>(), P.normal_k, E.d_errflag.as<int>(), E.d_stats.as<unsigned long long>(), f->stat.as<float>());
+        APD_HIP(hipGetLastError());
+        searched = true;
+      }
+    }
+    hipLaunchKernelGGL(k_floor_nf_count, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, f->stat.as<float>(), D, rec, bsum + nb);
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, f->stream, bsum + nb, nb, &rec->n_filtered);
+    hipLaunchKernelGGL(k_floor_nf_scatter, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, clip, f->clip_src.as<int>(), f->stat.as<float>(), D, rec, bsum + nb, filt, f->filt_src.as<int>());
+    // 3. - 5. hypotheses, scores, the sequential loop over the scores, acceptance and the callback's memory
+    hipLaunchKernelGGL(k_floor_hypotheses, dim3((K + 63) / 64), dim3(64), 0, f->stream, filt, f->words.as<unsigned>(), D, rec, coef, bad, f->samples.as<int>());
+    hipLaunchKernelGGL(k_floor_score, dim3((ni + FLOOR_TILE - 1) / FLOOR_TILE, (K + FLOOR_GROUP - 1) / FLOOR_GROUP), dim3(FLOOR_TILE), 0, f->stream, filt, coef, bad, D, rec,
+                       f->n_in.as<int>());
+    hipLaunchKernelGGL(k_floor_replay, dim3(1), dim3(64), 0, f->stream, coef, bad, f->n_in.as<int>(), D, rec, st);
+    // the inlier list and the under-floor clip
+    hipLaunchKernelGGL(k_floor_emit_count, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, filt, d_in, ni, stride, D, rec, st, bsum + 2 * nb, bsum + 3 * nb);
+    hipLaunchKernelGGL(k_floor_emit_scan, dim3(1), dim3(SCAN_BLK), 0, f->stream, bsum + 2 * nb, bsum + 3 * nb, nb, rec);
+    hipLaunchKernelGGL(k_floor_emit_scatter, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, filt, f->filt_src.as<int>(), d_in, ni, stride, ioff, D, rec, st, bsum + 2 * nb,
+                       bsum + 3 * nb, f->in_xyzi.as<float4>(), f->in_src.as<int>(), f->in_row.as<int>(), f->under_xyzi.as<float4>(), f->under_src.as<int>());
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(f->h_rec, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
+    if (searched) APD_HIP(hipMemcpyAsync(f->h_rec + sizeof(FloorRecord), f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));  // the wait for the result record
+    const int flag = *(int*)(f->h_rec + sizeof(FloorRecord));
+    if (flag) {
+      APD_HIP(hipMemsetAsync(f->eng->d_errflag.p, 0, sizeof(int), f->stream));
+      return fail(APDGICP_ERR_INTERNAL, "normal filter k-NN: " + Engine::errflag_text(flag));
+    }
+    FloorRecord* h = f->record();
+    h->n_input = ni, h->K = K;
+    memcpy(result, h, sizeof(*result));
+    result->reserved[0] = 0;
+    f->n_last = n, f->ran = true, f->stat_valid = searched;
+    return 0;
+  });
+}
+
+// which: 0 clipped, 1 filtered, 2 inliers, 3 under floor
+static int floor_cloud(apdgicp_floor* f, int which, const float** xyzi, const int32_t** index, int64_t* n) {
+  if (!f || which < 0 || which > 3) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+  const FloorRecord* h = f->record();
+  const int64_t cnt = !f->ran ? 0 : which == 0 ? h->n_clipped : which == 1 ? h->n_filtered : which == 2 ? h->n_inlier_list : h->n_under_floor;
+  DevBuf& pts = which == 0 ? f->clip : which == 1 ? f->filt : which == 2 ? f->in_xyzi : f->under_xyzi;
+  DevBuf& idx = which == 0 ? f->clip_src : which == 1 ? f->filt_src : which == 2 ? f->in_src : f->under_src;
+  if (xyzi) *xyzi = cnt ? pts.as<float>() : nullptr;
+  if (index) *index = cnt ? idx.as<int32_t>() : nullptr;
+  if (n) *n = cnt;
+  return 0;
+}
+int apdgicp_floor_inliers(apdgicp_floor* f, const float** device_xyzi, const int32_t** device_index, int64_t* n) {
+  return guarded([&]() -> int { return floor_cloud(f, 2, device_xyzi, device_index, n); });
+}
+int apdgicp_floor_under_floor_filtered(apdgicp_floor* f, const float** device_xyzi, const int32_t** device_index, int64_t* n) {
+  return guarded([&]() -> int { return floor_cloud(f, 3, device_xyzi, device_index, n); });
+}
+
+int apdgicp_floor_copy(apdgicp_floor* f, int which, float* xyzi, int32_t* index, int64_t capacity) {
+  return guarded([&]() -> int {
+    int64_t n = 0;
+    const float* p = nullptr;
+    const int32_t* idx = nullptr;
+    APD_TRY(floor_cloud(f, which, &p, &idx, &n));
+    if (capacity < n) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer points than the cloud");
+    if (!n) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    if (xyzi) APD_HIP(hipMemcpyAsync(xyzi, p, (size_t)n * 16, hipMemcpyDeviceToHost, f->stream));
+    if (index) APD_HIP(hipMemcpyAsync(index, idx, (size_t)n * 4, hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+  });
+}
+
+int apdgicp_floor_hypotheses(apdgicp_floor* f, float* coeffs, uint8_t* bad, int32_t* n_in, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int K = f->ran ? f->K_last : 0;
+    if ((coeffs || bad || n_in) && capacity < K) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer entries than hypotheses");
+    if (!K) return 0;
+    APD_HIP(hipSetDevice(f->device));
+    if (coeffs) APD_HIP(hipMemcpyAsync(coeffs, f->coef.p, (size_t)K * 16, hipMemcpyDeviceToHost, f->stream));
+    if (bad) APD_HIP(hipMemcpyAsync(bad, f->bad.p, (size_t)K, hipMemcpyDeviceToHost, f->stream));
+    if (n_in) APD_HIP(hipMemcpyAsync(n_in, f->n_in.p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));
+    return 0;
+  });
+}
+
+int apdgicp_floor_debug(apdgicp_floor* f, uint8_t* clip_mask, int64_t mask_capacity, float* normal_stat, int64_t stat_capacity, int32_t* samples, int64_t samples_capacity) {
+  return guarded([&]() -> int {
+    if (!f) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (!f->ran) return 0;
+    const FloorRecord* h = f->record();
+    const bool ransac = h->n_filtered >= f->prm.floor_pts_thresh && h->n_filtered >= 3;
+    if ((clip_mask && mask_capacity < f->n_last) || (normal_stat && f->stat_valid && stat_capacity < h->n_clipped) || (samples && ransac && samples_capacity < (int64_t)f->K_last * 3))
+      return fail(APDGICP_ERR_INVALID_ARG, "a destination holds fewer entries than the last run produced");
+    APD_HIP(hipSetDevice(f->device));
+    if (clip_mask) APD_HIP(hipMemcpyAsync(clip_mask, f->mask.p, (size_t)f->n_last, hipMemcpyDeviceToHost, f->stream));
+    if (normal_stat && f->stat_valid) APD_HIP(hipMemcpyAsync(normal_stat, f->stat.p, (size_t)h->n_clipped * 4, hipMemcpyDeviceToHost, f->stream));
+    if (samples && ransac) APD_HIP(hipMemcpyAsync(samples, f->samples.p, (size_t)f->K_last * 3 * sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipStreamSynchronize(f->stream));
     return 0;
   });
 }

@@ -101,6 +101,8 @@ SYMBOLS = [
     "apdgicp_ego_velocity_default_params", "apdgicp_ego_velocity_create", "apdgicp_ego_velocity_destroy", "apdgicp_ego_velocity_set_params",
     "apdgicp_ego_velocity_hypothesis_count", "apdgicp_ego_velocity_run", "apdgicp_ego_velocity_inliers", "apdgicp_ego_velocity_outliers",
     "apdgicp_ego_velocity_copy", "apdgicp_ego_velocity_hypotheses", "apdgicp_ego_velocity_debug",
+    "apdgicp_floor_default_params", "apdgicp_floor_create", "apdgicp_floor_destroy", "apdgicp_floor_set_params", "apdgicp_floor_reset", "apdgicp_floor_run",
+    "apdgicp_floor_inliers", "apdgicp_floor_under_floor_filtered", "apdgicp_floor_copy", "apdgicp_floor_hypotheses", "apdgicp_floor_debug",
 ]
 
 _lib = None
@@ -234,6 +236,18 @@ def load_library(path: str | None = None):
     L.apdgicp_ego_velocity_copy.argtypes = [vp, i32, vp, vp, vp, vp, i64]
     L.apdgicp_ego_velocity_hypotheses.argtypes = [vp, vp, vp, i64]
     L.apdgicp_ego_velocity_debug.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp]
+    L.apdgicp_floor_default_params.argtypes = [vp]
+    L.apdgicp_floor_default_params.restype = None
+    L.apdgicp_floor_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.apdgicp_floor_destroy.argtypes = [vp]
+    L.apdgicp_floor_set_params.argtypes = [vp, vp]
+    L.apdgicp_floor_reset.argtypes = [vp]
+    L.apdgicp_floor_run.argtypes = [vp, vp, i64, i64, i64, i32, vp, i64, vp]
+    for f in (L.apdgicp_floor_inliers, L.apdgicp_floor_under_floor_filtered):
+        f.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_floor_copy.argtypes = [vp, i32, vp, vp, i64]
+    L.apdgicp_floor_hypotheses.argtypes = [vp, vp, vp, vp, i64]
+    L.apdgicp_floor_debug.argtypes = [vp, vp, i64, vp, i64, vp, i64]
     if path is None:
         _lib = L
     return L

@@ -232,6 +232,35 @@ def raw_doppler_scan(n: int, seed: int, v_sensor=(2.0, 0.3, -0.1), moving_share:
     return np.ascontiguousarray(np.concatenate([base, doppler[:, None].astype(np.float32)], axis=1))
 
 
+def floor_scan(n: int, seed: int, sensor_height: float = 2.0, tilt_deg: float = 0.0, floor_share: float = 0.5, below_share: float = 0.05,
+               noise: float = 0.02) -> np.ndarray:
+    """A raw scan as FloorDetectionNodelet::cloud_callback receives it (floor_detection_nodelet.cpp:88-90): [n, 4] float32
+    {x, y, z, intensity}, shuffled, deterministic per seed.  In the level frame (the sensor frame turned by R_y(tilt_deg), :156-161)
+    `floor_share` of the points lie on the floor z = -sensor_height (+ gaussian `noise`), `below_share` are ghost returns 0.3 .. 6 m
+    below it, 40 % of the rest lie on four vertical walls that reach from the floor to 3 m above the sensor, the others are clutter
+    spread from 0.2 m above the floor upwards.  The points are handed out in the SENSOR frame: R_y(tilt_deg)^T times the level ones."""
+    rng = np.random.default_rng([seed, 0xF1])
+    n_floor, n_below = int(floor_share * n), int(below_share * n)
+    n_wall = int(0.4 * (n - n_floor - n_below))
+    n_clutter = n - n_floor - n_below - n_wall
+    h = float(sensor_height)
+    floor = np.stack([rng.uniform(2.0, 40.0, n_floor), rng.uniform(-15.0, 15.0, n_floor), -h + noise * rng.normal(size=n_floor)], axis=1)
+    below = np.stack([rng.uniform(2.0, 40.0, n_below), rng.uniform(-15.0, 15.0, n_below), -h - rng.uniform(0.3, 6.0, n_below)], axis=1)
+    side = rng.integers(0, 4, n_wall)
+    along, up = rng.uniform(0.0, 1.0, n_wall), rng.uniform(-h, 3.0, n_wall)
+    thick = noise * rng.normal(size=n_wall)
+    wx = np.where(side == 0, 40.0 + thick, np.where(side == 1, 2.0 + 38.0 * along, np.where(side == 2, 2.0 + 38.0 * along, 25.0 + thick)))
+    wy = np.where(side == 0, -15.0 + 30.0 * along, np.where(side == 1, -15.0 + thick, np.where(side == 2, 15.0 + thick, -6.0 + 12.0 * along)))
+    walls = np.stack([wx, wy, up], axis=1)
+    clutter = np.stack([rng.uniform(2.0, 40.0, n_clutter), rng.uniform(-15.0, 15.0, n_clutter), rng.uniform(-h + 0.2, 4.0, n_clutter)], axis=1)
+    level = np.concatenate([floor, below, walls, clutter], axis=0)
+    a = np.deg2rad(tilt_deg)
+    R = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+    xyz = level @ R   # rows: (R^T p)^T = p^T R
+    out = np.concatenate([xyz, rng.uniform(0.0, 40.0, (n, 1))], axis=1).astype(np.float32)
+    return np.ascontiguousarray(out[rng.permutation(n)])
+
+
 def pose_error(T_ref: np.ndarray, T_est: np.ndarray):
     """(t_err [m], r_err [rad]) of delta = T_ref^-1 * T_est; metric of
     fast_apdgicp/src/test/gicp_test.cpp:73-78."""
