@@ -1,15 +1,17 @@
 """Scan preprocessing on the device (riv-slam_amd/scan_filter.py, csrc/apd_filter.hpp): the range gate, the voxel grid and the
 outlier filters of PreprocessingNodelet::cloud_callback (preprocessing_nodelet.cpp:812-815).
 
-The expected values come from a numpy restatement of include/apdgicp_hip.h's "scan preprocessing" section (PCL as published; PCL is
-not installed here).  Its k-NN distances come from the checker's kd-tree (ref.RefAPDGICP.knn_kdtree_batch, pinned bit for bit to the
-reference tree's nanoflann by tests/test_oracle.py) and, on the CPU, from a chunked numpy brute force in FLANN L2_Simple order.
+The expected values come from tests/scan_filter_np.py, a numpy restatement of include/apdgicp_hip.h's "scan preprocessing" section
+(PCL as published; PCL is not installed here).  Its k-NN distances come from the checker's kd-tree (ref.RefAPDGICP.knn_kdtree_batch,
+pinned bit for bit to the reference tree's nanoflann by tests/test_oracle.py) and, on the CPU, from a chunked numpy brute force in FLANN
+L2_Simple order.
 
 Bars (GPU): gate -- kept indices and output exact; voxel grid -- byte-equal to a one-cloud identity-pose apdgicp_submap_assemble and
 the bars of tests/test_submap.py against the checker; STATISTICAL -- every score bit for bit, mean / stddev / thr within 1e-9 relative
 of the sequential restatement (the device adds the n <= 2^17 doubles in a fixed tree, PCL one after the other), the kept mask
 identical after asserting on the restatement alone that no score lies within 1e-9 thr of thr; RADIUS -- d2[k-1] bit for bit, no value
-equal to r^2, the mask identical.
+equal to r^2, the mask identical.  Those two conditions keep `<=` away from equality on the scene's scans; the line and the lattice of
+"inputs that sit on the threshold" put every statistic exactly on it.
 """
 import importlib
 import os
@@ -19,65 +21,13 @@ import numpy as np
 import pytest
 
 import ref as R
+from scan_filter_np import knn_d2_brute, knn_d2_kdtree, np_radius, np_range_gate, np_statistical
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
 NEW_SYMBOLS = ["apdgicp_scan_filter_default_params", "apdgicp_scan_filter_create", "apdgicp_scan_filter_destroy", "apdgicp_scan_filter_set_params",
                "apdgicp_scan_filter_run", "apdgicp_scan_filter_points", "apdgicp_scan_filter_copy", "apdgicp_scan_filter_stage_counts",
                "apdgicp_scan_filter_scores"]
-
-
-# ------------------------------------------------------------------ the restatement
-def np_range_gate(cloud, near=1.0, far=100.0, z_low=-5.0, z_high=20.0):
-    """preprocessing_nodelet.cpp:881-889: d = fp32 sqrtf((x*x + y*y) + z*z) widened to double; NaN fails every comparison"""
-    x, y, z = (cloud[:, q].astype(F32) for q in range(3))
-    with np.errstate(invalid="ignore", over="ignore"):
-        d = np.sqrt((x * x + y * y) + z * z).astype(np.float64)
-        zz = z.astype(np.float64)
-        return (d > near) & (d < far) & (zz < z_high) & (zz > z_low)
-
-
-def knn_d2_kdtree(xyz, k):
-    o = R.RefAPDGICP(R.default_params())
-    o.setInputTarget(np.ascontiguousarray(xyz[:, :3], dtype=F32))
-    return o.knn_kdtree_batch("target", xyz[:, :3], k)[1]
-
-
-def knn_d2_brute(xyz, k, chunk=256):
-    """the k smallest fp32 squared distances of every point, FLANN L2_Simple: ((dx*dx) + dy*dy) + dz*dz, every step rounded to fp32"""
-    p = np.ascontiguousarray(xyz[:, :3], dtype=F32)
-    out = np.empty((len(p), k), dtype=F32)
-    for a in range(0, len(p), chunk):
-        q = p[a:a + chunk]
-        dx, dy, dz = (q[:, None, c] - p[None, :, c] for c in range(3))
-        d = dx * dx
-        d = d + dy * dy
-        d = d + dz * dz
-        assert d.dtype == F32
-        out[a:a + chunk] = np.sort(np.partition(d, k - 1, axis=1)[:, :k], axis=1)
-    return out
-
-
-def np_statistical(d2, mean_k, stddev_mul):
-    """pcl::StatisticalOutlierRemoval::applyFilterIndices on rank-ordered fp32 squared distances [n, >= mean_k + 1] (rank 0: the point itself)"""
-    acc = np.zeros(len(d2), dtype=np.float64)
-    for r in range(1, mean_k + 1):
-        acc = acc + np.sqrt(d2[:, r].astype(F32)).astype(np.float64)   # std::sqrt(float), double sum in rank order
-    score = (acc / mean_k).astype(F32)
-    n = len(score)
-    s = float(np.cumsum(score.astype(np.float64))[-1])                 # (cumsum adds one after the other, np.sum pairwise)
-    sq = float(np.cumsum((score * score).astype(np.float64))[-1])      # fp32 product, double sum
-    mean = s / n
-    var = (sq - s * s / n) / (n - 1)
-    stddev = float(np.sqrt(var))
-    thr = mean + stddev_mul * stddev
-    return score, mean, stddev, thr, score.astype(np.float64) <= thr
-
-
-def np_radius(d2, min_neighbors, radius):
-    stat = d2[:, min_neighbors].astype(F32)
-    return stat, stat.astype(np.float64) <= radius * radius
-
 
 def bench_scene_with_clutter(scene, n, share=0.05, seed=0):
     """the bench scene (bench.py's pair generator) with `share` of the points replaced by clutter spread over the frustum"""
@@ -131,6 +81,101 @@ def test_the_two_restatements_agree(scene, name):
         sa, ma = np_radius(knn_d2_kdtree(c, mn + 1), mn, radius)
         sb, mb = np_radius(knn_d2_brute(c, mn + 1), mn, radius)
         assert np.array_equal(sa.view(np.uint32), sb.view(np.uint32)) and np.array_equal(ma, mb) and 0 < ma.sum() < len(c)
+
+
+# ---- the outlier filters at a controlled n2: no gate, no voxel grid and a finite input, so the filter sees the n rows it is given
+EDGE_SEED = 6     # chosen on the CPU: no case below has a score within 1e-9 thr of thr or a statistic equal to r^2 (asserted)
+# around: 4 queries per wave of k_knn_stat_coop, 64-lane waves, the 1024-thread compaction blocks, the cloud sort's classes (2048, 16384)
+EDGE_SIZES = ("k", "k+1", 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 16383, 16384, 16385)
+EDGE_MEAN_K = (1, 20, 31)
+EDGE_RADIUS = ((0.8, 2), (2.0, 20))
+_edge_cache = {}
+
+
+def edge_size(size, k):
+    return {"k": k, "k+1": k + 1}.get(size, size)
+
+
+def edge_scan(scene, n):
+    if "scan" not in _edge_cache:
+        c = scene.raw_scan(20000, EDGE_SEED)
+        _edge_cache["scan"] = np.ascontiguousarray(c[np.isfinite(c).all(1)])
+    return _edge_cache["scan"][:n]
+
+
+def edge_d2(scene, n, k):
+    """the restatement's k-NN distances of the first n finite rows: computed once, shared by the CPU and the GPU tests"""
+    if (n, k) not in _edge_cache:
+        d2 = knn_d2_kdtree(edge_scan(scene, n), k)
+        d2.setflags(write=False)
+        _edge_cache[n, k] = d2
+    return _edge_cache[n, k]
+
+
+def statistical_expected(d2, mean_k, mul):
+    score, mean, stddev, thr, keep = np_statistical(d2, mean_k, mul)
+    gap = np.abs(score.astype(np.float64) - thr).min()
+    assert gap > 1e-9 * thr, "the input has a score on the threshold: choose another cloud"   # a condition on the input
+    return score, mean, stddev, thr, keep, gap
+
+
+def radius_expected(d2, mn, radius):
+    stat, keep = np_radius(d2, mn, radius)
+    assert not (stat.astype(np.float64) == radius * radius).any()   # a condition on the input
+    return stat, keep
+
+
+def line_cloud(n):
+    c = np.zeros((n, 4), dtype=F32)
+    c[:, 0] = F32(0.5) * np.arange(n, dtype=F32)
+    c[:, 3] = np.arange(n, dtype=F32)
+    return c
+
+
+def lattice_cloud():
+    """8 x 8 x 8 points 0.5 apart from -2.0 (they straddle the origin), shuffled; every coordinate and every distance is exact in fp32"""
+    g = (F32(-2.0) + F32(0.5) * np.arange(8, dtype=F32)).astype(F32)
+    xyz = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    c = np.concatenate([xyz, np.arange(512, dtype=F32)[:, None]], 1)
+    return np.ascontiguousarray(c[np.random.default_rng(8).permutation(512)], dtype=F32)
+
+
+LINE_SIZES = (2, 3, 64, 65, 1025)
+LATTICE_RADIUS_KEPT = {3: 512, 4: 504, 5: 432, 6: 216}   # corners, then edges, then faces go
+LATTICE_MEAN_K6_KEPT = {0.5: 432, 1.0: 432, 2.0: 504}
+
+
+def test_controlled_sizes_meet_the_input_conditions(scene):
+    assert len(edge_scan(scene, 20000)) >= 16385
+    for size in EDGE_SIZES:
+        for mean_k in EDGE_MEAN_K:
+            n = edge_size(size, mean_k + 1)
+            statistical_expected(edge_d2(scene, n, mean_k + 1), mean_k, 1.0)
+        for radius, mn in EDGE_RADIUS:
+            n = edge_size(size, mn + 1)
+            radius_expected(edge_d2(scene, n, mn + 1), mn, radius)
+    few = scene.raw_scan(2048, 9)
+    few = np.ascontiguousarray(few[np.isfinite(few).all(1)][:15])
+    statistical_expected(knn_d2_kdtree(few, 15), 14, 1.0)   # test_edge_cases' n2 = k = 15
+
+
+@pytest.mark.parametrize("knn", (knn_d2_kdtree, knn_d2_brute))
+def test_threshold_inputs_sit_on_the_threshold(knn):
+    """the numbers the GPU tests assert as literals, from the restatement: every statistic EQUAL to the threshold, so `<=` keeps all"""
+    for n in LINE_SIZES:
+        for mul in (0.5, 1.0, 2.0):
+            score, mean, stddev, thr, keep = np_statistical(knn(line_cloud(n), 2), 1, mul)
+            assert (score == F32(0.5)).all() and (mean, stddev, thr) == (0.5, 0.0, 0.5) and keep.all()
+    c = lattice_cloud()
+    assert c[:, :3].min() == -2.0 and c[:, :3].max() == 1.5 and len(np.unique(c[:, :3], axis=0)) == 512
+    for mn, kept in LATTICE_RADIUS_KEPT.items():
+        stat, keep = np_radius(knn(c, mn + 1), mn, 0.5)
+        assert keep.sum() == kept and np.array_equal(keep, stat == F32(0.25)) and set(np.unique(stat)) <= {F32(0.25), F32(0.5)}
+    score, mean, stddev, thr, keep = np_statistical(knn(c, 4), 3, 1.0)
+    assert (score == F32(0.5)).all() and (mean, stddev, thr) == (0.5, 0.0, 0.5) and keep.all()
+    for mul, kept in LATTICE_MEAN_K6_KEPT.items():
+        score, mean, stddev, thr, keep, gap = statistical_expected(knn(c, 7), 6, mul)
+        assert len(np.unique(score)) == 4 and keep.sum() == kept
 
 
 @pytest.fixture(scope="module")
@@ -313,6 +358,154 @@ def test_radius_outlier_removal(mods, scene, name):
         assert np.array_equal(sc["kept"], keep) and n == keep.sum() and np.array_equal(bits(f.to_numpy()), bits(s2[keep]))
 
 
+def assert_statistical(f, c, s2, d2, mean_k, mul, tag):
+    """test_statistical_outlier_removal's bars for one run of `f` on `c`; s2: the cloud the outlier filter sees, d2: its k-NN distances"""
+    score, mean, stddev, thr, keep, gap = statistical_expected(d2, mean_k, mul)
+    f.set_params(outlier_method="STATISTICAL", mean_k=mean_k, stddev_mul=mul)
+    n = f.run(c)
+    sc = f.scores()
+    rel = max(abs(sc["mean"] - mean) / mean, abs(sc["stddev"] - stddev) / stddev, abs(sc["thr"] - thr) / thr)
+    print(f"{tag} mean_k {mean_k} mul {mul}: n2 {len(s2)} kept {keep.sum()} thr {thr:.6f} nearest score {gap / thr:.2e} thr away, sums rel diff {rel:.2e}, "
+          f"score bits equal {np.array_equal(bits(sc['stat']), bits(score))}")
+    assert np.array_equal(bits(sc["stat"]), bits(score))
+    assert rel <= 1e-9
+    assert np.array_equal(sc["kept"], keep) and n == keep.sum()
+    assert np.array_equal(bits(f.to_numpy()), bits(s2[keep]))
+    assert f.stage_counts()[2:] == (len(s2), n)
+    return rel
+
+
+def assert_radius(f, c, s2, d2, mn, radius, tag):
+    """test_radius_outlier_removal's bars for one run of `f` on `c`"""
+    stat, keep = radius_expected(d2, mn, radius)
+    f.set_params(outlier_method="RADIUS", radius=radius, min_neighbors=mn)
+    n = f.run(c)
+    sc = f.scores()
+    print(f"{tag} radius {radius} min_neighbors {mn}: n2 {len(s2)} kept {keep.sum()}, stat bits equal {np.array_equal(bits(sc['stat']), bits(stat))}")
+    assert np.array_equal(bits(sc["stat"]), bits(stat)) and sc["thr"] == radius * radius
+    assert np.array_equal(sc["kept"], keep) and n == keep.sum() and np.array_equal(bits(f.to_numpy()), bits(s2[keep]))
+    assert f.stage_counts()[2:] == (len(s2), n)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", EDGE_SIZES, ids=str)
+def test_statistical_at_controlled_sizes(mods, scene, size):
+    """n2 = the input size (leaf None, no gate, finite rows); the bars and their derivation are test_statistical_outlier_removal's"""
+    reg, sf, _ = mods
+    f = sf.ScanFilter(leaf=None, use_distance_filter=0)
+    for mean_k in EDGE_MEAN_K:
+        n = edge_size(size, mean_k + 1)
+        if n < mean_k + 1:
+            continue
+        c = edge_scan(scene, n)
+        assert_statistical(f, c, c, edge_d2(scene, n, mean_k + 1), mean_k, 1.0, f"n2 {n}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", EDGE_SIZES, ids=str)
+def test_radius_at_controlled_sizes(mods, scene, size):
+    reg, sf, _ = mods
+    f = sf.ScanFilter(leaf=None, use_distance_filter=0, outlier_method="RADIUS")
+    for radius, mn in EDGE_RADIUS:
+        n = edge_size(size, mn + 1)
+        if n < mn + 1:
+            continue
+        c = edge_scan(scene, n)
+        assert_radius(f, c, c, edge_d2(scene, n, mn + 1), mn, radius, f"n2 {n}")
+
+
+def knn_mode(monkeypatch, mode):
+    if mode == "brute":
+        monkeypatch.setenv("APDGICP_KNN_MODE", "brute")   # (read when the filter's engine is created: a new ScanFilter per mode)
+    else:
+        monkeypatch.delenv("APDGICP_KNN_MODE", raising=False)
+
+
+def assert_all_on_the_threshold(f, c, thr):
+    """every statistic EQUALS the threshold, so `<=` keeps every point and `<` none; == throughout: the sums are exact in any order"""
+    n = f.run(c)
+    sc = f.scores()
+    assert (sc["stat"] == F32(thr)).all() and sc["thr"] == thr
+    assert sc["kept"].all() and n == len(c) and np.array_equal(bits(f.to_numpy()), bits(c))
+    assert f.stage_counts() == (len(c), len(c), len(c), len(c))
+    return sc
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ("pruned", "brute"))
+def test_statistical_keeps_scores_equal_to_the_threshold(mods, monkeypatch, mode):
+    """Points 0.5 apart on a line, mean_k = 1: every score is exactly 0.5, their sum 0.5 n and the sum of squares 0.25 n in any order, so
+    mean = 0.5, stddev = 0 and thr = 0.5 = every score, whatever stddev_mul.  The lattice with mean_k = 3 is the same in three dimensions."""
+    reg, sf, _ = mods
+    knn_mode(monkeypatch, mode)
+    f = sf.ScanFilter(leaf=None, use_distance_filter=0, mean_k=1)
+    for n in LINE_SIZES:
+        for mul in (0.5, 1.0, 2.0):
+            f.set_params(stddev_mul=mul)
+            sc = assert_all_on_the_threshold(f, line_cloud(n), 0.5)
+            assert (sc["mean"], sc["stddev"], sc["thr"]) == (0.5, 0.0, 0.5)
+    c = lattice_cloud()
+    f.set_params(mean_k=3, stddev_mul=1.0)
+    sc = assert_all_on_the_threshold(f, c, 0.5)
+    assert (sc["mean"], sc["stddev"], sc["thr"]) == (0.5, 0.0, 0.5)
+    d2 = knn_d2_kdtree(c, 7)
+    for mul, kept in LATTICE_MEAN_K6_KEPT.items():   # four distinct scores (corner, edge, face, inside), none on the threshold
+        assert_statistical(f, c, c, d2, 6, mul, f"lattice {mode}")
+        assert f.n == kept
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ("pruned", "brute"))
+def test_radius_keeps_distances_equal_to_the_radius(mods, monkeypatch, mode):
+    """The lattice with radius = 0.5 = its spacing: d2 to a face neighbour is 0.25 = r^2 exactly, to the next one 0.5.  A corner has 3
+    face neighbours, an edge point 4, a face point 5, an inner point 6."""
+    reg, sf, _ = mods
+    knn_mode(monkeypatch, mode)
+    c = lattice_cloud()
+    f = sf.ScanFilter(leaf=None, use_distance_filter=0, outlier_method="RADIUS", radius=0.5, min_neighbors=3)
+    assert_all_on_the_threshold(f, c, 0.25)
+    for mn, kept in LATTICE_RADIUS_KEPT.items():
+        stat, keep = np_radius(knn_d2_kdtree(c, mn + 1), mn, 0.5)
+        f.set_params(min_neighbors=mn)
+        n = f.run(c)
+        sc = f.scores()
+        assert np.array_equal(bits(sc["stat"]), bits(stat)) and sc["thr"] == 0.25
+        assert n == kept == keep.sum() and np.array_equal(sc["kept"], keep) and np.array_equal(bits(f.to_numpy()), bits(c[keep]))
+        assert np.array_equal(sc["kept"], sc["stat"] == F32(0.25))   # kept: exactly the points whose statistic equals r^2
+
+
+def cloud_past_1024_blocks():
+    """1024 * 1024 + 1025 rows, ranges 0 .. 200 m so that the default gate keeps about half, 300 rows with a NaN or an infinity on both
+    sides of row 1 048 576 (the first row of compaction block 1024)"""
+    n, edge = 1024 * 1024 + 1025, 1024 * 1024
+    rng = np.random.default_rng(1_048_577)
+    r, az = rng.uniform(0.0, 200.0, n), rng.uniform(-np.pi, np.pi, n)
+    c = np.stack([r * np.cos(az), r * np.sin(az), rng.uniform(-4.0, 15.0, n), rng.uniform(0.0, 40.0, n)], 1).astype(F32)
+    bad = np.concatenate([edge - 1 - rng.choice(5000, 150, replace=False), edge + rng.choice(1025, 150, replace=False)])
+    c[bad, rng.integers(0, 3, 300)] = rng.choice(np.array([np.nan, np.inf, -np.inf], dtype=F32), 300)
+    return np.ascontiguousarray(c), edge
+
+
+@pytest.mark.gpu
+def test_compaction_past_1024_blocks(mods):
+    """scan_filter_compact's per-block counts are scanned by k_scan_bsum in passes of 1024 blocks with a running total carried from one
+    pass into the next: 1026 blocks of 1024 rows take the second pass.  Points are kept on both sides of row 1 048 576 and the first 1024
+    blocks keep some rows but not all, so a wrong carry moves the rows of blocks 1024 and 1025 (and the total).  No k-NN at this size."""
+    reg, sf, _ = mods
+    c, edge = cloud_past_1024_blocks()
+    fin = np.isfinite(c[:, :3]).all(1)
+    f = sf.ScanFilter(leaf=None, outlier_method="NONE")
+    for gate in (1, 0):
+        keep = np_range_gate(c) if gate else fin
+        assert 0 < keep[:edge].sum() < edge and 0 < keep[edge:].sum() < len(c) - edge   # conditions on the input
+        f.set_params(use_distance_filter=gate)
+        n = f.run(c)
+        print(f"gate {gate}: kept {n} of {len(c)}, {keep[:edge].sum()} in the first 1024 blocks, {keep[edge:].sum()} behind")
+        assert n == keep.sum() and np.array_equal(bits(f.to_numpy()), bits(c[keep]))
+        assert f.stage_counts() == (len(c), n if gate else len(c), n, n)
+    assert 0.4 * len(c) < np_range_gate(c).sum() < 0.6 * len(c) and (~fin[:edge]).sum() == (~fin[edge:]).sum() == 150
+
+
 @pytest.mark.gpu
 def test_edge_cases(mods, scene):
     import torch
@@ -324,8 +517,7 @@ def test_edge_cases(mods, scene):
     with pytest.raises(reg.ApdgicpError) as e:
         f.run(few)
     assert e.value.code == -4   # APDGICP_ERR_TOO_FEW_POINTS
-    f.set_params(mean_k=14)
-    assert 0 < f.run(few) <= 15
+    assert_statistical(f, few, few, knn_d2_kdtree(few, 15), 14, 1.0, "few")   # n2 = k = 15: every point is a neighbour of every other
     with pytest.raises(reg.ApdgicpError) as e:
         f.set_params(mean_k=32)
     assert e.value.code == -5   # APDGICP_ERR_UNSUPPORTED

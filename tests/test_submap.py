@@ -76,6 +76,203 @@ def centroids_close(a, b, cnt=None):
     return bool((np.abs(a.astype(np.float64) - b) <= tol).all())
 
 
+# ---- voxel grid edges: one cloud, identity pose.  The inputs and what the two CPU restatements say about them
+VOX_TILE = 4096    # csrc/apd_sort.hpp: the key sort pads to powers of two from here; k_vox_heads scans 4096 keys per block
+EDGE_SIZES = tuple(sorted({1, 2, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193, VOX_TILE - 1, VOX_TILE + 1}))
+POPULATIONS = ("own_voxel", "one_voxel", "four_per_voxel")
+_oracle_cache = {}
+
+
+def with_intensity(xyz, seed=0):
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    w = np.random.default_rng([len(xyz), seed]).uniform(1, 40, (len(xyz), 1)).astype(np.float32)
+    return np.ascontiguousarray(np.concatenate([xyz, w], 1))
+
+
+def sized_cloud(n, population):
+    """leaf 0.5.  own_voxel: a 32 x 32 x ... lattice of voxel centres around the origin, filled in voxel order and then shuffled;
+    one_voxel: n points inside one voxel; four_per_voxel: uniform in a cube of n / 4 voxels around the origin"""
+    rng = np.random.default_rng([n, POPULATIONS.index(population)])
+    if population == "own_voxel":
+        lin = np.arange(n)
+        ijk = np.stack([lin % 32 - 16, lin // 32 % 32 - 16, lin // 1024 - 4], 1)
+        c = with_intensity((ijk + 0.5) * 0.5)
+        return c[rng.permutation(n)], c   # (and the expected output: ascending voxel index = the order the lattice was filled in)
+    if population == "one_voxel":
+        return with_intensity(rng.uniform(-0.45, -0.05, (n, 3))), None
+    side = 0.5 * max(n / 4.0, 1.0) ** (1.0 / 3.0)
+    return with_intensity(rng.uniform(-side / 2, side / 2, (n, 3))), None
+
+
+def lattice_faces(leaf, scaled=False):
+    """j * leaf for j in -8 .. 8 on each axis: every point on three voxel faces (leaf 0.5 / 0.25: exactly; 0.1: float32(j * 0.1), where the
+    fp32 product p * inverse_leaf decides the side), and each point's neighbour towards -inf in all three coordinates"""
+    g = (np.arange(-8, 9) * (np.float64(leaf) if scaled else np.float32(leaf))).astype(np.float32)
+    on = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    below = np.nextafter(on, np.float32(-np.inf))
+    return on, below
+
+
+def face_clouds():
+    out = {}
+    for leaf in (0.5, 0.25, 0.1):
+        on, below = lattice_faces(leaf, scaled=leaf == 0.1)
+        rng = np.random.default_rng(int(leaf * 100))
+        both = np.concatenate([on, below])
+        out[f"faces{leaf}"] = (with_intensity(both[rng.permutation(len(both))]), leaf)
+        # -0.0 beside +0.0: the rows on a coordinate plane once more with their zeros negative
+        zero = on[(on == 0).any(1)].copy()
+        zero[zero == 0] = -0.0
+        mixed = np.concatenate([on, zero])
+        out[f"signed_zero{leaf}"] = (with_intensity(mixed[rng.permutation(len(mixed))]), leaf)
+        # a cloud whose minimum is -0.0 on every axis (no +0.0 in it)
+        pos = on[(on >= 0).all(1)].copy()
+        pos[pos == 0] = -0.0
+        assert np.signbit(pos.min(0)).all() and (pos.min(0) == 0).all()
+        out[f"min_negative_zero{leaf}"] = (with_intensity(pos[rng.permutation(len(pos))]), leaf)
+    return out
+
+
+FACE_CLOUDS = tuple(f"{kind}{leaf}" for leaf in (0.5, 0.25, 0.1) for kind in ("faces", "signed_zero", "min_negative_zero"))
+
+
+def limit_cloud(corner):
+    """leaf 1.0: the first two points share voxel 0, `corner` sets the extent, the rest are voxel centres in between"""
+    inner = np.unique(np.random.default_rng(3).integers(1, 1000, (12, 3)), axis=0)
+    return with_intensity(np.concatenate([np.array([[0, 0, 0], [0.25, 0.25, 0.25], corner], dtype=np.float64), inner + 0.5]))
+
+
+def both_restatements(c, leaf, key=None):
+    """the oracle's answer for cloud `c`, after asserting that the numpy restatement gives the same voxel indices and populations"""
+    if key is not None and key in _oracle_cache:
+        return _oracle_cache[key]
+    exp, idx, cnt = R.submap_assemble([c], None, leaf)
+    u, c2, cen = np_voxelgrid(c, leaf)
+    assert np.array_equal(idx, u) and np.array_equal(cnt, c2) and centroids_close(exp, cen, cnt)   # a condition on the inputs
+    for a in (exp, idx, cnt):
+        a.setflags(write=False)
+    if key is not None:
+        _oracle_cache[key] = (exp, idx, cnt)
+    return exp, idx, cnt
+
+
+def voxel_index(rows, c, leaf):
+    """the voxel index of `rows` in the grid of cloud `c`, in PCL's fp32 arithmetic"""
+    inv = np.float32(1) / np.float32(leaf)
+    min_b = np.floor(c[:, :3].min(0) * inv).astype(np.int64)
+    div_b = np.floor(c[:, :3].max(0) * inv).astype(np.int64) - min_b + 1
+    ijk = np.floor(rows[:, :3] * inv).astype(np.int64) - min_b
+    return ijk[:, 0] + ijk[:, 1] * div_b[0] + ijk[:, 2] * div_b[0] * div_b[1]
+
+
+def test_sized_clouds_on_the_cpu():
+    for n in EDGE_SIZES:
+        c, want = sized_cloud(n, "own_voxel")
+        exp, idx, cnt = both_restatements(c, 0.5, (n, "own_voxel"))
+        assert (cnt == 1).all() and np.array_equal(exp.view(np.uint32), want.view(np.uint32))   # the input, reordered by voxel index
+        assert (c[:, :3] < 0).any() and (n < 1023 or (c[:, :2] > 0).any(0).all())   # the lattice straddles zero
+        c, _ = sized_cloud(n, "one_voxel")
+        exp, idx, cnt = both_restatements(c, 0.5, (n, "one_voxel"))
+        assert exp.shape[0] == 1 and cnt[0] == n
+        c, _ = sized_cloud(n, "four_per_voxel")
+        exp, idx, cnt = both_restatements(c, 0.5, (n, "four_per_voxel"))
+        assert n < 64 or (0.15 * n < exp.shape[0] < 0.5 * n and cnt.max() > 4)
+
+
+@pytest.mark.parametrize("name", FACE_CLOUDS)
+def test_faces_and_signed_zeros_on_the_cpu(name):
+    """oracle and numpy restatement agree on index and population of every voxel; a point on a face belongs to the voxel above it, its
+    neighbour towards -inf to the one below"""
+    c, leaf = face_clouds()[name]
+    exp, idx, cnt = both_restatements(c, leaf, name)
+    assert np.array_equal(voxel_index(exp, c, leaf), idx) and (np.diff(idx) > 0).all()
+    if name.startswith("faces") and leaf != 0.1:
+        on, below = lattice_faces(leaf)
+        j = np.round(on / np.float32(leaf)).astype(np.int64)
+        inv = np.float32(1) / np.float32(leaf)
+        assert np.array_equal(np.floor(on * inv).astype(np.int64), j) and np.array_equal(np.floor(below * inv).astype(np.int64), j - 1)
+        assert exp.shape[0] == 2 * 17 ** 3 - 16 ** 3 and cnt.max() == 2 and (cnt == 2).sum() == 16 ** 3   # (x, y, z) and the point below (x + 1, y + 1, z + 1)
+    if name.startswith("signed_zero"):
+        assert exp.shape[0] == 17 ** 3 and cnt.max() == 2 and (cnt == 2).sum() == 17 ** 3 - 16 ** 3   # -0.0 falls into +0.0's voxel
+    if name.startswith("min_negative_zero"):
+        assert exp.shape[0] == 9 ** 3 and idx[0] == 0 and (cnt == 1).all()
+
+
+def test_leaf_too_small_limit_on_the_cpu():
+    """dx dy dz = 2048 * 1024 * 1023 = 2 145 386 496 <= INT32_MAX is filtered; 2048 * 1024 * 1024 = 2^31 is not"""
+    c = limit_cloud((2047, 1023, 1022))
+    exp, idx, cnt = both_restatements(c, 1.0)
+    assert exp.shape[0] == len(c) - 1 and cnt[0] == 2 and (cnt[1:] == 1).all() and idx[0] == 0
+    assert idx[-1] == 2047 + 1023 * 2048 + 1022 * 2048 * 1024 == 2_145_386_495 and np.array_equal(exp[-1], c[2])
+    c = limit_cloud((2047, 1023, 1023))
+    out, idx, cnt = R.submap_assemble([c], None, 1.0)
+    assert np.array_equal(out, c) and (idx == -1).all() and (cnt == 1).all()
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_voxel_grid(a, c, leaf, exp, idx, cnt, index_rows=None):
+    """the file's bars for one cloud at the identity pose: rows, one-point voxels bit for bit, centroids; index_rows: the rows whose voxel
+    index is recomputed from the device's output (the order)"""
+    assert a.assemble([c], None, leaf) == exp.shape[0]
+    got = a.to_numpy()
+    single = cnt == 1
+    assert np.array_equal(bits(got[single]), bits(exp[single])) and centroids_close(got, exp, cnt)
+    rows = single if index_rows is None else index_rows
+    assert np.array_equal(voxel_index(got[rows], c, leaf), idx[rows])
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", EDGE_SIZES)
+def test_voxel_grid_at_size_edges(mods, n):
+    """n at the sort's padding (powers of two from VOX_TILE) and at the 4096-key scan blocks, each with n, 1 and about n / 4 voxels"""
+    reg, sub = mods
+    a = sub.SubmapAssembler()
+    every = np.ones(0, dtype=bool)
+    for population in POPULATIONS:
+        c, want = sized_cloud(n, population)
+        exp, idx, cnt = both_restatements(c, 0.5, (n, population))
+        got = assert_voxel_grid(a, c, 0.5, exp, idx, cnt, index_rows=np.ones(len(idx), dtype=bool))
+        print(f"n {n} {population}: {exp.shape[0]} voxels, largest {cnt.max()}")
+        if want is not None:
+            assert np.array_equal(bits(got), bits(want))   # the input reordered by ascending voxel index
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FACE_CLOUDS)
+def test_voxel_grid_faces_and_signed_zeros(mods, name):
+    reg, sub = mods
+    c, leaf = face_clouds()[name]
+    exp, idx, cnt = both_restatements(c, leaf, name)
+    # leaf 0.5 / 0.25: the mean of a voxel's points lies inside it; 0.1: only the one-point voxels repeat the input's own product
+    assert_voxel_grid(sub.SubmapAssembler(), c, leaf, exp, idx, cnt, index_rows=None if leaf == 0.1 else np.ones(len(idx), dtype=bool))
+
+
+@pytest.mark.gpu
+def test_leaf_too_small_limit(mods, capfd):
+    reg, sub = mods
+    L = reg.load_library()
+    a = sub.SubmapAssembler()
+    c = limit_cloud((2047, 1023, 1022))
+    exp, idx, cnt = both_restatements(c, 1.0)
+    with pytest.raises(reg.ApdgicpError):
+        a.assemble([c], None, (1.0, 0.0, 1.0))          # (leaves a message of its own in last_error)
+    before = L.apdgicp_last_error()
+    assert b"leaf sizes must be positive" in before
+    capfd.readouterr()
+    # 2048 * 1024 * 1023 voxels: filtered, the largest voxel index 0x7FDFFFFF in the key's upper word, next to the padding's 0xFFFFFFFF
+    got = assert_voxel_grid(a, c, 1.0, exp, idx, cnt)
+    assert a.n == len(c) - 1 and np.array_equal(bits(got[-1]), bits(c[2]))
+    assert L.apdgicp_last_error() == before and "Leaf size is too small" not in capfd.readouterr().err   # no warning
+    # 2048 * 1024 * 1024 = 2^31 voxels: PCL's branch, the input comes back unfiltered with status 0 and the warning
+    c = limit_cloud((2047, 1023, 1023))
+    assert a.assemble([c], None, 1.0) == len(c) and np.array_equal(bits(a.to_numpy()), bits(c))
+    assert b"leaf size is too small" in L.apdgicp_last_error() and "Leaf size is too small" in capfd.readouterr().err
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("n_frames,n_pts", ((2, 700), (5, 3000), (5, 8192)))
 def test_assemble_vs_oracle(mods, scene, n_frames, n_pts):
