@@ -153,6 +153,7 @@ class Estimate:
     zero_velocity: bool = False
     sigma_in_bounds: bool = False
     selected_abs_v: float = 0.0
+    n0: int = 0                      # the rank of the zero-velocity test (E:104)
     v: np.ndarray = field(default_factory=lambda: np.zeros(3))
     sigma: np.ndarray = field(default_factory=lambda: np.zeros(3))
     samples: np.ndarray | None = None   # [K, S]
@@ -186,7 +187,7 @@ def estimate(scan: np.ndarray, cfg: Config, words: np.ndarray | None = None) -> 
     absv = np.abs(rows[:, 3].astype(F32))
     n0 = min(m - 1, int(float(m) * (1.0 - cfg.f("allowed_outlier_percentage"))))   # E:104 (clamped: the reference reads [m] at 0 %)
     sel = np.sort(absv.view(np.uint32))[n0:n0 + 1].view(F32)[0]                      # E:105-106 (bit order = value order for |v|)
-    out.selected_abs_v = float(sel)
+    out.selected_abs_v, out.n0 = float(sel), n0
     thr0 = F32(cfg.thresh_zero_velocity)
     if sel < thr0:                                                                   # E:108-118
         out.zero_velocity = out.success = out.sigma_in_bounds = True

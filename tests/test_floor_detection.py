@@ -229,8 +229,10 @@ def cfg_kw(cfg):
     return {k: (int(v) if isinstance(v, bool) else v) for k, v in ((k, getattr(cfg, k)) for k in cfg.__dataclass_fields__)}
 
 
-def preconditions(scan, cfg, words, state):
-    """on the restatement alone: the share of points in the band, no inlier decision within 1 ulp of the threshold"""
+def preconditions(scan, cfg, words, state, on_threshold=None):
+    """on the restatement alone: the share of points in the band, no inlier decision within 1 ulp of the threshold.  on_threshold (the
+    hand-built scans): instead of excluding such decisions, the filtered points whose distance to the WINNING plane lies within 1 fp32
+    ulp of the threshold are exactly these rows"""
     r = F.detect(scan, cfg, words, F.State(state.prev.copy(), state.initialized))
     if r.stat is not None:
         thr = math.cos(cfg.normal_filter_thresh * math.pi / 180.0)
@@ -238,7 +240,10 @@ def preconditions(scan, cfg, words, state):
         assert in_band.sum() <= 0.005 * len(r.stat)
     t = F32(cfg.distance_threshold)
     lo, hi = float(np.nextafter(t, F32(0))), float(np.nextafter(t, F32(1)))
-    if r.ransac:
+    if on_threshold is not None:
+        d = np.abs(F.plane_dist(r.coef[r.winner], r.filtered[:, :3])).astype(np.float64) if r.winner >= 0 else np.zeros(0)
+        assert np.flatnonzero((d >= lo) & (d <= hi)).tolist() == list(on_threshold)
+    elif r.ransac:
         xyz = r.filtered[:, :3]
         for k in np.flatnonzero(~r.bad):
             d = np.abs(F.plane_dist(r.coef[k], xyz)).astype(np.float64)
@@ -246,12 +251,20 @@ def preconditions(scan, cfg, words, state):
     return r
 
 
-def run_and_compare(fd, scan, cfg, words=None, det=None, state=None, device_input=False):
-    """one run on the device against the restatement; returns (restatement, result, detector, state)"""
+def same_bits(got, ref, nan_ok=False):
+    """bit for bit; with nan_ok a NaN matches a NaN of any sign and payload"""
+    got, ref = np.asarray(got, dtype=F32), np.asarray(ref, dtype=F32)
+    both_nan = np.isnan(got) & np.isnan(ref) if nan_ok else np.zeros(ref.shape, dtype=bool)
+    return got.shape == ref.shape and bool(((bits(got) == bits(ref)) | both_nan).all())
+
+
+def run_and_compare(fd, scan, cfg, words=None, det=None, state=None, device_input=False, on_threshold=None, nan_ok=False):
+    """one run on the device against the restatement; returns (restatement, result, detector, state).  on_threshold: see preconditions.
+    nan_ok: a hypothesis's coefficients match where both sides are NaN and are bit-equal elsewhere."""
     if words is None:
         words = words_for(cfg.n_hypotheses)
     state = state if state is not None else F.State.initial(cfg)
-    pre = preconditions(scan, cfg, words, state)
+    pre = preconditions(scan, cfg, words, state, on_threshold)
     det = det if det is not None else fd.FloorDetector(**cfg_kw(cfg))
     cloud = scan
     if device_input:
@@ -277,7 +290,7 @@ def run_and_compare(fd, scan, cfg, words=None, det=None, state=None, device_inpu
     assert np.array_equal(bits(filtered["xyzi"]), bits(ref.filtered)) and np.array_equal(filtered["index"], ref.filt_src)
     coef, bad, n_in = det.hypotheses()
     assert np.array_equal(d["samples"], ref.samples) and np.array_equal(bad, ref.bad)
-    assert np.array_equal(bits(coef), bits(ref.coef)) and np.array_equal(n_in, ref.n_in)
+    assert same_bits(coef, ref.coef, nan_ok) and np.array_equal(n_in, ref.n_in)
     assert (r.iterations, r.skipped, r.winner, r.table_exhausted) == (ref.iterations, ref.skipped, ref.winner, ref.exhausted)
     assert (bool(r.detected), r.reject_reason, bool(r.ground_initialized)) == (ref.detected, ref.reason, ref.initialized)
     assert np.array_equal(bits(list(r.coeffs)), bits(ref.coeffs)) and np.array_equal(bits(list(r.raw_coeffs)), bits(ref.raw)) and r.n_inliers == ref.n_inliers
@@ -457,3 +470,234 @@ def test_cpp_class_returns_the_python_paths_record(mods, scene, tmp_path):
     n_under = int(np.frombuffer(raw, dtype=np.int32, count=1, offset=100 + 16 * n_floor)[0])
     uf = np.frombuffer(raw, dtype=F32, count=4 * n_under, offset=104 + 16 * n_floor).reshape(-1, 4)
     assert np.array_equal(bits(fp), bits(det.to_numpy("inliers")["xyzi"])) and np.array_equal(bits(uf), bits(det.to_numpy("under_floor")["xyzi"]))
+
+
+# ------------------------------------------------------------------ hand-built scans: comparisons at equality, degenerate samples, 1025 blocks
+# Every case is (scan, config, words, check, the rows on the distance threshold): `check` holds the assertions on the restatement alone and
+# runs in test_hand_built_inputs_are_the_edges_they_claim without a device, and again in front of the device run of its GPU test.
+def nxt(x, towards):
+    return np.nextafter(F32(x), F32(towards))
+
+
+def words_to_draw(rows_wanted):
+    """the words with which sample() draws exactly these (distinct) rows, in this order"""
+    return np.array([[r - sum(1 for t in rows[:i] if t < r) for i, r in enumerate(rows)] for rows in rows_wanted], dtype=np.uint32)
+
+
+def flat_floor(n, seed, z=-2.0):
+    """n points with z exactly z: every plane through three of them is (0, 0, +-1, -+z) without a rounding"""
+    g = np.random.default_rng([seed, 0xF2])
+    return np.stack([g.uniform(2, 30, n), g.uniform(-10, 10, n), np.full(n, z), g.uniform(0, 40, n)], axis=1).astype(F32)
+
+
+def pts(rows):
+    return np.array([list(r) + [7.0] for r in rows], dtype=F32)
+
+
+OFF = dict(use_normal_filtering=False)
+
+
+class Case:
+    def __init__(self, scan, cfg, words, check, on_threshold=(), nan_ok=False):
+        self.scan, self.cfg, self.words, self.check = np.ascontiguousarray(scan, dtype=F32), cfg, np.asarray(words, dtype=np.uint32), check
+        self.how = dict(on_threshold=list(on_threshold), nan_ok=nan_ok)
+
+    def restate(self, state=None):
+        state = F.State.initial(self.cfg) if state is None else F.State(state.prev.copy(), state.initialized)
+        ref = F.detect(self.scan, self.cfg, self.words, state)
+        self.check(ref)
+        return ref
+
+    def run(self, fd, det=None, state=None):
+        self.restate(state)   # (the edge is asserted before the device is touched)
+        return run_and_compare(fd, self.scan, self.cfg, self.words, det=det, state=state, **self.how)
+
+
+def exact_plane(ref, d):
+    """the winner is (0, 0, +-1, +-d) and the published plane (0, 0, 1, d), exactly"""
+    return np.abs(ref.raw).tolist() == [0.0, 0.0, 1.0, d] and ref.raw[2] * ref.raw[3] >= 0 and ref.coeffs.tolist() == [0.0, 0.0, 1.0, d] and not np.signbit(ref.coeffs[2])
+
+
+def height_band_case():
+    """plane_clip(+) keeps distance >= 0, plane_clip(-, negative) drops it: [-(h + range), -(h - range)) = [-3, -1).  Non-finite points
+    fail both the band and the under-floor clip (0 * inf is NaN), except z = +inf, which the under-floor clip keeps"""
+    inf = np.inf
+    edge = pts([(5, 1, -3.0), (5, 1, nxt(-3.0, -4)), (5, 1, -1.0), (5, 1, nxt(-1.0, -2)), (np.nan,) * 3, (inf,) * 3, (-inf,) * 3, (5, 1, inf), (5, 1, -inf)])
+    scan = np.concatenate([edge, flat_floor(60, 1)], axis=0)
+    cfg = F.Config(n_hypotheses=4, **OFF)
+
+    def check(ref):
+        assert ref.clip_mask.tolist() == [True, False, False, True] + [False] * 5 + [True] * 60 and len(ref.filtered) == 62
+        assert ref.detected and ref.winner == 0 and ref.n_inliers == 60 and exact_plane(ref, 2.0)
+        assert ref.under_src.tolist() == [2, 3, 7] + list(range(9, 69))
+    return Case(scan, cfg, words_to_draw([(2, 3, 4), (5, 9, 20), (1, 2, 3), (0, 10, 30)]), check)
+
+
+def distance_threshold_case():
+    """distance_threshold = 0.0625 on the exact plane (0, 0, +-1, +-2): |z + 2| == 0.0625 is an outlier (strict <), one fp32 ulp less an inlier"""
+    edge = pts([(5, 1, -1.9375), (5, 1, nxt(-1.9375, -2)), (5, 1, -2.0625), (5, 1, nxt(-2.0625, -2))])
+    scan = np.concatenate([flat_floor(60, 2), edge], axis=0)
+    cfg = F.Config(distance_threshold=0.0625, n_hypotheses=2, **OFF)
+
+    def check(ref):
+        d = np.abs(F.plane_dist(ref.raw, ref.filtered[:, :3])).astype(np.float64)
+        assert exact_plane(ref, 2.0) and d[60] == 0.0625 == d[62] == cfg.distance_threshold and d[61] == 0.0625 - 2.0**-23 and d[63] == 0.0625 - 2.0**-22
+        assert ref.detected and ref.winner == 0 and ref.n_in[0] == 62 == ref.n_inliers and ref.inlier_rows.tolist() == list(range(60)) + [61, 63]
+    return Case(scan, cfg, words_to_draw([(0, 1, 2), (3, 60, 62)]), check, on_threshold=[60, 62])
+
+
+def fp64_comparison_case():
+    """the fp32 distance is widened and compared with the DOUBLE 0.06: (double)0.06f = 0.0599999986... < 0.06, so a point at exactly 0.06f
+    from the plane z = 0 is an inlier; compared in fp32 (0.06f < 0.06f) it would not be.  Its neighbour above is an outlier either way"""
+    t = F32(0.06)
+    edge = pts([(5, 1, t), (5, 1, nxt(t, 1)), (5, 1, -t), (5, 1, nxt(-t, -1))])
+    scan = np.concatenate([flat_floor(60, 3, 0.0), edge], axis=0)
+    cfg = F.Config(sensor_height=0.0, n_hypotheses=2, **OFF)
+
+    def check(ref):
+        assert cfg.distance_threshold == 0.06 and float(t) < 0.06 < float(nxt(t, 1)) and not t < F32(0.06)
+        d = np.abs(F.plane_dist(ref.raw, ref.filtered[:, :3]))
+        assert exact_plane(ref, 0.0) and d.dtype == F32 and d[60] == t == d[62] and d[61] == nxt(t, 1) == d[63] and len(ref.filtered) == 64
+        assert ref.detected and ref.winner == 0 and ref.n_in[0] == 62 == ref.n_inliers and ref.inlier_rows.tolist() == list(range(61)) + [62]
+    return Case(scan, cfg, words_to_draw([(0, 1, 2), (3, 60, 62)]), check, on_threshold=[60, 61, 62, 63])
+
+
+def pts_thresh_case(n_floor):
+    """n_best < floor_pts_thresh: 50 inliers of 60 filtered points are a floor, 49 are FEW_INLIERS"""
+    scan = np.concatenate([flat_floor(n_floor, 4), flat_floor(60 - n_floor, 5, -2.5)], axis=0)
+    cfg = F.Config(n_hypotheses=2, **OFF)
+
+    def check(ref):
+        assert len(ref.filtered) == 60 >= cfg.floor_pts_thresh == 50 and ref.ransac and ref.winner == 0 and ref.n_in.tolist()[0] == n_floor == ref.n_inliers
+        assert ref.n_in[1] < 49 and ref.detected == (n_floor == 50) and ref.reason == (F.OK if n_floor == 50 else F.FEW_INLIERS)
+    return Case(scan, cfg, words_to_draw([(0, 1, 2), (n_floor, n_floor + 1, 0)]), check)
+
+
+def under_floor_case(detecting):
+    """plane_clip(prev + (0, 0, 0, floor_tolerance)) keeps distance >= 0: with the exact plane (0, 0, 1, 2) and tolerance 0.125, z == -2.125 is
+    kept and its neighbour below removed -- on the detecting scan and, with the remembered plane, on a scan that detects nothing"""
+    edge = pts([(5, 1, -2.125), (5, 1, nxt(-2.125, -3)), (5, 1, 0.5)])
+    scan = np.concatenate([flat_floor(60, 6), edge], axis=0) if detecting else edge
+    cfg = F.Config(floor_tolerance=0.125, n_hypotheses=2, **OFF)
+
+    def check(ref):
+        n = len(scan)
+        assert float(F32(2.0 + 0.125)) == 2.125 and ref.coeffs.tolist() == [0.0, 0.0, 1.0, 2.0] and ref.initialized
+        assert ref.detected == detecting and (detecting or ref.reason == F.FEW_POINTS)
+        assert ref.under_src.tolist() == list(range(n - 3)) + [n - 3, n - 1]
+    return Case(scan, cfg, words_to_draw([(0, 1, 2), (3, 4, 5)]), check)
+
+
+def degenerate_samples_case():
+    """computeModelCoefficients on samples that are no triangles.  Rows 0 and 1 are the same point.
+      (0, 1, 2): p1 == p0, p2 - p0 without a zero: the ratios are (0, 0, -0), all equal: collinear, bad;
+      (0, 2, 3): p2 - p0 = (0, 3, 0.5): a division by zero in the test (inf), not collinear: a plane;
+      (0, 2, 1): p2 == p0: the ratios are (inf, inf, -inf): PASSES, the cross product is zero: NaN coefficients, no inlier;
+      (2, 0, 1): p1 - p0 == p2 - p0: ratios (1, 1, 1): bad;      (0, 3, 1): ratios (NaN, inf, inf): passes, NaN coefficients;
+      (10, 20, 30): three floor points: the winner"""
+    g = np.random.default_rng(8)
+    special = pts([(1, 1, -2), (1, 1, -2), (2, 3, -2.5), (1, 4, -1.5)])
+    floor = flat_floor(60, 7)
+    floor[:, 2] += (0.002 * g.normal(size=60)).astype(F32)   # (not exactly flat: a flat sample has 0 / 0 among its ratios)
+    scan = np.concatenate([special, floor], axis=0)
+    cfg = F.Config(n_hypotheses=7, **OFF)
+    draws = [(0, 1, 2), (0, 2, 3), (0, 2, 1), (2, 0, 1), (0, 3, 2), (10, 20, 30), (0, 3, 1)]
+
+    def check(ref):
+        assert ref.samples.tolist() == [list(d) for d in draws] and len(ref.filtered) == 64
+        assert ref.bad.tolist() == [True, False, False, True, False, False, False]
+        assert np.isnan(ref.coef[2]).all() and np.isnan(ref.coef[6]).all() and np.isfinite(ref.coef[[1, 4, 5]]).all()
+        assert ref.n_in[2] == 0 == ref.n_in[6] and ref.n_in[1] > 0 and ref.n_in[5] > 50
+        assert (ref.winner, ref.skipped, ref.iterations, ref.exhausted) == (5, 2, 4, 0) and ref.detected
+    return Case(scan, cfg, words_to_draw(draws), check, nan_ok=True)
+
+
+BIG_N = 1024 * 1024 + 1025
+
+
+@functools.lru_cache(maxsize=None)
+def more_than_1024_blocks_case():
+    """1025 blocks of 1024 points and one point: the second trip of the b0 loop of k_scan_bsum and k_floor_emit_scan, with its carries.  A
+    tiled floor_scan (every tile with an intensity of its own); under-floor points in the last two blocks"""
+    base = scene_mod().floor_scan(4096, 41)
+    reps = BIG_N // 4096 + 1
+    scan = np.tile(base, (reps, 1))
+    scan[:, 3] = np.repeat(np.arange(reps, dtype=F32), 4096)
+    scan = np.ascontiguousarray(scan[:BIG_N])
+    below = np.array([1024 * 1024, 1024 * 1024 + 4, 1024 * 1024 + 424, BIG_N - 2, BIG_N - 1])
+    scan[below, 2] = F32(-5.0)
+    cfg = F.Config(n_hypotheses=4, **OFF)
+
+    def check(ref):
+        assert len(scan) == BIG_N == 1049601 and (BIG_N + 1023) // 1024 == 1026 and set(below // 1024) == {1024, 1025}
+        assert ref.detected and len(ref.filtered) > 1024 * 512 and ref.n_inliers > 1024 * 400 and not ref.bad.any()
+        assert not np.isin(below, ref.under_src).any() and np.isin(below - 1, ref.under_src).any() and 0.9 * BIG_N < len(ref.under_src) < 0.96 * BIG_N
+        assert ref.inlier_rows[-1] // 1024 >= 512   # (the inlier list's own scan runs over the filtered points: more than 512 blocks of them)
+    return Case(scan, cfg, words_for(4, 3), check, on_threshold=[])
+
+
+HAND_BUILT = {"height-band": height_band_case, "distance-threshold": distance_threshold_case, "fp64-comparison": fp64_comparison_case,
+              "pts-thresh-50": lambda: pts_thresh_case(50), "pts-thresh-49": lambda: pts_thresh_case(49), "under-floor-detecting": lambda: under_floor_case(True),
+              "degenerate-samples": degenerate_samples_case, "more-than-1024-blocks": more_than_1024_blocks_case}
+
+
+@pytest.mark.parametrize("name", list(HAND_BUILT))
+def test_hand_built_inputs_are_the_edges_they_claim(name):
+    """the restatement-only half of every hand-built GPU case below: equalities with ==, literal counts and lists, which rows sit on the threshold"""
+    case = HAND_BUILT[name]()
+    case.restate()
+    preconditions(case.scan, case.cfg, case.words, F.State.initial(case.cfg), case.how["on_threshold"])
+
+
+def test_under_floor_edge_with_the_remembered_plane():
+    """(the second scan of test_under_floor_clip_at_equality, on the restatement: it needs the state the first one leaves)"""
+    st = F.State.initial(F.Config(floor_tolerance=0.125, **OFF))
+    a, b = under_floor_case(True), under_floor_case(False)
+    a.check(F.detect(a.scan, a.cfg, a.words, st))
+    b.restate(st)
+
+
+@pytest.mark.gpu
+def test_height_band_at_equality(mods):
+    """z == -3 kept, below dropped; z == -1 dropped, below kept; NaN / inf points dropped"""
+    height_band_case().run(mods[1])
+
+
+@pytest.mark.gpu
+def test_distance_threshold_at_equality(mods):
+    ref, r, _, _ = distance_threshold_case().run(mods[1])
+    assert r.n_inliers == 62 and list(r.coeffs) == [0.0, 0.0, 1.0, 2.0]
+
+
+@pytest.mark.gpu
+def test_distance_is_compared_in_double(mods):
+    ref, r, _, _ = fp64_comparison_case().run(mods[1])
+    assert r.n_inliers == 62
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_floor", [50, 49])
+def test_floor_pts_thresh_on_the_inlier_count(mods, n_floor):
+    ref, r, _, _ = pts_thresh_case(n_floor).run(mods[1])
+    assert (r.detected, r.n_inliers, r.reject_reason) == ((1, 50, F.OK) if n_floor == 50 else (0, 49, F.FEW_INLIERS))
+
+
+@pytest.mark.gpu
+def test_under_floor_clip_at_equality(mods):
+    ref, r, det, st = under_floor_case(True).run(mods[1])
+    assert r.detected and r.n_under_floor == 62
+    ref, r, _, _ = under_floor_case(False).run(mods[1], det=det, state=st)
+    assert not r.detected and r.ground_initialized and r.n_under_floor == 2 and list(r.coeffs) == [0.0, 0.0, 1.0, 2.0]
+
+
+@pytest.mark.gpu
+def test_degenerate_samples(mods):
+    ref, r, det, _ = degenerate_samples_case().run(mods[1])
+    coef, bad, n_in = det.hypotheses()
+    assert np.isnan(coef[[2, 6]]).all() and bad.tolist() == [True, False, False, True, False, False, False] and (r.winner, r.skipped) == (5, 2)
+
+
+@pytest.mark.gpu
+def test_more_than_1024_blocks(mods):
+    ref, r, _, _ = more_than_1024_blocks_case().run(mods[1])
+    assert r.detected and r.n_input == BIG_N and r.n_filtered > 1024 * 512
