@@ -39,7 +39,8 @@ extern "C" {
                                    6: + APDGICP_FLAG_ALGEBRAIC_APD, build_flags, nearest_neighbours_of, get_trace_step_norms;
                                       still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal);
                                       still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal);
-                                      still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal) */
+                                      still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal);
+                                      still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -658,6 +659,57 @@ int apdgicp_floor_hypotheses(apdgicp_floor* f, float* coeffs, uint8_t* bad, int3
  * normal_stat [n_clipped] floats (step 2; untouched unless the search ran), samples [3 * K] row indices of the filtered cloud (untouched
  * when RANSAC did not run).  A destination that is too small: APDGICP_ERR_INVALID_ARG, nothing is written. */
 int apdgicp_floor_debug(apdgicp_floor* f, uint8_t* clip_mask, int64_t mask_capacity, float* normal_stat, int64_t stat_capacity, int32_t* samples, int64_t samples_capacity);
+
+/* ------------------------------------------------------------------ map cloud generation
+ * radar_graph_slam::MapCloudGenerator::generate (radar_graph_slam/src/radar_graph_slam/map_cloud_generator.cpp:13-53, "M:"), which the
+ * back end calls after every graph optimisation (radar_graph_slam_nodelet.cpp:793) and for the save-map service (:1246) with all
+ * keyframes and map_cloud_resolution.  The keyframe clouds do not change between two calls, only their poses do: a cloud is uploaded
+ * once (add_keyframe) and stays in device memory the object owns; generate uploads poses only.  PCL is not part of the reference tree;
+ * the octree follows PCL 1.10 as published (octree/impl/octree_pointcloud.hpp: addPointsFromInputCloud, adoptBoundingBoxToPoint,
+ * getKeyBitSize, genOctreeKeyforPoint, genLeafNodeCenterFromOctreeKey; octree_base.hpp / octree_key.h:
+ * getOccupiedVoxelCentersRecursive, pushBranch).  eps = FLT_EPSILON widened to double, res = the resolution.
+ *   M1 (M:22-31): keyframes in the order given, points in cloud order.  d = (double)sqrtf((x*x + y*y) + z*z), every fp32 operation
+ *      rounded on its own; a point is skipped iff d > 50 (a NaN point is kept).  P = the 16 doubles of the pose rounded to fp32;
+ *      dst = P * (x, y, z, 1) in fp32, per row (r0*x + r1*y) + (r2*z + t), with APDGICP_FLAG_XF_LINEAR_CHAIN in `flags`
+ *      ((r0*x + r1*y) + r2*z) + t -- the two orders of apdgicp_params.flags; the intensity is copied.  The "pushed" cloud, in order.
+ *   M2 (M:38-39): res <= 0: the output is the pushed cloud itself, intensities and non-finite points included.
+ *   M3: the bounding box, replayed over the finite pushed points in order; comparisons on the fp32 coordinate widened to double.
+ *      First point p: min = p - res/2, max = p + res/2; mk = ceil((max - min - eps) / res) per axis; depth = ceil(log2(max(mk, 2)) - eps);
+ *      side = 2^depth * res; per axis o = (side - (max - min)) / 2, and if o > eps: min -= o, max += o.  Every later point: while
+ *      p[a] < min[a] or p[a] >= max[a] on any axis: side = (double)(1 << depth) * res; min[a] -= side on every axis with !(p[a] >= max[a]);
+ *      depth += 1; max[a] = min[a] + ((double)(1 << depth) * res - eps) on all axes.  A depth above 21: APDGICP_ERR_UNSUPPORTED (PCL shifts
+ *      an int by the depth; 21 keeps the interleaved key within 63 bits; at 0.05 m depth 21 is 104 km).
+ *   M4: key[a] = (unsigned)(((double)p[a] - min[a]) / res) with the final min, an IEEE fp64 division, truncated.
+ *   M5: one output point per distinct (kx, ky, kz), ascending in the interleaved key whose bit triple at level L, from the most
+ *      significant, is (kx_L << 2) | (ky_L << 1) | kz_L -- the depth-first walk; coordinates (float)(((double)key[a] + 0.5) * res + min[a]);
+ *      intensity 0 (the reference pushes a default-constructed point).
+ *   M6: no keyframes: APDGICP_ERR_INVALID_ARG (the reference returns nullptr); no finite pushed point: n_out = 0, status 0; more than
+ *      2^31 - 1 input points: APDGICP_ERR_UNSUPPORTED; a resolution that is NaN or infinite: APDGICP_ERR_INVALID_ARG.
+ * Nothing per point goes to the host.  The distinct keys come from a stable radix sort of the interleaved keys (environment
+ * APDGICP_MAP_SORT=bitonic at create time: the bitonic sort of the submap assembler instead, for measurements).  The calls wait for
+ * their own work. */
+typedef struct {
+  int64_t n_input, n_pushed, n_finite, n_out;   /* points of the keyframes given, M1's cloud, its finite points, the output */
+  double min[3], max[3];                        /* M3's final box (zeros without an octree) */
+  int32_t depth, rounds;                        /* octree depth; points after the first that made the box grow */
+  int32_t sort_passes, sort_kind;               /* radix passes (8-bit digits over 3 * depth bits); 0 = radix, 1 = bitonic */
+  float stage_ms[4];                            /* device time of the last generate: M1, M3, keys + sort, heads + centres */
+} apdgicp_map_cloud_stats;
+typedef struct apdgicp_map_cloud apdgicp_map_cloud;
+int apdgicp_map_cloud_create(int device, void* stream, apdgicp_map_cloud** out);
+int apdgicp_map_cloud_destroy(apdgicp_map_cloud* m);
+/* copies a keyframe's cloud (n >= 0 points, stride_bytes apart, host or device memory; intensity_offset_bytes < 0: intensity 0) into
+ * device memory the object owns; *id = 0, 1, 2 ... in the order of the calls */
+int apdgicp_map_cloud_add_keyframe(apdgicp_map_cloud* m, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device, int32_t* id);
+int apdgicp_map_cloud_clear(apdgicp_map_cloud* m);   /* forgets every keyframe and the last result; ids start at 0 again */
+/* ids: n_keyframes ids in visiting order (any subset, repeats allowed; NULL: 0 .. n_keyframes - 1), an unknown id: APDGICP_ERR_INVALID_ARG;
+ * poses: n_keyframes x 16 doubles, column-major 4x4; flags: 0 or APDGICP_FLAG_XF_LINEAR_CHAIN */
+int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const int32_t* ids, const double* poses, double resolution, int32_t flags, int64_t* n_out);
+/* device pointer to the last generated cloud: n points of {x, y, z, intensity} floats, valid until the next generate / clear; what
+ * apdgicp_set_target accepts (16-byte stride) */
+int apdgicp_map_cloud_points(apdgicp_map_cloud* m, const float** device_xyzi, int64_t* n);
+int apdgicp_map_cloud_copy(apdgicp_map_cloud* m, float* dst_xyzi, int64_t capacity_points, int dst_on_device);
+int apdgicp_map_cloud_info(apdgicp_map_cloud* m, apdgicp_map_cloud_stats* info);
 
 #ifdef __cplusplus
 }

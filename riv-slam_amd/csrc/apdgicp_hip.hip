@@ -11,6 +11,7 @@
 #include "apd_filter.hpp"
 #include "apd_ego.hpp"
 #include "apd_floor.hpp"
+#include "apd_map.hpp"
 
 using namespace apd;
 
@@ -112,6 +113,39 @@ struct apdgicp_floor {
     delete eng;
     if (h_rec) (void)hipHostFree(h_rec);
     for (DevBuf* b : bufs()) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_map_cloud {
+  struct Keyframe {
+    DevBuf pts;  // float4 {x, y, z, intensity}
+    int64_t n = 0;
+  };
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  bool bitonic = false;  // APDGICP_MAP_SORT=bitonic at create time
+  std::vector<Keyframe> kfs;
+  DevBuf stage, pushed, keys_a, keys_b, hist, rs_bsum, bsum, bmin, out, state;
+  CachedTable jobs;
+  MapState* h_state = nullptr;  // pinned mirror of state
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  apdgicp_map_cloud_stats info;
+  const float* result = nullptr;
+  int64_t n_last = 0;
+  void forget() {
+    result = nullptr, n_last = 0;
+    memset(&info, 0, sizeof(info));
+    info.sort_kind = bitonic ? 1 : 0;
+  }
+  ~apdgicp_map_cloud() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (Keyframe& k : kfs) k.pts.release();
+    if (h_state) (void)hipHostFree(h_state);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (DevBuf* b : {&stage, &pushed, &keys_a, &keys_b, &hist, &rs_bsum, &bsum, &bmin, &out, &state, &jobs.dev}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -2111,6 +2145,259 @@ int apdgicp_floor_debug(apdgicp_floor* f, uint8_t* clip_mask, int64_t mask_capac
     APD_HIP(hipStreamSynchronize(f->stream));
     return 0;
   });
+}
+
+// ------------------------------------------------------------------ map cloud generation (apd_map.hpp)
+static_assert(sizeof(MapState) == 96 && sizeof(apdgicp_map_cloud_stats) == 112, "map cloud record layouts");
+
+int apdgicp_map_cloud_create(int device, void* stream, apdgicp_map_cloud** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_map_cloud> m(new apdgicp_map_cloud);
+    m->device = device;
+    const char* sort = getenv("APDGICP_MAP_SORT");
+    m->bitonic = sort && !strcmp(sort, "bitonic");
+    m->forget();
+    if (stream) {
+      m->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+      m->own_stream = true;
+    }
+    APD_HIP(hipHostMalloc((void**)&m->h_state, sizeof(MapState), hipHostMallocDefault));
+    APD_TRY(m->state.ensure(sizeof(MapState)));
+    for (hipEvent_t& e : m->ev) APD_HIP(hipEventCreate(&e));
+    *out = m.release();
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_destroy(apdgicp_map_cloud* m) {
+  return guarded([&]() -> int {
+    if (m) (void)hipSetDevice(m->device);
+    delete m;
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_add_keyframe(apdgicp_map_cloud* m, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device, int32_t* id) {
+  return guarded([&]() -> int {
+    if (!m || !id || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative point count");
+    if (n > 2147483647ll) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^31 - 1 points");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity offset outside the point");
+    if (m->kfs.size() >= 2147483647u) return fail(APDGICP_ERR_UNSUPPORTED, "too many keyframes");
+    APD_HIP(hipSetDevice(m->device));
+    apdgicp_map_cloud::Keyframe kf;
+    kf.n = n;
+    if (n > 0) {
+      APD_TRY(kf.pts.ensure((size_t)n * 16));
+      const int rc = [&]() -> int {
+        const float* src = xyz;
+        if (!on_device) {
+          APD_HIP(hipStreamSynchronize(m->stream));  // the staging buffer may still be read by the previous call
+          APD_TRY(m->stage.ensure((size_t)n * stride_bytes));
+          // the last point may be shorter than the stride in the caller's buffer: copy up to its last used float only
+          const size_t used = std::max<int64_t>(12, intensity_offset_bytes >= 0 ? intensity_offset_bytes + 4 : 12);
+          APD_HIP(hipMemcpyAsync(m->stage.p, xyz, (size_t)(n - 1) * stride_bytes + used, hipMemcpyHostToDevice, m->stream));
+          src = m->stage.as<float>();
+        }
+        hipLaunchKernelGGL(k_map_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->stream, src, (long long)n, (int)(stride_bytes / 4),
+                           intensity_offset_bytes >= 0 ? (int)(intensity_offset_bytes / 4) : -1, kf.pts.as<float4>());
+        APD_HIP(hipGetLastError());
+        APD_HIP(hipStreamSynchronize(m->stream));  // the caller's memory is free again when the call returns
+        return 0;
+      }();
+      if (rc < 0) {
+        kf.pts.release();
+        return rc;
+      }
+    }
+    m->kfs.push_back(kf);
+    *id = (int32_t)(m->kfs.size() - 1);
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_clear(apdgicp_map_cloud* m) {
+  return guarded([&]() -> int {
+    if (!m) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(m->device));
+    APD_HIP(hipStreamSynchronize(m->stream));
+    for (auto& k : m->kfs) k.pts.release();
+    m->kfs.clear();
+    m->forget();
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const int32_t* ids, const double* poses, double resolution, int32_t flags, int64_t* n_out) {
+  return guarded([&]() -> int {
+    if (!m || !n_out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *n_out = 0;
+    m->forget();
+    if (n_keyframes < 1) return fail(APDGICP_ERR_INVALID_ARG, "no keyframes (the reference returns nullptr)");
+    if (!poses) return fail(APDGICP_ERR_INVALID_ARG, "poses is null");
+    if (flags & ~APDGICP_FLAG_XF_LINEAR_CHAIN) return fail(APDGICP_ERR_INVALID_ARG, "unknown bit in flags");
+    if (!(resolution <= 0.0) && !std::isfinite(resolution)) return fail(APDGICP_ERR_INVALID_ARG, "the resolution is NaN or infinite");
+    std::vector<MapJob> jobs((size_t)n_keyframes);
+    int64_t total = 0;
+    for (int c = 0; c < n_keyframes; c++) {
+      const int64_t id = ids ? ids[c] : c;
+      if (id < 0 || id >= (int64_t)m->kfs.size()) return fail(APDGICP_ERR_INVALID_ARG, "unknown keyframe id " + std::to_string(id));
+      MapJob& j = jobs[(size_t)c];
+      memset(&j, 0, sizeof(j));
+      j.pts = m->kfs[(size_t)id].pts.as<float4>(), j.in_off = total;
+      for (int r = 0; r < 3; r++)
+        for (int q = 0; q < 4; q++) j.P[4 * r + q] = (float)poses[(size_t)c * 16 + r + 4 * q];  // pose.matrix().cast<float>() (M:23)
+      total += m->kfs[(size_t)id].n;
+    }
+    if (total > 2147483647ll) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^31 - 1 input points");
+    m->info.n_input = total;
+    if (total == 0) return 0;
+    APD_HIP(hipSetDevice(m->device));
+    MapState* st = m->state.as<MapState>();
+    auto fetch_state = [&]() -> int {
+      APD_HIP(hipGetLastError());
+      APD_HIP(hipMemcpyAsync(m->h_state, st, sizeof(MapState), hipMemcpyDeviceToHost, m->stream));
+      APD_HIP(hipStreamSynchronize(m->stream));
+      return 0;
+    };
+    auto stage_times = [&](int last) {  // events 0 .. last were recorded and have completed
+      for (int q = 0; q < last; q++) (void)hipEventElapsedTime(&m->info.stage_ms[q], m->ev[q], m->ev[q + 1]);
+    };
+    // ---- M1
+    APD_TRY(m->jobs.upload(jobs.data(), jobs.size() * sizeof(MapJob), m->stream));
+    const unsigned nb = (unsigned)((total + MAP_BLK - 1) / MAP_BLK);
+    APD_TRY(m->bsum.ensure((size_t)nb * 4));
+    APD_TRY(m->pushed.ensure((size_t)total * 16));
+    const int linear = (flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;
+    APD_HIP(hipEventRecord(m->ev[0], m->stream));
+    hipLaunchKernelGGL(k_map_reset, dim3(1), dim3(64), 0, m->stream, st);
+    hipLaunchKernelGGL(k_map_gate_count, dim3(nb), dim3(MAP_BLK), 0, m->stream, m->jobs.as<MapJob>(), n_keyframes, (long long)total, m->bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, m->stream, m->bsum.as<int>(), (int)nb, &st->n_pushed);
+    hipLaunchKernelGGL(k_map_push, dim3(nb), dim3(MAP_BLK), 0, m->stream, m->jobs.as<MapJob>(), n_keyframes, (long long)total, linear, m->bsum.as<int>(),
+                       m->pushed.as<float4>(), st);
+    APD_HIP(hipEventRecord(m->ev[1], m->stream));
+    APD_TRY(fetch_state());
+    const MapState& h = *m->h_state;
+    const int n_pushed = h.n_pushed, n_fin = h.n_finite;
+    m->info.n_pushed = n_pushed, m->info.n_finite = n_fin;
+    if (resolution <= 0.0) {  // M2
+      stage_times(1);
+      m->result = n_pushed ? m->pushed.as<float>() : nullptr, m->n_last = n_pushed;
+      m->info.n_out = *n_out = n_pushed;
+      return 0;
+    }
+    if (n_fin == 0) {
+      stage_times(1);
+      return 0;
+    }
+    // ---- M3: rounds until none finds a violator; two are enqueued per look at the state (a round after the last one returns at once)
+    const unsigned nfb = (unsigned)(((int64_t)n_pushed + MAP_FIND_TILE - 1) / MAP_FIND_TILE);
+    APD_TRY(m->bmin.ensure((size_t)nfb * 4));
+    for (;;) {
+      for (int r = 0; r < 2; r++) {
+        hipLaunchKernelGGL(k_map_find, dim3(nfb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), st, m->bmin.as<int>());
+        hipLaunchKernelGGL(k_map_grow, dim3(1), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), m->bmin.as<int>(), (int)nfb, resolution, st);
+      }
+      APD_TRY(fetch_state());
+      if (h.err) return fail(APDGICP_ERR_UNSUPPORTED, "the octree would be deeper than 21 levels at this resolution (extent / resolution > 2^21)");
+      if (!h.found) break;
+    }
+    APD_HIP(hipEventRecord(m->ev[2], m->stream));
+    const int depth = h.depth;
+    for (int a = 0; a < 3; a++) m->info.min[a] = h.mn[a], m->info.max[a] = h.mx[a];
+    m->info.depth = depth, m->info.rounds = h.rounds;
+    // ---- M4 + the sort
+    const int n = n_fin;
+    const unsigned npb = (unsigned)(((int64_t)n_pushed + MAP_BLK - 1) / MAP_BLK);
+    int n_sorted = n;
+    unsigned long long* keys = nullptr;
+    if (m->bitonic) {
+      int64_t np2 = VOX_TILE;
+      while (np2 < n) np2 <<= 1;
+      if (np2 > (1ll << 30)) return fail(APDGICP_ERR_UNSUPPORTED, "too many points for the bitonic sort");
+      APD_TRY(m->keys_a.ensure((size_t)np2 * 8));
+      keys = m->keys_a.as<unsigned long long>();
+      hipLaunchKernelGGL(k_map_keys, dim3(npb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), resolution, st, keys);
+      if (np2 > n) hipLaunchKernelGGL(k_map_pad, dim3((unsigned)((np2 - n + 255) / 256)), dim3(256), 0, m->stream, keys, n, (int)np2);
+      hipLaunchKernelGGL(k_bitonic_tile_sort, dim3((unsigned)(np2 / VOX_TILE)), dim3(1024), 0, m->stream, keys);
+      for (int64_t k = 2 * VOX_TILE; k <= np2; k <<= 1) {
+        for (int64_t j = k >> 1; j >= VOX_TILE; j >>= 1)
+          hipLaunchKernelGGL(k_bitonic_global, dim3((unsigned)((np2 / 2 + 255) / 256)), dim3(256), 0, m->stream, keys, (int)np2, (int)k, (int)j);
+        hipLaunchKernelGGL(k_bitonic_tile_merge, dim3((unsigned)(np2 / VOX_TILE)), dim3(1024), 0, m->stream, keys, (int)k);
+      }
+      n_sorted = (int)np2;
+    } else {
+      const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+      const int64_t entries = 256ll * nblk;
+      const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+      APD_TRY(m->keys_a.ensure((size_t)n * 8));
+      APD_TRY(m->keys_b.ensure((size_t)n * 8));
+      APD_TRY(m->hist.ensure((size_t)entries * 4));
+      APD_TRY(m->rs_bsum.ensure((size_t)nsb * 4));
+      unsigned long long *src = m->keys_a.as<unsigned long long>(), *dst = m->keys_b.as<unsigned long long>();
+      hipLaunchKernelGGL(k_map_keys, dim3(npb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), resolution, st, src);
+      const int passes = (3 * depth + 7) / 8;
+      for (int p = 0; p < passes; p++) {
+        hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, m->stream, src, n, 8 * p, nblk, m->hist.as<int>());
+        hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, m->stream, m->hist.as<int>(), (int)entries, m->rs_bsum.as<int>());
+        hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, m->stream, m->rs_bsum.as<int>(), nsb, &st->pad_[0]);
+        hipLaunchKernelGGL(k_map_rs_scatter, dim3(nblk), dim3(MAP_RS_BLK), 0, m->stream, src, dst, n, 8 * p, nblk, m->hist.as<int>(), m->rs_bsum.as<int>());
+        std::swap(src, dst);
+      }
+      keys = src;
+      m->info.sort_passes = passes;
+    }
+    APD_HIP(hipEventRecord(m->ev[3], m->stream));
+    // ---- M5
+    const unsigned nhb = (unsigned)((n_sorted + MAP_BLK - 1) / MAP_BLK);
+    APD_TRY(m->bsum.ensure((size_t)nhb * 4));
+    APD_TRY(m->out.ensure((size_t)n * 16));
+    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n_sorted, m->bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, m->stream, m->bsum.as<int>(), (int)nhb, &st->n_out);
+    hipLaunchKernelGGL(k_map_centres, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n_sorted, m->bsum.as<int>(), resolution, st, m->out.as<float4>(), n);
+    APD_HIP(hipEventRecord(m->ev[4], m->stream));
+    APD_TRY(fetch_state());
+    stage_times(4);
+    if (h.n_keys != n || h.n_out < 1 || h.n_out > n) return fail(APDGICP_ERR_INTERNAL, "map cloud: inconsistent counts");
+    m->result = m->out.as<float>(), m->n_last = h.n_out;
+    m->info.n_out = *n_out = h.n_out;
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_points(apdgicp_map_cloud* m, const float** device_xyzi, int64_t* n) {
+  if (!m || !device_xyzi || !n) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *device_xyzi = m->n_last ? m->result : nullptr;
+  *n = m->n_last;
+  return 0;
+}
+
+int apdgicp_map_cloud_copy(apdgicp_map_cloud* m, float* dst_xyzi, int64_t capacity_points, int dst_on_device) {
+  return guarded([&]() -> int {
+    if (!m || !dst_xyzi) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (capacity_points < m->n_last) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer points than the generated cloud");
+    if (!m->n_last) return 0;
+    APD_HIP(hipSetDevice(m->device));
+    APD_HIP(hipMemcpyAsync(dst_xyzi, m->result, (size_t)m->n_last * 16, dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, m->stream));
+    APD_HIP(hipStreamSynchronize(m->stream));
+    return 0;
+  });
+}
+
+int apdgicp_map_cloud_info(apdgicp_map_cloud* m, apdgicp_map_cloud_stats* info) {
+  if (!m || !info) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *info = m->info;
+  return 0;
 }
 
 }  // extern "C"

@@ -103,6 +103,8 @@ SYMBOLS = [
     "apdgicp_ego_velocity_copy", "apdgicp_ego_velocity_hypotheses", "apdgicp_ego_velocity_debug",
     "apdgicp_floor_default_params", "apdgicp_floor_create", "apdgicp_floor_destroy", "apdgicp_floor_set_params", "apdgicp_floor_reset", "apdgicp_floor_run",
     "apdgicp_floor_inliers", "apdgicp_floor_under_floor_filtered", "apdgicp_floor_copy", "apdgicp_floor_hypotheses", "apdgicp_floor_debug",
+    "apdgicp_map_cloud_create", "apdgicp_map_cloud_destroy", "apdgicp_map_cloud_add_keyframe", "apdgicp_map_cloud_clear", "apdgicp_map_cloud_generate",
+    "apdgicp_map_cloud_points", "apdgicp_map_cloud_copy", "apdgicp_map_cloud_info",
 ]
 
 _lib = None
@@ -248,6 +250,14 @@ def load_library(path: str | None = None):
     L.apdgicp_floor_copy.argtypes = [vp, i32, vp, vp, i64]
     L.apdgicp_floor_hypotheses.argtypes = [vp, vp, vp, vp, i64]
     L.apdgicp_floor_debug.argtypes = [vp, vp, i64, vp, i64, vp, i64]
+    L.apdgicp_map_cloud_create.argtypes = [i32, vp, C.POINTER(vp)]
+    L.apdgicp_map_cloud_destroy.argtypes = [vp]
+    L.apdgicp_map_cloud_add_keyframe.argtypes = [vp, vp, i64, i64, i64, i32, C.POINTER(C.c_int32)]
+    L.apdgicp_map_cloud_clear.argtypes = [vp]
+    L.apdgicp_map_cloud_generate.argtypes = [vp, i32, vp, vp, dbl, i32, C.POINTER(i64)]
+    L.apdgicp_map_cloud_points.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_map_cloud_copy.argtypes = [vp, vp, i64, i32]
+    L.apdgicp_map_cloud_info.argtypes = [vp, vp]
     if path is None:
         _lib = L
     return L
