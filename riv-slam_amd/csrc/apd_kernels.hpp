@@ -973,6 +973,19 @@ __device__ __forceinline__ NNStart nn_warm_start(const CloudDesc& src, int M, co
 
 // What every search ends with, for the wave that holds the final (merged) minima: the exact index of each point's neighbour, ties
 // settled, and the record the next search keeps its neighbour by.  Lanes without a point come in with pidx = -1 (or kept).
+//
+// The keep record needs the second smallest of all SCANNED distances (as a multiset).  The chunk scans only hand over g1 / g2 = the two
+// smallest CHUNK MINIMA; the rest comes from the re-scan of the winner's chunk c* below, which recomputes its sixteen distances anyway:
+//     second smallest scanned distance = min( second smallest chunk minimum, second smallest distance inside c* ),
+// because the runner-up is either another chunk's best target -- that chunk's minimum, and the smallest minimum but one -- or a target of
+// c* itself.  Both sides are multisets of the same fp32 numbers (the re-scan uses the scan's arithmetic, the `d == best` test relies on it
+// already; beyond the cloud both see +inf), so the record is bit for bit what tracking a runner-up in every chunk scan gave, at two vector
+// instructions less per pair of targets.  It holds scan by scan: a chunk enters once per point (the seed group is taken out of `cand`,
+// the waves of a block take disjoint groups), and were one scanned twice its minimum would be counted twice on both sides alike.  A chunk
+// minimum equals `best` exactly when the chunk is c* or a tie, so the lanes that do not re-scan need nothing: a tie ends with sb = 0 or,
+// settled, with g2 = best from the two equal minima; without any chunk only g1 is used; g1 != best gives sb = 0; kept lanes write no
+// record.  Everything never scanned stays covered by the radius term of sb.  (k_nn_compact's point-serial path comes in with g1 / g2 over
+// the TARGETS inside the radius: the winner's runner-up is one of those, or lies beyond the radius -- the min with it changes nothing.)
 template <int S>
 __device__ __forceinline__ void nn_finish(const CloudDesc& tgt, const Work& w, int pair, int lane, bool skin_on, float k_mul, float k_add, float (&px)[S],
                                           float (&py)[S], float (&pz)[S], float (&best)[S], unsigned (&bestc)[S], int (&pidx)[S], bool (&kept)[S],
@@ -1019,18 +1032,28 @@ __device__ __forceinline__ void nn_finish(const CloudDesc& tgt, const Work& w, i
         const int c0 = (int)(bestc[s] & kChunkMask) * kChunk;
         int j = -1, jorig = 0x7fffffff;
         float4 tq = make_float4(0.f, 0.f, 0.f, 0.f);
+        float r1 = __builtin_inff(), r2 = r1;  // smallest / second smallest of the chunk's sixteen distances, as a multiset
 #pragma unroll 1
         for (int h = 0; h < kChunk; h += 8) {  // eight loads in flight at a time: 32 registers, not 64
           float4 t[8];
 #pragma unroll
           for (int jj = 0; jj < 8; jj++) t[jj] = G(tgt.pts)[min(c0 + h + jj, M - 1)];
 #pragma unroll
-          for (int jj = 0; jj < 8; jj++) {
-            const float d = sqdist1(t[jj].x, t[jj].y, t[jj].z, px[s], py[s], pz[s]);
-            const int po = __float_as_int(t[jj].w);  // (the sorted points carry their original index in .w)
-            if (c0 + h + jj < M && d == best[s] && po < jorig) jorig = po, j = c0 + h + jj, tq = t[jj];
+          for (int jj = 0; jj < 8; jj += 2) {
+            float dd[2];
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+              const float d = sqdist1(t[jj + u].x, t[jj + u].y, t[jj + u].z, px[s], py[s], pz[s]);
+              const int po = __float_as_int(t[jj + u].w);  // (the sorted points carry their original index in .w)
+              const bool in = c0 + h + jj + u < M;
+              if (in && d == best[s] && po < jorig) jorig = po, j = c0 + h + jj + u, tq = t[jj + u];
+              dd[u] = in ? d : __builtin_inff();  // (beyond the cloud: the scan saw +inf there)
+            }
+            r2 = fminf(r2, __builtin_amdgcn_fmed3f(r1, dd[0], dd[1]));  // (what the chunk scans did per pair of targets until this took it over)
+            r1 = fminf(fminf(r1, dd[0]), dd[1]);
           }
         }
+        g2[s] = fminf(g2[s], r2);
         if (j >= 0) {
           w.nnpt[(size_t)pair * w.nstride + pidx[s]] = make_float4(tq.x, tq.y, tq.z, __int_as_float(j));
           bestc[s] |= kKeptBit;
@@ -1092,7 +1115,7 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
 
   bool all_hinted = hinted_in;
   float bestR[S], sk_mul[S], sk_add[S];   // pruning radius of the point and how it follows `best` (kept points: always -1)
-  float g1[S], g2[S];                     // smallest and second smallest computed distance among the SCANNED targets
+  float g1[S], g2[S];                     // smallest and second smallest CHUNK MINIMUM among the scanned chunks (nn_finish adds the winner's own runner-up)
   const bool skin_on = !cold && w.nnaux != nullptr && w.skin_mul > 0.f;
   const float k_mul = skin_on ? w.skin_mul : 1.f, k_add = skin_on ? w.skin_add : 0.f;
 #pragma unroll
@@ -1183,9 +1206,9 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
       const int ch = __builtin_ctz(cmask);
       cmask &= cmask - 1;
       n_cscan++;
-      float m[S], m2[S];  // smallest / second smallest distance of this chunk (v_min3 + v_med3 + v_min per two targets)
+      float m[S];  // smallest distance of this chunk (one v_min3 per two targets; the chunk's runner-up is nn_finish's business)
 #pragma unroll
-      for (int s = 0; s < S; s++) m[s] = inf, m2[s] = inf;
+      for (int s = 0; s < S; s++) m[s] = inf;
 #pragma unroll
       for (int jj = 0; jj < kChunk / 2; jj++) {
         // (throughput kernel: the compiler may not pull all sixteen targets' LDS reads to the top of the scan -- four at a time keep
@@ -1212,14 +1235,13 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
             d0 = sqdist1(A.x, A.z, Z.x, px[s], py[s], pz[s]);
             d1 = sqdist1(A.y, A.w, Z.y, px[s], py[s], pz[s]);
           }
-          m2[s] = fminf(m2[s], __builtin_amdgcn_fmed3f(m[s], d0, d1));
           m[s] = fminf(fminf(m[s], d0), d1);
         }
       }
       const unsigned c = (unsigned)(g * kGroupChunks + ch);
 #pragma unroll
       for (int s = 0; s < S; s++) {
-        g2[s] = fminf(fmaxf(g1[s], m[s]), fminf(g2[s], m2[s]));
+        g2[s] = __builtin_amdgcn_fmed3f(g1[s], g2[s], m[s]);  // (g1 <= g2 from the inf, inf start on: the middle one is the new runner-up)
         g1[s] = fminf(g1[s], m[s]);
         if (m[s] < best[s]) best[s] = m[s], bestc[s] = c, bestR[s] = fmaf(m[s], sk_mul[s], sk_add[s]);
         else if (m[s] == best[s] && m[s] < inf && (bestc[s] & kChunkMask) != c) bestc[s] |= kTieBit;
@@ -1390,7 +1412,7 @@ __device__ __forceinline__ void nn_search(const CloudDesc& src, const CloudDesc&
           if ((co & kChunkMask) != (cc & kChunkMask)) cc |= kTieBit;
           cc |= co & kTieBit;
         }
-        const float2 gg = mrg2[(o * S + s) * 64 + lane];  // the waves scanned disjoint sets of targets
+        const float2 gg = mrg2[(o * S + s) * 64 + lane];  // the waves scanned disjoint sets of chunks: the two smallest chunk minima of the union
         a2 = fminf(fmaxf(a1, gg.x), fminf(a2, gg.y));
         a1 = fminf(a1, gg.x);
       }
