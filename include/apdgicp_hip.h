@@ -40,7 +40,8 @@ extern "C" {
                                       still 6 (additive, nothing existing changed): + the apdgicp_scan_filter_* object (range gate, voxel grid, outlier removal);
                                       still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal);
                                       still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal);
-                                      still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres) */
+                                      still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres);
+                                      still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -710,6 +711,76 @@ int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const 
 int apdgicp_map_cloud_points(apdgicp_map_cloud* m, const float** device_xyzi, int64_t* n);
 int apdgicp_map_cloud_copy(apdgicp_map_cloud* m, float* dst_xyzi, int64_t capacity_points, int dst_on_device);
 int apdgicp_map_cloud_info(apdgicp_map_cloud* m, apdgicp_map_cloud_stats* info);
+
+/* ------------------------------------------------------------------ Scan Context place recognition
+ * radar_graph_slam::SCManager (radar_graph_slam/src/radar_graph_slam/Scancontext.cpp, "SC:"), called from
+ * LoopDetector::performScanContextLoopClosure (loop_detector.cpp:208) with sc_dist_thresh 0.5 and sc_azimuth_range 56.5.  The database of
+ * descriptors lives in device memory.  Two knobs generalise the reference's cost limits: num_candidates (the reference scores the 3 nearest
+ * ring keys; 0 or >= n: every candidate) and search_ratio (the reference tries the shifts within 0.1 * S / 2 of the sector-key alignment; 1.0:
+ * all).  R = num_ring, S = num_sector, each 1 .. 64.
+ *   S1 (SC:162-214) descriptor.  Per point (x, y, intensity), z unused: range = sqrtf(x*x + y*y), fp32, every operation rounded on its own;
+ *      angle = (float)(((double)atan2f(x, y) - M_PI_2) * 180.0 / M_PI) with apd_atan2f (note the argument order); the point is skipped if
+ *      fabsf(angle) > azimuth_max or (double)range > max_radius; ring = clamp((int)ceil(((double)range / max_radius) * R), 1, R);
+ *      sector = clamp((int)ceil((((double)angle - azimuth_min) / (azimuth_max - azimuth_min)) * S), 1, S); bin[ring-1][sector-1] = the maximum
+ *      intensity among its points with intensity > -1000, 0 for a bin nobody wrote.  Stored as R x S fp32, ring-major (exact: every entry is
+ *      an intensity or 0); every later operation is fp64 on the widened values.
+ *   S2 (SC:217-246) ring_key[r] = (float)(sum_c d[r][c] / S); sector_key[c] = sum_r d[r][c] / R; col_norm[c] = sqrt(sum_r d[r][c]^2): fp64,
+ *      ascending index, one accumulator, unfused; computed once, when the descriptor is added.
+ *   S3 (SC:284-305) query_id < num_exclude_recent: no loop, zero matches.  Otherwise the candidate set is the given ids with
+ *      query_id - id >= num_exclude_recent, in the given order; "position" is the position in this filtered list, n its length.
+ *   S4 (SC:322-328) d2 = sum_r (q[r] - k[r])^2 in fp32, ascending r, result += diff * diff (nanoflann's L2_Simple_Adaptor).  The
+ *      num_candidates smallest by (d2, position) are kept, in this order: their ring-key rank.  num_candidates <= 0 or >= n: all, same order.
+ *   S5 (SC:104-124, :42-62) shifted(B, s)[:, j] = B[:, (j - s) mod S].  a = argmin_s sqrt(sum_c (vq[c] - vk[(c - s) mod S])^2), ascending c,
+ *      the square roots compared with strict < over s = 0 .. S-1 from 1e7 (the lowest shift wins a tie).
+ *   S6 (SC:127-159, :80-101) radius = (int)floor(0.5 * search_ratio * S + 0.5).  Shifts: a and (a +- i) mod S, i = 1 .. radius, visited in
+ *      ascending numeric order.  Per shift s, per column c ascending: n1 = col_norm_q[c], n2 = col_norm_k[(c - s) mod S]; the column is skipped
+ *      if either is 0; otherwise sum += (sum_r q[r][c] * k[r][(c - s) mod S], ascending r) / (n1 * n2) and eff += 1.  dist(s) = 1.0 - sum /
+ *      (double)eff (NaN when eff == 0).  The minimum over the shifts with strict < from 1e7; a NaN never wins; a candidate whose shifts all
+ *      give NaN reports distance NaN and shift 0.
+ *   S7 matches ranked by (distance, ring-key rank), NaN last; the first top_k are returned.  loop_id = the first match's id if its distance
+ *      < dist_thresh, else -1; yaw = (float)((double)(float)(shift * ((azimuth_max - azimuth_min) / S)) * M_PI / 180.0) of the first match
+ *      (SC:374), 0 without a match.
+ *   S8 deviations: a point with a non-finite x, y or intensity is skipped; a stored -0.0 is written as +0.0; the candidate set is rebuilt at
+ *      every call (the reference rebuilds its tree every 10th call and indexes the current list with the stale tree's positions); fewer than
+ *      num_candidates candidates are scored once each (the reference re-scores index 0); ring-key ties go to the lower position; the
+ *      summation orders of S2, S5, S6 are the ones above (Eigen's depend on its SIMD width).
+ * One detect call waits for the device once.  set_params may change S3 .. S7 parameters at any time, S1 parameters only while the database
+ * is empty.  The capacity doubles as descriptors arrive, up to 65 536. */
+typedef struct {
+  int32_t num_ring, num_sector;                /* 40, 20 */
+  double max_radius, azimuth_max, azimuth_min; /* 80.0, 56.5, -56.5 (what setAzimuthRange(56.5) leaves, loop_detector.cpp:89) */
+  int32_t num_exclude_recent, num_candidates;  /* 10, 3 */
+  double search_ratio, dist_thresh;            /* 0.1, 0.5 */
+} apdgicp_scan_context_params;
+typedef struct {
+  int32_t id, shift;  /* keyframe id; the column shift of the minimum distance */
+  double distance;    /* S6 */
+  float ring_d2;      /* S4 */
+  int32_t ring_rank;  /* S4: 0 = nearest ring key */
+} apdgicp_scan_context_match;
+typedef struct apdgicp_scan_context apdgicp_scan_context;
+int apdgicp_scan_context_default_params(apdgicp_scan_context_params* p);  /* Scancontext.h's constants after setAzimuthRange(56.5) */
+int apdgicp_scan_context_create(const apdgicp_scan_context_params* params, int device, void* stream, apdgicp_scan_context** out);
+int apdgicp_scan_context_destroy(apdgicp_scan_context* h);
+int apdgicp_scan_context_set_params(apdgicp_scan_context* h, const apdgicp_scan_context_params* params);  /* SC:64-71 and the two knobs */
+/* SC:255-269 makeAndSaveScancontextAndKeys: S1 + S2 of one cloud (n >= 0 points, stride_bytes apart, host or device memory, e.g. the
+ * pointer apdgicp_scan_filter_points returns; intensity_offset_bytes < 0: intensity 0); *id = 0, 1, 2 ... in the order of the calls */
+int apdgicp_scan_context_add(apdgicp_scan_context* h, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device, int32_t* id);
+/* a ready descriptor (R x S floats, ring-major, host memory): S2 only (SC:258-265); for saved maps */
+int apdgicp_scan_context_add_descriptor(apdgicp_scan_context* h, const float* ring_major_RxS, int32_t* id);
+int apdgicp_scan_context_clear(apdgicp_scan_context* h);  /* forgets every descriptor; ids start at 0 again */
+int apdgicp_scan_context_size(apdgicp_scan_context* h, int32_t* n);
+/* SC:272-379 detectLoopClosureID: S3 .. S7.  matches: room for top_k records; *n_matches = min(top_k, kept candidates).  A candidate id
+ * out of range or given twice: APDGICP_ERR_INVALID_ARG. */
+int apdgicp_scan_context_detect(apdgicp_scan_context* h, int32_t query_id, const int32_t* candidate_ids, int32_t n_candidates, int32_t top_k,
+                                apdgicp_scan_context_match* matches, int32_t* n_matches, int32_t* loop_id, float* yaw_rad);
+/* the new keyframes of one LoopDetector::detect call (loop_detector.cpp:102) in one launch sequence: query q's candidates are
+ * cand_ids[cand_offsets[q] .. cand_offsets[q + 1]), its records matches[q * top_k ...]; the records equal those of single calls */
+int apdgicp_scan_context_detect_batch(apdgicp_scan_context* h, int32_t n_queries, const int32_t* query_ids, const int32_t* cand_offsets, const int32_t* cand_ids,
+                                      int32_t top_k, apdgicp_scan_context_match* matches, int32_t* n_matches, int32_t* loop_ids, float* yaws);
+/* reads back descriptors first .. first + count - 1 (SC:249-252 getConstRefRecentSCD and the keys): desc count x R x S floats, ring_keys
+ * count x R floats, sector_keys and col_norms count x S doubles; any destination may be NULL */
+int apdgicp_scan_context_descriptors(apdgicp_scan_context* h, int32_t first, int32_t count, float* desc, float* ring_keys, double* sector_keys, double* col_norms);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 #include "apd_ego.hpp"
 #include "apd_floor.hpp"
 #include "apd_map.hpp"
+#include "apd_scan_context.hpp"
 
 using namespace apd;
 
@@ -146,6 +147,32 @@ struct apdgicp_map_cloud {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
     for (DevBuf* b : {&stage, &pushed, &keys_a, &keys_b, &hist, &rs_bsum, &bsum, &bmin, &out, &state, &jobs.dev}) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_scan_context {
+  apdgicp_scan_context_params prm;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  int cap = 0, size = 0;  // descriptors the four database buffers hold / in use
+  DevBuf desc, ring_key, sector_key, col_norm;
+  DevBuf stage, hi1, lo1, inv1, rec, hi2, lo2, inv2, out;
+  CachedTable qtab, cand;
+  ScRec* h_out = nullptr;  // pinned
+  size_t h_out_cap = 0;
+  std::vector<uint32_t> seen;  // per id: the call that listed it last (duplicate check)
+  uint32_t epoch = 0;
+  ScDb db() const { return ScDb{desc.as<float>(), ring_key.as<float>(), sector_key.as<double>(), col_norm.as<double>()}; }
+  ScDb slot(int id) const {
+    const size_t R = (size_t)prm.num_ring, S = (size_t)prm.num_sector;
+    return ScDb{desc.as<float>() + id * R * S, ring_key.as<float>() + id * R, sector_key.as<double>() + id * S, col_norm.as<double>() + id * S};
+  }
+  ~apdgicp_scan_context() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (h_out) (void)hipHostFree(h_out);
+    for (DevBuf* b : {&desc, &ring_key, &sector_key, &col_norm, &stage, &hi1, &lo1, &inv1, &rec, &hi2, &lo2, &inv2, &out, &qtab.dev, &cand.dev}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -2398,6 +2425,304 @@ int apdgicp_map_cloud_info(apdgicp_map_cloud* m, apdgicp_map_cloud_stats* info) 
   if (!m || !info) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
   *info = m->info;
   return 0;
+}
+
+// ------------------------------------------------------------------ Scan Context place recognition (apd_scan_context.hpp)
+static_assert(sizeof(ScRec) == 24 && sizeof(apdgicp_scan_context_match) == 24 && sizeof(apdgicp_scan_context_params) == 56, "scan context record layouts");
+static_assert(offsetof(ScRec, distance) == offsetof(apdgicp_scan_context_match, distance) && offsetof(ScRec, ring_rank) == offsetof(apdgicp_scan_context_match, ring_rank),
+              "ScRec is apdgicp_scan_context_match");
+
+namespace {
+constexpr int kScMaxDescriptors = 65536, kScFirstCapacity = 256;
+
+int sc_check_params(const apdgicp_scan_context_params& p) {
+  if (p.num_ring < 1 || p.num_ring > SC_MAX_DIM || p.num_sector < 1 || p.num_sector > SC_MAX_DIM) return fail(APDGICP_ERR_INVALID_ARG, "num_ring and num_sector must be 1 .. 64");
+  if (!(p.max_radius > 0.0) || !std::isfinite(p.max_radius)) return fail(APDGICP_ERR_INVALID_ARG, "max_radius must be positive and finite");
+  if (!std::isfinite(p.azimuth_max) || !std::isfinite(p.azimuth_min) || !(p.azimuth_max > p.azimuth_min)) return fail(APDGICP_ERR_INVALID_ARG, "azimuth_max must be above azimuth_min");
+  if (p.num_exclude_recent < 0) return fail(APDGICP_ERR_INVALID_ARG, "num_exclude_recent is negative");
+  if (!std::isfinite(p.search_ratio) || p.search_ratio < 0.0 || p.search_ratio > 2.0) return fail(APDGICP_ERR_INVALID_ARG, "search_ratio must be 0 .. 2");
+  if (p.dist_thresh != p.dist_thresh) return fail(APDGICP_ERR_INVALID_ARG, "dist_thresh is NaN");
+  return 0;
+}
+
+// room for one more descriptor: the capacity doubles (the old contents are copied on the stream), up to 65 536
+int sc_reserve(apdgicp_scan_context* h) {
+  if (h->size < h->cap) return 0;
+  if (h->size >= kScMaxDescriptors) return fail(APDGICP_ERR_UNSUPPORTED, "the database is full (65536 descriptors)");
+  const size_t R = (size_t)h->prm.num_ring, S = (size_t)h->prm.num_sector;
+  const int ncap = h->cap ? 2 * h->cap : kScFirstCapacity;
+  const size_t per[4] = {R * S * 4, R * 4, S * 8, S * 8};
+  DevBuf* old[4] = {&h->desc, &h->ring_key, &h->sector_key, &h->col_norm};
+  DevBuf fresh[4];
+  for (int b = 0; b < 4; b++) {
+    const int rc = fresh[b].ensure(per[b] * ncap);
+    if (rc < 0) {
+      for (DevBuf& f : fresh) f.release();
+      return rc;
+    }
+  }
+  hipError_t e = hipSuccess;
+  for (int b = 0; b < 4 && e == hipSuccess; b++)
+    if (h->size) e = hipMemcpyAsync(fresh[b].p, old[b]->p, per[b] * h->size, hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    for (DevBuf& f : fresh) f.release();
+    return fail(APDGICP_ERR_HIP, std::string("scan context: growing the database: ") + hipGetErrorString(e));
+  }
+  for (int b = 0; b < 4; b++) {
+    old[b]->release();
+    *old[b] = fresh[b];
+  }
+  h->cap = ncap;
+  return 0;
+}
+
+int sc_build(apdgicp_scan_context* h, const float* dev_pts, int64_t n, int stride, int ioff, const float* dev_ready) {
+  const apdgicp_scan_context_params& p = h->prm;
+  const ScGeom g{p.num_ring, p.num_sector, p.max_radius, p.azimuth_max, p.azimuth_min};
+  const size_t lds = (size_t)(APD_ATAN_TAB_ROWS * APD_ATAN_TAB_STRIDE + p.num_ring * p.num_sector) * 4;
+  hipLaunchKernelGGL(k_sc_build, dim3(1), dim3(SC_BLK), lds, h->stream, dev_pts, (long long)n, stride, ioff, dev_ready, g, h->slot(h->size));
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipStreamSynchronize(h->stream));  // the caller's memory is free again when the call returns
+  h->size++;
+  return 0;
+}
+}  // namespace
+
+int apdgicp_scan_context_default_params(apdgicp_scan_context_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  memset(p, 0, sizeof(*p));
+  p->num_ring = 40, p->num_sector = 20, p->max_radius = 80.0;  // Scancontext.h: PC_NUM_RING, PC_NUM_SECTOR, PC_MAX_RADIUS
+  p->azimuth_max = 56.5, p->azimuth_min = -56.5;               // SC:67-71 after loop_detector.cpp:89
+  p->num_exclude_recent = 10, p->num_candidates = 3;           // NUM_EXCLUDE_RECENT, NUM_CANDIDATES_FROM_TREE
+  p->search_ratio = 0.1, p->dist_thresh = 0.5;                 // SEARCH_RATIO, sc_dist_thresh
+  return 0;
+}
+
+int apdgicp_scan_context_create(const apdgicp_scan_context_params* params, int device, void* stream, apdgicp_scan_context** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_scan_context_params p;
+    apdgicp_scan_context_default_params(&p);
+    if (params) p = *params;
+    APD_TRY(sc_check_params(p));
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_scan_context> h(new apdgicp_scan_context);
+    h->prm = p;
+    h->device = device;
+    if (stream) {
+      h->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+      h->own_stream = true;
+    }
+    *out = h.release();
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_destroy(apdgicp_scan_context* h) {
+  return guarded([&]() -> int {
+    if (h) (void)hipSetDevice(h->device);
+    delete h;
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_set_params(apdgicp_scan_context* h, const apdgicp_scan_context_params* params) {
+  return guarded([&]() -> int {
+    if (!h || !params) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(sc_check_params(*params));
+    const apdgicp_scan_context_params& o = h->prm;
+    const bool s1 = params->num_ring != o.num_ring || params->num_sector != o.num_sector || params->max_radius != o.max_radius ||
+                    params->azimuth_max != o.azimuth_max || params->azimuth_min != o.azimuth_min;
+    if (s1 && h->size) return fail(APDGICP_ERR_INVALID_ARG, "the descriptor's geometry (S1) can change only while the database is empty");
+    if (s1) {  // the buffers are laid out by R and S
+      APD_HIP(hipSetDevice(h->device));
+      APD_HIP(hipStreamSynchronize(h->stream));
+      for (DevBuf* b : {&h->desc, &h->ring_key, &h->sector_key, &h->col_norm}) b->release();
+      h->cap = 0;
+    }
+    h->prm = *params;
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_add(apdgicp_scan_context* h, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device, int32_t* id) {
+  return guarded([&]() -> int {
+    if (!h || !id || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative point count");
+    if (n > 2147483647ll) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^31 - 1 points");
+    if (stride_bytes < 8 || stride_bytes % 4 || stride_bytes > (1ll << 20)) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 8");
+    if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity offset outside the point");
+    APD_HIP(hipSetDevice(h->device));
+    APD_TRY(sc_reserve(h));
+    const float* src = xyz;
+    if (n > 0 && !on_device) {
+      APD_TRY(h->stage.ensure((size_t)n * stride_bytes));  // (every earlier call has waited for its own work)
+      const size_t used = std::max<int64_t>(8, intensity_offset_bytes >= 0 ? intensity_offset_bytes + 4 : 8);  // of the last point
+      APD_HIP(hipMemcpyAsync(h->stage.p, xyz, (size_t)(n - 1) * stride_bytes + used, hipMemcpyHostToDevice, h->stream));
+      src = h->stage.as<float>();
+    }
+    APD_TRY(sc_build(h, src, n, (int)(stride_bytes / 4), intensity_offset_bytes >= 0 ? (int)(intensity_offset_bytes / 4) : -1, nullptr));
+    *id = h->size - 1;
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_add_descriptor(apdgicp_scan_context* h, const float* ring_major_RxS, int32_t* id) {
+  return guarded([&]() -> int {
+    if (!h || !id || !ring_major_RxS) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(h->device));
+    APD_TRY(sc_reserve(h));
+    const size_t bytes = (size_t)h->prm.num_ring * h->prm.num_sector * 4;
+    APD_TRY(h->stage.ensure(bytes));
+    APD_HIP(hipMemcpyAsync(h->stage.p, ring_major_RxS, bytes, hipMemcpyHostToDevice, h->stream));
+    APD_TRY(sc_build(h, nullptr, 0, 0, -1, h->stage.as<float>()));
+    *id = h->size - 1;
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_clear(apdgicp_scan_context* h) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    h->size = 0;
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_size(apdgicp_scan_context* h, int32_t* n) {
+  if (!h || !n) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n = h->size;
+  return 0;
+}
+
+int apdgicp_scan_context_detect_batch(apdgicp_scan_context* h, int32_t n_queries, const int32_t* query_ids, const int32_t* cand_offsets, const int32_t* cand_ids,
+                                      int32_t top_k, apdgicp_scan_context_match* matches, int32_t* n_matches, int32_t* loop_ids, float* yaws) {
+  return guarded([&]() -> int {
+    if (!h || !query_ids || !cand_offsets || !matches || !n_matches) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (n_queries < 1 || n_queries > 65535) return fail(APDGICP_ERR_INVALID_ARG, "n_queries must be 1 .. 65535");
+    if (top_k < 1) return fail(APDGICP_ERR_INVALID_ARG, "top_k must be at least 1");
+    const apdgicp_scan_context_params& p = h->prm;
+    const int R = p.num_ring, S = p.num_sector;
+    // ---- S3 on the host: the ids are host memory
+    std::vector<ScQuery> qs((size_t)n_queries);
+    std::vector<int> cand;
+    h->seen.resize((size_t)h->size, 0u);
+    int max_n = 0, max_keep = 0, max_out = 0;
+    int64_t total_out = 0;
+    for (int q = 0; q < n_queries; q++) {
+      const int qid = query_ids[q];
+      const int64_t c0 = cand_offsets[q], c1 = cand_offsets[q + 1];
+      if (qid < 0 || qid >= h->size) return fail(APDGICP_ERR_INVALID_ARG, "unknown query id " + std::to_string(qid));
+      if (c0 < 0 || c1 < c0 || (c1 > c0 && !cand_ids)) return fail(APDGICP_ERR_INVALID_ARG, "candidate offsets must ascend from 0");
+      if (++h->epoch == 0) {  // the counter wrapped: every mark is stale
+        std::fill(h->seen.begin(), h->seen.end(), 0u);
+        h->epoch = 1;
+      }
+      ScQuery& Q = qs[(size_t)q];
+      Q.qid = qid, Q.base = (int)cand.size(), Q.out_base = (int)total_out;
+      for (int64_t c = c0; c < c1; c++) {
+        const int id = cand_ids[c];
+        if (id < 0 || id >= h->size) return fail(APDGICP_ERR_INVALID_ARG, "candidate id " + std::to_string(id) + " is not in the database");
+        if (h->seen[(size_t)id] == h->epoch) return fail(APDGICP_ERR_INVALID_ARG, "candidate id " + std::to_string(id) + " is given twice");
+        h->seen[(size_t)id] = h->epoch;
+        if (qid >= p.num_exclude_recent && (int64_t)qid - id >= p.num_exclude_recent) cand.push_back(id);  // SC:284, :300-305
+      }
+      Q.n = (int)cand.size() - Q.base;
+      Q.keep = (p.num_candidates <= 0 || p.num_candidates >= Q.n) ? Q.n : p.num_candidates;
+      Q.m_out = std::min(top_k, Q.keep);
+      total_out += Q.m_out;
+      max_n = std::max(max_n, Q.n), max_keep = std::max(max_keep, Q.keep), max_out = std::max(max_out, Q.m_out);
+      if (cand.size() > (size_t)(1 << 30)) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^30 candidates in one call");
+    }
+    const size_t total = cand.size();
+    if (total) {
+      APD_HIP(hipSetDevice(h->device));
+      APD_TRY(h->qtab.upload(qs.data(), qs.size() * sizeof(ScQuery), h->stream));
+      APD_TRY(h->cand.upload(cand.data(), total * sizeof(int), h->stream));
+      APD_TRY(h->hi1.ensure(total * 8));
+      APD_TRY(h->lo1.ensure(total * 4));
+      APD_TRY(h->inv1.ensure(total * 4));
+      APD_TRY(h->rec.ensure(total * sizeof(ScRec)));
+      APD_TRY(h->hi2.ensure(total * 8));
+      APD_TRY(h->lo2.ensure(total * 4));
+      APD_TRY(h->inv2.ensure(total * 4));
+      APD_TRY(h->out.ensure((size_t)total_out * sizeof(ScRec)));
+      if ((size_t)total_out > h->h_out_cap) {
+        if (h->h_out) APD_HIP(hipHostFree(h->h_out));
+        h->h_out = nullptr, h->h_out_cap = 0;
+        APD_HIP(hipHostMalloc((void**)&h->h_out, (size_t)total_out * 2 * sizeof(ScRec), hipHostMallocDefault));
+        h->h_out_cap = (size_t)total_out * 2;
+      }
+      const ScQuery* dq = h->qtab.dev.as<ScQuery>();
+      const int* dc = h->cand.dev.as<int>();
+      const unsigned nq = (unsigned)n_queries;
+      const int radius = (int)std::floor(0.5 * p.search_ratio * (double)S + 0.5);  // SC:134 (C's round for a non-negative argument)
+      const int region = sc_region_doubles(R, S) * 8;
+      const int W = std::max(1, std::min(SC_MAX_WAVES, 65536 / region - 1));
+      hipLaunchKernelGGL(k_sc_ring, dim3((unsigned)((max_n + SC_BLK - 1) / SC_BLK), nq), dim3(SC_BLK), 0, h->stream, h->ring_key.as<float>(), R, dq, dc,
+                         h->hi1.as<unsigned long long>(), h->lo1.as<unsigned>());
+      hipLaunchKernelGGL(k_sc_rank, dim3((unsigned)((max_n + SC_BLK - 1) / SC_BLK), nq), dim3(SC_BLK), 0, h->stream, h->hi1.as<unsigned long long>(),
+                         h->lo1.as<unsigned>(), dq, 0, h->inv1.as<int>());
+      hipLaunchKernelGGL(k_sc_dist, dim3((unsigned)((max_keep + W - 1) / W), nq), dim3(64 * W), (size_t)(1 + W) * region, h->stream, h->db(), R, S, radius, dq, dc,
+                         h->inv1.as<int>(), h->hi1.as<unsigned long long>(), h->rec.as<ScRec>(), h->hi2.as<unsigned long long>(), h->lo2.as<unsigned>());
+      hipLaunchKernelGGL(k_sc_rank, dim3((unsigned)((max_keep + SC_BLK - 1) / SC_BLK), nq), dim3(SC_BLK), 0, h->stream, h->hi2.as<unsigned long long>(),
+                         h->lo2.as<unsigned>(), dq, 1, h->inv2.as<int>());
+      hipLaunchKernelGGL(k_sc_emit, dim3((unsigned)((max_out + SC_BLK - 1) / SC_BLK), nq), dim3(SC_BLK), 0, h->stream, dq, h->inv2.as<int>(), h->rec.as<ScRec>(),
+                         h->out.as<ScRec>());
+      APD_HIP(hipGetLastError());
+      APD_HIP(hipMemcpyAsync(h->h_out, h->out.p, (size_t)total_out * sizeof(ScRec), hipMemcpyDeviceToHost, h->stream));
+      APD_HIP(hipStreamSynchronize(h->stream));  // the call's one wait
+    }
+    for (int q = 0; q < n_queries; q++) {
+      const ScQuery& Q = qs[(size_t)q];
+      n_matches[q] = Q.m_out;
+      if (Q.m_out) memcpy(matches + (size_t)q * top_k, h->h_out + Q.out_base, (size_t)Q.m_out * sizeof(ScRec));
+      int loop = -1;
+      float yaw = 0.f;
+      if (Q.m_out) {
+        const ScRec& m = h->h_out[Q.out_base];
+        if (m.distance < p.dist_thresh) loop = m.id;  // SC:359-361
+        yaw = (float)((double)(float)(m.shift * ((p.azimuth_max - p.azimuth_min) / (double)S)) * 3.14159265358979323846 / 180.0);  // SC:374, :18-21
+      }
+      if (loop_ids) loop_ids[q] = loop;
+      if (yaws) yaws[q] = yaw;
+    }
+    return 0;
+  });
+}
+
+int apdgicp_scan_context_detect(apdgicp_scan_context* h, int32_t query_id, const int32_t* candidate_ids, int32_t n_candidates, int32_t top_k,
+                                apdgicp_scan_context_match* matches, int32_t* n_matches, int32_t* loop_id, float* yaw_rad) {
+  if (n_candidates < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative candidate count");
+  const int32_t off[2] = {0, n_candidates};
+  return apdgicp_scan_context_detect_batch(h, 1, &query_id, off, candidate_ids, top_k, matches, n_matches, loop_id, yaw_rad);
+}
+
+int apdgicp_scan_context_descriptors(apdgicp_scan_context* h, int32_t first, int32_t count, float* desc, float* ring_keys, double* sector_keys, double* col_norms) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (first < 0 || count < 0 || (int64_t)first + count > h->size) return fail(APDGICP_ERR_INVALID_ARG, "descriptor range outside the database");
+    if (!count) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    const size_t R = (size_t)h->prm.num_ring, S = (size_t)h->prm.num_sector, c = (size_t)count;
+    const ScDb s = h->slot(first);
+    if (desc) APD_HIP(hipMemcpyAsync(desc, s.desc, c * R * S * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ring_keys) APD_HIP(hipMemcpyAsync(ring_keys, s.ring_key, c * R * 4, hipMemcpyDeviceToHost, h->stream));
+    if (sector_keys) APD_HIP(hipMemcpyAsync(sector_keys, s.sector_key, c * S * 8, hipMemcpyDeviceToHost, h->stream));
+    if (col_norms) APD_HIP(hipMemcpyAsync(col_norms, s.col_norm, c * S * 8, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
 }
 
 }  // extern "C"

@@ -105,6 +105,9 @@ SYMBOLS = [
     "apdgicp_floor_inliers", "apdgicp_floor_under_floor_filtered", "apdgicp_floor_copy", "apdgicp_floor_hypotheses", "apdgicp_floor_debug",
     "apdgicp_map_cloud_create", "apdgicp_map_cloud_destroy", "apdgicp_map_cloud_add_keyframe", "apdgicp_map_cloud_clear", "apdgicp_map_cloud_generate",
     "apdgicp_map_cloud_points", "apdgicp_map_cloud_copy", "apdgicp_map_cloud_info",
+    "apdgicp_scan_context_default_params", "apdgicp_scan_context_create", "apdgicp_scan_context_destroy", "apdgicp_scan_context_set_params",
+    "apdgicp_scan_context_add", "apdgicp_scan_context_add_descriptor", "apdgicp_scan_context_clear", "apdgicp_scan_context_size",
+    "apdgicp_scan_context_detect", "apdgicp_scan_context_detect_batch", "apdgicp_scan_context_descriptors",
 ]
 
 _lib = None
@@ -258,6 +261,17 @@ def load_library(path: str | None = None):
     L.apdgicp_map_cloud_points.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.apdgicp_map_cloud_copy.argtypes = [vp, vp, i64, i32]
     L.apdgicp_map_cloud_info.argtypes = [vp, vp]
+    L.apdgicp_scan_context_default_params.argtypes = [vp]
+    L.apdgicp_scan_context_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.apdgicp_scan_context_destroy.argtypes = [vp]
+    L.apdgicp_scan_context_set_params.argtypes = [vp, vp]
+    L.apdgicp_scan_context_add.argtypes = [vp, vp, i64, i64, i64, i32, C.POINTER(C.c_int32)]
+    L.apdgicp_scan_context_add_descriptor.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    L.apdgicp_scan_context_clear.argtypes = [vp]
+    L.apdgicp_scan_context_size.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apdgicp_scan_context_detect.argtypes = [vp, i32, vp, i32, i32, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+    L.apdgicp_scan_context_detect_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.apdgicp_scan_context_descriptors.argtypes = [vp, i32, i32, vp, vp, vp, vp]
     if path is None:
         _lib = L
     return L
