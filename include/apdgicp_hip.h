@@ -41,7 +41,8 @@ extern "C" {
                                       still 6 (additive): + the apdgicp_ego_velocity_* object (Doppler ego velocity, moving-point removal);
                                       still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal);
                                       still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres);
-                                      still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K) */
+                                      still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K);
+                                      still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -252,6 +253,74 @@ int apdgicp_wait_producer(apdgicp_handle* h, void* producer_stream);
  * work -- or their timing events -- against the handle without a host-side wait.  Every call of a handle ends with all
  * of its work joined back onto this stream. */
 int apdgicp_get_stream(apdgicp_handle* h, void** stream);
+
+/* ------------------------------------------------------------------ voxelized GICP as a mode of the handle
+ * fast_gicp::FastVGICP, the FAST_VGICP branch of select_registration_method() (registrations.cpp:62-70; it sets reg_resolution and
+ * leaves DIRECT1 / ADDITIVE).  "V:" = fast_apdgicp/include/fast_gicp/gicp/impl/fast_vgicp_impl.hpp, "VX:" = .../gicp/fast_vgicp_voxel.hpp.
+ * Covariances of both clouds are FastGICP::calculate_covariances (gicp/impl/fast_gicp_impl.hpp:255-312), line for line the computation
+ * of A:303-363 -- what apdgicp_compute_covariances does.  The kernels (riv-slam_amd/csrc/apd_vgicp.hpp) and the restatement the tests
+ * compare with (tests/vgicp_np.py) follow this list:
+ *   V1. Voxel coordinate (VX:158-160): c = (int32) floor(x / res - 0.5) per axis, x the fp64 value of the fp32 coordinate, a true fp64
+ *       division (not a multiplication by 1 / res).
+ *   V2. Validity and key range.  Target points must be finite with |c| < 2^20 per axis; otherwise apdgicp_linearize / apdgicp_align
+ *       (and apdgicp_vgicp_voxel_count) return APDGICP_ERR_INVALID_ARG and name the first offending point.  The key of a voxel is its
+ *       three coordinates, each biased by 2^20 into 21 bits, x highest, in a uint64.  A SOURCE point whose coordinate, after an offset
+ *       has been added, leaves that range, or whose transformed position is not finite, is a miss; the range is tested BEFORE the key
+ *       is packed, so an out-of-range coordinate never aliases a valid key.  The edges, exactly: a coordinate x = 2^20 res has
+ *       c = 2^20 - 1 and is still VALID; the first refused positions are x = (2^20 + 0.5) res (c = 2^20) and x = -(2^20 - 0.5) res
+ *       (c = -2^20); the last valid ones just inside them.
+ *   V3. Voxel order and sums (VX:129-156).  Voxels are numbered in ascending key order (= lexicographic (cx, cy, cz); the reference's
+ *       std::unordered_map has no defined order).  Within a voxel the mean and the six unique covariance entries are fp64 sums, started
+ *       at 0, over its points IN THE CALLER'S ORDER, then each divided by the count (ADDITIVE; ADDITIVE_WEIGHTED takes the same branch,
+ *       VX:138-141): counts, means and covariances are bit-equal to the reference's sequential loop.  A voxel that holds every point
+ *       is legal and is summed by one lane.  The map is a pure function of target, covariances, resolution and mode (the reference
+ *       rebuilds it in every computeTransformation, V:67); the handle caches it.
+ *   V4. Transform (V:84-85): q_r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r in fp64 -- unlike APD-GICP, whose search transforms in fp32.
+ *       Eigen's own summation order for Isometry3d * Vector4d is not pinned by the reference tree.
+ *   V5. Correspondences (V:86-94).  c(q) + each offset of DIRECT1 / DIRECT7 / DIRECT27 in the order of VX:17-43 ({0}; {0, +x, -x, +y,
+ *       -y, +z, -z}; (i - 1, j - 1, k - 1) with k fastest) is looked up; every hit is a correspondence (point, voxel) with
+ *       M = (C_voxel + R C_A R^T)^-1 (3x3 block, by cofactors); no distance gate.  linearize (V:119-180): e = mean_voxel - q,
+ *       w = sqrt(count), cost += w (e . (M e)), H += w J^T M J, b += w J^T (M e), J = [skew(q) | -I].  A point's correspondences are
+ *       added in offset order, points in the caller's order one per lane; lanes, waves and blocks are added in a fixed tree / block
+ *       order in fp64 (the reference's own order depends on the OpenMP schedule): the same bits on every run.
+ *   V6. Frozen state (V:183-204).  compute_error evaluates the same cost at the trial pose over the voxel indices of the last linearize
+ *       and the M of the last linearize POSE.  The handle stores the index per (point, offset) (4 bytes) and that pose and recomputes M
+ *       with the same device function -- the same bits as a stored M (6 doubles per correspondence: 1.3 kB per point for DIRECT27).
+ *       Which of the two is faster has not been measured.
+ *   V7. Degenerate cases.  No correspondence at a linearize inside align: the loop stops there with converged = 0, lm_failed = 0,
+ *       T = the pose so far, n_matched = 0 (the reference would solve a singular system).  max_correspondence_distance is ignored, as in
+ *       the reference.  MULTIPLICATIVE: APDGICP_ERR_UNSUPPORTED (the ROS factory never selects it).
+ * With the mode on, apdgicp_linearize / apdgicp_compute_error run these kernels; apdgicp_align and apdgicp_align_host_loop both run the
+ * host-driven loop of apdgicp_align_host_loop over them (trace, final Hessian and apdgicp_result as there; n_matched = the number of
+ * correspondences, up to 27 per source point: the int32 field saturates at 2^31 - 1, i.e. beyond 79 million source points with DIRECT27); apdgicp_get_correspondences / apdgicp_get_mahalanobis return APDGICP_ERR_UNSUPPORTED; fitness_score,
+ * nearest_neighbours*, transform_source and get_points are unchanged.  The APD flags of apdgicp_params have no meaning for this cost.
+ * The map is kept until the target changes (set_target with another token, set_covariances(TARGET), swap_source_and_target,
+ * clear_target, a parameter change that invalidates the covariances) or the resolution / mode does.  The handle tracks this by identity, not
+ * by call: the map remembers which setting of the target's points and which writing of its covariances it was built from and is rebuilt
+ * whenever either is another one -- whichever entry point (with the mode on or off) replaced the cloud or recomputed the covariances in
+ * between; the frozen state behind apdgicp_compute_error is tied to the source's points and covariances and to the map in the same way
+ * (otherwise APDGICP_ERR_NO_INPUT).  With the mode off nothing differs
+ * from a handle that never had it on.  Batch handles have no such mode. */
+typedef enum { APDGICP_VGICP_DIRECT1 = 0, APDGICP_VGICP_DIRECT7 = 1, APDGICP_VGICP_DIRECT27 = 2 } apdgicp_vgicp_search;   /* NeighborSearchMethod, gicp_settings.hpp */
+typedef enum { APDGICP_VGICP_ADDITIVE = 0, APDGICP_VGICP_ADDITIVE_WEIGHTED = 1, APDGICP_VGICP_MULTIPLICATIVE = 2 } apdgicp_vgicp_mode;   /* VoxelAccumulationMode */
+typedef struct {
+  double resolution;         /* setResolution, V:31 ; default 1.0, V:22 ; finite and > 0 */
+  int32_t neighbor_search;   /* apdgicp_vgicp_search ; default DIRECT1, V:23 */
+  int32_t voxel_mode;        /* apdgicp_vgicp_mode ; default ADDITIVE, V:24 */
+} apdgicp_vgicp_params;
+void apdgicp_vgicp_default_params(apdgicp_vgicp_params* p);                      /* 1.0, DIRECT1, ADDITIVE: V:19-25 */
+/* p != NULL: the mode on with these parameters; NULL: back to APD-GICP / plain GICP as apdgicp_params says */
+int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p);
+int apdgicp_get_vgicp(const apdgicp_handle* h, apdgicp_vgicp_params* p, int* enabled);   /* either output may be NULL */
+/* number of voxels of the target's map (built if it is not there; needs the target only) */
+int apdgicp_vgicp_voxel_count(apdgicp_handle* h, int64_t* n_voxels);
+/* the map in voxel order (V3), host memory, any pointer may be NULL: coordinates (n x 3), counts, means (n x 3), covariances (n x 9,
+ * the 3x3 block); capacity >= the voxel count */
+int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9);
+/* voxel_correspondences_ of the last linearize: n_source x n_offsets voxel indices in offset order, -1 = miss */
+int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_source);
+/* Debug: how many times this handle has built a voxel map (the tests of the cache rules read it) */
+int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds);
 
 /* ------------------------------------------------------------------ batched registrations
  * Independent (source, target) pairs -- loop-closure candidates (loop_detector.cpp:222-236,404-423)

@@ -35,6 +35,11 @@ namespace fast_gicp {
 #ifndef FAST_GICP_GICP_SETTINGS_HPP  // same enum as gicp/gicp_settings.hpp:6 when that header is absent
 #define FAST_GICP_GICP_SETTINGS_HPP
 enum class RegularizationMethod { NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS };
+// ... and the two enums of gicp/gicp_settings.hpp:8,10 that FastVGICPHip's setters take (fast_vgicp_hip.hpp): the same names in the same order,
+// which source compatibility with callers of fast_gicp::FastVGICP requires.  DIRECT_RADIUS ("supported on only VGICP_CUDA" there) is accepted
+// by the type and refused at run time, like MULTIPLICATIVE.
+enum class NeighborSearchMethod { DIRECT27, DIRECT7, DIRECT1, DIRECT_RADIUS };
+enum class VoxelAccumulationMode { ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE };
 #endif
 
 template <typename PointSource, typename PointTarget>
@@ -384,6 +389,7 @@ class FastAPDGICPHip : public pcl::Registration<PointSource, PointTarget, float>
   }
 
  protected:
+  apdgicp_handle* handle() const { return handle_; }  // for classes that switch the handle into another mode (FastVGICPHip)
   static constexpr std::size_t kDeviceSingleQueryMin = 32768;  // targets above this size: a single stray query goes to the device (~60 us) instead of a host scan
   std::size_t target_size() const { return device_target_n_ ? device_target_n_ : (target_ ? target_->size() : 0); }
   void forget_search_state() {  // swap / clear: the cached pass, a device target's host copy and its size belong to the old clouds

@@ -173,6 +173,7 @@ class Engine {
     int n = 0;
     bool sorted = false;
     bool cov_valid = false;
+    uint64_t cov_gen = 0;            // Engine::cov_epoch when `cov` was last written (a launch of the covariance kernels, set_covariances): unique per writing
     uint64_t token = 0;
     // a host cloud of the tiled-sort size class stays in this pinned buffer until the sort has read it (TileJob::staged)
     char* stage_p = nullptr;
@@ -202,6 +203,7 @@ class Engine {
   apdgicp_params params;
   std::vector<Cloud> clouds;
   bool desc_dirty = true;
+  uint64_t cov_epoch = 0;            // counts the writings of any cloud's covariances (Cloud::cov_gen)
 
   // batch state
   int npairs = 0, nmax_src = 0, nmax_tgt = 0;
@@ -879,7 +881,7 @@ class Engine {
                            params.regularization, d_errflag.as<int>());
     }
     APD_HIP(hipGetLastError());
-    for (int i = 0; i < count; i++) clouds[ids[i]].cov_valid = true;
+    for (int i = 0; i < count; i++) clouds[ids[i]].cov_valid = true, clouds[ids[i]].cov_gen = ++cov_epoch;
     return 0;
   }
 
@@ -1180,7 +1182,7 @@ class Engine {
         hipLaunchKernelGGL(k_knn_and_search, dim3((unsigned)(knn_blocks + (t_nmax_src() + 63) / 64)), dim3(512), (size_t)8 * knn_coop_lds_bytes(4), sp.st,
                            d_desc.as<CloudDesc>(), d_ids.as<int>(), (int)pending_knn.size(), tasks, params.k_correspondences, params.regularization,
                            d_errflag.as<int>(), d_stats.as<unsigned long long>(), t_pairs(), (const PairState*)t_state(), w);
-        for (int id : pending_knn) clouds[id].cov_valid = true;
+        for (int id : pending_knn) clouds[id].cov_valid = true, clouds[id].cov_gen = ++cov_epoch;
         pending_knn.clear();
       } else {
         rc_nn = flush_pending_knn();

@@ -292,8 +292,10 @@ __global__ __launch_bounds__(SCAN_BLK) void k_map_scan_tiles(int* v, int n, int*
 // rank of a key among the keys of its wave with the same digit: the wave's running count of that digit (LDS, one row per wave) + the
 // lanes below it with the same digit in this round (eight ballots).  Then the digit's global base for this block (scanned histogram) and
 // the counts of the waves in front give every key its place.  Equal digits keep their order: the pass is stable.
-__global__ __launch_bounds__(MAP_RS_BLK) void k_map_rs_scatter(const unsigned long long* in, unsigned long long* out, int n, int shift, int nblk, const int* hist,
-                                                               const int* bsum) {
+// WITH_VALUE: every key carries a 32-bit payload along (vin -> vout; the voxelized GICP map sorts (voxel key, point index) pairs with it).
+template <bool WITH_VALUE>
+__device__ __forceinline__ void map_rs_scatter(const unsigned long long* in, const int* vin, unsigned long long* out, int* vout, int n, int shift, int nblk, const int* hist,
+                                               const int* bsum) {
   __shared__ int cnt[MAP_RS_BLK / 64][256];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int w = 0; w < MAP_RS_BLK / 64; w++) cnt[w][tid] = 0;
@@ -336,9 +338,20 @@ __global__ __launch_bounds__(MAP_RS_BLK) void k_map_rs_scatter(const unsigned lo
     const long long i = base + u * 64 + lane;
     if (i < n) {
       const int pos = cnt[wave][(int)(key[u] >> shift) & 255] + rank[u];
-      if (pos >= 0 && pos < n) out[pos] = key[u];
+      if (pos >= 0 && pos < n) {
+        out[pos] = key[u];
+        if constexpr (WITH_VALUE) vout[pos] = vin[i];
+      }
     }
   }
+}
+__global__ __launch_bounds__(MAP_RS_BLK) void k_map_rs_scatter(const unsigned long long* in, unsigned long long* out, int n, int shift, int nblk, const int* hist,
+                                                               const int* bsum) {
+  map_rs_scatter<false>(in, nullptr, out, nullptr, n, shift, nblk, hist, bsum);
+}
+__global__ __launch_bounds__(MAP_RS_BLK) void k_map_rs_scatter_pairs(const unsigned long long* in, const int* vin, unsigned long long* out, int* vout, int n, int shift,
+                                                                     int nblk, const int* hist, const int* bsum) {
+  map_rs_scatter<true>(in, vin, out, vout, n, shift, nblk, hist, bsum);
 }
 
 // ---- M5: the first key of every run of equal keys is a voxel; count, scan (k_scan_bsum -> n_out), centres

@@ -13,11 +13,47 @@
 #include "apd_floor.hpp"
 #include "apd_map.hpp"
 #include "apd_scan_context.hpp"
+#include "apd_vgicp.hpp"
 
 using namespace apd;
 
+// apdgicp_set_vgicp: the voxel map of the target and the frozen state of the last linearize (include/apdgicp_hip.h, V1 .. V7)
+struct VgState {
+  bool on = false;
+  apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
+  // What the cached pieces were made FROM, by identity: apdgicp_handle::cloud_gen names the points of a slot (and their order on the curve),
+  // Engine::Cloud::cov_gen one writing of a cloud's covariances.  A piece is used only while those still name what the handle holds, so no call
+  // that replaces a cloud or recomputes covariances -- with the mode on or off, through whichever entry point -- can leave a stale piece in use.
+  bool map_built = false;      // the map: target points map_tgt_gen, their covariances map_cov_gen, map_res, map_mode
+  uint64_t map_tgt_gen = 0, map_cov_gen = 0;
+  double map_res = 0.0;
+  int map_mode = 0;
+  uint64_t inv_src_gen = 0;    // inv_s: the inverse of the permutation of source points inv_src_gen, inv_n entries
+  int inv_n = 0;
+  bool have_lin = false;       // corr / T_lin: a linearize of source lin_src_gen with covariances lin_src_cov_gen against map number lin_build
+  uint64_t lin_src_gen = 0, lin_src_cov_gen = 0;
+  int64_t lin_build = 0;
+  int64_t n_vox = 0, builds = 0;
+  int n_src_lin = 0, noff_lin = 0;
+  double T_lin[12];
+  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum, scal, inv_t, inv_s, vkeys, vcount, vmean, vcov, corr, part, T, out;
+  void release() {
+    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &inv_t, &inv_s, &vkeys, &vcount, &vmean, &vcov, &corr, &part, &T, &out}) b->release();
+  }
+  VgMap map() const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), (int)n_vox}; }
+  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+};
+
 struct apdgicp_handle {
   Engine eng;
+  VgState vg;  // (released by ~apdgicp_handle, while the engine's stream still exists)
+  ~apdgicp_handle() {
+    if (vg.keys_a.p || vg.T.p || vg.inv_s.p) {
+      if (eng.stream) (void)hipStreamSynchronize(eng.stream);
+      vg.release();
+    }
+  }
+  uint64_t cloud_epoch = 0, cloud_gen[2] = {0, 0};  // cloud_gen[slot]: which setting of points the slot holds (0: none); swapped with the clouds
   bool pair_ready = false;   // work buffers / descriptors match the current source+target
   bool have_corr = false;    // correspondences_/mahalanobis_ hold a linearize result
   int n_src_at_corr = 0;
@@ -235,6 +271,265 @@ int scan_filter_compact(apdgicp_scan_filter* f, const float4* src, const float* 
   return 0;
 }
 
+// ---- voxelized GICP (include/apdgicp_hip.h V1 .. V7; kernels: apd_vgicp.hpp)
+constexpr int kVgBadNone = 0x7f7f7f7f;  // (what hipMemsetAsync(0x7f) leaves: above every point index)
+
+// V1 .. V3: the voxel map of the target.  Needs the target only; its covariances are computed here when they are missing.
+int vg_build_map(apdgicp_handle* h) {
+  Engine& e = h->eng;
+  VgState& v = h->vg;
+  if (e.clouds.size() < 2 || e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
+  if (v.prm.voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
+  APD_TRY(e.compute_covariances({kTgt}));
+  Engine::Cloud& c = e.clouds[kTgt];
+  if (v.map_built && v.map_tgt_gen == h->cloud_gen[kTgt] && v.map_cov_gen == c.cov_gen && v.map_res == v.prm.resolution && v.map_mode == v.prm.voxel_mode) return 0;
+  const int n = c.n;
+  APD_HIP(hipSetDevice(e.device));
+  APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
+  v.map_built = v.have_lin = false;
+  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+  const int64_t entries = 256ll * nblk;
+  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+  const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
+  APD_TRY(v.keys_a.ensure((size_t)n * 8));
+  APD_TRY(v.keys_b.ensure((size_t)n * 8));
+  APD_TRY(v.idx_a.ensure((size_t)n * 4));
+  APD_TRY(v.idx_b.ensure((size_t)n * 4));
+  APD_TRY(v.hist.ensure((size_t)entries * 4));
+  APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
+  APD_TRY(v.bsum.ensure((size_t)nhb * 4));
+  APD_TRY(v.scal.ensure(16));
+  APD_TRY(v.inv_t.ensure((size_t)n * 4));
+  int* scal = v.scal.as<int>();
+  APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
+  unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
+  int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
+  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
+  hipLaunchKernelGGL(k_vg_inverse_perm, dim3(nb256), dim3(256), 0, e.stream, c.perm.as<int>(), n, v.inv_t.as<int>());
+  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
+    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
+    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
+    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
+    std::swap(ks, kd), std::swap(is, id);
+  }
+  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
+  APD_HIP(hipGetLastError());
+  int hs[4];
+  APD_HIP(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (hs[0] != kVgBadNone)
+    return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: target point " + std::to_string(hs[0]) + " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " +
+                                             std::to_string(v.prm.resolution) + ")");
+  const int nv = hs[1];
+  if (nv < 1 || nv > n) return fail(APDGICP_ERR_INTERNAL, "voxelized GICP: inconsistent voxel count");
+  APD_TRY(v.vkeys.ensure((size_t)nv * 8));
+  APD_TRY(v.vcount.ensure((size_t)nv * 4));
+  APD_TRY(v.vmean.ensure((size_t)nv * 24));
+  APD_TRY(v.vcov.ensure((size_t)nv * 48));
+  hipLaunchKernelGGL(k_vg_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), v.inv_t.as<int>(),
+                     v.vkeys.as<unsigned long long>(), v.vcount.as<int>(), v.vmean.as<double>(), v.vcov.as<double>(), nv);
+  APD_HIP(hipGetLastError());
+  v.n_vox = nv;
+  v.map_built = true, v.map_tgt_gen = h->cloud_gen[kTgt], v.map_cov_gen = c.cov_gen, v.map_res = v.prm.resolution, v.map_mode = v.prm.voxel_mode;
+  v.builds++;
+  return 0;
+}
+
+// the pair, the map and the source's inverse permutation: everything k_vg_linearize reads
+int vg_prepare(apdgicp_handle* h) {
+  Engine& e = h->eng;
+  VgState& v = h->vg;
+  APD_TRY(ensure_pair(h));  // (both clouds sorted, both covariances there)
+  APD_TRY(vg_build_map(h));
+  const Engine::Cloud& s = e.clouds[kSrc];
+  if (!v.inv_s.p || v.inv_src_gen != h->cloud_gen[kSrc] || v.inv_n != s.n || (size_t)s.n * 4 > v.inv_s.cap) {
+    v.inv_n = 0;
+    if ((size_t)s.n * 4 > v.inv_s.cap) APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(v.inv_s.ensure((size_t)s.n * 4));
+    hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((s.n + 255) / 256)), dim3(256), 0, e.stream, s.perm.as<int>(), s.n, v.inv_s.as<int>());
+    APD_HIP(hipGetLastError());
+    v.inv_src_gen = h->cloud_gen[kSrc], v.inv_n = s.n;
+  }
+  return 0;
+}
+
+void colmajor_to_rows12(const double* T16, double* r12) {
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) r12[4 * i + j] = T16[i + 4 * j];
+}
+
+// linearize (V:119-180) at T (column-major 4x4)
+int vg_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
+  APD_TRY(vg_prepare(h));
+  Engine& e = h->eng;
+  VgState& v = h->vg;
+  const Engine::Cloud& s = e.clouds[kSrc];
+  const int n = s.n, noff = v.n_offsets(), nblk = (n + VG_BLK - 1) / VG_BLK;
+  if ((size_t)n * noff * 4 > v.corr.cap || (size_t)nblk * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.corr.ensure((size_t)n * noff * 4));
+  APD_TRY(v.part.ensure((size_t)nblk * VG_RED * 8));
+  APD_TRY(v.T.ensure(24 * sizeof(double)));
+  APD_TRY(v.out.ensure(64 * sizeof(double)));
+  colmajor_to_rows12(T16, v.T_lin);
+  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  const int want = H && b ? 1 : 0;
+  hipLaunchKernelGGL(k_vg_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(),
+                     v.prm.resolution, (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 0, v.out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (want) {
+    memcpy(H, e.h_probe, 36 * sizeof(double));
+    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
+  }
+  if (cost) *cost = e.h_probe[42];
+  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
+  v.lin_src_gen = h->cloud_gen[kSrc], v.lin_src_cov_gen = s.cov_gen, v.lin_build = v.builds;
+  return 0;
+}
+
+// compute_error (V:183-204): the voxel indices and the pose of the last linearize (V6)
+int vg_error(apdgicp_handle* h, const double* T16, double* cost) {
+  Engine& e = h->eng;
+  VgState& v = h->vg;
+  if (e.clouds.size() < 2) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
+  const Engine::Cloud &s = e.clouds[kSrc], &t = e.clouds[kTgt];
+  // the frozen state must still describe what the handle holds: the same source points and covariances, the same map of the same target
+  const bool frozen_ok = v.have_lin && s.n > 0 && s.n == v.n_src_lin && s.cov_valid && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_src_cov_gen == s.cov_gen &&
+                         v.inv_src_gen == h->cloud_gen[kSrc] && v.inv_n == s.n && v.map_built && v.lin_build == v.builds && t.cov_valid &&
+                         v.map_tgt_gen == h->cloud_gen[kTgt] && v.map_cov_gen == t.cov_gen && v.map_res == v.prm.resolution && v.map_mode == v.prm.voxel_mode;
+  if (!frozen_ok) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds, covariances and voxel map the handle holds now");
+  const int n = s.n, noff = v.noff_lin, nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_HIP(hipSetDevice(e.device));
+  double t24[24];
+  colmajor_to_rows12(T16, t24);
+  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
+  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(), noff,
+                     v.corr.as<int>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 27, v.out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  *cost = e.h_probe[42];
+  return 0;
+}
+
+// The reference's own control flow (L:55-173) on the host over two callables: lin(T16, H, b, &y0, &matched) and err(T16, &yi), the two
+// virtuals of LsqRegistration.  stop_on_empty (V7 of the voxelized mode): a linearize without a correspondence ends the loop.
+template <typename Lin, typename Err>
+int host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, Lin&& lin, Err&& err, bool stop_on_empty) {
+  Engine& e = h->eng;
+  const apdgicp_params& p = e.params;
+  float g[16];
+  if (guess) memcpy(g, guess, sizeof(g));
+  else identity16(g);
+  Rigid x0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) x0.m[4 * i + j] = (double)g[i + 4 * j];  // L:56
+  double lambda = -1.0;                                                   // L:58
+  bool converged = false;
+  int nr_iterations = 0, n_lin = 0, n_err = 0, failed = 0, matched = 0;
+  double final_H[36];
+  for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
+  double y0 = 0.0;
+  h->tr_lambda.clear(), h->tr_rho.clear(), h->tr_y0.clear(), h->tr_yi.clear(), h->tr_dnorm.clear(), h->tr_poses.clear();
+  h->trace_from_host_loop = true;
+  for (int it = 0; it < p.max_iterations && !converged; it++) {  // L:67
+    nr_iterations = it;
+    double T16[16], H[36], b[6], d[6];
+    rigid_to_colmajor(x0, T16);
+    APD_TRY(lin(T16, H, b, &y0, &matched));
+    n_lin++;
+    if (stop_on_empty && matched == 0) break;
+    Rigid delta = rigid_identity();
+    bool ok = false;
+    if (p.optimizer == APDGICP_OPT_GN) {  // L:107-123
+      solve6_spd(H, 0.0, b, d);
+      delta = make_delta(d);
+      x0 = rigid_mul(delta, x0);
+      memcpy(final_H, H, sizeof(H));
+      ok = true;
+    } else {  // L:127-173
+      if (lambda < 0.0) {
+        double mx = 0.0;
+        for (int q = 0; q < 6; q++) mx = std::max(mx, std::fabs(H[q + 6 * q]));
+        lambda = p.lm_init_lambda_factor * mx;
+      }
+      double nu = 2.0;
+      for (int in = 0; in < p.lm_max_iterations; in++) {
+        solve6_spd(H, lambda, b, d);
+        delta = make_delta(d);
+        const Rigid xi = rigid_mul(delta, x0);
+        double yi = 0.0;
+        rigid_to_colmajor(xi, T16);
+        APD_TRY(err(T16, &yi));
+        n_err++;
+        double den = 0.0;
+        for (int q = 0; q < 6; q++) den += d[q] * (lambda * d[q] - b[q]);
+        const double rho = (y0 - yi) / den;
+        if (e.trace_on) {
+          double nn = 0.0;
+          for (int q = 0; q < 6; q++) nn += d[q] * d[q];
+          h->tr_lambda.push_back(lambda), h->tr_rho.push_back(rho), h->tr_y0.push_back(y0), h->tr_yi.push_back(yi), h->tr_dnorm.push_back(std::sqrt(nn));
+        }
+        if (rho < 0) {
+          if (is_converged(delta, p.rotation_epsilon, p.transformation_epsilon)) {
+            ok = true;
+            break;
+          }
+          lambda = nu * lambda;
+          nu = 2 * nu;
+          continue;
+        }
+        x0 = xi;
+        const double t = 2 * rho - 1;
+        lambda = lambda * std::max(1.0 / 3.0, 1 - t * t * t);
+        memcpy(final_H, H, sizeof(H));
+        ok = true;
+        break;
+      }
+    }
+    if (!ok) {
+      failed = 1;
+      break;
+    }
+    if (e.trace_on) {
+      double P[16];
+      rigid_to_colmajor(x0, P);
+      h->tr_poses.insert(h->tr_poses.end(), P, P + 16);
+    }
+    converged = is_converged(delta, p.rotation_epsilon, p.transformation_epsilon);
+  }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) out->T[i + 4 * j] = (float)x0.m[4 * i + j];
+  out->T[3] = out->T[7] = out->T[11] = 0.f;
+  out->T[15] = 1.f;
+  out->final_cost = y0;
+  out->converged = converged;
+  out->iterations = nr_iterations;
+  out->n_linearize = n_lin;
+  out->n_compute_error = n_err;
+  out->lm_failed = failed;
+  out->n_matched = matched;
+  h->have_corr = n_lin > 0;
+  // keep getFinalHessian() coherent with this path
+  APD_HIP(hipMemcpyAsync((char*)e.d_state.p + offsetof(PairState, final_H), final_H, sizeof(final_H), hipMemcpyHostToDevice, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  return 0;
+}
+
+int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  APD_TRY(vg_prepare(h));
+  return host_loop(
+      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vg_linearize(h, T, H, b, y0, m); },
+      [&](const double* T, double* yi) { return vg_error(h, T, yi); }, true);
+}
+
 }  // namespace
 
 extern "C" {
@@ -364,6 +659,7 @@ static int set_cloud_common(apdgicp_handle* h, int slot, const float* xyz, int64
     APD_TRY(e.set_cloud(slot, xyz, n, stride, on_device, token));
     h->pair_ready = false;
     h->have_corr = false;
+    h->cloud_gen[slot] = ++h->cloud_epoch;
     return 0;
   });
 }
@@ -379,12 +675,14 @@ int apdgicp_clear_source(apdgicp_handle* h) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   h->eng.clear_cloud(kSrc);
   h->pair_ready = h->have_corr = false;
+  h->cloud_gen[kSrc] = ++h->cloud_epoch;
   return 0;
 }
 int apdgicp_clear_target(apdgicp_handle* h) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   h->eng.clear_cloud(kTgt);
   h->pair_ready = h->have_corr = false;
+  h->cloud_gen[kTgt] = ++h->cloud_epoch;
   return 0;
 }
 int apdgicp_swap_source_and_target(apdgicp_handle* h) {
@@ -392,6 +690,7 @@ int apdgicp_swap_source_and_target(apdgicp_handle* h) {
   std::swap(h->eng.clouds[kSrc], h->eng.clouds[kTgt]);  // input_.swap(target_), covs swap, A:68-75
   h->eng.desc_dirty = true;
   h->pair_ready = h->have_corr = false;
+  std::swap(h->cloud_gen[kSrc], h->cloud_gen[kTgt]);
   return 0;
 }
 
@@ -434,6 +733,7 @@ int apdgicp_set_covariances(apdgicp_handle* h, int which, const double* in, int6
                        c.cov.as<double>());
     APD_HIP(hipStreamSynchronize(e.stream));
     c.cov_valid = true;
+    c.cov_gen = ++e.cov_epoch;
     return 0;
   });
 }
@@ -441,6 +741,7 @@ int apdgicp_set_covariances(apdgicp_handle* h, int which, const double* in, int6
 int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], double b[6], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->vg.on) return vg_linearize(h, T, H, b, cost, nullptr);
     APD_TRY(ensure_pair(h));
     APD_TRY(h->eng.probe_linearize(T, H, b, cost, nullptr));
     h->have_corr = true;
@@ -451,6 +752,7 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
 int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T || !cost) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->vg.on) return vg_error(h, T, cost);
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
     return h->eng.probe_error(T, cost);
   });
@@ -459,6 +761,7 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
 int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int64_t n) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -478,6 +781,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
 int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP keeps no per-point Mahalanobis matrices");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -502,6 +806,7 @@ int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
 int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->vg.on) return vg_align(h, guess, out);
     float g[16];
     if (guess) memcpy(g, guess, sizeof(g));
     else identity16(g);
@@ -535,105 +840,106 @@ int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out)
 int apdgicp_align_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->vg.on) return vg_align(h, guess, out);
     APD_TRY(ensure_pair(h));
     Engine& e = h->eng;
-    const apdgicp_params& p = e.params;
-    float g[16];
-    if (guess) memcpy(g, guess, sizeof(g));
-    else identity16(g);
-    Rigid x0;
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 4; j++) x0.m[4 * i + j] = (double)g[i + 4 * j];  // L:56
-    double lambda = -1.0;                                                   // L:58
-    bool converged = false;
-    int nr_iterations = 0, n_lin = 0, n_err = 0, failed = 0, matched = 0;
-    double final_H[36];
-    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
-    double y0 = 0.0;
-    h->tr_lambda.clear(), h->tr_rho.clear(), h->tr_y0.clear(), h->tr_yi.clear(), h->tr_dnorm.clear(), h->tr_poses.clear();
-    h->trace_from_host_loop = true;
-    for (int it = 0; it < p.max_iterations && !converged; it++) {  // L:67
-      nr_iterations = it;
-      double T16[16], H[36], b[6], d[6];
-      rigid_to_colmajor(x0, T16);
-      APD_TRY(e.probe_linearize(T16, H, b, &y0, &matched));
-      n_lin++;
-      Rigid delta = rigid_identity();
-      bool ok = false;
-      if (p.optimizer == APDGICP_OPT_GN) {  // L:107-123
-        solve6_spd(H, 0.0, b, d);
-        delta = make_delta(d);
-        x0 = rigid_mul(delta, x0);
-        memcpy(final_H, H, sizeof(H));
-        ok = true;
-      } else {  // L:127-173
-        if (lambda < 0.0) {
-          double mx = 0.0;
-          for (int q = 0; q < 6; q++) mx = std::max(mx, std::fabs(H[q + 6 * q]));
-          lambda = p.lm_init_lambda_factor * mx;
-        }
-        double nu = 2.0;
-        for (int in = 0; in < p.lm_max_iterations; in++) {
-          solve6_spd(H, lambda, b, d);
-          delta = make_delta(d);
-          const Rigid xi = rigid_mul(delta, x0);
-          double yi = 0.0;
-          rigid_to_colmajor(xi, T16);
-          APD_TRY(e.probe_error(T16, &yi));
-          n_err++;
-          double den = 0.0;
-          for (int q = 0; q < 6; q++) den += d[q] * (lambda * d[q] - b[q]);
-          const double rho = (y0 - yi) / den;
-          if (e.trace_on) {
-            double nn = 0.0;
-            for (int q = 0; q < 6; q++) nn += d[q] * d[q];
-            h->tr_lambda.push_back(lambda), h->tr_rho.push_back(rho), h->tr_y0.push_back(y0), h->tr_yi.push_back(yi), h->tr_dnorm.push_back(std::sqrt(nn));
-          }
-          if (rho < 0) {
-            if (is_converged(delta, p.rotation_epsilon, p.transformation_epsilon)) {
-              ok = true;
-              break;
-            }
-            lambda = nu * lambda;
-            nu = 2 * nu;
-            continue;
-          }
-          x0 = xi;
-          const double t = 2 * rho - 1;
-          lambda = lambda * std::max(1.0 / 3.0, 1 - t * t * t);
-          memcpy(final_H, H, sizeof(H));
-          ok = true;
-          break;
-        }
-      }
-      if (!ok) {
-        failed = 1;
-        break;
-      }
-      if (e.trace_on) {
-        double P[16];
-        rigid_to_colmajor(x0, P);
-        h->tr_poses.insert(h->tr_poses.end(), P, P + 16);
-      }
-      converged = is_converged(delta, p.rotation_epsilon, p.transformation_epsilon);
+    return host_loop(
+        h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return e.probe_linearize(T, H, b, y0, m); },
+        [&](const double* T, double* yi) { return e.probe_error(T, yi); }, false);
+  });
+}
+
+// ------------------------------------------------------------------------------------ voxelized GICP
+void apdgicp_vgicp_default_params(apdgicp_vgicp_params* p) {
+  if (!p) return;
+  p->resolution = 1.0;                          // V:22
+  p->neighbor_search = APDGICP_VGICP_DIRECT1;   // V:23
+  p->voxel_mode = APDGICP_VGICP_ADDITIVE;       // V:24
+}
+
+int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  VgState& v = h->vg;
+  if (!p) {  // back to the APD-GICP / plain GICP kernels: their correspondences are those of their own last linearize, if any was left
+    if (v.on) h->have_corr = false;
+    v.on = false;
+    return 0;
+  }
+  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: the resolution must be finite and positive");
+  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown neighbour search method");
+  if (p->voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
+  if (p->voxel_mode != APDGICP_VGICP_ADDITIVE && p->voxel_mode != APDGICP_VGICP_ADDITIVE_WEIGHTED) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown accumulation mode");
+  if (!v.on || p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
+  if (!v.on) h->have_corr = false;
+  v.prm = *p;
+  v.on = true;
+  return 0;
+}
+
+int apdgicp_get_vgicp(const apdgicp_handle* h, apdgicp_vgicp_params* p, int* enabled) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (p) *p = h->vg.prm;
+  if (enabled) *enabled = h->vg.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_vgicp_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!h || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (!h->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    APD_TRY(vg_build_map(h));
+    *n_voxels = h->vg.n_vox;
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    if (!h->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    APD_TRY(vg_build_map(h));
+    VgState& v = h->vg;
+    Engine& e = h->eng;
+    const int64_t nv = v.n_vox;
+    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
+    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
+    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
+    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), v.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
+    if (counts) APD_HIP(hipMemcpyAsync(counts, v.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
+    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, v.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
+    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), v.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (int64_t i = 0; i < nv && coords_n3; i++) {
+      const unsigned long long k = keys[i];
+      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
     }
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 4; j++) out->T[i + 4 * j] = (float)x0.m[4 * i + j];
-    out->T[3] = out->T[7] = out->T[11] = 0.f;
-    out->T[15] = 1.f;
-    out->final_cost = y0;
-    out->converged = converged;
-    out->iterations = nr_iterations;
-    out->n_linearize = n_lin;
-    out->n_compute_error = n_err;
-    out->lm_failed = failed;
-    out->n_matched = matched;
-    h->have_corr = n_lin > 0;
-    // keep getFinalHessian() coherent with this path
-    APD_HIP(hipMemcpyAsync((char*)e.d_state.p + offsetof(PairState, final_H), final_H, sizeof(final_H), hipMemcpyHostToDevice, e.stream));
+    for (int64_t i = 0; i < nv && covs_n9; i++) {
+      const double* c = &c6[6 * i];
+      double* o = covs_n9 + 9 * i;
+      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
+    }
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_source) {
+  return guarded([&]() -> int {
+    if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    VgState& v = h->vg;
+    Engine& e = h->eng;
+    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
+    if (n_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_source does not match the source size");
+    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_source * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
     APD_HIP(hipStreamSynchronize(e.stream));
     return 0;
   });
+}
+
+int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds) {
+  if (!h || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n_builds = h->vg.builds;
+  return 0;
 }
 
 int apdgicp_set_trace(apdgicp_handle* h, int enable) {

@@ -108,6 +108,8 @@ SYMBOLS = [
     "apdgicp_scan_context_default_params", "apdgicp_scan_context_create", "apdgicp_scan_context_destroy", "apdgicp_scan_context_set_params",
     "apdgicp_scan_context_add", "apdgicp_scan_context_add_descriptor", "apdgicp_scan_context_clear", "apdgicp_scan_context_size",
     "apdgicp_scan_context_detect", "apdgicp_scan_context_detect_batch", "apdgicp_scan_context_descriptors",
+    "apdgicp_vgicp_default_params", "apdgicp_set_vgicp", "apdgicp_get_vgicp", "apdgicp_vgicp_voxel_count", "apdgicp_vgicp_get_voxels",
+    "apdgicp_vgicp_get_correspondences", "apdgicp_vgicp_build_count",
 ]
 
 _lib = None
@@ -272,6 +274,14 @@ def load_library(path: str | None = None):
     L.apdgicp_scan_context_detect.argtypes = [vp, i32, vp, i32, i32, vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float)]
     L.apdgicp_scan_context_detect_batch.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     L.apdgicp_scan_context_descriptors.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.apdgicp_vgicp_default_params.argtypes = [vp]
+    L.apdgicp_vgicp_default_params.restype = None
+    L.apdgicp_set_vgicp.argtypes = [vp, vp]
+    L.apdgicp_get_vgicp.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_vgicp_voxel_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_vgicp_get_voxels.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.apdgicp_vgicp_get_correspondences.argtypes = [vp, vp, i64]
+    L.apdgicp_vgicp_build_count.argtypes = [vp, C.POINTER(i64)]
     if path is None:
         _lib = L
     return L

@@ -1,0 +1,109 @@
+"""Voxelized GICP (fast_gicp::FastVGICP, the FAST_VGICP branch of select_registration_method(), registrations.cpp:62-70) as a mode of
+the registration handle: `FastVGICP` is `registration.FastAPDGICP` with apdgicp_set_vgicp switched on and the reference's three setters
+(fast_apdgicp/include/fast_gicp/gicp/fast_vgicp.hpp).  Semantics: the list V1 .. V7 in include/apdgicp_hip.h.
+
+There is NO CPU fallback: without the HIP library or a GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import registration as reg
+from .registration import _check, _ptr
+
+DIRECT1, DIRECT7, DIRECT27 = 0, 1, 2                    # NeighborSearchMethod (gicp_settings.hpp)
+ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE = 0, 1, 2   # VoxelAccumulationMode
+N_OFFSETS = {DIRECT1: 1, DIRECT7: 7, DIRECT27: 27}
+
+
+class VgicpParams(C.Structure):
+    """apdgicp_vgicp_params (include/apdgicp_hip.h)."""
+    _fields_ = [("resolution", C.c_double), ("neighbor_search", C.c_int32), ("voxel_mode", C.c_int32)]
+
+
+def default_vgicp_params() -> VgicpParams:
+    p = VgicpParams()
+    reg.load_library().apdgicp_vgicp_default_params(C.byref(p))
+    return p
+
+
+class FastVGICP(reg.FastAPDGICP):
+    """One registration object (== one fast_gicp::FastVGICP) on one GPU.  setInputSource / setInputTarget / align / linearize /
+    compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are the base class's; align always runs the
+    host-driven loop.  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.vparams = default_vgicp_params()
+        self._push_vgicp()
+
+    def _push_vgicp(self):
+        _check(self.L.apdgicp_set_vgicp(self.h, C.byref(self.vparams)))
+
+    def setResolution(self, resolution: float):
+        old = self.vparams.resolution
+        self.vparams.resolution = float(resolution)
+        try:
+            self._push_vgicp()
+        except reg.ApdgicpError:
+            self.vparams.resolution = old
+            raise
+
+    def setNeighborSearchMethod(self, method: int):
+        old = self.vparams.neighbor_search
+        self.vparams.neighbor_search = int(method)
+        try:
+            self._push_vgicp()
+        except reg.ApdgicpError:
+            self.vparams.neighbor_search = old
+            raise
+
+    def setVoxelAccumulationMode(self, mode: int):
+        old = self.vparams.voxel_mode
+        self.vparams.voxel_mode = int(mode)
+        try:
+            self._push_vgicp()
+        except reg.ApdgicpError:
+            self.vparams.voxel_mode = old
+            raise
+
+    def disable(self):
+        """apdgicp_set_vgicp(h, NULL): the handle is an APD-GICP / plain GICP object again."""
+        _check(self.L.apdgicp_set_vgicp(self.h, None))
+
+    def enable(self):
+        self._push_vgicp()
+
+    def enabled(self) -> bool:
+        on = C.c_int()
+        _check(self.L.apdgicp_get_vgicp(self.h, None, C.byref(on)))
+        return bool(on.value)
+
+    def voxel_count(self) -> int:
+        n = C.c_int64()
+        _check(self.L.apdgicp_vgicp_voxel_count(self.h, C.byref(n)))
+        return n.value
+
+    def voxels(self):
+        """The target's voxel map in voxel order (ascending key): dict(coords [n,3] int32, counts [n] int32, means [n,3], covs [n,3,3])."""
+        n = self.voxel_count()
+        coords = np.empty((n, 3), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        means = np.empty((n, 3))
+        covs = np.empty((n, 9))
+        _check(self.L.apdgicp_vgicp_get_voxels(self.h, n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
+        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+
+    def voxel_correspondences(self) -> np.ndarray:
+        """[n_source, n_offsets] voxel indices of the last linearize, in offset order; -1 = miss."""
+        out = np.empty((self.n_src, N_OFFSETS[self.vparams.neighbor_search]), dtype=np.int32)
+        _check(self.L.apdgicp_vgicp_get_correspondences(self.h, _ptr(out), self.n_src))
+        return out
+
+    def build_count(self) -> int:
+        """How many voxel maps this handle has built (the cache rules' test hook)."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_vgicp_build_count(self.h, C.byref(n)))
+        return n.value
