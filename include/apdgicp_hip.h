@@ -42,7 +42,8 @@ extern "C" {
                                       still 6 (additive): + the apdgicp_floor_* object (floor plane detection, under-floor removal);
                                       still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres);
                                       still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K);
-                                      still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle) */
+                                      still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle);
+                                      still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -300,7 +301,37 @@ int apdgicp_get_stream(apdgicp_handle* h, void** stream);
  * whenever either is another one -- whichever entry point (with the mode on or off) replaced the cloud or recomputed the covariances in
  * between; the frozen state behind apdgicp_compute_error is tied to the source's points and covariances and to the map in the same way
  * (otherwise APDGICP_ERR_NO_INPUT).  With the mode off nothing differs
- * from a handle that never had it on.  Batch handles have no such mode. */
+ * from a handle that never had it on.
+ *
+ * Batch handles have the same mode (apdgicp_batch_set_vgicp, declared with the batch calls below; kernels: riv-slam_amd/csrc/apd_vgicp_batch.hpp),
+ * with the optimiser loop on the device:
+ *   V8. Maps per cloud slot.  Every slot named as target_cloud by a pair of the batch gets the voxel map of V1 .. V3; counts, means and
+ *       covariances are bit-equal to those the single handle builds from the same points and covariances.  The map is cached per slot, by
+ *       identity: it is rebuilt when the slot's points were set again, its covariances were rewritten, the resolution or the accumulation
+ *       mode changed, or apdgicp_batch_clear ran.  A slot used only as a source gets no map.  Building the maps of a batch costs at most
+ *       ONE host wait for the whole batch: a slot's voxel buffers are sized for as many voxels as it has points, the voxel count stays on
+ *       the device, and the "first offending point" words and voxel counts of all slots come back in one copy.  A target with a point that
+ *       V2 refuses fails the align with APDGICP_ERR_INVALID_ARG, the message naming the slot and the point; no pair has run, and the
+ *       handle stays usable.
+ *   V9. The per-point arithmetic is that of V4 .. V6, bit for bit: the same device functions, the 29 sums in the same written order, one
+ *       source point per lane in the caller's order in blocks of 256, the block rows added in block order starting from 0.0.  Hence H, b,
+ *       cost and correspondence count of a pair's FIRST linearize equal apdgicp_linearize of a single handle at the same guess, bit for bit.
+ *   V10. Optimiser.  The control flow of apdgicp_align_host_loop (L:55-173), run per pair by the device state machine of the APD batch
+ *       path, plus V7: a linearize without any correspondence ends that pair there with converged = 0, lm_failed = 0, n_linearize counted,
+ *       iterations = the current iteration, T = the pose so far, final_cost = that linearize's cost, n_matched = 0.  The frozen state of
+ *       V6 is per pair: the voxel indices per (point, offset) and the pose of the pair's last linearize.  sin / cos of the step's rotation
+ *       come from the device library instead of the host's, so iterates agree with the single handle's to rounding, not bit for bit.
+ *   V11. A pair's record is a pure function of the pair: the same (source, target, guess, parameters) gives byte-identical records whether
+ *       the pair runs alone or among any others, at any position of the list, on a first align and on a reused handle.
+ *   V12. No host round trip per iteration.  One tick is two launches (per-point pass, per-pair step); the host enqueues ticks in chunks and
+ *       looks at one word in pinned memory, the number of finished pairs, between chunks, with at least one chunk enqueued ahead while it
+ *       waits.  A finished pair's blocks exit on reading its status.  The loop ends when every pair is done, or after
+ *       max_iterations * (1 + lm_max_iterations) ticks (max_iterations with Gauss-Newton).
+ * With the mode on, apdgicp_batch_align / _align_async / _copy_results / _synchronize run this path and fill the same apdgicp_result records
+ * (n_matched = the number of correspondences, saturating as above; align_async may wait internally -- the run length is data dependent --
+ * and returns with the device records complete); apdgicp_batch_fitness and the cloud calls are unchanged; apdgicp_batch_set_pair_groups is
+ * accepted and has no effect; apdgicp_batch_align_enqueue / _collect / _pump return APDGICP_ERR_UNSUPPORTED (one batch at a time) and
+ * apdgicp_batch_is_pooled returns 0.  With the mode off a batch handle does exactly what one that never had it on does. */
 typedef enum { APDGICP_VGICP_DIRECT1 = 0, APDGICP_VGICP_DIRECT7 = 1, APDGICP_VGICP_DIRECT27 = 2 } apdgicp_vgicp_search;   /* NeighborSearchMethod, gicp_settings.hpp */
 typedef enum { APDGICP_VGICP_ADDITIVE = 0, APDGICP_VGICP_ADDITIVE_WEIGHTED = 1, APDGICP_VGICP_MULTIPLICATIVE = 2 } apdgicp_vgicp_mode;   /* VoxelAccumulationMode */
 typedef struct {
@@ -426,6 +457,17 @@ int apdgicp_batch_last_nn_kernel(apdgicp_batch* b, char* name, int capacity);
  * slot-ticks = the sum over the tick launches of the pair slots they covered (grid y; slots behind the end of a list execute nothing).
  * bench.py turns per-slot counter profiles into a per-batch figure with it (the LM line's valu_busy).  Zeros for a handle without a pool. */
 int apdgicp_batch_pool_counters(apdgicp_batch* b, int64_t* chunks, int64_t* ticks, int64_t* slot_ticks);
+
+/* Voxelized GICP as a mode of the batch handle: V8 .. V12 above.  p != NULL: the mode on with these parameters (MULTIPLICATIVE:
+ * APDGICP_ERR_UNSUPPORTED, V7); NULL: mode off.  The maps built so far are kept across off / on. */
+int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p);
+int apdgicp_batch_get_vgicp(const apdgicp_batch* b, apdgicp_vgicp_params* p, int* enabled);   /* either output may be NULL */
+/* number of voxels of the map of cloud slot `cloud` (built if it is not current; needs the mode on and that slot only) */
+int apdgicp_batch_vgicp_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels);
+/* that map in voxel order, as apdgicp_vgicp_get_voxels */
+int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9);
+/* Debug: how many voxel maps this handle has built, all slots together (the tests of the cache rules read it) */
+int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds);
 int apdgicp_batch_debug_stats(apdgicp_batch* b, unsigned long long out[16]);
 /* APDGICP_STATS=2 and a library built with -DAPD_BLOCK_TIMELINE (a diagnostics variant: tools/build_variant.py) only: {start, end} (100 MHz wall-clock ticks) and the index of every block of the LAST one-pair dense search launch
  * (k_nn_pruned), three words per block, up to 8192 blocks; reading resets.  For tools/c5_blocks.py: where the time of a 100k x 500k

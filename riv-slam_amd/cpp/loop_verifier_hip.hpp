@@ -47,6 +47,9 @@ class LoopVerifierHip {
   LoopVerifierHip& operator=(const LoopVerifierHip&) = delete;
   bool ok() const { return batch_ != nullptr; }
   int setParams(const apdgicp_params& p) { return batch_ ? apdgicp_batch_set_params(batch_, &p) : APDGICP_ERR_HIP; }
+  /// registration_method = FAST_VGICP: the candidates are registered with voxelized GICP (apdgicp_batch_set_vgicp, V8 .. V12 of the C header);
+  /// nullptr: back to APD-GICP / plain GICP as the parameters say
+  int setVGICP(const apdgicp_vgicp_params* p) { return batch_ ? apdgicp_batch_set_vgicp(batch_, p) : APDGICP_ERR_HIP; }
 
   /// guesses: n_candidates x 16 floats, column-major ((new_keyframe_estimate^-1 * candidate_estimate) with guess(2,3) = 0,
   /// loop_detector.cpp:405-411), or nullptr for the identity (:225).  Returns 0 or a negative apdgicp_status.

@@ -175,6 +175,7 @@ class Engine {
     bool cov_valid = false;
     uint64_t cov_gen = 0;            // Engine::cov_epoch when `cov` was last written (a launch of the covariance kernels, set_covariances): unique per writing
     uint64_t token = 0;
+    uint64_t pts_gen = 0;            // Engine::pts_epoch when the slot's points were last set: names one setting of the points (0: none)
     // a host cloud of the tiled-sort size class stays in this pinned buffer until the sort has read it (TileJob::staged)
     char* stage_p = nullptr;
     char* stage_dev = nullptr;
@@ -204,6 +205,7 @@ class Engine {
   std::vector<Cloud> clouds;
   bool desc_dirty = true;
   uint64_t cov_epoch = 0;            // counts the writings of any cloud's covariances (Cloud::cov_gen)
+  uint64_t pts_epoch = 0;            // counts the settings of any cloud's points (Cloud::pts_gen)
 
   // batch state
   int npairs = 0, nmax_src = 0, nmax_tgt = 0;
@@ -532,6 +534,7 @@ class Engine {
     c.sorted = false;  // Z-curve sort is deferred so that a batch of clouds is sorted by ONE launch
     c.cov_valid = false;
     c.token = token;
+    c.pts_gen = ++pts_epoch;
     desc_dirty = true;
     return 0;
   }
@@ -613,6 +616,7 @@ class Engine {
       c.cov_valid = false;
       c.token = 0;
       c.staged = false;  // (a host cloud set before and never sorted: its pinned copy is void now)
+      c.pts_gen = ++pts_epoch;
     }
     APD_TRY(d_packjobs.upload(jobs.data(), jobs.size() * sizeof(PackJob), cstream));
     hipLaunchKernelGGL(k_pack_points_multi, dim3((unsigned)((nmax + 255) / 256), (unsigned)count), dim3(256), 0, cstream, d_packjobs.as<PackJob>());
@@ -630,6 +634,7 @@ class Engine {
       clouds[slot].sorted = false;
       clouds[slot].cov_valid = false;
       clouds[slot].token = 0;
+      clouds[slot].pts_gen = 0;
       desc_dirty = true;
     }
   }

@@ -148,6 +148,76 @@ __device__ __forceinline__ void vg_block_sums(double* acc, double* red /* [VG_BL
   }
 }
 
+// V4 / V5: source point i of a linearize at pose T -- its noff voxel indices to corr, its terms onto the 29 sums `acc`.  The one per-point body of
+// k_vg_linearize and of the batch tick (apd_vgicp_batch.hpp): the same operations in the same written order wherever it is called from.
+__device__ __forceinline__ void vg_linearize_point(const float4* opts, const double* cov_src, const int* inv_src, int n, const VgMap& map, const Rigid& T, double res,
+                                                   int mode, int noff, int want_Hb, int* corr, int i, double* acc) {
+  const float4 p = opts[i];
+  const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+  const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
+  const double cx = vg_coord(vx, res), cy = vg_coord(vy, res), cz = vg_coord(vz, res);
+  // a coordinate this far out cannot come back into range with an offset of one; also catches a q that is not finite
+  const bool inr = fabs(cx) <= (double)VG_LIM && fabs(cy) <= (double)VG_LIM && fabs(cz) <= (double)VG_LIM;
+  const int ix = inr ? (int)cx : 0, iy = inr ? (int)cy : 0, iz = inr ? (int)cz : 0;
+  Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool have_rca = false;
+  for (int k = 0; k < noff; k++) {
+    int ox, oy, oz;
+    vg_offset(mode, k, ox, oy, oz);
+    const int ax = ix + ox, ay = iy + oy, az = iz + oz;
+    int v = -1;
+    if (inr && abs(ax) < VG_LIM && abs(ay) < VG_LIM && abs(az) < VG_LIM) v = vg_find(map, vg_pack(ax, ay, az));  // V2: the range test comes first
+    corr[(size_t)i * noff + k] = v;
+    if (v < 0) continue;
+    if (!have_rca) {
+      const int s = min(max(inv_src[i], 0), n - 1);
+      RCA = sym3_rotate(T, vg_load_cov(cov_src, n, s));
+      have_rca = true;
+    }
+    const Sym3 Mi = vg_mahalanobis(map, v, RCA);
+    const double* mu = map.mean + 3 * (size_t)v;
+    const double w = sqrt((double)map.count[v]);
+    const double ex = mu[0] - vx, ey = mu[1] - vy, ez = mu[2] - vz;
+    const double mex = (Mi.xx * ex + Mi.xy * ey) + Mi.xz * ez;
+    const double mey = (Mi.xy * ex + Mi.yy * ey) + Mi.yz * ez;
+    const double mez = (Mi.xz * ex + Mi.yz * ey) + Mi.zz * ez;
+    acc[27] += w * ((ex * mex + ey * mey) + ez * mez);
+    acc[28] += 1.0;
+    if (!want_Hb) continue;
+    // J = [skew(q) | -I]; MA = M skew(q)
+    const double m0x = Mi.xy * vz - Mi.xz * vy, m0y = Mi.yy * vz - Mi.yz * vy, m0z = Mi.yz * vz - Mi.zz * vy;
+    const double m1x = Mi.xz * vx - Mi.xx * vz, m1y = Mi.yz * vx - Mi.xy * vz, m1z = Mi.zz * vx - Mi.xz * vz;
+    const double m2x = Mi.xx * vy - Mi.xy * vx, m2y = Mi.xy * vy - Mi.yy * vx, m2z = Mi.xz * vy - Mi.yz * vx;
+    acc[0] += w * (vz * m0y - vy * m0z);
+    acc[1] += w * (vz * m1y - vy * m1z);
+    acc[2] += w * (vz * m2y - vy * m2z);
+    acc[3] += w * -m0x;
+    acc[4] += w * -m0y;
+    acc[5] += w * -m0z;
+    acc[6] += w * (vx * m1z - vz * m1x);
+    acc[7] += w * (vx * m2z - vz * m2x);
+    acc[8] += w * -m1x;
+    acc[9] += w * -m1y;
+    acc[10] += w * -m1z;
+    acc[11] += w * (vy * m2x - vx * m2y);
+    acc[12] += w * -m2x;
+    acc[13] += w * -m2y;
+    acc[14] += w * -m2z;
+    acc[15] += w * Mi.xx;
+    acc[16] += w * Mi.xy;
+    acc[17] += w * Mi.xz;
+    acc[18] += w * Mi.yy;
+    acc[19] += w * Mi.yz;
+    acc[20] += w * Mi.zz;
+    acc[21] += w * (vz * mey - vy * mez);
+    acc[22] += w * (vx * mez - vz * mex);
+    acc[23] += w * (vy * mex - vx * mey);
+    acc[24] += w * -mex;
+    acc[25] += w * -mey;
+    acc[26] += w * -mez;
+  }
+}
+
 // T2[0..12): the pose, row-major 3x4.  corr: n x noff voxel indices (-1: miss), written here.
 __global__ __launch_bounds__(VG_BLK) void k_vg_linearize(const float4* opts, const double* cov_src, const int* inv_src, int n, VgMap map, const double* T12, double res,
                                                          int mode, int noff, int want_Hb, int* corr, double* part) {
@@ -160,72 +230,36 @@ __global__ __launch_bounds__(VG_BLK) void k_vg_linearize(const float4* opts, con
 #pragma unroll
   for (int r = 0; r < VG_SUMS; r++) acc[r] = 0.0;
   if (i < n) {
-    const float4 p = opts[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
-    const double cx = vg_coord(vx, res), cy = vg_coord(vy, res), cz = vg_coord(vz, res);
-    // a coordinate this far out cannot come back into range with an offset of one; also catches a q that is not finite
-    const bool inr = fabs(cx) <= (double)VG_LIM && fabs(cy) <= (double)VG_LIM && fabs(cz) <= (double)VG_LIM;
-    const int ix = inr ? (int)cx : 0, iy = inr ? (int)cy : 0, iz = inr ? (int)cz : 0;
-    Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    bool have_rca = false;
-    for (int k = 0; k < noff; k++) {
-      int ox, oy, oz;
-      vg_offset(mode, k, ox, oy, oz);
-      const int ax = ix + ox, ay = iy + oy, az = iz + oz;
-      int v = -1;
-      if (inr && abs(ax) < VG_LIM && abs(ay) < VG_LIM && abs(az) < VG_LIM) v = vg_find(map, vg_pack(ax, ay, az));  // V2: the range test comes first
-      corr[(size_t)i * noff + k] = v;
-      if (v < 0) continue;
-      if (!have_rca) {
-        const int s = min(max(inv_src[i], 0), n - 1);
-        RCA = sym3_rotate(T, vg_load_cov(cov_src, n, s));
-        have_rca = true;
-      }
-      const Sym3 Mi = vg_mahalanobis(map, v, RCA);
-      const double* mu = map.mean + 3 * (size_t)v;
-      const double w = sqrt((double)map.count[v]);
-      const double ex = mu[0] - vx, ey = mu[1] - vy, ez = mu[2] - vz;
-      const double mex = (Mi.xx * ex + Mi.xy * ey) + Mi.xz * ez;
-      const double mey = (Mi.xy * ex + Mi.yy * ey) + Mi.yz * ez;
-      const double mez = (Mi.xz * ex + Mi.yz * ey) + Mi.zz * ez;
-      acc[27] += w * ((ex * mex + ey * mey) + ez * mez);
-      acc[28] += 1.0;
-      if (!want_Hb) continue;
-      // J = [skew(q) | -I]; MA = M skew(q)
-      const double m0x = Mi.xy * vz - Mi.xz * vy, m0y = Mi.yy * vz - Mi.yz * vy, m0z = Mi.yz * vz - Mi.zz * vy;
-      const double m1x = Mi.xz * vx - Mi.xx * vz, m1y = Mi.yz * vx - Mi.xy * vz, m1z = Mi.zz * vx - Mi.xz * vz;
-      const double m2x = Mi.xx * vy - Mi.xy * vx, m2y = Mi.xy * vy - Mi.yy * vx, m2z = Mi.xz * vy - Mi.yz * vx;
-      acc[0] += w * (vz * m0y - vy * m0z);
-      acc[1] += w * (vz * m1y - vy * m1z);
-      acc[2] += w * (vz * m2y - vy * m2z);
-      acc[3] += w * -m0x;
-      acc[4] += w * -m0y;
-      acc[5] += w * -m0z;
-      acc[6] += w * (vx * m1z - vz * m1x);
-      acc[7] += w * (vx * m2z - vz * m2x);
-      acc[8] += w * -m1x;
-      acc[9] += w * -m1y;
-      acc[10] += w * -m1z;
-      acc[11] += w * (vy * m2x - vx * m2y);
-      acc[12] += w * -m2x;
-      acc[13] += w * -m2y;
-      acc[14] += w * -m2z;
-      acc[15] += w * Mi.xx;
-      acc[16] += w * Mi.xy;
-      acc[17] += w * Mi.xz;
-      acc[18] += w * Mi.yy;
-      acc[19] += w * Mi.yz;
-      acc[20] += w * Mi.zz;
-      acc[21] += w * (vz * mey - vy * mez);
-      acc[22] += w * (vx * mez - vz * mex);
-      acc[23] += w * (vy * mex - vx * mey);
-      acc[24] += w * -mex;
-      acc[25] += w * -mey;
-      acc[26] += w * -mez;
-    }
+    vg_linearize_point(opts, cov_src, inv_src, n, map, T, res, mode, noff, want_Hb, corr, i, acc);
   }
   vg_block_sums<VG_SUMS>(acc, red, part, tid);
+}
+
+// V6: source point i at the trial pose T over the voxel indices and the pose T0 of the last linearize -- cost and count onto acc[0], acc[1]
+__device__ __forceinline__ void vg_error_point(const float4* opts, const double* cov_src, const int* inv_src, int n, const VgMap& map, const Rigid& T, const Rigid& T0,
+                                               int noff, const int* corr, int i, double* acc) {
+  const float4 p = opts[i];
+  const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
+  const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
+  Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool have_rca = false;
+  for (int k = 0; k < noff; k++) {
+    const int v = corr[(size_t)i * noff + k];
+    if (v < 0 || v >= map.nv) continue;
+    if (!have_rca) {
+      RCA = sym3_rotate(T0, vg_load_cov(cov_src, n, min(max(inv_src[i], 0), n - 1)));
+      have_rca = true;
+    }
+    const Sym3 Mi = vg_mahalanobis(map, v, RCA);
+    const double* mu = map.mean + 3 * (size_t)v;
+    const double w = sqrt((double)map.count[v]);
+    const double ex = mu[0] - vx, ey = mu[1] - vy, ez = mu[2] - vz;
+    const double mex = (Mi.xx * ex + Mi.xy * ey) + Mi.xz * ez;
+    const double mey = (Mi.xy * ex + Mi.yy * ey) + Mi.yz * ez;
+    const double mez = (Mi.xz * ex + Mi.yz * ey) + Mi.zz * ez;
+    acc[0] += w * ((ex * mex + ey * mey) + ez * mez);
+    acc[1] += 1.0;
+  }
 }
 
 // V6: T12 = the trial pose, T12 + 12 = the pose of the last linearize
@@ -238,28 +272,7 @@ __global__ __launch_bounds__(VG_BLK) void k_vg_error(const float4* opts, const d
   for (int q = 0; q < 12; q++) T.m[q] = T12[q], T0.m[q] = T12[12 + q];
   double acc[2] = {0.0, 0.0};
   if (i < n) {
-    const float4 p = opts[i];
-    const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
-    const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
-    Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    bool have_rca = false;
-    for (int k = 0; k < noff; k++) {
-      const int v = corr[(size_t)i * noff + k];
-      if (v < 0 || v >= map.nv) continue;
-      if (!have_rca) {
-        RCA = sym3_rotate(T0, vg_load_cov(cov_src, n, min(max(inv_src[i], 0), n - 1)));
-        have_rca = true;
-      }
-      const Sym3 Mi = vg_mahalanobis(map, v, RCA);
-      const double* mu = map.mean + 3 * (size_t)v;
-      const double w = sqrt((double)map.count[v]);
-      const double ex = mu[0] - vx, ey = mu[1] - vy, ez = mu[2] - vz;
-      const double mex = (Mi.xx * ex + Mi.xy * ey) + Mi.xz * ez;
-      const double mey = (Mi.xy * ex + Mi.yy * ey) + Mi.yz * ez;
-      const double mez = (Mi.xz * ex + Mi.yz * ey) + Mi.zz * ez;
-      acc[0] += w * ((ex * mex + ey * mey) + ez * mez);
-      acc[1] += 1.0;
-    }
+    vg_error_point(opts, cov_src, inv_src, n, map, T, T0, noff, corr, i, acc);
   }
   // (the cost goes to slot 27 and the count to slot 28 of the block's row, like k_vg_linearize)
   block_reduce<2, VG_BLK>(acc, red, tid);

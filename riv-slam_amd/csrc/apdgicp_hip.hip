@@ -14,6 +14,7 @@
 #include "apd_map.hpp"
 #include "apd_scan_context.hpp"
 #include "apd_vgicp.hpp"
+#include "apd_vgicp_batch.hpp"
 
 using namespace apd;
 
@@ -62,9 +63,62 @@ struct apdgicp_handle {
   std::vector<double> tr_lambda, tr_rho, tr_y0, tr_yi, tr_dnorm, tr_poses;  // poses: 16 doubles each, column-major
 };
 
+// apdgicp_batch_set_vgicp (include/apdgicp_hip.h, V8 .. V12): per cloud slot the voxel map and the inverse permutation, cached by identity like
+// VgState's pieces; per align the pair table, the frozen indices and the block rows.
+struct VgbState {
+  struct Slot {
+    bool map_built = false;    // the map: points map_pts_gen, covariances map_cov_gen, map_res, map_mode
+    uint64_t map_pts_gen = 0, map_cov_gen = 0;
+    double map_res = 0.0;
+    int map_mode = 0;
+    uint64_t inv_pts_gen = 0;  // inv: the inverse of the permutation of points inv_pts_gen (0: none)
+    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
+    DevBuf inv, vkeys, vcount, vmean, vcov;  // map buffers sized for nv <= n
+    void release() {
+      for (DevBuf* b : {&inv, &vkeys, &vcount, &vmean, &vcov}) b->release();
+      map_built = false, inv_pts_gen = 0, nv = 0;
+    }
+  };
+  bool on = false;
+  apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
+  std::vector<Slot> slots;
+  int64_t builds = 0;
+  int last_ticks = 0;
+  int chunk = 0;               // ticks per enqueued chunk (create time: APDGICP_VGB_CHUNK, default kVgbChunk)
+  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum;  // scratch of one map build; builds follow each other in stream order
+  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
+  int scal_slots = 0;
+  DevBuf corr, part, done;
+  CachedTable pairs;
+  int* h_words = nullptr;      // pinned: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
+  size_t h_words_cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+  void release() {
+    for (Slot& sl : slots) sl.release();
+    slots.clear();
+    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &corr, &part, &done, &pairs.dev}) b->release();
+    scal_slots = 0;
+    if (h_words) (void)hipHostFree(h_words);
+    h_words = nullptr, h_words_cap = 0;
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 struct apdgicp_batch {
   Engine eng;
+  VgbState vg;  // (released by ~apdgicp_batch, while the engine's stream still exists)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
+  ~apdgicp_batch() {
+    if (eng.stream) {
+      (void)hipSetDevice(eng.device);
+      (void)hipStreamSynchronize(eng.stream);
+    }
+    vg.release();
+  }
 };
 
 struct apdgicp_submap {
@@ -530,6 +584,249 @@ int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
       [&](const double* T, double* yi) { return vg_error(h, T, yi); }, true);
 }
 
+// ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
+constexpr int kVgbChunk = 4;  // ticks enqueued per look at the done counter (docs/experiments.md, "VGICP batch: chunk length")
+
+int vgb_ensure_words(apdgicp_batch* b, size_t ints) {
+  VgbState& v = b->vg;
+  if (v.h_words && ints <= v.h_words_cap) return 0;
+  APD_HIP(hipStreamSynchronize(b->eng.stream));
+  if (v.h_words) APD_HIP(hipHostFree(v.h_words));
+  v.h_words = nullptr, v.h_words_cap = 0;
+  const size_t cap = std::max<size_t>(ints * 2, 1024);
+  APD_HIP(hipHostMalloc((void**)&v.h_words, cap * sizeof(int), hipHostMallocDefault));
+  memset(v.h_words, 0, cap * sizeof(int));
+  v.h_words_cap = cap;
+  return 0;
+}
+
+// room for the scal words of every slot of the engine; the words of built maps survive a growth
+int vgb_ensure_slots(apdgicp_batch* b) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  const int want = (int)e.clouds.size();
+  if ((int)v.slots.size() < want) v.slots.resize(want);
+  if (want <= v.scal_slots) return 0;
+  const int cap = std::max(64, 2 * want);
+  DevBuf grown;
+  APD_TRY(grown.ensure((size_t)cap * 16));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (v.scal_slots) APD_HIP(hipMemcpy(grown.p, v.scal.p, (size_t)v.scal_slots * 16, hipMemcpyDeviceToDevice));
+  v.scal.release();
+  v.scal = grown;
+  v.scal_slots = cap;
+  return 0;
+}
+
+bool vgb_map_current(const apdgicp_batch* b, int slot) {
+  const VgbState& v = b->vg;
+  const Engine::Cloud& c = b->eng.clouds[slot];
+  const VgbState::Slot& sl = v.slots[slot];
+  return sl.map_built && c.cov_valid && sl.map_pts_gen == c.pts_gen && sl.map_cov_gen == c.cov_gen && sl.map_res == v.prm.resolution && sl.map_mode == v.prm.voxel_mode;
+}
+
+// the inverse permutation of a sorted slot, once per setting of its points
+int vgb_ensure_inv(apdgicp_batch* b, int slot) {
+  Engine& e = b->eng;
+  Engine::Cloud& c = e.clouds[slot];
+  VgbState::Slot& sl = b->vg.slots[slot];
+  if (sl.inv.p && sl.inv_pts_gen == c.pts_gen && (size_t)c.n * 4 <= sl.inv.cap) return 0;
+  sl.inv_pts_gen = 0;
+  if ((size_t)c.n * 4 > sl.inv.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(sl.inv.ensure((size_t)c.n * 4));
+  hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, e.stream, c.perm.as<int>(), c.n, sl.inv.as<int>());
+  APD_HIP(hipGetLastError());
+  sl.inv_pts_gen = c.pts_gen;
+  return 0;
+}
+
+// V8: the maps of the listed slots (sorted, covariances there) that are not current: enqueued one after the other with no wait in between, then
+// ONE copy of every slot's {first bad point, voxel count} and one wait for all of them
+int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  APD_TRY(vgb_ensure_slots(b));
+  std::vector<int> todo;
+  int nmax = 0;
+  for (int t : targets)
+    if (!vgb_map_current(b, t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t), nmax = std::max(nmax, e.clouds[t].n);
+  if (todo.empty()) return 0;
+  const int lo = *std::min_element(todo.begin(), todo.end()), hi = *std::max_element(todo.begin(), todo.end());
+  APD_TRY(vgb_ensure_words(b, 4 + 4 * (size_t)(hi - lo + 1)));
+  {
+    const int nblk = (nmax + MAP_RS_TILE - 1) / MAP_RS_TILE;
+    const int64_t entries = 256ll * nblk;
+    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+    const size_t nhb = (size_t)(nmax + MAP_BLK - 1) / MAP_BLK;
+    bool grows = (size_t)nmax * 8 > v.keys_a.cap || (size_t)entries * 4 > v.hist.cap || (size_t)nsb * 4 > v.rs_bsum.cap || nhb * 4 > v.bsum.cap;
+    for (int t : todo) grows |= (size_t)e.clouds[t].n * 48 > v.slots[t].vcov.cap || (size_t)e.clouds[t].n * 4 > v.slots[t].inv.cap;
+    if (grows) APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced; never on a reused handle with clouds of the same sizes)
+    APD_TRY(v.keys_a.ensure((size_t)nmax * 8));
+    APD_TRY(v.keys_b.ensure((size_t)nmax * 8));
+    APD_TRY(v.idx_a.ensure((size_t)nmax * 4));
+    APD_TRY(v.idx_b.ensure((size_t)nmax * 4));
+    APD_TRY(v.hist.ensure((size_t)entries * 4));
+    APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
+    APD_TRY(v.bsum.ensure(nhb * 4));
+  }
+  for (int t : todo) {
+    Engine::Cloud& c = e.clouds[t];
+    VgbState::Slot& sl = v.slots[t];
+    const int n = c.n;
+    sl.map_built = false;
+    APD_TRY(sl.vkeys.ensure((size_t)n * 8));
+    APD_TRY(sl.vcount.ensure((size_t)n * 4));
+    APD_TRY(sl.vmean.ensure((size_t)n * 24));
+    APD_TRY(sl.vcov.ensure((size_t)n * 48));
+    APD_TRY(vgb_ensure_inv(b, t));
+    const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+    const int64_t entries = 256ll * nblk;
+    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+    const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
+    int* scal = v.scal.as<int>() + 4 * (size_t)t;
+    APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
+    unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
+    int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
+    hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
+    for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
+      hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
+      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
+      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
+      hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
+      std::swap(ks, kd), std::swap(is, id);
+    }
+    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
+    // (a target with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
+    hipLaunchKernelGGL(k_vg_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), sl.inv.as<int>(),
+                       sl.vkeys.as<unsigned long long>(), sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vcov.as<double>(), n);
+    APD_HIP(hipGetLastError());
+  }
+  int* hw = v.h_words + 4;
+  APD_HIP(hipMemcpyAsync(hw, v.scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(v.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));  // (the covariance kernels' flag, with the same wait)
+  APD_HIP(hipStreamSynchronize(e.stream));
+  int rc = 0;
+  for (int t : todo) {
+    const int* w = hw + 4 * (size_t)(t - lo);
+    VgbState::Slot& sl = v.slots[t];
+    const Engine::Cloud& c = e.clouds[t];
+    if (w[0] != kVgBadNone) {
+      if (rc == 0)
+        rc = fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: point " + std::to_string(w[0]) + " of cloud slot " + std::to_string(t) +
+                                               " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
+      continue;
+    }
+    if (w[1] < 1 || w[1] > c.n) {
+      if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, "voxelized GICP: inconsistent voxel count");
+      continue;
+    }
+    sl.nv = w[1];
+    sl.map_built = true, sl.map_pts_gen = c.pts_gen, sl.map_cov_gen = c.cov_gen, sl.map_res = v.prm.resolution, sl.map_mode = v.prm.voxel_mode;
+    v.builds++;
+  }
+  if (v.h_words[2]) {  // a point that is not finite trips the covariance kernels too: the message about the point is the useful one
+    const int flag = v.h_words[2];
+    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+    if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
+  }
+  return rc;
+}
+
+// one slot's map for the getters: sorted, covariances computed, built
+int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
+  Engine& e = b->eng;
+  if (!b->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_batch_set_vgicp)");
+  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.pool_leave());
+  APD_TRY(e.finish_align());
+  APD_TRY(e.compute_covariances({cloud}));
+  APD_TRY(e.upload_desc());
+  return vgb_build_maps(b, {cloud});
+}
+
+// V10 / V12: the optimiser loop of every pair on the device; returns with the device records complete
+int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
+  APD_TRY(e.setup_pairs(pairs, n_pairs, true));  // clouds sorted, covariances there, d_state / d_results / d_guess
+  e.results_on_host = false;
+  const int np = e.npairs, noff = v.n_offsets();
+  std::vector<int> targets;
+  for (int i = 0; i < np; i++) targets.push_back(e.h_pairs[i].tgt);
+  APD_TRY(vgb_build_maps(b, targets));
+  for (int i = 0; i < np; i++) APD_TRY(vgb_ensure_inv(b, e.h_pairs[i].src));
+  std::vector<VgbPair> tab(np);
+  for (int i = 0; i < np; i++) {
+    const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
+    const VgbState::Slot& st = v.slots[t];
+    tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0,
+                     VgbMap{st.vkeys.as<unsigned long long>(), st.vcount.as<int>(), st.vmean.as<double>(), st.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)t + 1}};
+  }
+  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
+  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
+  const size_t corr_stride = (size_t)e.nmax_src * noff;
+  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
+  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(v.done.ensure(16));
+  APD_TRY(vgb_ensure_words(b, 4));
+  for (hipEvent_t& ev : v.ev)
+    if (!ev) APD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  const apdgicp_params& p = e.params;
+  const Consts cst = e.consts();
+  PairState* st = e.d_state.as<PairState>();
+  ResultRec* recs = e.d_results.as<ResultRec>();
+  hipLaunchKernelGGL(k_vgb_init, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, e.stream, st, e.d_guess.as<Rigid>(), np, p.max_iterations, v.done.as<int>());
+  const long long bound = p.max_iterations <= 0 ? 0 : (p.optimizer == APDGICP_OPT_GN ? (long long)p.max_iterations : (long long)p.max_iterations * (1 + (long long)std::max(0, p.lm_max_iterations)));
+  const int chunk = std::max(1, v.chunk);
+  long long ticks = 0;
+  int nchunks = 0;
+  auto enqueue_chunk = [&]() -> int {
+    const int todo = (int)std::min<long long>(chunk, bound - ticks);
+    for (int q = 0; q < todo; q++) {
+      hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution,
+                         (int)v.prm.neighbor_search, noff, v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
+      hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, v.done.as<int>());
+    }
+    APD_HIP(hipGetLastError());
+    ticks += todo;
+    // the done counter as of this chunk, mirrored into the pinned word of the chunk's parity
+    APD_HIP(hipMemcpyAsync(v.h_words + (nchunks & 1), v.done.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipEventRecord(v.ev[nchunks & 1], e.stream));
+    nchunks++;
+    return 0;
+  };
+  if (bound == 0) {
+    hipLaunchKernelGGL(k_vgb_records, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, e.stream, st, np, recs);
+    APD_HIP(hipGetLastError());
+  } else {
+    APD_TRY(enqueue_chunk());
+    for (int waited = 0;; waited++) {
+      if (ticks < bound) APD_TRY(enqueue_chunk());  // (one chunk ahead while the host waits for the one before)
+      APD_HIP(hipEventSynchronize(v.ev[waited & 1]));
+      if (v.h_words[waited & 1] >= np || waited + 1 >= nchunks) break;
+    }
+  }
+  // the covariance kernels' error flag (deferred by setup_pairs) with the final wait
+  APD_HIP(hipMemcpyAsync(v.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  for (Engine::Cloud& c : e.clouds) c.stage_pending = false, c.stage_wait = nullptr, c.stage_seq_word = nullptr;  // (every sort has run)
+  e.n_stage_pending = 0;
+  v.last_ticks = (int)ticks;
+  e.last_ticks = (int)ticks;
+  if (v.h_words[2]) {
+    const int flag = v.h_words[2];
+    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+    return fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
+  }
+  return 0;
+}
+
+const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+
 }  // namespace
 
 extern "C" {
@@ -942,6 +1239,82 @@ int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds) {
   return 0;
 }
 
+int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
+  return guarded([&]() -> int {
+    // (the parameters first: what is wrong with them does not depend on the handle)
+    if (p && (!(p->resolution > 0.0) || !std::isfinite(p->resolution))) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: the resolution must be finite and positive");
+    if (p && (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27)) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown neighbour search method");
+    if (p && p->voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
+    if (p && p->voxel_mode != APDGICP_VGICP_ADDITIVE && p->voxel_mode != APDGICP_VGICP_ADDITIVE_WEIGHTED) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown accumulation mode");
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    VgbState& v = b->vg;
+    if (!p) {
+      v.on = false;
+      return 0;
+    }
+    if (!v.on) {  // the pooled / deferred aligns of the APD path finish as what they were enqueued as
+      if (b->eng.stream) {
+        APD_TRY(b->eng.pool_leave());
+        APD_TRY(b->eng.finish_align());
+      }
+      if (!v.chunk) v.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
+    }
+    v.prm = *p;
+    v.on = true;
+    return 0;
+  });
+}
+
+int apdgicp_batch_get_vgicp(const apdgicp_batch* b, apdgicp_vgicp_params* p, int* enabled) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (p) *p = b->vg.prm;
+  if (enabled) *enabled = b->vg.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_batch_vgicp_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(vgb_slot_map(b, cloud));
+    *n_voxels = b->vg.slots[cloud].nv;
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    APD_TRY(vgb_slot_map(b, cloud));
+    const VgbState::Slot& sl = b->vg.slots[cloud];
+    Engine& e = b->eng;
+    const int64_t nv = sl.nv;
+    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
+    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
+    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
+    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), sl.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
+    if (counts) APD_HIP(hipMemcpyAsync(counts, sl.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
+    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, sl.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
+    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), sl.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (int64_t i = 0; i < nv && coords_n3; i++) {
+      const unsigned long long k = keys[i];
+      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
+    }
+    for (int64_t i = 0; i < nv && covs_n9; i++) {
+      const double* c = &c6[6 * i];
+      double* o = covs_n9 + 9 * i;
+      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
+    }
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds) {
+  if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n_builds = b->vg.builds;
+  return 0;
+}
+
 int apdgicp_set_trace(apdgicp_handle* h, int enable) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   h->eng.trace_on = enable != 0;
@@ -1253,6 +1626,7 @@ int apdgicp_batch_clear(apdgicp_batch* b) {
   for (auto& c : b->eng.clouds) c.release_all();
   b->eng.clouds.clear();
   b->eng.desc_dirty = true;
+  b->vg.release();  // (V8: every slot's map and inverse permutation go with the clouds)
   return 0;
 }
 
@@ -1300,6 +1674,11 @@ int apdgicp_batch_compute_covariances(apdgicp_batch* b) {
 int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, void** d_results) {
   return guarded([&]() -> int {
     if (!b || !pairs) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (b->vg.on) {  // voxelized GICP: complete on return (V12)
+      APD_TRY(vgb_align(b, pairs, n_pairs));
+      if (d_results) *d_results = b->eng.d_results.p;
+      return 0;
+    }
     if (b->eng.pool_eligible()) {  // Levenberg-Marquardt: through the pair pool (complete on return, like every LM run)
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
@@ -1315,6 +1694,7 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
 int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, uint64_t* ticket) {
   return guarded([&]() -> int {
     if (!b || !pairs || !ticket) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_eligible()) return e.pool_enqueue(pairs, n_pairs, ticket);
     APD_TRY(e.ensure_alt_slot());
@@ -1331,18 +1711,21 @@ int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int
 int apdgicp_batch_pump(apdgicp_batch* b) {
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     return b->eng.pool.on ? b->eng.pool_pump(false) : 0;
   });
 }
 
 int apdgicp_batch_is_pooled(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (b->vg.on) return 0;
   return b->eng.pool_eligible() ? Engine::pool_lanes_cfg() : 0;
 }
 
 int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_results, apdgicp_result* host_results) {
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_find(ticket)) return e.pool_collect(ticket, d_results, host_results);
     const bool previous = ticket + 1 == e.align_seq;
@@ -1369,7 +1752,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
 int apdgicp_batch_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, apdgicp_result* results) {
   return guarded([&]() -> int {
     if (!results) return fail(APDGICP_ERR_INVALID_ARG, "results is null");
-    if (b && pairs && b->eng.pool_eligible()) {
+    if (b && pairs && !b->vg.on && b->eng.pool_eligible()) {
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
       return b->eng.pool_collect(ticket, nullptr, results);

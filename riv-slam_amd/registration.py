@@ -110,6 +110,7 @@ SYMBOLS = [
     "apdgicp_scan_context_detect", "apdgicp_scan_context_detect_batch", "apdgicp_scan_context_descriptors",
     "apdgicp_vgicp_default_params", "apdgicp_set_vgicp", "apdgicp_get_vgicp", "apdgicp_vgicp_voxel_count", "apdgicp_vgicp_get_voxels",
     "apdgicp_vgicp_get_correspondences", "apdgicp_vgicp_build_count",
+    "apdgicp_batch_set_vgicp", "apdgicp_batch_get_vgicp", "apdgicp_batch_vgicp_voxel_count", "apdgicp_batch_vgicp_get_voxels", "apdgicp_batch_vgicp_build_count",
 ]
 
 _lib = None
@@ -282,6 +283,11 @@ def load_library(path: str | None = None):
     L.apdgicp_vgicp_get_voxels.argtypes = [vp, i64, vp, vp, vp, vp]
     L.apdgicp_vgicp_get_correspondences.argtypes = [vp, vp, i64]
     L.apdgicp_vgicp_build_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_batch_set_vgicp.argtypes = [vp, vp]
+    L.apdgicp_batch_get_vgicp.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_batch_vgicp_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
+    L.apdgicp_batch_vgicp_get_voxels.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp]
+    L.apdgicp_batch_vgicp_build_count.argtypes = [vp, C.POINTER(i64)]
     if path is None:
         _lib = L
     return L

@@ -1,6 +1,7 @@
 """Voxelized GICP (fast_gicp::FastVGICP, the FAST_VGICP branch of select_registration_method(), registrations.cpp:62-70) as a mode of
 the registration handle: `FastVGICP` is `registration.FastAPDGICP` with apdgicp_set_vgicp switched on and the reference's three setters
-(fast_apdgicp/include/fast_gicp/gicp/fast_vgicp.hpp).  Semantics: the list V1 .. V7 in include/apdgicp_hip.h.
+(fast_apdgicp/include/fast_gicp/gicp/fast_vgicp.hpp).  Semantics: the list V1 .. V7 in include/apdgicp_hip.h.  `BatchVGICP` is
+`registration.BatchAPDGICP` with apdgicp_batch_set_vgicp switched on: per-slot voxel maps and the optimiser loop on the device (V8 .. V12).
 
 There is NO CPU fallback: without the HIP library or a GPU every call raises.
 """
@@ -106,4 +107,72 @@ class FastVGICP(reg.FastAPDGICP):
         """How many voxel maps this handle has built (the cache rules' test hook)."""
         n = C.c_int64()
         _check(self.L.apdgicp_vgicp_build_count(self.h, C.byref(n)))
+        return n.value
+
+
+class BatchVGICP(reg.BatchAPDGICP):
+    """Many independent voxelized-GICP registrations on one GPU: a batch handle with apdgicp_batch_set_vgicp on (V8 .. V12).  Clouds, align,
+    align_async / synchronize and fitness are the base class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is;
+    align_enqueue / align_collect raise (one batch at a time).  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.vparams = default_vgicp_params()
+        self._push_vgicp()
+
+    def _push_vgicp(self):
+        _check(self.L.apdgicp_batch_set_vgicp(self.b, C.byref(self.vparams)))
+
+    def _set(self, field: str, value):
+        old = getattr(self.vparams, field)
+        setattr(self.vparams, field, value)
+        try:
+            self._push_vgicp()
+        except reg.ApdgicpError:
+            setattr(self.vparams, field, old)
+            raise
+
+    def setResolution(self, resolution: float):
+        self._set("resolution", float(resolution))
+
+    def setNeighborSearchMethod(self, method: int):
+        self._set("neighbor_search", int(method))
+
+    def setVoxelAccumulationMode(self, mode: int):
+        self._set("voxel_mode", int(mode))
+
+    def get_vgicp(self):
+        """(VgicpParams, enabled) as the library holds them."""
+        p, on = VgicpParams(), C.c_int()
+        _check(self.L.apdgicp_batch_get_vgicp(self.b, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def disable(self):
+        _check(self.L.apdgicp_batch_set_vgicp(self.b, None))
+
+    def enable(self):
+        self._push_vgicp()
+
+    def enabled(self) -> bool:
+        return self.get_vgicp()[1]
+
+    def voxel_count(self, cloud: int) -> int:
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_voxel_count(self.b, int(cloud), C.byref(n)))
+        return n.value
+
+    def voxels(self, cloud: int):
+        """The voxel map of cloud slot `cloud` (built if it is not current), as FastVGICP.voxels()."""
+        n = self.voxel_count(cloud)
+        coords = np.empty((n, 3), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        means = np.empty((n, 3))
+        covs = np.empty((n, 9))
+        _check(self.L.apdgicp_batch_vgicp_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
+        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+
+    def build_count(self) -> int:
+        """How many voxel maps this handle has built, all slots together (the cache rules' test hook)."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_build_count(self.b, C.byref(n)))
         return n.value
