@@ -43,7 +43,8 @@ extern "C" {
                                       still 6 (additive): + the apdgicp_map_cloud_* object (map cloud generation: pose transform, gate, octree voxel centres);
                                       still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K);
                                       still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle);
-                                      still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle) */
+                                      still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle);
+                                      still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -352,6 +353,78 @@ int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coord
 int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_source);
 /* Debug: how many times this handle has built a voxel map (the tests of the cache rules read it) */
 int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds);
+
+/* ------------------------------------------------------------------ NDT (P2D / D2D) as a mode of the handle
+ * fast_gicp::NDTCuda, the NDT the reference tree holds (the factory's own NDT_OMP fallback, registrations.cpp:101-134, is pclomp, whose
+ * sources are not in the tree).  "NC:" = fast_apdgicp/src/fast_gicp/cuda/ndt_cuda.cu, "ND:" = .../cuda/ndt_compute_derivatives.cu,
+ * "GV:" = .../cuda/gaussian_voxelmap.cu, "CR:" = .../cuda/covariance_regularization.cu.  The reference is fp32 throughout and leaves several
+ * orders to chance: atomic float adds in accumulate_points_kernel, thrust::transform_reduce, and a hash table that may drop up to 1 % of the
+ * points (GV:276).  None of that can be pinned, so -- as for voxelized GICP -- the reference's FORMULAS are evaluated in fp64, in a written
+ * order, over the exact voxel set.  The deviations from the reference, all in one place:
+ *     - fp64 instead of fp32 everywhere: the voxel coordinate (vector3_hash.cuh:35-38 takes it in fp32), the sums, the pose (the reference
+ *       casts it to fp32), the cost;
+ *     - voxels are numbered in ascending key order (the reference: atomic arrival order), sums run in the caller's order, reductions in a
+ *       fixed tree / block order;
+ *     - every point reaches its voxel (no hash table, no dropped points);
+ *     - the symmetric eigen-decomposition of N3 is the handle's Jacobi routine, not Eigen's SelfAdjointEigenSolver;
+ *     - N8 (the reference would solve a singular system).
+ * The kernels (riv-slam_amd/csrc/apd_ndt.hpp) and the restatement the tests compare with (tests/ndt_np.py) follow this list:
+ *   N1. Keys, range and voxel order are V1 .. V3's: c = floor(x / res - 0.5) per axis in fp64, a true division; points of a cloud that gets
+ *       a map must be finite with |c| < 2^20; voxels are numbered in ascending key order.
+ *   N2. Voxel statistic (GV:118-143, 174-194).  For each voxel, over its points in the caller's order, fp64 sums started at 0:
+ *       S1 = sum x and S2 = sum x x^T (six unique entries); mean = S1 / n; the raw covariance is the LOWER triangle of the reference's
+ *       expression, which SelfAdjointEigenSolver reads: c_rc = (S2_rc - mean_r S1_c) / n for r >= c.  Counts, means and raw covariance
+ *       entries are bit-equal to a sequential loop written this way.
+ *   N3. Regularisation (CR:73-87, always MIN_EIG, NC:128,139): C = V diag(max(lambda_i, 1e-3)) V^T.  The floor is absolute, not relative.
+ *       A voxel with one point has raw covariance 0 and becomes 1e-3 I.
+ *   N4. Two maps.  The target always gets a map, the source only in D2D (NC:120-129).  Both are pure functions of (points, resolution),
+ *       separate from the voxelized-GICP map (another statistic); no k-NN covariance is involved: with the mode on apdgicp_align /
+ *       apdgicp_linearize do not compute them and accept clouds smaller than k_correspondences.  Caching is by identity, as for the
+ *       voxelized-GICP map: the setting of the cloud's points, the resolution.  apdgicp_swap_source_and_target swaps the maps with the
+ *       clouds: in D2D with both maps built it rebuilds nothing (NC:90-93); in P2D the new target's map is built on demand.  A target
+ *       point refused by V2 gives APDGICP_ERR_INVALID_ARG naming the cloud and the point, and so does a source point in D2D; in P2D a
+ *       refused source point is a miss.  The handle stays usable.
+ *   N5. Rows.  A row is a source voxel in voxel order (D2D: its mean is the position, its regularised covariance C_A) or a source point in
+ *       the caller's order (P2D).  q_r = ((R_r0 x + R_r1 y) + R_r2 z) + t_r in fp64 (V4).  c(q) + each offset of DIRECT1 / DIRECT7 /
+ *       DIRECT27 in the order of NC:43-68 (identical to V5's) is looked up; every hit is stored as a voxel index per (row, offset), -1 for
+ *       a miss.  DIRECT_RADIUS: APDGICP_ERR_UNSUPPORTED.
+ *   N6. Cost (ND:50-91, 120-163).  A hit whose target voxel has count <= 6 contributes nothing.  Otherwise M = (C_B + R_lin C_A R_lin^T)^-1
+ *       (D2D; R_lin the rotation of the last linearize pose) or M = C_B^-1 (P2D), by cofactors; e = mean_B - q; w = res^2 / (res^2 + e.e),
+ *       the Cauchy weight with k = resolution; cost += w e.(M e), H += w J^T M J, b += w J^T (M e), J = [skew(q) | -I].  Terms of a row are
+ *       added in offset order, one row per lane in blocks of 256; lanes, waves and blocks are added in the fixed tree / block order of V5.
+ *       No floating-point atomics.  n_matched is the number of contributing terms.
+ *   N7. Frozen state (NC:162-177).  compute_error evaluates the same cost at the trial pose over the stored indices with R_lin of the last
+ *       linearize; q, e and w come from the trial pose; M is recomputed by the same device function, as in V6.  The frozen state is tied by
+ *       identity to the source's points and to the maps it was made against (otherwise APDGICP_ERR_NO_INPUT).
+ *   N8. No contributing term at a linearize inside align: the loop stops there with converged = 0, lm_failed = 0, n_matched = 0 and T = the
+ *       pose so far (V7's rule).  max_correspondence_distance and the APD flags have no meaning for this cost.
+ *   N9. Mode rules.  Defaults: resolution 1.0, D2D, DIRECT7 (NC:15-22).  apdgicp_set_ndt and apdgicp_set_vgicp are exclusive: switching one
+ *       on switches the other off; NULL returns to what apdgicp_params says.  With NDT on, apdgicp_align and apdgicp_align_host_loop both
+ *       run the host-driven loop of apdgicp_align_host_loop over the two kernels (trace, final Hessian and apdgicp_result as there);
+ *       apdgicp_get_correspondences / apdgicp_get_mahalanobis return APDGICP_ERR_UNSUPPORTED; the covariance calls are untouched (they
+ *       compute, return or set the k-NN covariances, which this cost does not read); fitness_score, nearest_neighbours*, transform_source
+ *       and get_points are unchanged.  Batch handles have no NDT mode.  With the mode off nothing differs from a handle that never had it on. */
+typedef enum { APDGICP_NDT_P2D = 0, APDGICP_NDT_D2D = 1 } apdgicp_ndt_distance;   /* NDTDistanceMode, ndt_settings.hpp */
+#define APDGICP_NDT_DIRECT_RADIUS 3   /* NeighborSearchMethod::DIRECT_RADIUS as a value of neighbor_search: refused (N5) */
+typedef struct {
+  double resolution;         /* setResolution ; default 1.0 ; finite and > 0 */
+  int32_t distance_mode;     /* apdgicp_ndt_distance ; default D2D */
+  int32_t neighbor_search;   /* apdgicp_vgicp_search ; default DIRECT7 */
+} apdgicp_ndt_params;
+void apdgicp_ndt_default_params(apdgicp_ndt_params* p);                          /* 1.0, D2D, DIRECT7: NC:15-22 */
+/* p != NULL: the mode on with these parameters (and voxelized GICP off); NULL: back to what apdgicp_params says */
+int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p);
+int apdgicp_get_ndt(const apdgicp_handle* h, apdgicp_ndt_params* p, int* enabled);   /* either output may be NULL */
+/* number of voxels of the map of `which` (APDGICP_SOURCE / APDGICP_TARGET; built if it is not there; needs that cloud only) */
+int apdgicp_ndt_voxel_count(apdgicp_handle* h, int which, int64_t* n_voxels);
+/* that map in voxel order (N1), host memory, any pointer may be NULL: coordinates (n x 3), counts, means (n x 3), raw covariances of N2
+ * (n x 6: xx, yx, zx, yy, zy, zz), regularised covariances of N3 (n x 9, the 3x3 block); capacity >= the voxel count */
+int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6, double* covs_n9);
+/* the stored indices of the last linearize: n_rows x n_offsets target voxel indices in offset order, -1 = miss; n_rows = the source's
+ * voxel count (D2D) or point count (P2D) */
+int apdgicp_ndt_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_rows);
+/* Debug: how many voxel maps (of either cloud) this handle has built in this mode (the tests of the cache rules read it) */
+int apdgicp_ndt_build_count(apdgicp_handle* h, int64_t* n_builds);
 
 /* ------------------------------------------------------------------ batched registrations
  * Independent (source, target) pairs -- loop-closure candidates (loop_detector.cpp:222-236,404-423)

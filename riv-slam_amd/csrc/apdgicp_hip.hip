@@ -15,6 +15,7 @@
 #include "apd_scan_context.hpp"
 #include "apd_vgicp.hpp"
 #include "apd_vgicp_batch.hpp"
+#include "apd_ndt.hpp"
 
 using namespace apd;
 
@@ -45,13 +46,53 @@ struct VgState {
   int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
 };
 
+// apdgicp_set_ndt: the voxel maps of target and source and the frozen state of the last linearize (include/apdgicp_hip.h, N1 .. N9)
+struct NdState {
+  struct Map {                 // one cloud's map: a pure function of (points, resolution), cached by identity like VgState's
+    bool built = false;
+    uint64_t pts_gen = 0;      // apdgicp_handle::cloud_gen of the points it was made from
+    double res = 0.0;
+    int64_t id = 0;            // which build this is (NdState::builds when it was made): names the map for the frozen state
+    int nv = 0;
+    DevBuf vkeys, vcount, vmean, vraw, vcov;
+    void release() {
+      for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
+      built = false, nv = 0;
+    }
+    VgMap map() const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv}; }
+  };
+  bool on = false;
+  apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
+  Map maps[2];                 // [source, target]; swapped with the clouds
+  int64_t builds = 0;
+  bool have_lin = false;       // corr / T_lin: a linearize of source lin_src_gen against map lin_tgt_id (and, D2D, over the rows of map lin_src_id)
+  uint64_t lin_src_gen = 0;
+  int64_t lin_tgt_id = 0, lin_src_id = 0;
+  int lin_mode = 0, n_rows_lin = 0, noff_lin = 0;
+  double T_lin[12];
+  double final_H[36];          // of the last align in this mode (identity until then)
+  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum, scal, corr, part, T, out;
+  NdState() { reset_final_H(); }
+  void reset_final_H() {
+    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
+  }
+  bool allocated() const { return keys_a.p || T.p || maps[0].vkeys.p || maps[1].vkeys.p; }
+  void release() {
+    for (Map& m : maps) m.release();
+    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &corr, &part, &T, &out}) b->release();
+  }
+  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+};
+
 struct apdgicp_handle {
   Engine eng;
   VgState vg;  // (released by ~apdgicp_handle, while the engine's stream still exists)
+  NdState nd;  // (likewise)
   ~apdgicp_handle() {
-    if (vg.keys_a.p || vg.T.p || vg.inv_s.p) {
+    if (vg.keys_a.p || vg.T.p || vg.inv_s.p || nd.allocated()) {
       if (eng.stream) (void)hipStreamSynchronize(eng.stream);
       vg.release();
+      nd.release();
     }
   }
   uint64_t cloud_epoch = 0, cloud_gen[2] = {0, 0};  // cloud_gen[slot]: which setting of points the slot holds (0: none); swapped with the clouds
@@ -476,7 +517,7 @@ int vg_error(apdgicp_handle* h, const double* T16, double* cost) {
 // The reference's own control flow (L:55-173) on the host over two callables: lin(T16, H, b, &y0, &matched) and err(T16, &yi), the two
 // virtuals of LsqRegistration.  stop_on_empty (V7 of the voxelized mode): a linearize without a correspondence ends the loop.
 template <typename Lin, typename Err>
-int host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, Lin&& lin, Err&& err, bool stop_on_empty) {
+int host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, Lin&& lin, Err&& err, bool stop_on_empty, double* final_H_out = nullptr) {
   Engine& e = h->eng;
   const apdgicp_params& p = e.params;
   float g[16];
@@ -571,7 +612,11 @@ int host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, Lin
   out->lm_failed = failed;
   out->n_matched = matched;
   h->have_corr = n_lin > 0;
-  // keep getFinalHessian() coherent with this path
+  // keep getFinalHessian() coherent with this path (final_H_out: the caller keeps it on the host, there may be no pair state on the device)
+  if (final_H_out) {
+    memcpy(final_H_out, final_H, sizeof(final_H));
+    return 0;
+  }
   APD_HIP(hipMemcpyAsync((char*)e.d_state.p + offsetof(PairState, final_H), final_H, sizeof(final_H), hipMemcpyHostToDevice, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   return 0;
@@ -582,6 +627,168 @@ int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return host_loop(
       h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vg_linearize(h, T, H, b, y0, m); },
       [&](const double* T, double* yi) { return vg_error(h, T, yi); }, true);
+}
+
+// ---- NDT (include/apdgicp_hip.h N1 .. N9; kernels: apd_ndt.hpp)
+const char* nd_cloud_name(int which) { return which == kSrc ? "source" : "target"; }
+
+// N1 .. N4: the voxel map of one cloud.  Needs that cloud's points only: no covariances, any size.
+int nd_build_map(apdgicp_handle* h, int which) {
+  Engine& e = h->eng;
+  NdState& v = h->nd;
+  if (e.clouds.size() < 2 || e.clouds[which].n <= 0) return fail(APDGICP_ERR_NO_INPUT, std::string(nd_cloud_name(which)) + " cloud is not set");
+  NdState::Map& m = v.maps[which];
+  if (m.built && m.pts_gen == h->cloud_gen[which] && m.res == v.prm.resolution) return 0;
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+  Engine::Cloud& c = e.clouds[which];
+  const int n = c.n;
+  APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
+  m.built = false;
+  v.have_lin = false;
+  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+  const int64_t entries = 256ll * nblk;
+  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+  const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
+  APD_TRY(v.keys_a.ensure((size_t)n * 8));
+  APD_TRY(v.keys_b.ensure((size_t)n * 8));
+  APD_TRY(v.idx_a.ensure((size_t)n * 4));
+  APD_TRY(v.idx_b.ensure((size_t)n * 4));
+  APD_TRY(v.hist.ensure((size_t)entries * 4));
+  APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
+  APD_TRY(v.bsum.ensure((size_t)nhb * 4));
+  APD_TRY(v.scal.ensure(16));
+  int* scal = v.scal.as<int>();
+  APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
+  unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
+  int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
+  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
+  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
+    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
+    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
+    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
+    std::swap(ks, kd), std::swap(is, id);
+  }
+  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
+  APD_HIP(hipGetLastError());
+  int hs[4];
+  APD_HIP(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (hs[0] != kVgBadNone)
+    return fail(APDGICP_ERR_INVALID_ARG, std::string("NDT: ") + nd_cloud_name(which) + " point " + std::to_string(hs[0]) +
+                                             " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
+  const int nv = hs[1];
+  if (nv < 1 || nv > n) return fail(APDGICP_ERR_INTERNAL, "NDT: inconsistent voxel count");
+  APD_TRY(m.vkeys.ensure((size_t)nv * 8));
+  APD_TRY(m.vcount.ensure((size_t)nv * 4));
+  APD_TRY(m.vmean.ensure((size_t)nv * 24));
+  APD_TRY(m.vraw.ensure((size_t)nv * 48));
+  APD_TRY(m.vcov.ensure((size_t)nv * 48));
+  hipLaunchKernelGGL(k_ndt_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), m.vkeys.as<unsigned long long>(),
+                     m.vcount.as<int>(), m.vmean.as<double>(), m.vraw.as<double>(), m.vcov.as<double>(), nv);
+  APD_HIP(hipGetLastError());
+  m.nv = nv;
+  m.built = true, m.pts_gen = h->cloud_gen[which], m.res = v.prm.resolution;
+  m.id = ++v.builds;
+  return 0;
+}
+
+// both clouds in caller's order on the device and the maps the mode needs (N4): everything k_ndt_linearize reads
+int nd_prepare(apdgicp_handle* h) {
+  Engine& e = h->eng;
+  if (e.clouds.size() < 2 || e.clouds[kSrc].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "source cloud is not set");
+  if (e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.upload_desc());
+  APD_TRY(nd_build_map(h, kTgt));
+  if (h->nd.prm.distance_mode == APDGICP_NDT_D2D) APD_TRY(nd_build_map(h, kSrc));
+  return 0;
+}
+
+// linearize (NC:137-160) at T (column-major 4x4)
+int nd_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
+  APD_TRY(nd_prepare(h));
+  Engine& e = h->eng;
+  NdState& v = h->nd;
+  const Engine::Cloud& s = e.clouds[kSrc];
+  const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
+  const NdState::Map &mt = v.maps[kTgt], &ms = v.maps[kSrc];
+  const int nrows = d2d ? ms.nv : s.n, noff = v.n_offsets(), nblk = (nrows + VG_BLK - 1) / VG_BLK;
+  if ((size_t)nrows * noff * 4 > v.corr.cap || (size_t)nblk * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.corr.ensure((size_t)nrows * noff * 4));
+  APD_TRY(v.part.ensure((size_t)nblk * VG_RED * 8));
+  APD_TRY(v.T.ensure(24 * sizeof(double)));
+  APD_TRY(v.out.ensure(64 * sizeof(double)));
+  colmajor_to_rows12(T16, v.T_lin);
+  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  const int want = H && b ? 1 : 0;
+  const VgMap smap = d2d ? ms.map() : VgMap{nullptr, nullptr, nullptr, nullptr, 0};
+  if (d2d)
+    hipLaunchKernelGGL(k_ndt_linearize<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution,
+                       (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
+  else
+    hipLaunchKernelGGL(k_ndt_linearize<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution,
+                       (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 0, v.out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (want) {
+    memcpy(H, e.h_probe, 36 * sizeof(double));
+    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
+  }
+  if (cost) *cost = e.h_probe[42];
+  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  v.have_lin = true, v.n_rows_lin = nrows, v.noff_lin = noff, v.lin_mode = v.prm.distance_mode;
+  v.lin_src_gen = h->cloud_gen[kSrc], v.lin_tgt_id = mt.id, v.lin_src_id = d2d ? ms.id : 0;
+  return 0;
+}
+
+// compute_error (NC:162-177): the voxel indices and R_lin of the last linearize (N7)
+int nd_error(apdgicp_handle* h, const double* T16, double* cost) {
+  Engine& e = h->eng;
+  NdState& v = h->nd;
+  if (e.clouds.size() < 2) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
+  const Engine::Cloud& s = e.clouds[kSrc];
+  const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
+  const NdState::Map &mt = v.maps[kTgt], &ms = v.maps[kSrc];
+  // the frozen state must still describe what the handle holds: the same source points, the same maps, the same mode and resolution
+  const bool frozen_ok = v.have_lin && s.n > 0 && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_mode == v.prm.distance_mode && mt.built && mt.id == v.lin_tgt_id &&
+                         mt.pts_gen == h->cloud_gen[kTgt] && mt.res == v.prm.resolution && e.clouds[kTgt].n > 0 &&
+                         (d2d ? (ms.built && ms.id == v.lin_src_id && ms.pts_gen == h->cloud_gen[kSrc] && ms.res == v.prm.resolution && ms.nv == v.n_rows_lin)
+                              : s.n == v.n_rows_lin);
+  if (!frozen_ok) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds and voxel maps the handle holds now");
+  const int nrows = v.n_rows_lin, noff = v.noff_lin, nblk = (nrows + VG_BLK - 1) / VG_BLK;
+  APD_HIP(hipSetDevice(e.device));
+  double t24[24];
+  colmajor_to_rows12(T16, t24);
+  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
+  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  const VgMap smap = d2d ? ms.map() : VgMap{nullptr, nullptr, nullptr, nullptr, 0};
+  if (d2d)
+    hipLaunchKernelGGL(k_ndt_error<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution, noff,
+                       v.corr.as<int>(), v.part.as<double>());
+  else
+    hipLaunchKernelGGL(k_ndt_error<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution, noff,
+                       v.corr.as<int>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 27, v.out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  *cost = e.h_probe[42];
+  return 0;
+}
+
+int nd_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  APD_TRY(nd_prepare(h));
+  h->nd.reset_final_H();
+  const int rc = host_loop(
+      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return nd_linearize(h, T, H, b, y0, m); },
+      [&](const double* T, double* yi) { return nd_error(h, T, yi); }, true, h->nd.final_H);
+  h->have_corr = false;  // (the APD kernels' correspondences are not what this mode wrote)
+  return rc;
 }
 
 // ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
@@ -988,6 +1195,8 @@ int apdgicp_swap_source_and_target(apdgicp_handle* h) {
   h->eng.desc_dirty = true;
   h->pair_ready = h->have_corr = false;
   std::swap(h->cloud_gen[kSrc], h->cloud_gen[kTgt]);
+  std::swap(h->nd.maps[kSrc], h->nd.maps[kTgt]);  // NC:90-93: the NDT maps go with their clouds (tied to them by identity either way)
+  h->nd.have_lin = false;
   return 0;
 }
 
@@ -1038,6 +1247,7 @@ int apdgicp_set_covariances(apdgicp_handle* h, int which, const double* in, int6
 int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], double b[6], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->nd.on) return nd_linearize(h, T, H, b, cost, nullptr);
     if (h->vg.on) return vg_linearize(h, T, H, b, cost, nullptr);
     APD_TRY(ensure_pair(h));
     APD_TRY(h->eng.probe_linearize(T, H, b, cost, nullptr));
@@ -1049,6 +1259,7 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
 int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T || !cost) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->nd.on) return nd_error(h, T, cost);
     if (h->vg.on) return vg_error(h, T, cost);
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
     return h->eng.probe_error(T, cost);
@@ -1058,6 +1269,7 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
 int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int64_t n) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
@@ -1078,6 +1290,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
 int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT keeps no per-point Mahalanobis matrices");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP keeps no per-point Mahalanobis matrices");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
@@ -1103,6 +1316,7 @@ int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
 int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
     float g[16];
     if (guess) memcpy(g, guess, sizeof(g));
@@ -1137,6 +1351,7 @@ int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out)
 int apdgicp_align_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
     APD_TRY(ensure_pair(h));
     Engine& e = h->eng;
@@ -1170,6 +1385,7 @@ int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
   if (!v.on) h->have_corr = false;
   v.prm = *p;
   v.on = true;
+  h->nd.on = false;  // N9: the two modes are exclusive
   return 0;
 }
 
@@ -1236,6 +1452,104 @@ int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, i
 int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds) {
   if (!h || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
   *n_builds = h->vg.builds;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ NDT
+void apdgicp_ndt_default_params(apdgicp_ndt_params* p) {
+  if (!p) return;
+  p->resolution = 1.0;                          // NC:15
+  p->distance_mode = APDGICP_NDT_D2D;           // NC:16
+  p->neighbor_search = APDGICP_VGICP_DIRECT7;   // NC:17
+}
+
+int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  NdState& v = h->nd;
+  if (!p) {  // back to what apdgicp_params says: the APD kernels' correspondences are those of their own last linearize, if any was left
+    if (v.on) h->have_corr = false;
+    v.on = false;
+    return 0;
+  }
+  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "NDT: the resolution must be finite and positive");
+  if (p->distance_mode != APDGICP_NDT_P2D && p->distance_mode != APDGICP_NDT_D2D) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown distance mode");
+  if (p->neighbor_search == APDGICP_NDT_DIRECT_RADIUS) return fail(APDGICP_ERR_UNSUPPORTED, "NDT: DIRECT_RADIUS neighbour search is not offered");
+  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown neighbour search method");
+  if (!v.on || p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
+  if (!v.on) {
+    h->have_corr = false;
+    v.reset_final_H();
+  }
+  v.prm = *p;
+  v.on = true;
+  h->vg.on = false;  // N9: the two modes are exclusive
+  return 0;
+}
+
+int apdgicp_get_ndt(const apdgicp_handle* h, apdgicp_ndt_params* p, int* enabled) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (p) *p = h->nd.prm;
+  if (enabled) *enabled = h->nd.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_ndt_voxel_count(apdgicp_handle* h, int which, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!h || !n_voxels || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    if (!h->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    APD_TRY(nd_build_map(h, which));
+    *n_voxels = h->nd.maps[which].nv;
+    return 0;
+  });
+}
+
+int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6, double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!h || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    if (!h->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    APD_TRY(nd_build_map(h, which));
+    NdState::Map& m = h->nd.maps[which];
+    Engine& e = h->eng;
+    const int64_t nv = m.nv;
+    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
+    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
+    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
+    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), m.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
+    if (counts) APD_HIP(hipMemcpyAsync(counts, m.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
+    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, m.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
+    if (raw_covs_n6) APD_HIP(hipMemcpyAsync(raw_covs_n6, m.vraw.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), m.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (int64_t i = 0; i < nv && coords_n3; i++) {
+      const unsigned long long k = keys[i];
+      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
+    }
+    for (int64_t i = 0; i < nv && covs_n9; i++) {
+      const double* c = &c6[6 * i];
+      double* o = covs_n9 + 9 * i;
+      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
+    }
+    return 0;
+  });
+}
+
+int apdgicp_ndt_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_rows) {
+  return guarded([&]() -> int {
+    if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    NdState& v = h->nd;
+    Engine& e = h->eng;
+    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
+    if (n_rows != v.n_rows_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_rows does not match the rows of the last linearize");
+    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_rows * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    return 0;
+  });
+}
+
+int apdgicp_ndt_build_count(apdgicp_handle* h, int64_t* n_builds) {
+  if (!h || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n_builds = h->nd.builds;
   return 0;
 }
 
@@ -1408,6 +1722,10 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
   return guarded([&]() -> int {
     if (!h || !H) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     Engine& e = h->eng;
+    if (h->nd.on) {  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
+      memcpy(H, h->nd.final_H, 36 * sizeof(double));
+      return 0;
+    }
     if (!h->pair_ready) {  // L:23: identity until the first accepted step
       for (int q = 0; q < 36; q++) H[q] = (q % 7 == 0) ? 1.0 : 0.0;
       return 0;

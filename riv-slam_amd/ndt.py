@@ -1,0 +1,112 @@
+"""NDT registration (fast_gicp::NDTCuda: point-to-distribution and distribution-to-distribution) as a mode of the registration handle:
+`NDT` is `registration.FastAPDGICP` with apdgicp_set_ndt switched on and the reference's setters
+(fast_apdgicp/include/fast_gicp/ndt/ndt_cuda.hpp).  Semantics: the list N1 .. N9 in include/apdgicp_hip.h.
+
+There is NO CPU fallback: without the HIP library or a GPU every call raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import registration as reg
+from .registration import SOURCE, TARGET, _check, _ptr
+from .vgicp import DIRECT1, DIRECT7, DIRECT27, N_OFFSETS  # noqa: F401  NeighborSearchMethod, as the voxelized GICP mode numbers it
+
+P2D, D2D = 0, 1          # NDTDistanceMode (ndt_settings.hpp)
+DIRECT_RADIUS = 3        # refused: APDGICP_ERR_UNSUPPORTED
+
+
+class NdtParams(C.Structure):
+    """apdgicp_ndt_params (include/apdgicp_hip.h)."""
+    _fields_ = [("resolution", C.c_double), ("distance_mode", C.c_int32), ("neighbor_search", C.c_int32)]
+
+
+def default_ndt_params() -> NdtParams:
+    p = NdtParams()
+    reg.load_library().apdgicp_ndt_default_params(C.byref(p))
+    return p
+
+
+class NDT(reg.FastAPDGICP):
+    """One registration object (== one fast_gicp::NDTCuda) on one GPU.  setInputSource / setInputTarget / swapSourceAndTarget /
+    clearSource / clearTarget / align / linearize / compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are
+    the base class's; align always runs the host-driven loop.  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.nparams = default_ndt_params()
+        self._push_ndt()
+
+    def _push_ndt(self):
+        _check(self.L.apdgicp_set_ndt(self.h, C.byref(self.nparams)))
+
+    def _set(self, field: str, value):
+        old = getattr(self.nparams, field)
+        setattr(self.nparams, field, value)
+        try:
+            self._push_ndt()
+        except reg.ApdgicpError:
+            setattr(self.nparams, field, old)
+            raise
+
+    def setDistanceMode(self, mode: int):
+        self._set("distance_mode", int(mode))
+
+    def setResolution(self, resolution: float):
+        self._set("resolution", float(resolution))
+
+    def setNeighborSearchMethod(self, method: int, radius: float = -1.0):
+        """`radius` belongs to DIRECT_RADIUS, which is not offered."""
+        self._set("neighbor_search", int(method))
+
+    def get_ndt(self):
+        """(NdtParams, enabled) as the library holds them."""
+        p, on = NdtParams(), C.c_int()
+        _check(self.L.apdgicp_get_ndt(self.h, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def disable(self):
+        """apdgicp_set_ndt(h, NULL): the handle is an APD-GICP / plain GICP object again."""
+        _check(self.L.apdgicp_set_ndt(self.h, None))
+
+    def enable(self):
+        self._push_ndt()
+
+    def enabled(self) -> bool:
+        return self.get_ndt()[1]
+
+    def voxel_count(self, which: int = TARGET) -> int:
+        n = C.c_int64()
+        _check(self.L.apdgicp_ndt_voxel_count(self.h, int(which), C.byref(n)))
+        return n.value
+
+    def voxels(self, which: int = TARGET):
+        """The voxel map of SOURCE or TARGET in voxel order (ascending key): dict(coords [n,3] int32, counts [n] int32, means [n,3],
+        raw [n,6] (N2: xx, yx, zx, yy, zy, zz), covs [n,3,3] (N3))."""
+        n = self.voxel_count(which)
+        coords = np.empty((n, 3), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        means = np.empty((n, 3))
+        raw = np.empty((n, 6))
+        covs = np.empty((n, 9))
+        _check(self.L.apdgicp_ndt_get_voxels(self.h, int(which), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(raw), _ptr(covs)))
+        return {"coords": coords, "counts": counts, "means": means, "raw": raw, "covs": covs.reshape(n, 3, 3)}
+
+    def n_rows(self) -> int:
+        """Rows of a linearize: source voxels (D2D) or source points (P2D)."""
+        return self.voxel_count(SOURCE) if self.nparams.distance_mode == D2D else self.n_src
+
+    def voxel_correspondences(self) -> np.ndarray:
+        """[n_rows, n_offsets] target voxel indices of the last linearize, in offset order; -1 = miss."""
+        n = self.n_rows()
+        out = np.empty((n, N_OFFSETS[self.nparams.neighbor_search]), dtype=np.int32)
+        _check(self.L.apdgicp_ndt_get_correspondences(self.h, _ptr(out), n))
+        return out
+
+    def build_count(self) -> int:
+        """How many voxel maps this handle has built in this mode (the cache rules' test hook)."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_ndt_build_count(self.h, C.byref(n)))
+        return n.value
