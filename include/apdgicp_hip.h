@@ -499,7 +499,8 @@ int apdgicp_batch_is_pooled(apdgicp_batch* b);
 int apdgicp_batch_set_pair_groups(apdgicp_batch* b, int max_groups);
 int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_results, apdgicp_result* host_results);
 /* pcl getFitnessScore(max_range) of every pair at the given poses (T: n_pairs x 16 floats, column-major;
- * NULL = the poses found by the last align of the same pair list): mean squared nearest-neighbour distance of the
+ * NULL = the poses found by the last align of the same pair list -- APDGICP_ERR_NO_INPUT when there is none, when a cloud of the
+ * list was set again since, or when a call with explicit poses has come between): mean squared nearest-neighbour distance of the
  * transformed source over the points with squared distance <= max_range, DBL_MAX when none qualifies.  One NN launch
  * for the whole batch -- the per-candidate getFitnessScore of LoopDetector::matching (loop_detector.cpp:415).
  * inliers may be NULL. */

@@ -204,6 +204,17 @@ class Engine {
   apdgicp_params params;
   std::vector<Cloud> clouds;
   bool desc_dirty = true;
+  // What apdgicp_batch_fitness may reuse of the batch state (h_pairs / d_pairs / d_state), in ONE place:
+  //   pairs_current   d_pairs describes h_pairs with the clouds as they are now: set by setup_pairs, cleared by every write of a cloud
+  //                   slot (clouds_written).  An explicit-pose call on the same list skips setup_pairs only while it holds.
+  //   poses_of_align  ... and d_state still holds the poses the LAST align found for h_pairs: set by the aligns (run_align, vgb_align,
+  //                   and the fitness call that has just copied a pooled batch's records in), cleared by setup_pairs, by an explicit-pose
+  //                   call, by a pooled enqueue (an align of its own, with its own state) and by clouds_written.  T == NULL on the state
+  //                   path needs exactly this flag.
+  // The pool path (T == NULL straight behind a pooled batch) reads the batch's records instead and needs only PoolJob::clouds_replaced.
+  // desc_dirty is NOT such a signal: every upload_desc clears it (compute_covariances, set_covariances, a pooled enqueue of another list).
+  bool pairs_current = false, poses_of_align = false;
+  void clouds_written() { desc_dirty = true, pairs_current = false, poses_of_align = false; }
   uint64_t cov_epoch = 0;            // counts the writings of any cloud's covariances (Cloud::cov_gen)
   uint64_t pts_epoch = 0;            // counts the settings of any cloud's points (Cloud::pts_gen)
 
@@ -471,6 +482,7 @@ class Engine {
     if (stride_bytes < 12 || (stride_bytes & 3)) return fail(APDGICP_ERR_INVALID_ARG, "stride_bytes must be a multiple of 4 and >= 12");
     APD_HIP(hipSetDevice(device));
     APD_TRY(pool_release_clouds(slot, 1));
+    clouds_written();  // (before the first change: an error return below leaves the slot half written)
     roctx_range rr("apdgicp:pack");
     if ((int)clouds.size() <= slot) clouds.resize(slot + 1);
     Cloud& c = clouds[slot];
@@ -596,6 +608,7 @@ class Engine {
     if (stride_bytes < 12 || (stride_bytes & 3)) return fail(APDGICP_ERR_INVALID_ARG, "stride_bytes must be a multiple of 4 and >= 12");
     APD_HIP(hipSetDevice(device));
     APD_TRY(pool_release_clouds(first, count));
+    clouds_written();
     roctx_range rr("apdgicp:pack");
     if ((int)clouds.size() < first + count) clouds.resize(first + count);
     bool grew = false;
@@ -635,7 +648,7 @@ class Engine {
       clouds[slot].cov_valid = false;
       clouds[slot].token = 0;
       clouds[slot].pts_gen = 0;
-      desc_dirty = true;
+      clouds_written();
     }
   }
 
@@ -904,6 +917,7 @@ class Engine {
   // need_cov = false: the pairs are searched only (apdgicp_nearest_neighbours_of): no covariance launch for clouds that lack them
   int setup_pairs(const apdgicp_pair* pairs, int64_t n, bool with_guess, bool pipeline_cov = false, bool need_cov = true) {
     if (n <= 0 || n > 65536) return fail(APDGICP_ERR_INVALID_ARG, "n_pairs must be in [1, 65536]");
+    pairs_current = false, poses_of_align = false;  // (see their declaration)
     APD_HIP(hipSetDevice(device));
     APD_TRY(pool_leave());
     h_pairs.resize(n);
@@ -1020,6 +1034,7 @@ class Engine {
     work.post = nullptr, work.post_seq = 0;
     work.pair0 = 0;
     work.npairs = npairs;
+    pairs_current = true;
     return 0;
   }
 
@@ -1395,6 +1410,7 @@ class Engine {
         pending = true, pending_npairs = npairs, pending_ticks = (int)ticks;
         work.active = nullptr;
         APD_HIP(hipGetLastError());
+        poses_of_align = true;
         return 0;
       }
       {
@@ -1431,6 +1447,7 @@ class Engine {
       APD_HIP(hipStreamSynchronize(stream));
       APD_TRY(collect_nn_profile());
     }
+    poses_of_align = true;
     return 0;
   }
 
@@ -1448,6 +1465,7 @@ class Engine {
     int np = 0;
     int list = 0;                     // the pair list (tick stream) the batch runs on
     bool collected = false;
+    bool clouds_replaced = false;     // one of its cloud slots was set again since: its records no longer describe the handle's clouds
     int err = 0;
     std::string errmsg;
     std::vector<int> cloud_ids;       // (unique) clouds the batch reads
@@ -1850,6 +1868,11 @@ class Engine {
   }
   // before a cloud slot is replaced: the batches in flight that read it
   int pool_release_clouds(int first, int count) {
+    if (pool.last_lane >= 0) {  // (the only batch whose records anything reads later: apdgicp_batch_fitness with T == NULL)
+      PoolJob& j = pool.jobs[pool.last_lane];
+      const auto it = std::lower_bound(j.cloud_ids.begin(), j.cloud_ids.end(), first);  // (sorted, unique)
+      if (it != j.cloud_ids.end() && *it < first + count) j.clouds_replaced = true;
+    }
     if (!pool.on) return 0;
     for (int q = first; q < first + count; q++)
       while (q >= 0 && q < (int)pool.cloud_busy.size() && pool.cloud_busy[q] > 0) APD_TRY(pool_pump(true));
@@ -1860,6 +1883,7 @@ class Engine {
     if (n <= 0 || n > 65536) return fail(APDGICP_ERR_INVALID_ARG, "n_pairs must be in [1, 65536]");
     APD_HIP(hipSetDevice(device));
     APD_TRY(pool_enter());
+    poses_of_align = false;  // (the last align is this batch from here on: its poses are in its records, not in d_state)
     std::vector<int> need;
     int nsrc = 0, ntgt = 0;
     for (int64_t i = 0; i < n; i++) {
@@ -1930,7 +1954,7 @@ class Engine {
     if (pool.cloud_busy.size() < clouds.size()) pool.cloud_busy.resize(clouds.size(), 0);
     for (int id : need) pool.cloud_busy[id]++;
     j.cloud_ids = need;
-    j.state = PoolJob::PENDING, j.ticket = ++align_seq, j.np = (int)n, j.collected = false, j.err = 0, j.errmsg.clear(), j.admit_seq = 0, j.list = list;
+    j.state = PoolJob::PENDING, j.ticket = ++align_seq, j.np = (int)n, j.collected = false, j.clouds_replaced = false, j.err = 0, j.errmsg.clear(), j.admit_seq = 0, j.list = list;
     j.layout_gen = pool.layout_gen;
     pool.last_lane = lane;
     *ticket = j.ticket;

@@ -1029,6 +1029,7 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
     APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
     return fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
   }
+  e.poses_of_align = true;
   return 0;
 }
 
@@ -1192,7 +1193,7 @@ int apdgicp_clear_target(apdgicp_handle* h) {
 int apdgicp_swap_source_and_target(apdgicp_handle* h) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   std::swap(h->eng.clouds[kSrc], h->eng.clouds[kTgt]);  // input_.swap(target_), covs swap, A:68-75
-  h->eng.desc_dirty = true;
+  h->eng.clouds_written();
   h->pair_ready = h->have_corr = false;
   std::swap(h->cloud_gen[kSrc], h->cloud_gen[kTgt]);
   std::swap(h->nd.maps[kSrc], h->nd.maps[kTgt]);  // NC:90-93: the NDT maps go with their clouds (tied to them by identity either way)
@@ -1943,7 +1944,7 @@ int apdgicp_batch_clear(apdgicp_batch* b) {
   APD_HIP(hipStreamSynchronize(b->eng.stream));
   for (auto& c : b->eng.clouds) c.release_all();
   b->eng.clouds.clear();
-  b->eng.desc_dirty = true;
+  b->eng.clouds_written();
   b->vg.release();  // (V8: every slot's map and inverse permutation go with the clouds)
   return 0;
 }
@@ -2092,14 +2093,14 @@ int apdgicp_batch_fitness(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n
   return guarded([&]() -> int {
     if (!b || !pairs || !scores) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     Engine& e = b->eng;
-    const bool same = e.npairs == n_pairs && (int64_t)e.h_pairs.size() == n_pairs && !e.desc_dirty;  // no cloud replaced since
+    const bool same = e.npairs == n_pairs && (int64_t)e.h_pairs.size() == n_pairs && e.pairs_current;  // (no cloud slot written since: Engine::pairs_current)
     bool same_pairs = same;
     for (int64_t i = 0; same_pairs && i < n_pairs; i++)
       same_pairs = e.h_pairs[i].src == pairs[i].source_cloud && e.h_pairs[i].tgt == pairs[i].target_cloud;
     std::vector<float> pool_T;
     if (!T && e.pool.on && e.pool.last_lane >= 0) {  // the last align ran in the pair pool: its poses are in the batch's records
       const Engine::PoolJob& j = e.pool.jobs[e.pool.last_lane];
-      bool match = j.state != Engine::PoolJob::FREE && (int64_t)j.pair_ids.size() == n_pairs;
+      bool match = j.state != Engine::PoolJob::FREE && !j.clouds_replaced && (int64_t)j.pair_ids.size() == n_pairs;  // (no cloud replaced since)
       for (int64_t i = 0; match && i < n_pairs; i++) match = j.pair_ids[i].first == pairs[i].source_cloud && j.pair_ids[i].second == pairs[i].target_cloud;
       if (match) {
         APD_TRY(e.pool_collect(j.ticket, nullptr, nullptr));
@@ -2109,8 +2110,11 @@ int apdgicp_batch_fitness(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n
         same_pairs = false;
       }
     }
-    if (!T && !same_pairs) return fail(APDGICP_ERR_NO_INPUT, "T == NULL needs a previous align of the same pair list");
+    // (the state's poses are the align's only until somebody else writes them: an explicit-pose call on the same list does)
+    if (!T && !(same_pairs && e.poses_of_align)) return fail(APDGICP_ERR_NO_INPUT, "T == NULL needs a previous align of the same pair list");
     if (!same_pairs) APD_TRY(e.setup_pairs(pairs, n_pairs, true));
+    else APD_TRY(e.pool_leave());  // (a pooled batch of ANOTHER list may have come since: the launches below are not the pool's)
+    if (T) e.poses_of_align = !pool_T.empty();  // (the pool's records ARE the last align's poses; the caller's are not)
     APD_HIP(hipStreamSynchronize(e.stream));
     APD_TRY(e.d_stage.ensure((size_t)n_pairs * (16 * sizeof(float) + 2 * sizeof(double))));
     double* d_out = e.d_stage.as<double>();
