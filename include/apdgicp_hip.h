@@ -44,7 +44,8 @@ extern "C" {
                                       still 6 (additive): + the apdgicp_scan_context_* object (Scan Context place recognition: descriptors, ring-key ranking, shift search, top-K);
                                       still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle);
-                                      still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle) */
+                                      still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle);
+                                      still 6 (additive): + apdgicp_batch_set_ndt / _get_ndt and the apdgicp_batch_ndt_* calls (NDT as a mode of the batch handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -403,7 +404,38 @@ int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds);
  *       run the host-driven loop of apdgicp_align_host_loop over the two kernels (trace, final Hessian and apdgicp_result as there);
  *       apdgicp_get_correspondences / apdgicp_get_mahalanobis return APDGICP_ERR_UNSUPPORTED; the covariance calls are untouched (they
  *       compute, return or set the k-NN covariances, which this cost does not read); fitness_score, nearest_neighbours*, transform_source
- *       and get_points are unchanged.  Batch handles have no NDT mode.  With the mode off nothing differs from a handle that never had it on. */
+ *       and get_points are unchanged.  Batch handles: N10 .. N15.  With the mode off nothing differs from a handle that never had it on.
+ *
+ * Batch handles have the same mode (apdgicp_batch_set_ndt, declared with the batch calls below; kernels: riv-slam_amd/csrc/apd_ndt_batch.hpp),
+ * exclusive with their voxelized-GICP mode, with the optimiser loop on the device:
+ *   N10. One map per cloud slot.  The map is N1 .. N3's, a pure function of the slot's points and the resolution; the same map serves the
+ *       slot as a target and, in D2D, as a source.  A slot named as target_cloud by a pair of the batch gets one, in D2D a slot named as
+ *       source_cloud too; in P2D a source-only slot gets none.  Coordinates, counts, means, raw and regularised covariances are bit-equal to
+ *       what the single handle builds from the same points.  The map is cached by identity -- the setting of the slot's points, the
+ *       resolution -- and rebuilt when either is another one, or after apdgicp_batch_clear; maps are kept across mode off / on.  Building
+ *       all maps of a batch costs at most ONE host wait: buffers are sized for as many voxels as the slot has points, the voxel count stays
+ *       on the device, and the words of all slots come back in one copy (V8).  A target point refused by V2 fails the align with
+ *       APDGICP_ERR_INVALID_ARG, and so does a source point in D2D: the message names slot and point, no pair has run, the handle stays
+ *       usable.  In P2D a refused source point is a miss.
+ *   N11. No k-NN covariances.  With the mode on align does not compute them, and clouds smaller than k_correspondences align.  The
+ *       clouds' curve sort still runs where the engine needs it (a staged host cloud's points are written to the device by its sort).
+ *   N12. The per-row arithmetic is N5 .. N7's, bit for bit, through the same device functions the single handle's kernels call: one row per
+ *       lane in blocks of 256, the 29 sums added in the written order, the block rows added in block order from 0.0.  In D2D a pair's row
+ *       count is its source slot's voxel count, read on the device, never by the host.  Hence H, b, cost and n_matched of a pair's FIRST
+ *       linearize equal apdgicp_linearize of a single handle at the same guess, bit for bit.
+ *   N13. Optimiser.  V10's state machine with N8 in place of V7: a linearize without a contributing term ends that pair there with
+ *       converged = 0, lm_failed = 0, n_linearize counted, iterations = the current iteration, T = the pose so far, final_cost = that
+ *       linearize's cost, n_matched = 0.  The frozen state of N7 is per pair: the indices per (row, offset) and the pose of the pair's last
+ *       linearize, whose rotation is R_lin.  sin / cos of the step's rotation come from the device library instead of the host's, so
+ *       iterates agree with the single handle's to rounding, not bit for bit.
+ *   N14. A pair's record is a pure function of the pair: the same (source, target, guess, parameters) gives byte-identical records whether
+ *       the pair runs alone or among any others, at any position of the list, on a first align and on a reused handle.
+ *   N15. No host round trip per iteration: V12 -- two launches per tick, ticks enqueued in chunks, one pinned word looked at between chunks,
+ *       one chunk ahead, the same tick bound.  apdgicp_batch_align / _align_async / _copy_results / _synchronize run this path;
+ *       apdgicp_batch_align_enqueue / _collect / _pump return APDGICP_ERR_UNSUPPORTED and apdgicp_batch_is_pooled returns 0;
+ *       apdgicp_batch_set_pair_groups is accepted and has no effect; apdgicp_batch_fitness and the cloud calls are unchanged.
+ *       apdgicp_batch_set_ndt and apdgicp_batch_set_vgicp are exclusive, as on the single handle: switching one on switches the other
+ *       off.  With the mode off a batch handle does exactly what one that never had it on does. */
 typedef enum { APDGICP_NDT_P2D = 0, APDGICP_NDT_D2D = 1 } apdgicp_ndt_distance;   /* NDTDistanceMode, ndt_settings.hpp */
 #define APDGICP_NDT_DIRECT_RADIUS 3   /* NeighborSearchMethod::DIRECT_RADIUS as a value of neighbor_search: refused (N5) */
 typedef struct {
@@ -542,6 +574,17 @@ int apdgicp_batch_vgicp_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_
 int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9);
 /* Debug: how many voxel maps this handle has built, all slots together (the tests of the cache rules read it) */
 int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds);
+/* NDT as a mode of the batch handle: N10 .. N15 above.  p != NULL: the mode on with these parameters (and voxelized GICP off; DIRECT_RADIUS:
+ * APDGICP_ERR_UNSUPPORTED); NULL: mode off.  The parameters are checked before the handle.  The maps built so far are kept across off / on. */
+int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p);
+int apdgicp_batch_get_ndt(const apdgicp_batch* b, apdgicp_ndt_params* p, int* enabled);   /* either output may be NULL */
+/* number of voxels of the map of cloud slot `cloud` (built if it is not current; needs the mode on and that slot only) */
+int apdgicp_batch_ndt_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels);
+/* that map in voxel order, as apdgicp_ndt_get_voxels */
+int apdgicp_batch_ndt_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6,
+                                 double* covs_n9);
+/* Debug: how many NDT voxel maps this handle has built, all slots together (the tests of the cache rules read it) */
+int apdgicp_batch_ndt_build_count(apdgicp_batch* b, int64_t* n_builds);
 int apdgicp_batch_debug_stats(apdgicp_batch* b, unsigned long long out[16]);
 /* APDGICP_STATS=2 and a library built with -DAPD_BLOCK_TIMELINE (a diagnostics variant: tools/build_variant.py) only: {start, end} (100 MHz wall-clock ticks) and the index of every block of the LAST one-pair dense search launch
  * (k_nn_pruned), three words per block, up to 8192 blocks; reading resets.  For tools/c5_blocks.py: where the time of a 100k x 500k

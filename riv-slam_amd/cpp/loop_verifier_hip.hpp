@@ -46,10 +46,15 @@ class LoopVerifierHip {
   LoopVerifierHip(const LoopVerifierHip&) = delete;
   LoopVerifierHip& operator=(const LoopVerifierHip&) = delete;
   bool ok() const { return batch_ != nullptr; }
+  /// the C handle, for the calls this class does not wrap (apdgicp_batch_get_vgicp / _get_ndt, the voxel getters); nullptr when !ok()
+  apdgicp_batch* handle() const { return batch_; }
   int setParams(const apdgicp_params& p) { return batch_ ? apdgicp_batch_set_params(batch_, &p) : APDGICP_ERR_HIP; }
   /// registration_method = FAST_VGICP: the candidates are registered with voxelized GICP (apdgicp_batch_set_vgicp, V8 .. V12 of the C header);
   /// nullptr: back to APD-GICP / plain GICP as the parameters say
   int setVGICP(const apdgicp_vgicp_params* p) { return batch_ ? apdgicp_batch_set_vgicp(batch_, p) : APDGICP_ERR_HIP; }
+  /// registration_method = NDT: the candidates are registered with NDT, P2D or D2D (apdgicp_batch_set_ndt, N10 .. N15 of the C header); switches
+  /// voxelized GICP off, as setVGICP switches this off; nullptr: back to APD-GICP / plain GICP as the parameters say
+  int setNDT(const apdgicp_ndt_params* p) { return batch_ ? apdgicp_batch_set_ndt(batch_, p) : APDGICP_ERR_HIP; }
 
   /// guesses: n_candidates x 16 floats, column-major ((new_keyframe_estimate^-1 * candidate_estimate) with guess(2,3) = 0,
   /// loop_detector.cpp:405-411), or nullptr for the identity (:225).  Returns 0 or a negative apdgicp_status.

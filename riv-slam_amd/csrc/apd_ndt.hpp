@@ -12,6 +12,8 @@
 //   k_ndt_error<D>     N7: the same cost at the trial pose over the stored voxel indices; M is recomputed from the rotation of the last
 //                      linearize pose by the same device function
 //   k_vg_reduce        the per-block partials added in block order by one lane per sum (apd_vgicp.hpp)
+// The per-row bodies of the two kernels are the device functions nd_linearize_row / nd_error_row: the batch mode's kernel (apd_ndt_batch.hpp)
+// calls the same ones.
 // Everything here is fp64 except the stored points, compiled without contraction (sym3_eig / sym3_from_eig of apd_math.hpp allow it inside
 // themselves and are compared by tolerance): written order is evaluated order.  No floating-point atomics.  Every pointer is a kernel argument.
 //
@@ -148,6 +150,71 @@ __device__ __forceinline__ void nd_term(const VgMap& map, int v, const Sym3& RCA
   acc[26] += w * -mez;
 }
 
+// N5 / N6, one row: the searches of row i at pose T, its indices into corr (i x noff), its terms onto acc[0 .. 29).  The one function every
+// linearize kernel calls (k_ndt_linearize below, k_ndb_points of apd_ndt_batch.hpp): N12 holds by construction.
+template <bool D2D>
+__device__ __forceinline__ void nd_linearize_row(const float4* opts, const VgMap& smap, const VgMap& map, const Rigid& T, double res, int mode, int noff, int want_Hb,
+                                                 int* corr, int i, double* acc) {
+  double x, y, z;
+  nd_row<D2D>(opts, smap, i, x, y, z);
+  const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
+  const double cx = vg_coord(vx, res), cy = vg_coord(vy, res), cz = vg_coord(vz, res);
+  // a coordinate this far out cannot come back into range with an offset of one; also catches a q that is not finite
+  const bool inr = fabs(cx) <= (double)VG_LIM && fabs(cy) <= (double)VG_LIM && fabs(cz) <= (double)VG_LIM;
+  const int ix = inr ? (int)cx : 0, iy = inr ? (int)cy : 0, iz = inr ? (int)cz : 0;
+  const double res2 = res * res;
+  Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool have_rca = false;
+  for (int k = 0; k < noff; k++) {
+    int ox, oy, oz;
+    vg_offset(mode, k, ox, oy, oz);
+    const int ax = ix + ox, ay = iy + oy, az = iz + oz;
+    int v = -1;
+    if (inr && abs(ax) < VG_LIM && abs(ay) < VG_LIM && abs(az) < VG_LIM) v = vg_find(map, vg_pack(ax, ay, az));  // the range test comes first
+    corr[(size_t)i * noff + k] = v;
+    if (v < 0 || map.count[v] <= ND_MIN_POINTS) continue;
+    if (D2D && !have_rca) {
+      RCA = sym3_rotate(T, nd_load_cov(smap, i));
+      have_rca = true;
+    }
+    nd_term<D2D>(map, v, RCA, res2, vx, vy, vz, want_Hb, acc);
+  }
+}
+
+// N7, one row: the cost of row i at the trial pose T over its stored indices, M from the rotation of T0 (the pose of the last linearize);
+// cost onto acc[27], count onto acc[28]
+template <bool D2D>
+__device__ __forceinline__ void nd_error_row(const float4* opts, const VgMap& smap, const VgMap& map, const Rigid& T, const Rigid& T0, double res, int noff,
+                                             const int* corr, int i, double* acc) {
+  double x, y, z;
+  nd_row<D2D>(opts, smap, i, x, y, z);
+  const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
+  const double res2 = res * res;
+  Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool have_rca = false;
+  for (int k = 0; k < noff; k++) {
+    const int v = corr[(size_t)i * noff + k];
+    if (v < 0 || v >= map.nv || map.count[v] <= ND_MIN_POINTS) continue;
+    if (D2D && !have_rca) {
+      RCA = sym3_rotate(T0, nd_load_cov(smap, i));
+      have_rca = true;
+    }
+    nd_term<D2D>(map, v, RCA, res2, vx, vy, vz, 0, acc);
+  }
+}
+
+// the cost and the count of a block's error rows into slots 27 and 28 of the block's row, like a linearize
+__device__ __forceinline__ void nd_error_block_sums(const double* acc, double* red, double* part, int tid) {
+  double two[2] = {acc[27], acc[28]};
+  block_reduce<2, VG_BLK>(two, red, tid);
+  if (tid < 2) {
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < VG_BLK / 64; w++) s += red[w * 2 + tid];
+    part[(size_t)blockIdx.x * VG_RED + 27 + tid] = s;
+  }
+}
+
 // N5 / N6.  T12[0..12): the pose, row-major 3x4.  nrows = smap.nv (D2D) or the number of source points (P2D).  corr: nrows x noff voxel indices
 // (-1: miss), written here.
 template <bool D2D>
@@ -161,32 +228,7 @@ __global__ __launch_bounds__(VG_BLK) void k_ndt_linearize(const float4* opts, Vg
   double acc[VG_SUMS];
 #pragma unroll
   for (int r = 0; r < VG_SUMS; r++) acc[r] = 0.0;
-  if (i < nrows) {
-    double x, y, z;
-    nd_row<D2D>(opts, smap, i, x, y, z);
-    const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
-    const double cx = vg_coord(vx, res), cy = vg_coord(vy, res), cz = vg_coord(vz, res);
-    // a coordinate this far out cannot come back into range with an offset of one; also catches a q that is not finite
-    const bool inr = fabs(cx) <= (double)VG_LIM && fabs(cy) <= (double)VG_LIM && fabs(cz) <= (double)VG_LIM;
-    const int ix = inr ? (int)cx : 0, iy = inr ? (int)cy : 0, iz = inr ? (int)cz : 0;
-    const double res2 = res * res;
-    Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    bool have_rca = false;
-    for (int k = 0; k < noff; k++) {
-      int ox, oy, oz;
-      vg_offset(mode, k, ox, oy, oz);
-      const int ax = ix + ox, ay = iy + oy, az = iz + oz;
-      int v = -1;
-      if (inr && abs(ax) < VG_LIM && abs(ay) < VG_LIM && abs(az) < VG_LIM) v = vg_find(map, vg_pack(ax, ay, az));  // the range test comes first
-      corr[(size_t)i * noff + k] = v;
-      if (v < 0 || map.count[v] <= ND_MIN_POINTS) continue;
-      if (D2D && !have_rca) {
-        RCA = sym3_rotate(T, nd_load_cov(smap, i));
-        have_rca = true;
-      }
-      nd_term<D2D>(map, v, RCA, res2, vx, vy, vz, want_Hb, acc);
-    }
-  }
+  if (i < nrows) nd_linearize_row<D2D>(opts, smap, map, T, res, mode, noff, want_Hb, corr, i, acc);
   vg_block_sums<VG_SUMS>(acc, red, part, tid);
 }
 
@@ -202,32 +244,8 @@ __global__ __launch_bounds__(VG_BLK) void k_ndt_error(const float4* opts, VgMap 
   double acc[VG_SUMS];
 #pragma unroll
   for (int r = 0; r < VG_SUMS; r++) acc[r] = 0.0;
-  if (i < nrows) {
-    double x, y, z;
-    nd_row<D2D>(opts, smap, i, x, y, z);
-    const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
-    const double res2 = res * res;
-    Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    bool have_rca = false;
-    for (int k = 0; k < noff; k++) {
-      const int v = corr[(size_t)i * noff + k];
-      if (v < 0 || v >= map.nv || map.count[v] <= ND_MIN_POINTS) continue;
-      if (D2D && !have_rca) {
-        RCA = sym3_rotate(T0, nd_load_cov(smap, i));
-        have_rca = true;
-      }
-      nd_term<D2D>(map, v, RCA, res2, vx, vy, vz, 0, acc);
-    }
-  }
-  // (the cost goes to slot 27 and the count to slot 28 of the block's row, like k_ndt_linearize)
-  double two[2] = {acc[27], acc[28]};
-  block_reduce<2, VG_BLK>(two, red, tid);
-  if (tid < 2) {
-    double s = 0.0;
-#pragma unroll
-    for (int w = 0; w < VG_BLK / 64; w++) s += red[w * 2 + tid];
-    part[(size_t)blockIdx.x * VG_RED + 27 + tid] = s;
-  }
+  if (i < nrows) nd_error_row<D2D>(opts, smap, map, T, T0, res, noff, corr, i, acc);
+  nd_error_block_sums(acc, red, part, tid);
 }
 
 }  // namespace apd

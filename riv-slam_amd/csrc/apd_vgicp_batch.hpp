@@ -78,13 +78,14 @@ __global__ __launch_bounds__(VG_BLK) void k_vgb_points(const VgbPair* pairs, con
   }
 }
 
-__global__ __launch_bounds__(64) void k_vgb_step(const VgbPair* pairs, PairState* st, Consts cst, const double* part, int nblk_max, ResultRec* out, int* done) {
+// the step of one pair by one wave, shared by every batch mode that ticks this way (k_vgb_step, k_ndb_step of apd_ndt_batch.hpp): the first
+// nblk block rows of the pair added in block order from 0.0, then V7 / N8 or the GN / LM step in lane 0
+__device__ __forceinline__ void vgb_step_pair(int pair, int nblk, PairState* st, const Consts& cst, const double* part, int nblk_max, ResultRec* out, int* done) {
   __shared__ PairState ls;
   __shared__ double v[32], ws[48];
-  const int pair = blockIdx.x, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const int status = st[pair].status;
   if (status == ST_DONE) return;
-  const int nblk = (pairs[pair].n + VG_BLK - 1) / VG_BLK;
   const double* rows = part + (size_t)pair * nblk_max * VG_RED;
   if (tid < VG_SUMS && (status == ST_NEED_LIN || tid >= 27)) {
     double s = 0.0;
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(64) void k_vgb_step(const VgbPair* pairs, PairState
     if (status == ST_NEED_LIN) {
       fill_from_sums(ls, v);
       ls.n_matched = (int)fmin(v[28], 2147483647.0);  // (the int32 field saturates, as on the single handle)
-      if (v[28] == 0.0) {  // V7: no correspondence -- the loop ends here, the pose so far stands
+      if (v[28] == 0.0) {  // V7 / N8: no correspondence, no contributing term -- the loop ends here, the pose so far stands
         ls.n_lin += 1;
         ls.status = ST_DONE;
       } else {
@@ -113,6 +114,11 @@ __global__ __launch_bounds__(64) void k_vgb_step(const VgbPair* pairs, PairState
   }
   __syncthreads();
   for (int q = tid; q < (int)(sizeof(PairState) / 8); q += 64) ((double*)&st[pair])[q] = ((const double*)&ls)[q];
+}
+
+__global__ __launch_bounds__(64) void k_vgb_step(const VgbPair* pairs, PairState* st, Consts cst, const double* part, int nblk_max, ResultRec* out, int* done) {
+  const int pair = blockIdx.x;
+  vgb_step_pair(pair, (pairs[pair].n + VG_BLK - 1) / VG_BLK, st, cst, part, nblk_max, out, done);
 }
 
 // max_iterations <= 0: no tick runs, every pair's record is that of its initial state

@@ -16,6 +16,7 @@
 #include "apd_vgicp.hpp"
 #include "apd_vgicp_batch.hpp"
 #include "apd_ndt.hpp"
+#include "apd_ndt_batch.hpp"
 
 using namespace apd;
 
@@ -149,9 +150,42 @@ struct VgbState {
   }
 };
 
+// apdgicp_batch_set_ndt (include/apdgicp_hip.h, N10 .. N15): per cloud slot the NDT voxel map, cached by identity like NdState's; per align the
+// pair table, the frozen indices and the block rows.  The scratch of a map build, the pinned words, the events, the done counter and the chunk
+// length are VgbState's: the two modes never run together.
+struct NdbState {
+  struct Slot {
+    bool built = false;        // the map: points pts_gen, resolution res
+    uint64_t pts_gen = 0;
+    double res = 0.0;
+    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
+    DevBuf vkeys, vcount, vmean, vraw, vcov;  // sized for nv <= n
+    void release() {
+      for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
+      built = false, nv = 0;
+    }
+  };
+  bool on = false;
+  apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
+  std::vector<Slot> slots;
+  int64_t builds = 0;
+  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
+  int scal_slots = 0;
+  DevBuf corr, part;
+  CachedTable pairs;
+  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+  void release() {
+    for (Slot& sl : slots) sl.release();
+    slots.clear();
+    for (DevBuf* b : {&scal, &corr, &part, &pairs.dev}) b->release();
+    scal_slots = 0;
+  }
+};
+
 struct apdgicp_batch {
   Engine eng;
   VgbState vg;  // (released by ~apdgicp_batch, while the engine's stream still exists)
+  NdbState nd;  // (likewise)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
   ~apdgicp_batch() {
     if (eng.stream) {
@@ -159,6 +193,7 @@ struct apdgicp_batch {
       (void)hipStreamSynchronize(eng.stream);
     }
     vg.release();
+    nd.release();
   }
 };
 
@@ -808,21 +843,24 @@ int vgb_ensure_words(apdgicp_batch* b, size_t ints) {
 }
 
 // room for the scal words of every slot of the engine; the words of built maps survive a growth
-int vgb_ensure_slots(apdgicp_batch* b) {
-  Engine& e = b->eng;
-  VgbState& v = b->vg;
+int batch_ensure_slot_words(Engine& e, DevBuf& scal, int& scal_slots) {
   const int want = (int)e.clouds.size();
-  if ((int)v.slots.size() < want) v.slots.resize(want);
-  if (want <= v.scal_slots) return 0;
+  if (want <= scal_slots) return 0;
   const int cap = std::max(64, 2 * want);
   DevBuf grown;
   APD_TRY(grown.ensure((size_t)cap * 16));
   APD_HIP(hipStreamSynchronize(e.stream));
-  if (v.scal_slots) APD_HIP(hipMemcpy(grown.p, v.scal.p, (size_t)v.scal_slots * 16, hipMemcpyDeviceToDevice));
-  v.scal.release();
-  v.scal = grown;
-  v.scal_slots = cap;
+  if (scal_slots) APD_HIP(hipMemcpy(grown.p, scal.p, (size_t)scal_slots * 16, hipMemcpyDeviceToDevice));
+  scal.release();
+  scal = grown;
+  scal_slots = cap;
   return 0;
+}
+
+int vgb_ensure_slots(apdgicp_batch* b) {
+  VgbState& v = b->vg;
+  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
+  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
 }
 
 bool vgb_map_current(const apdgicp_batch* b, int slot) {
@@ -953,37 +991,25 @@ int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
   return vgb_build_maps(b, {cloud});
 }
 
-// V10 / V12: the optimiser loop of every pair on the device; returns with the device records complete
-int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
-  Engine& e = b->eng;
+// V12 / N15: what the tick loop needs besides the pairs -- the done counter, the pinned words, the two events
+int vgb_prepare_ticks(apdgicp_batch* b) {
   VgbState& v = b->vg;
-  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
-  APD_TRY(e.setup_pairs(pairs, n_pairs, true));  // clouds sorted, covariances there, d_state / d_results / d_guess
-  e.results_on_host = false;
-  const int np = e.npairs, noff = v.n_offsets();
-  std::vector<int> targets;
-  for (int i = 0; i < np; i++) targets.push_back(e.h_pairs[i].tgt);
-  APD_TRY(vgb_build_maps(b, targets));
-  for (int i = 0; i < np; i++) APD_TRY(vgb_ensure_inv(b, e.h_pairs[i].src));
-  std::vector<VgbPair> tab(np);
-  for (int i = 0; i < np; i++) {
-    const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
-    const VgbState::Slot& st = v.slots[t];
-    tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0,
-                     VgbMap{st.vkeys.as<unsigned long long>(), st.vcount.as<int>(), st.vmean.as<double>(), st.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)t + 1}};
-  }
-  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
-  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
-  const size_t corr_stride = (size_t)e.nmax_src * noff;
-  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
-  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
   APD_TRY(v.done.ensure(16));
   APD_TRY(vgb_ensure_words(b, 4));
   for (hipEvent_t& ev : v.ev)
     if (!ev) APD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  return 0;
+}
+
+// V10 / V12 / N13 / N15: the optimiser loop of every pair of the engine's list (setup_pairs done, vgb_prepare_ticks done) on the device.
+// launch_tick() enqueues the two launches of one tick on the engine's stream.  Ticks go out in chunks, one chunk ahead of the pinned word the
+// host looks at; returns with the device records complete and the deferred error flag read.
+template <class Tick>
+int vgb_run_ticks(apdgicp_batch* b, Tick&& launch_tick) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  const int np = e.npairs;
   const apdgicp_params& p = e.params;
-  const Consts cst = e.consts();
   PairState* st = e.d_state.as<PairState>();
   ResultRec* recs = e.d_results.as<ResultRec>();
   hipLaunchKernelGGL(k_vgb_init, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, e.stream, st, e.d_guess.as<Rigid>(), np, p.max_iterations, v.done.as<int>());
@@ -993,11 +1019,7 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   int nchunks = 0;
   auto enqueue_chunk = [&]() -> int {
     const int todo = (int)std::min<long long>(chunk, bound - ticks);
-    for (int q = 0; q < todo; q++) {
-      hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution,
-                         (int)v.prm.neighbor_search, noff, v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-      hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, v.done.as<int>());
-    }
+    for (int q = 0; q < todo; q++) launch_tick();
     APD_HIP(hipGetLastError());
     ticks += todo;
     // the done counter as of this chunk, mirrored into the pinned word of the chunk's parity
@@ -1033,7 +1055,214 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   return 0;
 }
 
+// V10 / V12: the optimiser loop of every pair on the device; returns with the device records complete
+int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
+  APD_TRY(e.setup_pairs(pairs, n_pairs, true));  // clouds sorted, covariances there, d_state / d_results / d_guess
+  e.results_on_host = false;
+  const int np = e.npairs, noff = v.n_offsets();
+  std::vector<int> targets;
+  for (int i = 0; i < np; i++) targets.push_back(e.h_pairs[i].tgt);
+  APD_TRY(vgb_build_maps(b, targets));
+  for (int i = 0; i < np; i++) APD_TRY(vgb_ensure_inv(b, e.h_pairs[i].src));
+  std::vector<VgbPair> tab(np);
+  for (int i = 0; i < np; i++) {
+    const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
+    const VgbState::Slot& st = v.slots[t];
+    tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0,
+                     VgbMap{st.vkeys.as<unsigned long long>(), st.vcount.as<int>(), st.vmean.as<double>(), st.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)t + 1}};
+  }
+  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
+  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
+  const size_t corr_stride = (size_t)e.nmax_src * noff;
+  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
+  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(vgb_prepare_ticks(b));
+  const Consts cst = e.consts();
+  PairState* st = e.d_state.as<PairState>();
+  ResultRec* recs = e.d_results.as<ResultRec>();
+  return vgb_run_ticks(b, [&]() {
+    hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution,
+                       (int)v.prm.neighbor_search, noff, v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
+    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, v.done.as<int>());
+  });
+}
+
+// ---- NDT on a batch handle (include/apdgicp_hip.h N10 .. N15; kernels: apd_ndt_batch.hpp)
+int ndb_ensure_slots(apdgicp_batch* b) {
+  NdbState& v = b->nd;
+  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
+  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
+}
+
+bool ndb_map_current(const apdgicp_batch* b, int slot) {
+  const NdbState::Slot& sl = b->nd.slots[slot];
+  return sl.built && sl.pts_gen == b->eng.clouds[slot].pts_gen && sl.res == b->nd.prm.resolution;
+}
+
+// N10: the maps of the listed slots (sorted) that are not current, as vgb_build_maps builds its own: enqueued one after the other with no wait
+// in between, then ONE copy of every slot's {first bad point, voxel count} and one wait for all of them.  No covariances, no inverse permutation.
+int ndb_build_maps(apdgicp_batch* b, const std::vector<int>& slots) {
+  Engine& e = b->eng;
+  NdbState& v = b->nd;
+  VgbState& w = b->vg;  // (the scratch of a build and the pinned words)
+  APD_TRY(ndb_ensure_slots(b));
+  std::vector<int> todo;
+  int nmax = 0;
+  for (int t : slots)
+    if (!ndb_map_current(b, t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t), nmax = std::max(nmax, e.clouds[t].n);
+  if (todo.empty()) return 0;
+  const int lo = *std::min_element(todo.begin(), todo.end()), hi = *std::max_element(todo.begin(), todo.end());
+  APD_TRY(vgb_ensure_words(b, 4 + 4 * (size_t)(hi - lo + 1)));
+  {
+    const int nblk = (nmax + MAP_RS_TILE - 1) / MAP_RS_TILE;
+    const int64_t entries = 256ll * nblk;
+    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+    const size_t nhb = (size_t)(nmax + MAP_BLK - 1) / MAP_BLK;
+    bool grows = (size_t)nmax * 8 > w.keys_a.cap || (size_t)entries * 4 > w.hist.cap || (size_t)nsb * 4 > w.rs_bsum.cap || nhb * 4 > w.bsum.cap;
+    for (int t : todo) grows |= (size_t)e.clouds[t].n * 48 > v.slots[t].vcov.cap;
+    if (grows) APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced; never on a reused handle with clouds of the same sizes)
+    APD_TRY(w.keys_a.ensure((size_t)nmax * 8));
+    APD_TRY(w.keys_b.ensure((size_t)nmax * 8));
+    APD_TRY(w.idx_a.ensure((size_t)nmax * 4));
+    APD_TRY(w.idx_b.ensure((size_t)nmax * 4));
+    APD_TRY(w.hist.ensure((size_t)entries * 4));
+    APD_TRY(w.rs_bsum.ensure((size_t)nsb * 4));
+    APD_TRY(w.bsum.ensure(nhb * 4));
+  }
+  for (int t : todo) {
+    Engine::Cloud& c = e.clouds[t];
+    NdbState::Slot& sl = v.slots[t];
+    const int n = c.n;
+    sl.built = false;
+    APD_TRY(sl.vkeys.ensure((size_t)n * 8));
+    APD_TRY(sl.vcount.ensure((size_t)n * 4));
+    APD_TRY(sl.vmean.ensure((size_t)n * 24));
+    APD_TRY(sl.vraw.ensure((size_t)n * 48));
+    APD_TRY(sl.vcov.ensure((size_t)n * 48));
+    const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+    const int64_t entries = 256ll * nblk;
+    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+    const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
+    int* scal = v.scal.as<int>() + 4 * (size_t)t;
+    APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
+    unsigned long long *ks = w.keys_a.as<unsigned long long>(), *kd = w.keys_b.as<unsigned long long>();
+    int *is = w.idx_a.as<int>(), *id = w.idx_b.as<int>();
+    hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
+    for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
+      hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, w.hist.as<int>());
+      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, w.hist.as<int>(), (int)entries, w.rs_bsum.as<int>());
+      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, w.rs_bsum.as<int>(), nsb, scal + 2);
+      hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, w.hist.as<int>(), w.rs_bsum.as<int>());
+      std::swap(ks, kd), std::swap(is, id);
+    }
+    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, w.bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, w.bsum.as<int>(), (int)nhb, scal + 1);
+    // (a slot with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
+    hipLaunchKernelGGL(k_ndt_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, w.bsum.as<int>(), c.opts.as<float4>(), sl.vkeys.as<unsigned long long>(),
+                       sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vraw.as<double>(), sl.vcov.as<double>(), n);
+    APD_HIP(hipGetLastError());
+  }
+  int* hw = w.h_words + 4;
+  APD_HIP(hipMemcpyAsync(hw, v.scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  int rc = 0;
+  for (int t : todo) {
+    const int* x = hw + 4 * (size_t)(t - lo);
+    NdbState::Slot& sl = v.slots[t];
+    const Engine::Cloud& c = e.clouds[t];
+    if (x[0] != kVgBadNone) {
+      if (rc == 0)
+        rc = fail(APDGICP_ERR_INVALID_ARG, "NDT: point " + std::to_string(x[0]) + " of cloud slot " + std::to_string(t) +
+                                               " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
+      continue;
+    }
+    if (x[1] < 1 || x[1] > c.n) {
+      if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, "NDT: inconsistent voxel count");
+      continue;
+    }
+    sl.nv = x[1];
+    sl.built = true, sl.pts_gen = c.pts_gen, sl.res = v.prm.resolution;
+    v.builds++;
+  }
+  return rc;
+}
+
+// one slot's map for the getters: sorted, built
+int ndb_slot_map(apdgicp_batch* b, int32_t cloud) {
+  Engine& e = b->eng;
+  if (!b->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_batch_set_ndt)");
+  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.pool_leave());
+  APD_TRY(e.finish_align());
+  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+  return ndb_build_maps(b, {cloud});
+}
+
+// N13 / N15: the optimiser loop of every pair on the device; returns with the device records complete
+int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
+  Engine& e = b->eng;
+  NdbState& v = b->nd;
+  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
+  APD_TRY(e.setup_pairs(pairs, n_pairs, true, /*pipeline_cov=*/false, /*need_cov=*/false));  // N11: clouds sorted, d_state / d_results / d_guess
+  e.results_on_host = false;
+  const int np = e.npairs, noff = v.n_offsets();
+  const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
+  std::vector<int> slots;
+  for (int i = 0; i < np; i++) {
+    slots.push_back(e.h_pairs[i].tgt);
+    if (d2d) slots.push_back(e.h_pairs[i].src);
+  }
+  APD_TRY(ndb_build_maps(b, slots));
+  auto map_of = [&](int slot) {
+    const NdbState::Slot& sl = v.slots[slot];
+    return VgbMap{sl.vkeys.as<unsigned long long>(), sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)slot + 1};
+  };
+  std::vector<NdbPair> tab(np);
+  for (int i = 0; i < np; i++) {
+    const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
+    tab[i] = NdbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].n, 0, d2d ? map_of(s) : VgbMap{nullptr, nullptr, nullptr, nullptr, nullptr}, map_of(t)};
+  }
+  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(NdbPair), e.stream));
+  // (a pair's rows are at most its source's points: the grid and the strides are sized by the points, the blocks beyond a pair's rows return)
+  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
+  const size_t corr_stride = (size_t)e.nmax_src * noff;
+  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
+  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(vgb_prepare_ticks(b));
+  const Consts cst = e.consts();
+  PairState* st = e.d_state.as<PairState>();
+  ResultRec* recs = e.d_results.as<ResultRec>();
+  const dim3 grid((unsigned)nblk_max, (unsigned)np);
+  return vgb_run_ticks(b, [&]() {
+    if (d2d)
+      hipLaunchKernelGGL(k_ndb_points<true>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
+                         v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
+    else
+      hipLaunchKernelGGL(k_ndb_points<false>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
+                         v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
+    hipLaunchKernelGGL(k_ndb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<NdbPair>(), st, cst, v.part.as<double>(), nblk_max, d2d ? 1 : 0, recs,
+                       b->vg.done.as<int>());
+  });
+}
+
 const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+const char* const kNdbNoPipeline = "NDT on a batch handle (apdgicp_batch_set_ndt) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+
+// the pooled / deferred aligns of the APD path finish as what they were enqueued as; the chunk length of the device loop is read once
+int batch_enter_device_loop_mode(apdgicp_batch* b) {
+  if (b->eng.stream) {
+    APD_TRY(b->eng.pool_leave());
+    APD_TRY(b->eng.finish_align());
+  }
+  if (!b->vg.chunk) b->vg.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
+  return 0;
+}
 
 }  // namespace
 
@@ -1567,15 +1796,10 @@ int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on) {  // the pooled / deferred aligns of the APD path finish as what they were enqueued as
-      if (b->eng.stream) {
-        APD_TRY(b->eng.pool_leave());
-        APD_TRY(b->eng.finish_align());
-      }
-      if (!v.chunk) v.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
-    }
+    if (!v.on && !b->nd.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.prm = *p;
     v.on = true;
+    b->nd.on = false;  // N15: the two modes are exclusive
     return 0;
   });
 }
@@ -1627,6 +1851,79 @@ int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capa
 int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds) {
   if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
   *n_builds = b->vg.builds;
+  return 0;
+}
+
+int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
+  return guarded([&]() -> int {
+    // (the parameters first: what is wrong with them does not depend on the handle)
+    if (p && (!(p->resolution > 0.0) || !std::isfinite(p->resolution))) return fail(APDGICP_ERR_INVALID_ARG, "NDT: the resolution must be finite and positive");
+    if (p && p->distance_mode != APDGICP_NDT_P2D && p->distance_mode != APDGICP_NDT_D2D) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown distance mode");
+    if (p && p->neighbor_search == APDGICP_NDT_DIRECT_RADIUS) return fail(APDGICP_ERR_UNSUPPORTED, "NDT: DIRECT_RADIUS neighbour search is not offered");
+    if (p && (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27)) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown neighbour search method");
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    NdbState& v = b->nd;
+    if (!p) {
+      v.on = false;
+      return 0;
+    }
+    if (!v.on && !b->vg.on) APD_TRY(batch_enter_device_loop_mode(b));
+    v.prm = *p;
+    v.on = true;
+    b->vg.on = false;  // N15: the two modes are exclusive
+    return 0;
+  });
+}
+
+int apdgicp_batch_get_ndt(const apdgicp_batch* b, apdgicp_ndt_params* p, int* enabled) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (p) *p = b->nd.prm;
+  if (enabled) *enabled = b->nd.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_batch_ndt_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(ndb_slot_map(b, cloud));
+    *n_voxels = b->nd.slots[cloud].nv;
+    return 0;
+  });
+}
+
+int apdgicp_batch_ndt_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6,
+                                 double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    APD_TRY(ndb_slot_map(b, cloud));
+    const NdbState::Slot& sl = b->nd.slots[cloud];
+    Engine& e = b->eng;
+    const int64_t nv = sl.nv;
+    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
+    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
+    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
+    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), sl.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
+    if (counts) APD_HIP(hipMemcpyAsync(counts, sl.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
+    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, sl.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
+    if (raw_covs_n6) APD_HIP(hipMemcpyAsync(raw_covs_n6, sl.vraw.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), sl.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (int64_t i = 0; i < nv && coords_n3; i++) {
+      const unsigned long long k = keys[i];
+      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
+    }
+    for (int64_t i = 0; i < nv && covs_n9; i++) {
+      const double* c = &c6[6 * i];
+      double* o = covs_n9 + 9 * i;
+      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
+    }
+    return 0;
+  });
+}
+
+int apdgicp_batch_ndt_build_count(apdgicp_batch* b, int64_t* n_builds) {
+  if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n_builds = b->nd.builds;
   return 0;
 }
 
@@ -1946,6 +2243,7 @@ int apdgicp_batch_clear(apdgicp_batch* b) {
   b->eng.clouds.clear();
   b->eng.clouds_written();
   b->vg.release();  // (V8: every slot's map and inverse permutation go with the clouds)
+  b->nd.release();  // (N10: likewise)
   return 0;
 }
 
@@ -1998,6 +2296,11 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
       if (d_results) *d_results = b->eng.d_results.p;
       return 0;
     }
+    if (b->nd.on) {  // NDT: likewise (N15)
+      APD_TRY(ndb_align(b, pairs, n_pairs));
+      if (d_results) *d_results = b->eng.d_results.p;
+      return 0;
+    }
     if (b->eng.pool_eligible()) {  // Levenberg-Marquardt: through the pair pool (complete on return, like every LM run)
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
@@ -2014,6 +2317,7 @@ int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int
   return guarded([&]() -> int {
     if (!b || !pairs || !ticket) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
+    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_eligible()) return e.pool_enqueue(pairs, n_pairs, ticket);
     APD_TRY(e.ensure_alt_slot());
@@ -2031,13 +2335,14 @@ int apdgicp_batch_pump(apdgicp_batch* b) {
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
+    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     return b->eng.pool.on ? b->eng.pool_pump(false) : 0;
   });
 }
 
 int apdgicp_batch_is_pooled(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-  if (b->vg.on) return 0;
+  if (b->vg.on || b->nd.on) return 0;
   return b->eng.pool_eligible() ? Engine::pool_lanes_cfg() : 0;
 }
 
@@ -2045,6 +2350,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
+    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_find(ticket)) return e.pool_collect(ticket, d_results, host_results);
     const bool previous = ticket + 1 == e.align_seq;
@@ -2071,7 +2377,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
 int apdgicp_batch_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, apdgicp_result* results) {
   return guarded([&]() -> int {
     if (!results) return fail(APDGICP_ERR_INVALID_ARG, "results is null");
-    if (b && pairs && !b->vg.on && b->eng.pool_eligible()) {
+    if (b && pairs && !b->vg.on && !b->nd.on && b->eng.pool_eligible()) {
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
       return b->eng.pool_collect(ticket, nullptr, results);

@@ -1,6 +1,7 @@
 """NDT registration (fast_gicp::NDTCuda: point-to-distribution and distribution-to-distribution) as a mode of the registration handle:
 `NDT` is `registration.FastAPDGICP` with apdgicp_set_ndt switched on and the reference's setters
-(fast_apdgicp/include/fast_gicp/ndt/ndt_cuda.hpp).  Semantics: the list N1 .. N9 in include/apdgicp_hip.h.
+(fast_apdgicp/include/fast_gicp/ndt/ndt_cuda.hpp).  Semantics: the list N1 .. N9 in include/apdgicp_hip.h.  `BatchNDT` is
+`registration.BatchAPDGICP` with apdgicp_batch_set_ndt switched on: many pairs at once, the optimiser loop on the device (N10 .. N15).
 
 There is NO CPU fallback: without the HIP library or a GPU every call raises.
 """
@@ -109,4 +110,74 @@ class NDT(reg.FastAPDGICP):
         """How many voxel maps this handle has built in this mode (the cache rules' test hook)."""
         n = C.c_int64()
         _check(self.L.apdgicp_ndt_build_count(self.h, C.byref(n)))
+        return n.value
+
+
+class BatchNDT(reg.BatchAPDGICP):
+    """Many independent NDT registrations on one GPU: a batch handle with apdgicp_batch_set_ndt on (N10 .. N15).  Clouds, align,
+    align_async / synchronize and fitness are the base class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is;
+    align_enqueue / align_collect raise (one batch at a time).  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.nparams = default_ndt_params()
+        self._push_ndt()
+
+    def _push_ndt(self):
+        _check(self.L.apdgicp_batch_set_ndt(self.b, C.byref(self.nparams)))
+
+    def _set(self, field: str, value):
+        old = getattr(self.nparams, field)
+        setattr(self.nparams, field, value)
+        try:
+            self._push_ndt()
+        except reg.ApdgicpError:
+            setattr(self.nparams, field, old)
+            raise
+
+    def setDistanceMode(self, mode: int):
+        self._set("distance_mode", int(mode))
+
+    def setResolution(self, resolution: float):
+        self._set("resolution", float(resolution))
+
+    def setNeighborSearchMethod(self, method: int, radius: float = -1.0):
+        """`radius` belongs to DIRECT_RADIUS, which is not offered."""
+        self._set("neighbor_search", int(method))
+
+    def get_ndt(self):
+        """(NdtParams, enabled) as the library holds them."""
+        p, on = NdtParams(), C.c_int()
+        _check(self.L.apdgicp_batch_get_ndt(self.b, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def disable(self):
+        _check(self.L.apdgicp_batch_set_ndt(self.b, None))
+
+    def enable(self):
+        self._push_ndt()
+
+    def enabled(self) -> bool:
+        return self.get_ndt()[1]
+
+    def voxel_count(self, cloud: int) -> int:
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_ndt_voxel_count(self.b, int(cloud), C.byref(n)))
+        return n.value
+
+    def voxels(self, cloud: int):
+        """The voxel map of cloud slot `cloud` (built if it is not current), as NDT.voxels()."""
+        n = self.voxel_count(cloud)
+        coords = np.empty((n, 3), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        means = np.empty((n, 3))
+        raw = np.empty((n, 6))
+        covs = np.empty((n, 9))
+        _check(self.L.apdgicp_batch_ndt_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(raw), _ptr(covs)))
+        return {"coords": coords, "counts": counts, "means": means, "raw": raw, "covs": covs.reshape(n, 3, 3)}
+
+    def build_count(self) -> int:
+        """How many NDT voxel maps this handle has built, all slots together (the cache rules' test hook)."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_ndt_build_count(self.b, C.byref(n)))
         return n.value

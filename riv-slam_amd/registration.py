@@ -113,6 +113,7 @@ SYMBOLS = [
     "apdgicp_batch_set_vgicp", "apdgicp_batch_get_vgicp", "apdgicp_batch_vgicp_voxel_count", "apdgicp_batch_vgicp_get_voxels", "apdgicp_batch_vgicp_build_count",
     "apdgicp_ndt_default_params", "apdgicp_set_ndt", "apdgicp_get_ndt", "apdgicp_ndt_voxel_count", "apdgicp_ndt_get_voxels",
     "apdgicp_ndt_get_correspondences", "apdgicp_ndt_build_count",
+    "apdgicp_batch_set_ndt", "apdgicp_batch_get_ndt", "apdgicp_batch_ndt_voxel_count", "apdgicp_batch_ndt_get_voxels", "apdgicp_batch_ndt_build_count",
 ]
 
 _lib = None
@@ -298,6 +299,11 @@ def load_library(path: str | None = None):
     L.apdgicp_ndt_get_voxels.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
     L.apdgicp_ndt_get_correspondences.argtypes = [vp, vp, i64]
     L.apdgicp_ndt_build_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_batch_set_ndt.argtypes = [vp, vp]
+    L.apdgicp_batch_get_ndt.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_batch_ndt_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
+    L.apdgicp_batch_ndt_get_voxels.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp, vp]
+    L.apdgicp_batch_ndt_build_count.argtypes = [vp, C.POINTER(i64)]
     if path is None:
         _lib = L
     return L
