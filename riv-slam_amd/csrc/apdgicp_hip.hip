@@ -20,7 +20,53 @@
 
 using namespace apd;
 
-// apdgicp_set_vgicp: the voxel map of the target and the frozen state of the last linearize (include/apdgicp_hip.h, V1 .. V7)
+// The scratch of one voxel-map build (k_vg_keys, the radix sort of apd_map.hpp, k_map_heads): one per handle, used by whichever voxel mode is
+// on.  Builds follow each other in stream order.
+struct VoxSortScratch {
+  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum;
+  // sized for a cloud of n points.  With `grows` given it only says whether that would replace a buffer and replaces none: the caller waits
+  // for the stream first, then calls again without.
+  int ensure(int n, bool* grows = nullptr) {
+    const int64_t entries = 256ll * ((n + MAP_RS_TILE - 1) / MAP_RS_TILE);
+    const size_t nsb = (size_t)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS)), nhb = (size_t)(n + MAP_BLK - 1) / MAP_BLK;
+    if (grows) {
+      *grows = (size_t)n * 8 > keys_a.cap || (size_t)entries * 4 > hist.cap || nsb * 4 > rs_bsum.cap || nhb * 4 > bsum.cap;
+      return 0;
+    }
+    APD_TRY(keys_a.ensure((size_t)n * 8));
+    APD_TRY(keys_b.ensure((size_t)n * 8));
+    APD_TRY(idx_a.ensure((size_t)n * 4));
+    APD_TRY(idx_b.ensure((size_t)n * 4));
+    APD_TRY(hist.ensure((size_t)entries * 4));
+    APD_TRY(rs_bsum.ensure(nsb * 4));
+    return bsum.ensure(nhb * 4);
+  }
+  void release() {
+    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum}) b->release();
+  }
+};
+
+// The buffers of one voxel map, voxels in ascending key order (vraw: NDT only).  What the map was made from stays with its owner, per mode.
+struct VoxMapBufs {
+  DevBuf vkeys, vcount, vmean, vraw, vcov;
+  int ensure(size_t voxels, bool raw) {
+    APD_TRY(vkeys.ensure(voxels * 8));
+    APD_TRY(vcount.ensure(voxels * 4));
+    APD_TRY(vmean.ensure(voxels * 24));
+    if (raw) APD_TRY(vraw.ensure(voxels * 48));
+    return vcov.ensure(voxels * 48);
+  }
+  void release() {
+    for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
+  }
+  VgMap map(int nv) const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv}; }
+  VgbMap map(const int* nv_word) const { return VgbMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv_word}; }
+};
+
+static int n_offsets(int neighbor_search) { return neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+
+// apdgicp_set_vgicp: the voxel map of the target and the frozen state of the last linearize (include/apdgicp_hip.h, V1 .. V7).  The scratch of
+// a map build is the handle's (apdgicp_handle::sort).
 struct VgState {
   bool on = false;
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
@@ -39,15 +85,17 @@ struct VgState {
   int64_t n_vox = 0, builds = 0;
   int n_src_lin = 0, noff_lin = 0;
   double T_lin[12];
-  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum, scal, inv_t, inv_s, vkeys, vcount, vmean, vcov, corr, part, T, out;
+  VoxMapBufs buf;
+  DevBuf scal, inv_t, inv_s, corr, part, T, out;
   void release() {
-    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &inv_t, &inv_s, &vkeys, &vcount, &vmean, &vcov, &corr, &part, &T, &out}) b->release();
+    buf.release();
+    for (DevBuf* b : {&scal, &inv_t, &inv_s, &corr, &part, &T, &out}) b->release();
   }
-  VgMap map() const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), (int)n_vox}; }
-  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
+  VgMap map() const { return buf.map((int)n_vox); }
 };
 
-// apdgicp_set_ndt: the voxel maps of target and source and the frozen state of the last linearize (include/apdgicp_hip.h, N1 .. N9)
+// apdgicp_set_ndt: the voxel maps of target and source and the frozen state of the last linearize (include/apdgicp_hip.h, N1 .. N9).  The
+// scratch of a map build is the handle's (apdgicp_handle::sort).
 struct NdState {
   struct Map {                 // one cloud's map: a pure function of (points, resolution), cached by identity like VgState's
     bool built = false;
@@ -55,12 +103,12 @@ struct NdState {
     double res = 0.0;
     int64_t id = 0;            // which build this is (NdState::builds when it was made): names the map for the frozen state
     int nv = 0;
-    DevBuf vkeys, vcount, vmean, vraw, vcov;
+    VoxMapBufs buf;
     void release() {
-      for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
+      buf.release();
       built = false, nv = 0;
     }
-    VgMap map() const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv}; }
+    VgMap map() const { return buf.map(nv); }
   };
   bool on = false;
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
@@ -72,28 +120,29 @@ struct NdState {
   int lin_mode = 0, n_rows_lin = 0, noff_lin = 0;
   double T_lin[12];
   double final_H[36];          // of the last align in this mode (identity until then)
-  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum, scal, corr, part, T, out;
+  DevBuf scal, corr, part, T, out;
   NdState() { reset_final_H(); }
   void reset_final_H() {
     for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
   }
-  bool allocated() const { return keys_a.p || T.p || maps[0].vkeys.p || maps[1].vkeys.p; }
+  bool allocated() const { return T.p || maps[0].buf.vkeys.p || maps[1].buf.vkeys.p; }
   void release() {
     for (Map& m : maps) m.release();
-    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &corr, &part, &T, &out}) b->release();
+    for (DevBuf* b : {&scal, &corr, &part, &T, &out}) b->release();
   }
-  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
 };
 
 struct apdgicp_handle {
   Engine eng;
   VgState vg;  // (released by ~apdgicp_handle, while the engine's stream still exists)
   NdState nd;  // (likewise)
+  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two are exclusive
   ~apdgicp_handle() {
-    if (vg.keys_a.p || vg.T.p || vg.inv_s.p || nd.allocated()) {
+    if (sort.keys_a.p || vg.T.p || vg.inv_s.p || nd.allocated()) {
       if (eng.stream) (void)hipStreamSynchronize(eng.stream);
       vg.release();
       nd.release();
+      sort.release();
     }
   }
   uint64_t cloud_epoch = 0, cloud_gen[2] = {0, 0};  // cloud_gen[slot]: which setting of points the slot holds (0: none); swapped with the clouds
@@ -106,7 +155,8 @@ struct apdgicp_handle {
 };
 
 // apdgicp_batch_set_vgicp (include/apdgicp_hip.h, V8 .. V12): per cloud slot the voxel map and the inverse permutation, cached by identity like
-// VgState's pieces; per align the pair table, the frozen indices and the block rows.
+// VgState's pieces; per align the pair table, the frozen indices and the block rows.  The scratch of a map build and the state of the device
+// loop are the handle's (apdgicp_batch::sort, apdgicp_batch::loop).
 struct VgbState {
   struct Slot {
     bool map_built = false;    // the map: points map_pts_gen, covariances map_cov_gen, map_res, map_mode
@@ -115,9 +165,11 @@ struct VgbState {
     int map_mode = 0;
     uint64_t inv_pts_gen = 0;  // inv: the inverse of the permutation of points inv_pts_gen (0: none)
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
-    DevBuf inv, vkeys, vcount, vmean, vcov;  // map buffers sized for nv <= n
+    DevBuf inv;
+    VoxMapBufs buf;            // sized for nv <= n
     void release() {
-      for (DevBuf* b : {&inv, &vkeys, &vcount, &vmean, &vcov}) b->release();
+      buf.release();
+      inv.release();
       map_built = false, inv_pts_gen = 0, nv = 0;
     }
   };
@@ -125,43 +177,29 @@ struct VgbState {
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
   std::vector<Slot> slots;
   int64_t builds = 0;
-  int last_ticks = 0;
-  int chunk = 0;               // ticks per enqueued chunk (create time: APDGICP_VGB_CHUNK, default kVgbChunk)
-  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum;  // scratch of one map build; builds follow each other in stream order
   DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
   int scal_slots = 0;
-  DevBuf corr, part, done;
+  DevBuf corr, part;
   CachedTable pairs;
-  int* h_words = nullptr;      // pinned: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
-  size_t h_words_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
   void release() {
     for (Slot& sl : slots) sl.release();
     slots.clear();
-    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum, &scal, &corr, &part, &done, &pairs.dev}) b->release();
+    for (DevBuf* b : {&scal, &corr, &part, &pairs.dev}) b->release();
     scal_slots = 0;
-    if (h_words) (void)hipHostFree(h_words);
-    h_words = nullptr, h_words_cap = 0;
-    for (hipEvent_t& e : ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
   }
 };
 
 // apdgicp_batch_set_ndt (include/apdgicp_hip.h, N10 .. N15): per cloud slot the NDT voxel map, cached by identity like NdState's; per align the
-// pair table, the frozen indices and the block rows.  The scratch of a map build, the pinned words, the events, the done counter and the chunk
-// length are VgbState's: the two modes never run together.
+// pair table, the frozen indices and the block rows.  Scratch and device-loop state: the handle's, as for VgbState.
 struct NdbState {
   struct Slot {
     bool built = false;        // the map: points pts_gen, resolution res
     uint64_t pts_gen = 0;
     double res = 0.0;
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
-    DevBuf vkeys, vcount, vmean, vraw, vcov;  // sized for nv <= n
+    VoxMapBufs buf;            // sized for nv <= n
     void release() {
-      for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
+      buf.release();
       built = false, nv = 0;
     }
   };
@@ -173,7 +211,6 @@ struct NdbState {
   int scal_slots = 0;
   DevBuf corr, part;
   CachedTable pairs;
-  int n_offsets() const { return prm.neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : prm.neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
   void release() {
     for (Slot& sl : slots) sl.release();
     slots.clear();
@@ -182,18 +219,45 @@ struct NdbState {
   }
 };
 
+// The device optimiser loop of a batch handle (V12 / N15), whichever voxel mode runs it: the done counter the step kernels count into, the
+// pinned words the host reads, the events of the last two chunks.
+struct DeviceLoop {
+  DevBuf done;
+  int* h_words = nullptr;      // pinned: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
+  size_t h_words_cap = 0;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int chunk = 0;               // ticks per enqueued chunk (create time: APDGICP_VGB_CHUNK, default kVgbChunk)
+  int last_ticks = 0;
+  void release() {
+    done.release();
+    if (h_words) (void)hipHostFree(h_words);
+    h_words = nullptr, h_words_cap = 0;
+    for (hipEvent_t& e : ev) {
+      if (e) (void)hipEventDestroy(e);
+      e = nullptr;
+    }
+  }
+};
+
 struct apdgicp_batch {
   Engine eng;
   VgbState vg;  // (released by ~apdgicp_batch, while the engine's stream still exists)
   NdbState nd;  // (likewise)
+  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two never run together
+  DeviceLoop loop;      // (likewise)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
+  void release_voxel_modes() {
+    vg.release();
+    nd.release();
+    sort.release();
+    loop.release();
+  }
   ~apdgicp_batch() {
     if (eng.stream) {
       (void)hipSetDevice(eng.device);
       (void)hipStreamSynchronize(eng.stream);
     }
-    vg.release();
-    nd.release();
+    release_voxel_modes();
   }
 };
 
@@ -346,6 +410,7 @@ struct apdgicp_scan_context {
 namespace {
 
 constexpr int kSrc = 0, kTgt = 1;
+const char* cloud_name(int which) { return which == kSrc ? "source" : "target"; }
 
 void identity16(float* g) {
   memset(g, 0, 16 * sizeof(float));
@@ -401,9 +466,110 @@ int scan_filter_compact(apdgicp_scan_filter* f, const float4* src, const float* 
   return 0;
 }
 
-// ---- voxelized GICP (include/apdgicp_hip.h V1 .. V7; kernels: apd_vgicp.hpp)
+// ---- voxel maps: what voxelized GICP and NDT share, on single and batch handles (kernels: apd_vgicp.hpp, apd_map.hpp)
 constexpr int kVgBadNone = 0x7f7f7f7f;  // (what hipMemsetAsync(0x7f) leaves: above every point index)
 
+struct VoxSorted {  // what enqueue_voxel_sort leaves for k_vg_voxels / k_ndt_voxels (and, in s.bsum, the voxel offset of every head block)
+  unsigned long long* keys;
+  int* idx;
+  unsigned nhb;
+};
+
+// The build chain up to the voxel kernel, on s (sized for n by the caller).  Enqueues only, never waits: the four scal words reset, the voxel
+// keys of pts[0 .. n) (scal[0]: the first point that has none), the (key, index) pairs sorted, the voxels counted (scal[1]).
+int enqueue_voxel_sort(hipStream_t stream, VoxSortScratch& s, const float4* pts, int n, double resolution, int* scal, VoxSorted* sorted) {
+  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+  const int64_t entries = 256ll * nblk;
+  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+  const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
+  APD_HIP(hipMemsetAsync(scal, 0x7f, 16, stream));
+  unsigned long long *ks = s.keys_a.as<unsigned long long>(), *kd = s.keys_b.as<unsigned long long>();
+  int *is = s.idx_a.as<int>(), *id = s.idx_b.as<int>();
+  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, stream, pts, n, resolution, ks, is, scal);
+  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
+    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, stream, ks, n, 8 * p, nblk, s.hist.as<int>());
+    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, stream, s.hist.as<int>(), (int)entries, s.rs_bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, stream, s.rs_bsum.as<int>(), nsb, scal + 2);
+    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, stream, ks, is, kd, id, n, 8 * p, nblk, s.hist.as<int>(), s.rs_bsum.as<int>());
+    std::swap(ks, kd), std::swap(is, id);
+  }
+  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, stream, ks, n, s.bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, stream, s.bsum.as<int>(), (int)nhb, scal + 1);
+  *sorted = VoxSorted{ks, is, nhb};
+  return 0;
+}
+
+// a build whose scal[0] names a point (what: "voxelized GICP: target point 7", "NDT: point 7 of cloud slot 2")
+int voxel_key_range_error(const std::string& what, double resolution) {
+  return fail(APDGICP_ERR_INVALID_ARG, what + " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(resolution) + ")");
+}
+
+// A single handle's build up to the voxel kernel: waits before the scratch may be replaced, sorts cloud `which`, waits again to read the voxel
+// count *nv.  prefix: "voxelized GICP: " / "NDT: ".
+int handle_sort_voxels(apdgicp_handle* h, int which, double resolution, DevBuf& scal, const char* prefix, VoxSorted* sorted, int* nv) {
+  Engine& e = h->eng;
+  const Engine::Cloud& c = e.clouds[which];
+  APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below, and the caller's after this, may be replaced)
+  APD_TRY(h->sort.ensure(c.n));
+  APD_TRY(scal.ensure(16));
+  APD_TRY(enqueue_voxel_sort(e.stream, h->sort, c.opts.as<float4>(), c.n, resolution, scal.as<int>(), sorted));
+  APD_HIP(hipGetLastError());
+  int hs[4];
+  APD_HIP(hipMemcpyAsync(hs, scal.p, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (hs[0] != kVgBadNone) return voxel_key_range_error(std::string(prefix) + cloud_name(which) + " point " + std::to_string(hs[0]), resolution);
+  if (hs[1] < 1 || hs[1] > c.n) return fail(APDGICP_ERR_INTERNAL, std::string(prefix) + "inconsistent voxel count");
+  *nv = hs[1];
+  return 0;
+}
+
+// the getters' read-back of a map of nv voxels: keys unpacked into coordinates, covariances expanded from 6 to 9 (every output may be null)
+int read_voxels(hipStream_t stream, const VoxMapBufs& m, int64_t nv, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6,
+                double* covs_n9) {
+  if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
+  std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
+  std::vector<double> c6(covs_n9 ? 6 * nv : 0);
+  if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), m.vkeys.p, nv * 8, hipMemcpyDeviceToHost, stream));
+  if (counts) APD_HIP(hipMemcpyAsync(counts, m.vcount.p, nv * 4, hipMemcpyDeviceToHost, stream));
+  if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, m.vmean.p, nv * 24, hipMemcpyDeviceToHost, stream));
+  if (raw_covs_n6) APD_HIP(hipMemcpyAsync(raw_covs_n6, m.vraw.p, nv * 48, hipMemcpyDeviceToHost, stream));
+  if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), m.vcov.p, nv * 48, hipMemcpyDeviceToHost, stream));
+  APD_HIP(hipStreamSynchronize(stream));
+  for (int64_t i = 0; i < nv && coords_n3; i++) {
+    const unsigned long long k = keys[i];
+    coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
+  }
+  for (int64_t i = 0; i < nv && covs_n9; i++) {
+    const double* c = &c6[6 * i];
+    double* o = covs_n9 + 9 * i;
+    o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
+  }
+  return 0;
+}
+
+// room for the frozen indices and the block rows of a linearize, waiting first when either buffer would be replaced
+int ensure_corr_part(Engine& e, DevBuf& corr, DevBuf& part, size_t corr_bytes, size_t part_bytes) {
+  if (corr_bytes > corr.cap || part_bytes > part.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(corr.ensure(corr_bytes));
+  return part.ensure(part_bytes);
+}
+
+// The tail of a single handle's linearize (offset 0) and compute_error (offset 27): the block rows reduced, the 44 doubles read with a wait.
+int reduce_and_read(Engine& e, const DevBuf& part, DevBuf& out, int nblk, int offset, double* H, double* b, double* cost, int* matched) {
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, part.as<double>(), nblk, offset, out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(e.h_probe, out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (H && b) {
+    memcpy(H, e.h_probe, 36 * sizeof(double));
+    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
+  }
+  if (cost) *cost = e.h_probe[42];
+  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  return 0;
+}
+
+// ---- voxelized GICP (include/apdgicp_hip.h V1 .. V7; kernels: apd_vgicp.hpp)
 // V1 .. V3: the voxel map of the target.  Needs the target only; its covariances are computed here when they are missing.
 int vg_build_map(apdgicp_handle* h) {
   Engine& e = h->eng;
@@ -415,51 +581,15 @@ int vg_build_map(apdgicp_handle* h) {
   if (v.map_built && v.map_tgt_gen == h->cloud_gen[kTgt] && v.map_cov_gen == c.cov_gen && v.map_res == v.prm.resolution && v.map_mode == v.prm.voxel_mode) return 0;
   const int n = c.n;
   APD_HIP(hipSetDevice(e.device));
-  APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
   v.map_built = v.have_lin = false;
-  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-  const int64_t entries = 256ll * nblk;
-  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-  const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
-  APD_TRY(v.keys_a.ensure((size_t)n * 8));
-  APD_TRY(v.keys_b.ensure((size_t)n * 8));
-  APD_TRY(v.idx_a.ensure((size_t)n * 4));
-  APD_TRY(v.idx_b.ensure((size_t)n * 4));
-  APD_TRY(v.hist.ensure((size_t)entries * 4));
-  APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
-  APD_TRY(v.bsum.ensure((size_t)nhb * 4));
-  APD_TRY(v.scal.ensure(16));
+  VoxSorted s;
+  int nv = 0;
+  APD_TRY(handle_sort_voxels(h, kTgt, v.prm.resolution, v.scal, "voxelized GICP: ", &s, &nv));
   APD_TRY(v.inv_t.ensure((size_t)n * 4));
-  int* scal = v.scal.as<int>();
-  APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
-  unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
-  int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
-  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
-  hipLaunchKernelGGL(k_vg_inverse_perm, dim3(nb256), dim3(256), 0, e.stream, c.perm.as<int>(), n, v.inv_t.as<int>());
-  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
-    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
-    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
-    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
-    std::swap(ks, kd), std::swap(is, id);
-  }
-  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
-  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
-  APD_HIP(hipGetLastError());
-  int hs[4];
-  APD_HIP(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  if (hs[0] != kVgBadNone)
-    return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: target point " + std::to_string(hs[0]) + " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " +
-                                             std::to_string(v.prm.resolution) + ")");
-  const int nv = hs[1];
-  if (nv < 1 || nv > n) return fail(APDGICP_ERR_INTERNAL, "voxelized GICP: inconsistent voxel count");
-  APD_TRY(v.vkeys.ensure((size_t)nv * 8));
-  APD_TRY(v.vcount.ensure((size_t)nv * 4));
-  APD_TRY(v.vmean.ensure((size_t)nv * 24));
-  APD_TRY(v.vcov.ensure((size_t)nv * 48));
-  hipLaunchKernelGGL(k_vg_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), v.inv_t.as<int>(),
-                     v.vkeys.as<unsigned long long>(), v.vcount.as<int>(), v.vmean.as<double>(), v.vcov.as<double>(), nv);
+  APD_TRY(v.buf.ensure((size_t)nv, false));
+  hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, c.perm.as<int>(), n, v.inv_t.as<int>());
+  hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, h->sort.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), v.inv_t.as<int>(),
+                     v.buf.vkeys.as<unsigned long long>(), v.buf.vcount.as<int>(), v.buf.vmean.as<double>(), v.buf.vcov.as<double>(), nv);
   APD_HIP(hipGetLastError());
   v.n_vox = nv;
   v.map_built = true, v.map_tgt_gen = h->cloud_gen[kTgt], v.map_cov_gen = c.cov_gen, v.map_res = v.prm.resolution, v.map_mode = v.prm.voxel_mode;
@@ -496,10 +626,8 @@ int vg_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   Engine& e = h->eng;
   VgState& v = h->vg;
   const Engine::Cloud& s = e.clouds[kSrc];
-  const int n = s.n, noff = v.n_offsets(), nblk = (n + VG_BLK - 1) / VG_BLK;
-  if ((size_t)n * noff * 4 > v.corr.cap || (size_t)nblk * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(v.corr.ensure((size_t)n * noff * 4));
-  APD_TRY(v.part.ensure((size_t)nblk * VG_RED * 8));
+  const int n = s.n, noff = n_offsets(v.prm.neighbor_search), nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)n * noff * 4, (size_t)nblk * VG_RED * 8));
   APD_TRY(v.T.ensure(24 * sizeof(double)));
   APD_TRY(v.out.ensure(64 * sizeof(double)));
   colmajor_to_rows12(T16, v.T_lin);
@@ -507,16 +635,7 @@ int vg_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   const int want = H && b ? 1 : 0;
   hipLaunchKernelGGL(k_vg_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(),
                      v.prm.resolution, (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
-  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 0, v.out.as<double>());
-  APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  if (want) {
-    memcpy(H, e.h_probe, 36 * sizeof(double));
-    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
-  }
-  if (cost) *cost = e.h_probe[42];
-  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));
   v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
   v.lin_src_gen = h->cloud_gen[kSrc], v.lin_src_cov_gen = s.cov_gen, v.lin_build = v.builds;
   return 0;
@@ -541,12 +660,7 @@ int vg_error(apdgicp_handle* h, const double* T16, double* cost) {
   APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
   hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(), noff,
                      v.corr.as<int>(), v.part.as<double>());
-  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 27, v.out.as<double>());
-  APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  *cost = e.h_probe[42];
-  return 0;
+  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
 }
 
 // The reference's own control flow (L:55-173) on the host over two callables: lin(T16, H, b, &y0, &matched) and err(T16, &yi), the two
@@ -665,64 +779,24 @@ int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
 }
 
 // ---- NDT (include/apdgicp_hip.h N1 .. N9; kernels: apd_ndt.hpp)
-const char* nd_cloud_name(int which) { return which == kSrc ? "source" : "target"; }
-
 // N1 .. N4: the voxel map of one cloud.  Needs that cloud's points only: no covariances, any size.
 int nd_build_map(apdgicp_handle* h, int which) {
   Engine& e = h->eng;
   NdState& v = h->nd;
-  if (e.clouds.size() < 2 || e.clouds[which].n <= 0) return fail(APDGICP_ERR_NO_INPUT, std::string(nd_cloud_name(which)) + " cloud is not set");
+  if (e.clouds.size() < 2 || e.clouds[which].n <= 0) return fail(APDGICP_ERR_NO_INPUT, std::string(cloud_name(which)) + " cloud is not set");
   NdState::Map& m = v.maps[which];
   if (m.built && m.pts_gen == h->cloud_gen[which] && m.res == v.prm.resolution) return 0;
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
   Engine::Cloud& c = e.clouds[which];
-  const int n = c.n;
-  APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
   m.built = false;
   v.have_lin = false;
-  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-  const int64_t entries = 256ll * nblk;
-  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-  const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
-  APD_TRY(v.keys_a.ensure((size_t)n * 8));
-  APD_TRY(v.keys_b.ensure((size_t)n * 8));
-  APD_TRY(v.idx_a.ensure((size_t)n * 4));
-  APD_TRY(v.idx_b.ensure((size_t)n * 4));
-  APD_TRY(v.hist.ensure((size_t)entries * 4));
-  APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
-  APD_TRY(v.bsum.ensure((size_t)nhb * 4));
-  APD_TRY(v.scal.ensure(16));
-  int* scal = v.scal.as<int>();
-  APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
-  unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
-  int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
-  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
-  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
-    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
-    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
-    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
-    std::swap(ks, kd), std::swap(is, id);
-  }
-  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
-  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
-  APD_HIP(hipGetLastError());
-  int hs[4];
-  APD_HIP(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  if (hs[0] != kVgBadNone)
-    return fail(APDGICP_ERR_INVALID_ARG, std::string("NDT: ") + nd_cloud_name(which) + " point " + std::to_string(hs[0]) +
-                                             " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
-  const int nv = hs[1];
-  if (nv < 1 || nv > n) return fail(APDGICP_ERR_INTERNAL, "NDT: inconsistent voxel count");
-  APD_TRY(m.vkeys.ensure((size_t)nv * 8));
-  APD_TRY(m.vcount.ensure((size_t)nv * 4));
-  APD_TRY(m.vmean.ensure((size_t)nv * 24));
-  APD_TRY(m.vraw.ensure((size_t)nv * 48));
-  APD_TRY(m.vcov.ensure((size_t)nv * 48));
-  hipLaunchKernelGGL(k_ndt_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), m.vkeys.as<unsigned long long>(),
-                     m.vcount.as<int>(), m.vmean.as<double>(), m.vraw.as<double>(), m.vcov.as<double>(), nv);
+  VoxSorted s;
+  int nv = 0;
+  APD_TRY(handle_sort_voxels(h, which, v.prm.resolution, v.scal, "NDT: ", &s, &nv));
+  APD_TRY(m.buf.ensure((size_t)nv, true));
+  hipLaunchKernelGGL(k_ndt_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, c.n, h->sort.bsum.as<int>(), c.opts.as<float4>(), m.buf.vkeys.as<unsigned long long>(),
+                     m.buf.vcount.as<int>(), m.buf.vmean.as<double>(), m.buf.vraw.as<double>(), m.buf.vcov.as<double>(), nv);
   APD_HIP(hipGetLastError());
   m.nv = nv;
   m.built = true, m.pts_gen = h->cloud_gen[which], m.res = v.prm.resolution;
@@ -750,10 +824,8 @@ int nd_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   const Engine::Cloud& s = e.clouds[kSrc];
   const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
   const NdState::Map &mt = v.maps[kTgt], &ms = v.maps[kSrc];
-  const int nrows = d2d ? ms.nv : s.n, noff = v.n_offsets(), nblk = (nrows + VG_BLK - 1) / VG_BLK;
-  if ((size_t)nrows * noff * 4 > v.corr.cap || (size_t)nblk * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(v.corr.ensure((size_t)nrows * noff * 4));
-  APD_TRY(v.part.ensure((size_t)nblk * VG_RED * 8));
+  const int nrows = d2d ? ms.nv : s.n, noff = n_offsets(v.prm.neighbor_search), nblk = (nrows + VG_BLK - 1) / VG_BLK;
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)nrows * noff * 4, (size_t)nblk * VG_RED * 8));
   APD_TRY(v.T.ensure(24 * sizeof(double)));
   APD_TRY(v.out.ensure(64 * sizeof(double)));
   colmajor_to_rows12(T16, v.T_lin);
@@ -766,16 +838,7 @@ int nd_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   else
     hipLaunchKernelGGL(k_ndt_linearize<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution,
                        (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
-  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 0, v.out.as<double>());
-  APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  if (want) {
-    memcpy(H, e.h_probe, 36 * sizeof(double));
-    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
-  }
-  if (cost) *cost = e.h_probe[42];
-  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));
   v.have_lin = true, v.n_rows_lin = nrows, v.noff_lin = noff, v.lin_mode = v.prm.distance_mode;
   v.lin_src_gen = h->cloud_gen[kSrc], v.lin_tgt_id = mt.id, v.lin_src_id = d2d ? ms.id : 0;
   return 0;
@@ -808,12 +871,7 @@ int nd_error(apdgicp_handle* h, const double* T16, double* cost) {
   else
     hipLaunchKernelGGL(k_ndt_error<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution, noff,
                        v.corr.as<int>(), v.part.as<double>());
-  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, 27, v.out.as<double>());
-  APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe, v.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  *cost = e.h_probe[42];
-  return 0;
+  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
 }
 
 int nd_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
@@ -826,20 +884,61 @@ int nd_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return rc;
 }
 
-// ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
+// ---- the voxel modes on a batch handle: what voxelized GICP (V8 .. V12) and NDT (N10 .. N15) share
 constexpr int kVgbChunk = 4;  // ticks enqueued per look at the done counter (docs/experiments.md, "VGICP batch: chunk length")
 
-int vgb_ensure_words(apdgicp_batch* b, size_t ints) {
-  VgbState& v = b->vg;
-  if (v.h_words && ints <= v.h_words_cap) return 0;
+int device_loop_ensure_words(apdgicp_batch* b, size_t ints) {
+  DeviceLoop& l = b->loop;
+  if (l.h_words && ints <= l.h_words_cap) return 0;
   APD_HIP(hipStreamSynchronize(b->eng.stream));
-  if (v.h_words) APD_HIP(hipHostFree(v.h_words));
-  v.h_words = nullptr, v.h_words_cap = 0;
+  if (l.h_words) APD_HIP(hipHostFree(l.h_words));
+  l.h_words = nullptr, l.h_words_cap = 0;
   const size_t cap = std::max<size_t>(ints * 2, 1024);
-  APD_HIP(hipHostMalloc((void**)&v.h_words, cap * sizeof(int), hipHostMallocDefault));
-  memset(v.h_words, 0, cap * sizeof(int));
-  v.h_words_cap = cap;
+  APD_HIP(hipHostMalloc((void**)&l.h_words, cap * sizeof(int), hipHostMallocDefault));
+  memset(l.h_words, 0, cap * sizeof(int));
+  l.h_words_cap = cap;
   return 0;
+}
+
+// V8 / N10: the maps of the listed slots (sorted) that are not current: enqueued one after the other with no wait in between, then ONE copy of
+// every slot's {first bad point, voxel count} and one wait for all of them.  The mode says which slots are current(t), whether a slot's own
+// buffers grow(t), sizes them and enqueues the build of slot t (launch(t): enqueue_voxel_sort, then its voxel kernel) and marks it
+// built(t, nv); prefix: "voxelized GICP: " / "NDT: ".  errflag (voxelized GICP): the covariance kernels' flag, read with the same wait.
+template <class Current, class Grows, class Launch, class Built>
+int batch_build_maps(apdgicp_batch* b, const std::vector<int>& slots, const char* prefix, double resolution, const DevBuf& scal, Current&& current, Grows&& grows,
+                     Launch&& launch, Built&& built, int* errflag = nullptr) {
+  Engine& e = b->eng;
+  std::vector<int> todo;
+  int nmax = 0;
+  for (int t : slots)
+    if (!current(t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t), nmax = std::max(nmax, e.clouds[t].n);
+  if (todo.empty()) return 0;
+  const int lo = *std::min_element(todo.begin(), todo.end()), hi = *std::max_element(todo.begin(), todo.end());
+  APD_TRY(device_loop_ensure_words(b, 4 + 4 * (size_t)(hi - lo + 1)));
+  bool any_grows = false;
+  APD_TRY(b->sort.ensure(nmax, &any_grows));
+  for (int t : todo) any_grows |= grows(t);
+  if (any_grows) APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced; never on a reused handle with clouds of the same sizes)
+  APD_TRY(b->sort.ensure(nmax));
+  // (a slot with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
+  for (int t : todo) APD_TRY(launch(t));
+  int* hw = b->loop.h_words + 4;
+  APD_HIP(hipMemcpyAsync(hw, scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
+  if (errflag) APD_HIP(hipMemcpyAsync(b->loop.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (errflag) *errflag = b->loop.h_words[2];
+  int rc = 0;
+  for (int t : todo) {
+    const int* w = hw + 4 * (size_t)(t - lo);
+    if (w[0] != kVgBadNone) {
+      if (rc == 0) rc = voxel_key_range_error(std::string(prefix) + "point " + std::to_string(w[0]) + " of cloud slot " + std::to_string(t), resolution);
+    } else if (w[1] < 1 || w[1] > e.clouds[t].n) {
+      if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, std::string(prefix) + "inconsistent voxel count");
+    } else {
+      built(t, w[1]);
+    }
+  }
+  return rc;
 }
 
 // room for the scal words of every slot of the engine; the words of built maps survive a growth
@@ -857,157 +956,23 @@ int batch_ensure_slot_words(Engine& e, DevBuf& scal, int& scal_slots) {
   return 0;
 }
 
-int vgb_ensure_slots(apdgicp_batch* b) {
-  VgbState& v = b->vg;
-  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
-  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
-}
-
-bool vgb_map_current(const apdgicp_batch* b, int slot) {
-  const VgbState& v = b->vg;
-  const Engine::Cloud& c = b->eng.clouds[slot];
-  const VgbState::Slot& sl = v.slots[slot];
-  return sl.map_built && c.cov_valid && sl.map_pts_gen == c.pts_gen && sl.map_cov_gen == c.cov_gen && sl.map_res == v.prm.resolution && sl.map_mode == v.prm.voxel_mode;
-}
-
-// the inverse permutation of a sorted slot, once per setting of its points
-int vgb_ensure_inv(apdgicp_batch* b, int slot) {
-  Engine& e = b->eng;
-  Engine::Cloud& c = e.clouds[slot];
-  VgbState::Slot& sl = b->vg.slots[slot];
-  if (sl.inv.p && sl.inv_pts_gen == c.pts_gen && (size_t)c.n * 4 <= sl.inv.cap) return 0;
-  sl.inv_pts_gen = 0;
-  if ((size_t)c.n * 4 > sl.inv.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(sl.inv.ensure((size_t)c.n * 4));
-  hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, e.stream, c.perm.as<int>(), c.n, sl.inv.as<int>());
-  APD_HIP(hipGetLastError());
-  sl.inv_pts_gen = c.pts_gen;
-  return 0;
-}
-
-// V8: the maps of the listed slots (sorted, covariances there) that are not current: enqueued one after the other with no wait in between, then
-// ONE copy of every slot's {first bad point, voxel count} and one wait for all of them
-int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
-  Engine& e = b->eng;
-  VgbState& v = b->vg;
-  APD_TRY(vgb_ensure_slots(b));
-  std::vector<int> todo;
-  int nmax = 0;
-  for (int t : targets)
-    if (!vgb_map_current(b, t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t), nmax = std::max(nmax, e.clouds[t].n);
-  if (todo.empty()) return 0;
-  const int lo = *std::min_element(todo.begin(), todo.end()), hi = *std::max_element(todo.begin(), todo.end());
-  APD_TRY(vgb_ensure_words(b, 4 + 4 * (size_t)(hi - lo + 1)));
-  {
-    const int nblk = (nmax + MAP_RS_TILE - 1) / MAP_RS_TILE;
-    const int64_t entries = 256ll * nblk;
-    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-    const size_t nhb = (size_t)(nmax + MAP_BLK - 1) / MAP_BLK;
-    bool grows = (size_t)nmax * 8 > v.keys_a.cap || (size_t)entries * 4 > v.hist.cap || (size_t)nsb * 4 > v.rs_bsum.cap || nhb * 4 > v.bsum.cap;
-    for (int t : todo) grows |= (size_t)e.clouds[t].n * 48 > v.slots[t].vcov.cap || (size_t)e.clouds[t].n * 4 > v.slots[t].inv.cap;
-    if (grows) APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced; never on a reused handle with clouds of the same sizes)
-    APD_TRY(v.keys_a.ensure((size_t)nmax * 8));
-    APD_TRY(v.keys_b.ensure((size_t)nmax * 8));
-    APD_TRY(v.idx_a.ensure((size_t)nmax * 4));
-    APD_TRY(v.idx_b.ensure((size_t)nmax * 4));
-    APD_TRY(v.hist.ensure((size_t)entries * 4));
-    APD_TRY(v.rs_bsum.ensure((size_t)nsb * 4));
-    APD_TRY(v.bsum.ensure(nhb * 4));
-  }
-  for (int t : todo) {
-    Engine::Cloud& c = e.clouds[t];
-    VgbState::Slot& sl = v.slots[t];
-    const int n = c.n;
-    sl.map_built = false;
-    APD_TRY(sl.vkeys.ensure((size_t)n * 8));
-    APD_TRY(sl.vcount.ensure((size_t)n * 4));
-    APD_TRY(sl.vmean.ensure((size_t)n * 24));
-    APD_TRY(sl.vcov.ensure((size_t)n * 48));
-    APD_TRY(vgb_ensure_inv(b, t));
-    const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-    const int64_t entries = 256ll * nblk;
-    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-    const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
-    int* scal = v.scal.as<int>() + 4 * (size_t)t;
-    APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
-    unsigned long long *ks = v.keys_a.as<unsigned long long>(), *kd = v.keys_b.as<unsigned long long>();
-    int *is = v.idx_a.as<int>(), *id = v.idx_b.as<int>();
-    hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
-    for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
-      hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, v.hist.as<int>());
-      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, v.hist.as<int>(), (int)entries, v.rs_bsum.as<int>());
-      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.rs_bsum.as<int>(), nsb, scal + 2);
-      hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, v.hist.as<int>(), v.rs_bsum.as<int>());
-      std::swap(ks, kd), std::swap(is, id);
-    }
-    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, v.bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), (int)nhb, scal + 1);
-    // (a target with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
-    hipLaunchKernelGGL(k_vg_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, v.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), sl.inv.as<int>(),
-                       sl.vkeys.as<unsigned long long>(), sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vcov.as<double>(), n);
-    APD_HIP(hipGetLastError());
-  }
-  int* hw = v.h_words + 4;
-  APD_HIP(hipMemcpyAsync(hw, v.scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipMemcpyAsync(v.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));  // (the covariance kernels' flag, with the same wait)
-  APD_HIP(hipStreamSynchronize(e.stream));
-  int rc = 0;
-  for (int t : todo) {
-    const int* w = hw + 4 * (size_t)(t - lo);
-    VgbState::Slot& sl = v.slots[t];
-    const Engine::Cloud& c = e.clouds[t];
-    if (w[0] != kVgBadNone) {
-      if (rc == 0)
-        rc = fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: point " + std::to_string(w[0]) + " of cloud slot " + std::to_string(t) +
-                                               " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
-      continue;
-    }
-    if (w[1] < 1 || w[1] > c.n) {
-      if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, "voxelized GICP: inconsistent voxel count");
-      continue;
-    }
-    sl.nv = w[1];
-    sl.map_built = true, sl.map_pts_gen = c.pts_gen, sl.map_cov_gen = c.cov_gen, sl.map_res = v.prm.resolution, sl.map_mode = v.prm.voxel_mode;
-    v.builds++;
-  }
-  if (v.h_words[2]) {  // a point that is not finite trips the covariance kernels too: the message about the point is the useful one
-    const int flag = v.h_words[2];
-    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
-    if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
-  }
-  return rc;
-}
-
-// one slot's map for the getters: sorted, covariances computed, built
-int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
-  Engine& e = b->eng;
-  if (!b->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_batch_set_vgicp)");
-  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
-  APD_HIP(hipSetDevice(e.device));
-  APD_TRY(e.pool_leave());
-  APD_TRY(e.finish_align());
-  APD_TRY(e.compute_covariances({cloud}));
-  APD_TRY(e.upload_desc());
-  return vgb_build_maps(b, {cloud});
-}
-
 // V12 / N15: what the tick loop needs besides the pairs -- the done counter, the pinned words, the two events
-int vgb_prepare_ticks(apdgicp_batch* b) {
-  VgbState& v = b->vg;
+int device_loop_prepare(apdgicp_batch* b) {
+  DeviceLoop& v = b->loop;
   APD_TRY(v.done.ensure(16));
-  APD_TRY(vgb_ensure_words(b, 4));
+  APD_TRY(device_loop_ensure_words(b, 4));
   for (hipEvent_t& ev : v.ev)
     if (!ev) APD_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
   return 0;
 }
 
-// V10 / V12 / N13 / N15: the optimiser loop of every pair of the engine's list (setup_pairs done, vgb_prepare_ticks done) on the device.
+// V10 / V12 / N13 / N15: the optimiser loop of every pair of the engine's list (setup_pairs done, device_loop_prepare done) on the device.
 // launch_tick() enqueues the two launches of one tick on the engine's stream.  Ticks go out in chunks, one chunk ahead of the pinned word the
 // host looks at; returns with the device records complete and the deferred error flag read.
 template <class Tick>
-int vgb_run_ticks(apdgicp_batch* b, Tick&& launch_tick) {
+int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
   Engine& e = b->eng;
-  VgbState& v = b->vg;
+  DeviceLoop& v = b->loop;
   const int np = e.npairs;
   const apdgicp_params& p = e.params;
   PairState* st = e.d_state.as<PairState>();
@@ -1055,6 +1020,86 @@ int vgb_run_ticks(apdgicp_batch* b, Tick&& launch_tick) {
   return 0;
 }
 
+// ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
+int vgb_ensure_slots(apdgicp_batch* b) {
+  VgbState& v = b->vg;
+  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
+  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
+}
+
+bool vgb_map_current(const apdgicp_batch* b, int slot) {
+  const VgbState& v = b->vg;
+  const Engine::Cloud& c = b->eng.clouds[slot];
+  const VgbState::Slot& sl = v.slots[slot];
+  return sl.map_built && c.cov_valid && sl.map_pts_gen == c.pts_gen && sl.map_cov_gen == c.cov_gen && sl.map_res == v.prm.resolution && sl.map_mode == v.prm.voxel_mode;
+}
+
+// the inverse permutation of a sorted slot, once per setting of its points
+int vgb_ensure_inv(apdgicp_batch* b, int slot) {
+  Engine& e = b->eng;
+  Engine::Cloud& c = e.clouds[slot];
+  VgbState::Slot& sl = b->vg.slots[slot];
+  if (sl.inv.p && sl.inv_pts_gen == c.pts_gen && (size_t)c.n * 4 <= sl.inv.cap) return 0;
+  sl.inv_pts_gen = 0;
+  if ((size_t)c.n * 4 > sl.inv.cap) APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(sl.inv.ensure((size_t)c.n * 4));
+  hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((c.n + 255) / 256)), dim3(256), 0, e.stream, c.perm.as<int>(), c.n, sl.inv.as<int>());
+  APD_HIP(hipGetLastError());
+  sl.inv_pts_gen = c.pts_gen;
+  return 0;
+}
+
+// V8: the maps of the listed slots (sorted, covariances there) that are not current
+int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
+  Engine& e = b->eng;
+  VgbState& v = b->vg;
+  APD_TRY(vgb_ensure_slots(b));
+  int flag = 0;
+  int rc = batch_build_maps(
+      b, targets, "voxelized GICP: ", v.prm.resolution, v.scal, [&](int t) { return vgb_map_current(b, t); },
+      [&](int t) { return (size_t)e.clouds[t].n * 48 > v.slots[t].buf.vcov.cap || (size_t)e.clouds[t].n * 4 > v.slots[t].inv.cap; },
+      [&](int t) -> int {
+        Engine::Cloud& c = e.clouds[t];
+        VgbState::Slot& sl = v.slots[t];
+        const int n = c.n;
+        sl.map_built = false;
+        APD_TRY(sl.buf.ensure((size_t)n, false));
+        APD_TRY(vgb_ensure_inv(b, t));
+        VoxSorted s;
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), sl.inv.as<int>(),
+                           sl.buf.vkeys.as<unsigned long long>(), sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vcov.as<double>(), n);
+        APD_HIP(hipGetLastError());
+        return 0;
+      },
+      [&](int t, int nv) {
+        VgbState::Slot& sl = v.slots[t];
+        const Engine::Cloud& c = e.clouds[t];
+        sl.nv = nv;
+        sl.map_built = true, sl.map_pts_gen = c.pts_gen, sl.map_cov_gen = c.cov_gen, sl.map_res = v.prm.resolution, sl.map_mode = v.prm.voxel_mode;
+        v.builds++;
+      },
+      &flag);
+  if (flag) {  // a point that is not finite trips the covariance kernels too: the message about the point is the useful one
+    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+    if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
+  }
+  return rc;
+}
+
+// one slot's map for the getters: sorted, covariances computed, built
+int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
+  Engine& e = b->eng;
+  if (!b->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_batch_set_vgicp)");
+  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.pool_leave());
+  APD_TRY(e.finish_align());
+  APD_TRY(e.compute_covariances({cloud}));
+  APD_TRY(e.upload_desc());
+  return vgb_build_maps(b, {cloud});
+}
+
 // V10 / V12: the optimiser loop of every pair on the device; returns with the device records complete
 int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   Engine& e = b->eng;
@@ -1062,7 +1107,7 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
   APD_TRY(e.setup_pairs(pairs, n_pairs, true));  // clouds sorted, covariances there, d_state / d_results / d_guess
   e.results_on_host = false;
-  const int np = e.npairs, noff = v.n_offsets();
+  const int np = e.npairs, noff = n_offsets(v.prm.neighbor_search);
   std::vector<int> targets;
   for (int i = 0; i < np; i++) targets.push_back(e.h_pairs[i].tgt);
   APD_TRY(vgb_build_maps(b, targets));
@@ -1070,24 +1115,22 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   std::vector<VgbPair> tab(np);
   for (int i = 0; i < np; i++) {
     const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
-    const VgbState::Slot& st = v.slots[t];
     tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0,
-                     VgbMap{st.vkeys.as<unsigned long long>(), st.vcount.as<int>(), st.vmean.as<double>(), st.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)t + 1}};
+                     v.slots[t].buf.map(v.scal.as<int>() + 4 * (size_t)t + 1)};
   }
   APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
   const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
   const size_t corr_stride = (size_t)e.nmax_src * noff;
-  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
-  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
-  APD_TRY(vgb_prepare_ticks(b));
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)np * corr_stride * 4, (size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(device_loop_prepare(b));
   const Consts cst = e.consts();
   PairState* st = e.d_state.as<PairState>();
   ResultRec* recs = e.d_results.as<ResultRec>();
-  return vgb_run_ticks(b, [&]() {
+  int* done = b->loop.done.as<int>();
+  return device_loop_run(b, [&]() {
     hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution,
                        (int)v.prm.neighbor_search, noff, v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, v.done.as<int>());
+    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, done);
   });
 }
 
@@ -1103,92 +1146,32 @@ bool ndb_map_current(const apdgicp_batch* b, int slot) {
   return sl.built && sl.pts_gen == b->eng.clouds[slot].pts_gen && sl.res == b->nd.prm.resolution;
 }
 
-// N10: the maps of the listed slots (sorted) that are not current, as vgb_build_maps builds its own: enqueued one after the other with no wait
-// in between, then ONE copy of every slot's {first bad point, voxel count} and one wait for all of them.  No covariances, no inverse permutation.
+// N10: the maps of the listed slots (sorted) that are not current.  No covariances (so no error flag to read), no inverse permutation.
 int ndb_build_maps(apdgicp_batch* b, const std::vector<int>& slots) {
   Engine& e = b->eng;
   NdbState& v = b->nd;
-  VgbState& w = b->vg;  // (the scratch of a build and the pinned words)
   APD_TRY(ndb_ensure_slots(b));
-  std::vector<int> todo;
-  int nmax = 0;
-  for (int t : slots)
-    if (!ndb_map_current(b, t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t), nmax = std::max(nmax, e.clouds[t].n);
-  if (todo.empty()) return 0;
-  const int lo = *std::min_element(todo.begin(), todo.end()), hi = *std::max_element(todo.begin(), todo.end());
-  APD_TRY(vgb_ensure_words(b, 4 + 4 * (size_t)(hi - lo + 1)));
-  {
-    const int nblk = (nmax + MAP_RS_TILE - 1) / MAP_RS_TILE;
-    const int64_t entries = 256ll * nblk;
-    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-    const size_t nhb = (size_t)(nmax + MAP_BLK - 1) / MAP_BLK;
-    bool grows = (size_t)nmax * 8 > w.keys_a.cap || (size_t)entries * 4 > w.hist.cap || (size_t)nsb * 4 > w.rs_bsum.cap || nhb * 4 > w.bsum.cap;
-    for (int t : todo) grows |= (size_t)e.clouds[t].n * 48 > v.slots[t].vcov.cap;
-    if (grows) APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced; never on a reused handle with clouds of the same sizes)
-    APD_TRY(w.keys_a.ensure((size_t)nmax * 8));
-    APD_TRY(w.keys_b.ensure((size_t)nmax * 8));
-    APD_TRY(w.idx_a.ensure((size_t)nmax * 4));
-    APD_TRY(w.idx_b.ensure((size_t)nmax * 4));
-    APD_TRY(w.hist.ensure((size_t)entries * 4));
-    APD_TRY(w.rs_bsum.ensure((size_t)nsb * 4));
-    APD_TRY(w.bsum.ensure(nhb * 4));
-  }
-  for (int t : todo) {
-    Engine::Cloud& c = e.clouds[t];
-    NdbState::Slot& sl = v.slots[t];
-    const int n = c.n;
-    sl.built = false;
-    APD_TRY(sl.vkeys.ensure((size_t)n * 8));
-    APD_TRY(sl.vcount.ensure((size_t)n * 4));
-    APD_TRY(sl.vmean.ensure((size_t)n * 24));
-    APD_TRY(sl.vraw.ensure((size_t)n * 48));
-    APD_TRY(sl.vcov.ensure((size_t)n * 48));
-    const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-    const int64_t entries = 256ll * nblk;
-    const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-    const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
-    int* scal = v.scal.as<int>() + 4 * (size_t)t;
-    APD_HIP(hipMemsetAsync(scal, 0x7f, 16, e.stream));
-    unsigned long long *ks = w.keys_a.as<unsigned long long>(), *kd = w.keys_b.as<unsigned long long>();
-    int *is = w.idx_a.as<int>(), *id = w.idx_b.as<int>();
-    hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, e.stream, c.opts.as<float4>(), n, v.prm.resolution, ks, is, scal);
-    for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
-      hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, n, 8 * p, nblk, w.hist.as<int>());
-      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, e.stream, w.hist.as<int>(), (int)entries, w.rs_bsum.as<int>());
-      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, w.rs_bsum.as<int>(), nsb, scal + 2);
-      hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, e.stream, ks, is, kd, id, n, 8 * p, nblk, w.hist.as<int>(), w.rs_bsum.as<int>());
-      std::swap(ks, kd), std::swap(is, id);
-    }
-    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, n, w.bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, w.bsum.as<int>(), (int)nhb, scal + 1);
-    // (a slot with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
-    hipLaunchKernelGGL(k_ndt_voxels, dim3(nhb), dim3(MAP_BLK), 0, e.stream, ks, is, n, w.bsum.as<int>(), c.opts.as<float4>(), sl.vkeys.as<unsigned long long>(),
-                       sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vraw.as<double>(), sl.vcov.as<double>(), n);
-    APD_HIP(hipGetLastError());
-  }
-  int* hw = w.h_words + 4;
-  APD_HIP(hipMemcpyAsync(hw, v.scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  int rc = 0;
-  for (int t : todo) {
-    const int* x = hw + 4 * (size_t)(t - lo);
-    NdbState::Slot& sl = v.slots[t];
-    const Engine::Cloud& c = e.clouds[t];
-    if (x[0] != kVgBadNone) {
-      if (rc == 0)
-        rc = fail(APDGICP_ERR_INVALID_ARG, "NDT: point " + std::to_string(x[0]) + " of cloud slot " + std::to_string(t) +
-                                               " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(v.prm.resolution) + ")");
-      continue;
-    }
-    if (x[1] < 1 || x[1] > c.n) {
-      if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, "NDT: inconsistent voxel count");
-      continue;
-    }
-    sl.nv = x[1];
-    sl.built = true, sl.pts_gen = c.pts_gen, sl.res = v.prm.resolution;
-    v.builds++;
-  }
-  return rc;
+  return batch_build_maps(
+      b, slots, "NDT: ", v.prm.resolution, v.scal, [&](int t) { return ndb_map_current(b, t); }, [&](int t) { return (size_t)e.clouds[t].n * 48 > v.slots[t].buf.vcov.cap; },
+      [&](int t) -> int {
+        Engine::Cloud& c = e.clouds[t];
+        NdbState::Slot& sl = v.slots[t];
+        const int n = c.n;
+        sl.built = false;
+        APD_TRY(sl.buf.ensure((size_t)n, true));
+        VoxSorted s;
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        hipLaunchKernelGGL(k_ndt_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), c.opts.as<float4>(), sl.buf.vkeys.as<unsigned long long>(),
+                           sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vraw.as<double>(), sl.buf.vcov.as<double>(), n);
+        APD_HIP(hipGetLastError());
+        return 0;
+      },
+      [&](int t, int nv) {
+        NdbState::Slot& sl = v.slots[t];
+        sl.nv = nv;
+        sl.built = true, sl.pts_gen = e.clouds[t].pts_gen, sl.res = v.prm.resolution;
+        v.builds++;
+      });
 }
 
 // one slot's map for the getters: sorted, built
@@ -1210,7 +1193,7 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
   APD_TRY(e.setup_pairs(pairs, n_pairs, true, /*pipeline_cov=*/false, /*need_cov=*/false));  // N11: clouds sorted, d_state / d_results / d_guess
   e.results_on_host = false;
-  const int np = e.npairs, noff = v.n_offsets();
+  const int np = e.npairs, noff = n_offsets(v.prm.neighbor_search);
   const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
   std::vector<int> slots;
   for (int i = 0; i < np; i++) {
@@ -1218,10 +1201,7 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
     if (d2d) slots.push_back(e.h_pairs[i].src);
   }
   APD_TRY(ndb_build_maps(b, slots));
-  auto map_of = [&](int slot) {
-    const NdbState::Slot& sl = v.slots[slot];
-    return VgbMap{sl.vkeys.as<unsigned long long>(), sl.vcount.as<int>(), sl.vmean.as<double>(), sl.vcov.as<double>(), v.scal.as<int>() + 4 * (size_t)slot + 1};
-  };
+  auto map_of = [&](int slot) { return v.slots[slot].buf.map(v.scal.as<int>() + 4 * (size_t)slot + 1); };
   std::vector<NdbPair> tab(np);
   for (int i = 0; i < np; i++) {
     const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
@@ -1231,15 +1211,14 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   // (a pair's rows are at most its source's points: the grid and the strides are sized by the points, the blocks beyond a pair's rows return)
   const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
   const size_t corr_stride = (size_t)e.nmax_src * noff;
-  if ((size_t)np * corr_stride * 4 > v.corr.cap || (size_t)np * nblk_max * VG_RED * 8 > v.part.cap) APD_HIP(hipStreamSynchronize(e.stream));
-  APD_TRY(v.corr.ensure((size_t)np * corr_stride * 4));
-  APD_TRY(v.part.ensure((size_t)np * nblk_max * VG_RED * 8));
-  APD_TRY(vgb_prepare_ticks(b));
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)np * corr_stride * 4, (size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(device_loop_prepare(b));
   const Consts cst = e.consts();
   PairState* st = e.d_state.as<PairState>();
   ResultRec* recs = e.d_results.as<ResultRec>();
+  int* done = b->loop.done.as<int>();
   const dim3 grid((unsigned)nblk_max, (unsigned)np);
-  return vgb_run_ticks(b, [&]() {
+  return device_loop_run(b, [&]() {
     if (d2d)
       hipLaunchKernelGGL(k_ndb_points<true>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
                          v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
@@ -1247,12 +1226,31 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
       hipLaunchKernelGGL(k_ndb_points<false>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
                          v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
     hipLaunchKernelGGL(k_ndb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<NdbPair>(), st, cst, v.part.as<double>(), nblk_max, d2d ? 1 : 0, recs,
-                       b->vg.done.as<int>());
+                       done);
   });
 }
 
 const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 const char* const kNdbNoPipeline = "NDT on a batch handle (apdgicp_batch_set_ndt) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+
+// what the single and the batch setters refuse (null: nothing to check -- the mode is being switched off)
+int check_vgicp_params(const apdgicp_vgicp_params* p) {
+  if (!p) return 0;
+  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: the resolution must be finite and positive");
+  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown neighbour search method");
+  if (p->voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
+  if (p->voxel_mode != APDGICP_VGICP_ADDITIVE && p->voxel_mode != APDGICP_VGICP_ADDITIVE_WEIGHTED) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown accumulation mode");
+  return 0;
+}
+
+int check_ndt_params(const apdgicp_ndt_params* p) {
+  if (!p) return 0;
+  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "NDT: the resolution must be finite and positive");
+  if (p->distance_mode != APDGICP_NDT_P2D && p->distance_mode != APDGICP_NDT_D2D) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown distance mode");
+  if (p->neighbor_search == APDGICP_NDT_DIRECT_RADIUS) return fail(APDGICP_ERR_UNSUPPORTED, "NDT: DIRECT_RADIUS neighbour search is not offered");
+  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown neighbour search method");
+  return 0;
+}
 
 // the pooled / deferred aligns of the APD path finish as what they were enqueued as; the chunk length of the device loop is read once
 int batch_enter_device_loop_mode(apdgicp_batch* b) {
@@ -1260,7 +1258,7 @@ int batch_enter_device_loop_mode(apdgicp_batch* b) {
     APD_TRY(b->eng.pool_leave());
     APD_TRY(b->eng.finish_align());
   }
-  if (!b->vg.chunk) b->vg.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
+  if (!b->loop.chunk) b->loop.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
   return 0;
 }
 
@@ -1607,10 +1605,7 @@ int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
     v.on = false;
     return 0;
   }
-  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: the resolution must be finite and positive");
-  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown neighbour search method");
-  if (p->voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
-  if (p->voxel_mode != APDGICP_VGICP_ADDITIVE && p->voxel_mode != APDGICP_VGICP_ADDITIVE_WEIGHTED) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown accumulation mode");
+  APD_TRY(check_vgicp_params(p));
   if (!v.on || p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
   if (!v.on) h->have_corr = false;
   v.prm = *p;
@@ -1641,27 +1636,7 @@ int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coord
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
     if (!h->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
     APD_TRY(vg_build_map(h));
-    VgState& v = h->vg;
-    Engine& e = h->eng;
-    const int64_t nv = v.n_vox;
-    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
-    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
-    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
-    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), v.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
-    if (counts) APD_HIP(hipMemcpyAsync(counts, v.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
-    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, v.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
-    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), v.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    for (int64_t i = 0; i < nv && coords_n3; i++) {
-      const unsigned long long k = keys[i];
-      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
-    }
-    for (int64_t i = 0; i < nv && covs_n9; i++) {
-      const double* c = &c6[6 * i];
-      double* o = covs_n9 + 9 * i;
-      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
-    }
-    return 0;
+    return read_voxels(h->eng.stream, h->vg.buf, h->vg.n_vox, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
   });
 }
 
@@ -1701,10 +1676,7 @@ int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
     v.on = false;
     return 0;
   }
-  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "NDT: the resolution must be finite and positive");
-  if (p->distance_mode != APDGICP_NDT_P2D && p->distance_mode != APDGICP_NDT_D2D) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown distance mode");
-  if (p->neighbor_search == APDGICP_NDT_DIRECT_RADIUS) return fail(APDGICP_ERR_UNSUPPORTED, "NDT: DIRECT_RADIUS neighbour search is not offered");
-  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown neighbour search method");
+  APD_TRY(check_ndt_params(p));
   if (!v.on || p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
   if (!v.on) {
     h->have_corr = false;
@@ -1738,28 +1710,8 @@ int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32
     if (!h || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
     if (!h->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
     APD_TRY(nd_build_map(h, which));
-    NdState::Map& m = h->nd.maps[which];
-    Engine& e = h->eng;
-    const int64_t nv = m.nv;
-    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
-    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
-    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
-    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), m.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
-    if (counts) APD_HIP(hipMemcpyAsync(counts, m.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
-    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, m.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
-    if (raw_covs_n6) APD_HIP(hipMemcpyAsync(raw_covs_n6, m.vraw.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), m.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    for (int64_t i = 0; i < nv && coords_n3; i++) {
-      const unsigned long long k = keys[i];
-      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
-    }
-    for (int64_t i = 0; i < nv && covs_n9; i++) {
-      const double* c = &c6[6 * i];
-      double* o = covs_n9 + 9 * i;
-      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
-    }
-    return 0;
+    const NdState::Map& m = h->nd.maps[which];
+    return read_voxels(h->eng.stream, m.buf, m.nv, capacity, coords_n3, counts, means_n3, raw_covs_n6, covs_n9);
   });
 }
 
@@ -1786,10 +1738,7 @@ int apdgicp_ndt_build_count(apdgicp_handle* h, int64_t* n_builds) {
 int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
   return guarded([&]() -> int {
     // (the parameters first: what is wrong with them does not depend on the handle)
-    if (p && (!(p->resolution > 0.0) || !std::isfinite(p->resolution))) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: the resolution must be finite and positive");
-    if (p && (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27)) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown neighbour search method");
-    if (p && p->voxel_mode == APDGICP_VGICP_MULTIPLICATIVE) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP: MULTIPLICATIVE accumulation is not offered");
-    if (p && p->voxel_mode != APDGICP_VGICP_ADDITIVE && p->voxel_mode != APDGICP_VGICP_ADDITIVE_WEIGHTED) return fail(APDGICP_ERR_INVALID_ARG, "voxelized GICP: unknown accumulation mode");
+    APD_TRY(check_vgicp_params(p));
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     VgbState& v = b->vg;
     if (!p) {
@@ -1825,26 +1774,7 @@ int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capa
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(vgb_slot_map(b, cloud));
     const VgbState::Slot& sl = b->vg.slots[cloud];
-    Engine& e = b->eng;
-    const int64_t nv = sl.nv;
-    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
-    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
-    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
-    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), sl.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
-    if (counts) APD_HIP(hipMemcpyAsync(counts, sl.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
-    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, sl.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
-    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), sl.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    for (int64_t i = 0; i < nv && coords_n3; i++) {
-      const unsigned long long k = keys[i];
-      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
-    }
-    for (int64_t i = 0; i < nv && covs_n9; i++) {
-      const double* c = &c6[6 * i];
-      double* o = covs_n9 + 9 * i;
-      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
-    }
-    return 0;
+    return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
   });
 }
 
@@ -1857,10 +1787,7 @@ int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds) {
 int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
   return guarded([&]() -> int {
     // (the parameters first: what is wrong with them does not depend on the handle)
-    if (p && (!(p->resolution > 0.0) || !std::isfinite(p->resolution))) return fail(APDGICP_ERR_INVALID_ARG, "NDT: the resolution must be finite and positive");
-    if (p && p->distance_mode != APDGICP_NDT_P2D && p->distance_mode != APDGICP_NDT_D2D) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown distance mode");
-    if (p && p->neighbor_search == APDGICP_NDT_DIRECT_RADIUS) return fail(APDGICP_ERR_UNSUPPORTED, "NDT: DIRECT_RADIUS neighbour search is not offered");
-    if (p && (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_DIRECT27)) return fail(APDGICP_ERR_INVALID_ARG, "NDT: unknown neighbour search method");
+    APD_TRY(check_ndt_params(p));
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     NdbState& v = b->nd;
     if (!p) {
@@ -1897,27 +1824,7 @@ int apdgicp_batch_ndt_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capaci
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(ndb_slot_map(b, cloud));
     const NdbState::Slot& sl = b->nd.slots[cloud];
-    Engine& e = b->eng;
-    const int64_t nv = sl.nv;
-    if (capacity < nv) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the voxel count");
-    std::vector<unsigned long long> keys(coords_n3 ? nv : 0);
-    std::vector<double> c6(covs_n9 ? 6 * nv : 0);
-    if (coords_n3) APD_HIP(hipMemcpyAsync(keys.data(), sl.vkeys.p, nv * 8, hipMemcpyDeviceToHost, e.stream));
-    if (counts) APD_HIP(hipMemcpyAsync(counts, sl.vcount.p, nv * 4, hipMemcpyDeviceToHost, e.stream));
-    if (means_n3) APD_HIP(hipMemcpyAsync(means_n3, sl.vmean.p, nv * 24, hipMemcpyDeviceToHost, e.stream));
-    if (raw_covs_n6) APD_HIP(hipMemcpyAsync(raw_covs_n6, sl.vraw.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    if (covs_n9) APD_HIP(hipMemcpyAsync(c6.data(), sl.vcov.p, nv * 48, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    for (int64_t i = 0; i < nv && coords_n3; i++) {
-      const unsigned long long k = keys[i];
-      coords_n3[3 * i] = (int32_t)((k >> 42) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 1] = (int32_t)((k >> 21) & 0x1fffff) - VG_LIM, coords_n3[3 * i + 2] = (int32_t)(k & 0x1fffff) - VG_LIM;
-    }
-    for (int64_t i = 0; i < nv && covs_n9; i++) {
-      const double* c = &c6[6 * i];
-      double* o = covs_n9 + 9 * i;
-      o[0] = c[0], o[1] = c[1], o[2] = c[2], o[3] = c[1], o[4] = c[3], o[5] = c[4], o[6] = c[2], o[7] = c[4], o[8] = c[5];
-    }
-    return 0;
+    return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, raw_covs_n6, covs_n9);
   });
 }
 
@@ -2242,8 +2149,7 @@ int apdgicp_batch_clear(apdgicp_batch* b) {
   for (auto& c : b->eng.clouds) c.release_all();
   b->eng.clouds.clear();
   b->eng.clouds_written();
-  b->vg.release();  // (V8: every slot's map and inverse permutation go with the clouds)
-  b->nd.release();  // (N10: likewise)
+  b->release_voxel_modes();  // (V8 / N10: every slot's map and inverse permutation go with the clouds)
   return 0;
 }
 

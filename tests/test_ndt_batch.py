@@ -517,6 +517,66 @@ def test_cache_rules_and_the_apd_path_is_left_alone(reg, nd, scene):
     assert b.build_count() == 13
 
 
+@gpu
+def test_aligns_across_mode_switches_on_one_handle(reg, nd, scene):
+    """One handle through voxelized GICP, NDT, a cloud one point past a radix tile (the shared build scratch grows from one block to two
+    between the modes), NDT, voxelized GICP and APD-GICP: every record is byte for byte the record of a fresh handle that only ever ran
+    that mode on the same pairs (V11 / N14: a record is a pure function of its pair), and a mode switch rebuilds no current map."""
+    vg = importlib.import_module("riv-slam_amd.vgicp")
+    src, tgt, _, guess = scene.make_pair(4099, 4099, scene.pair_seed(9, 0), "odometry")
+    clouds = [src[:517], src[:1031], tgt]
+    near = scene.make_transform(np.array([0.04, -0.03, 0.01]), 0.003, 0.0, 0.0).astype(np.float32)   # prefixes of one cloud: truth is identity
+    pairs = [(0, 1), (1, 0), (1, 2)]
+    guesses = [near, np.linalg.inv(near.astype(np.float64)).astype(np.float32), guess]
+    kw = dict(optimizer=LM)
+
+    fresh_vg = vg.BatchVGICP(reg.default_params(**kw))
+    fresh_vg.setResolution(2.0)
+    fresh_vg.set_clouds(0, clouds)
+    want_vg = fresh_vg.align(pairs, guesses)
+    fresh_nd = _batch(reg, nd, N.D2D, N.DIRECT7, 2.0, **kw)
+    fresh_nd.set_clouds(0, clouds)
+    want_nd = fresh_nd.align(pairs, guesses)
+    fresh_apd = reg.BatchAPDGICP(reg.default_params(**kw))
+    fresh_apd.set_clouds(0, clouds)
+    want_apd = fresh_apd.align(pairs, guesses)
+    assert int(want_vg[2]["n_linearize"]) >= 2 and int(want_nd[2]["n_linearize"]) >= 2 and int(want_apd[2]["n_linearize"]) >= 2
+
+    b = _batch(reg, nd, N.D2D, N.DIRECT7, 2.0, **kw)
+    vp = vg.default_vgicp_params()
+    vp.resolution = 2.0
+
+    def vgicp_on():
+        assert b.L.apdgicp_batch_set_vgicp(b.b, ctypes.byref(vp)) == 0 and not b.enabled()
+
+    def builds():
+        n = ctypes.c_int64()
+        assert b.L.apdgicp_batch_vgicp_build_count(b.b, ctypes.byref(n)) == 0
+        return n.value, b.build_count()
+
+    def same(got, want):
+        assert len(got) == len(want)
+        for i in range(len(got)):
+            assert got[i].tobytes() == want[i].tobytes(), i
+
+    b.set_clouds(0, clouds[:2])
+    vgicp_on()
+    same(b.align(pairs[:2], guesses[:2]), want_vg[:2])
+    assert builds() == (2, 0)                                    # voxelized GICP maps the targets: slots 1 and 0
+    b.enable()
+    same(b.align(pairs[:2], guesses[:2]), want_nd[:2])
+    assert builds() == (2, 2)                                    # D2D maps sources and targets: slots 0 and 1
+    assert b.add_cloud(clouds[2]) == 2
+    same(b.align(pairs, guesses), want_nd)
+    assert builds() == (2, 3)                                    # only the new slot
+    vgicp_on()
+    same(b.align(pairs, guesses), want_vg)
+    assert builds() == (3, 3)                                    # only the new target; slots 0 and 1 kept their maps through the NDT aligns
+    assert b.L.apdgicp_batch_set_vgicp(b.b, None) == 0 and not b.enabled()
+    same(b.align(pairs, guesses), want_apd)
+    assert builds() == (3, 3)
+
+
 # ---------------------------------------------------------------------- 10. unsupported calls
 @gpu
 def test_enqueue_is_unsupported_with_the_mode_on(reg, nd, scene):
