@@ -708,7 +708,8 @@ int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kep
  *      returns true on every path (E:302): success = 1 whenever the inlier list is not empty; sigma_in_bounds says whether
  *      diag C >= 0 and sigma < max_sigma_* held (if diag C < 0, sigma holds diag C as in the reference).
  *   use_ransac = 0 (E:138-142): every valid row is an inlier, step 6 alone.
- * Not part of this object: deskewing (:792), bdcSvd, the DBSCAN / radius filter on the outlier cloud (:766-774). */
+ * Not part of this object: deskewing (:792), bdcSvd.  The radius filter on the outlier cloud (:766-774) is the scan filter with
+ * APDGICP_OUTLIER_RADIUS, its clustering into moving objects apdgicp_dbscan_* below; both take the device pointers of _outliers. */
 typedef struct {
   float min_dist;                             /* EH:32 ; default 0.1 */
   float max_dist;                             /* EH:33 ; default 400 */
@@ -1009,6 +1010,86 @@ int apdgicp_scan_context_detect_batch(apdgicp_scan_context* h, int32_t n_queries
 /* reads back descriptors first .. first + count - 1 (SC:249-252 getConstRefRecentSCD and the keys): desc count x R x S floats, ring_keys
  * count x R floats, sector_keys and col_norms count x S doubles; any destination may be NULL */
 int apdgicp_scan_context_descriptors(apdgicp_scan_context* h, int32_t first, int32_t count, float* desc, float* ring_keys, double* sector_keys, double* col_norms);
+
+/* ------------------------------------------------------------------ DBSCAN clustering (moving objects from the ego-velocity outliers)
+ * DBSCANSimpleCluster<PointT>::extract ("DB:" = radar_graph_slam/include/dbscan/DBSCAN_simple.h): the clustering the
+ * reference ships for the points the ego-velocity estimate rejects.  DBSCAN_precomp.h stores the same distances and gives the same
+ * clusters; DBSCAN_kdtree.h searches through PCL's kd-tree, whose arithmetic is not in the tree: not offered.  The sequential loop of
+ * DB:27-90 is equivalent to the following properties, quirks included (tests/dbscan_np.py is the literal loop and checks exactly that):
+ *   D1. DB:118-142, adjacency.  Points i != j are adjacent iff  dx*dx + dy*dy + dz*dz <= eps*eps  with dx = (double)(x_j - x_i) -- an fp32
+ *       subtraction, then widened --, products and sum in fp64 left to right, eps*eps in fp64.  The relation is symmetric.  A point with a
+ *       non-finite coordinate is adjacent to nothing (every comparison with it is false).  The device prunes with an integer grid of cell
+ *       side h = eps * (1 + 2^-20): the fp32 difference is within a factor 1 + 2^-24 of the true one and the fp64 quotient x / h within
+ *       2^-32 inside the key range, so an accepted pair's quotients are less than 1 apart and its cells at most 1 apart on every axis; the
+ *       27 cells around a point hold every pair D1 accepts, and D1's arithmetic decides.  A finite point more than 2^20 cells from the
+ *       origin on an axis fails the run with APDGICP_ERR_UNSUPPORTED and a message naming the first such point; the handle stays usable.
+ *   D2. DB:124, 141, core.  cnt_i = 1 + the adjacent points: the point itself counts (whatever the comment at DB:112 says).  Core iff
+ *       cnt_i >= min_pts.
+ *   D3. DB:32-44, 61-70, clusters.  The outer loop opens a cluster at the first unprocessed core point in index order and the BFS closes
+ *       it before the loop goes on: a cluster is a connected component of core points under D1, its SEED is its smallest core index,
+ *       clusters are created in ascending seed order.  (Device: lock-free union-find, the larger root hooked under the smaller with
+ *       32-bit integer atomics; the root of a component is its seed whatever order the atomics land in.)
+ *   D4. DB:61-70, border points.  A non-core point adjacent to at least one core point joins the first-created cluster it touches: the
+ *       smallest seed among the components of its adjacent cores.  That is its primary label -- also when D6 discards that cluster.  A core
+ *       point's primary label is its own seed.  Every other point is noise (-1).
+ *   D5. DB:46-51, the seed quirk.  The seed's own neighbours are pushed without a look at their state: a border point that already belongs
+ *       to an earlier cluster and is adjacent to the SEED POINT of a later one is also a member of the later one -- in two member lists,
+ *       primary label unchanged.  Borders adjacent only to non-seed cores of the later cluster are not.
+ *   D6. DB:75, size filter.  size = members of D3 + D4 + D5 (the queue holds no duplicates: DB:82-83 change nothing).  Kept iff
+ *       min_cluster_size <= size <= max_cluster_size; the points of a discarded cluster get final label -1.
+ *   D7. DB:82, 89, order.  Member lists in ascending index; clusters by size, largest first.  std::sort leaves equal sizes unspecified:
+ *       here equal sizes go by ascending seed (a deviation).
+ * The table row of a kept cluster is taken over its member list (D5's guests included): the centroid is an fp64 sum of the widened fp32
+ * coordinates in a fixed order (lane t of 256 adds members t, t + 256, ... in list order, then a fixed tree) over the size -- the same bits on
+ * every run, the last bits may differ from a sequential sum --, min / max are fp32, the Doppler columns likewise when a Doppler lane is given
+ * (else 0).  Integer atomics only; no floating-point atomics.
+ * One run is 17 + 4 * (8 + p1 + p2) launches (the three radix sorts: 8 passes over the cell keys, p1 = ceil((2 b + 1) / 8) over the rank keys
+ * with n <= 2^b, p2 = ceil(bits of K / 8) over the member pairs; 6 fewer and no p2 when K = 0) and ONE wait, for {first refused point, K, CSR length}; a host cloud is staged by a copy on the object's stream. */
+typedef struct {
+  double eps;                 /* DB:111 eps_ (setClusterTolerance) ; default 0: a run is refused until it is finite and > 0 */
+  int32_t min_pts;            /* DB:112 minPts_ (setCorePointMinPts) ; default 1 ; >= 1 */
+  int32_t min_cluster_size;   /* DB:113 ; default 1 ; >= 1 */
+  int32_t max_cluster_size;   /* DB:114 ; default INT_MAX */
+  int32_t reserved;           /* 0 */
+} apdgicp_dbscan_params;
+typedef struct {
+  double centroid[3];
+  double doppler_mean;
+  float min[3], max[3];       /* axis-aligned extent */
+  float doppler_min, doppler_max;
+  int32_t seed;               /* D3 */
+  int32_t size;               /* D6 */
+  int32_t n_core;             /* core members */
+  int32_t reserved;
+} apdgicp_dbscan_cluster;
+typedef struct apdgicp_dbscan apdgicp_dbscan;
+void apdgicp_dbscan_default_params(apdgicp_dbscan_params* p);   /* DB:111-114 */
+/* The parameters are checked before the device (eps NaN, infinite or negative, min_pts / min_cluster_size < 1, max_cluster_size < 1:
+ * APDGICP_ERR_INVALID_ARG); eps = 0 is accepted here and by _set_params -- the reference's default -- and refused by _run.  NULL: the defaults. */
+int apdgicp_dbscan_create(const apdgicp_dbscan_params* p, int device, void* stream, apdgicp_dbscan** out);
+int apdgicp_dbscan_destroy(apdgicp_dbscan* h);
+int apdgicp_dbscan_set_params(apdgicp_dbscan* h, const apdgicp_dbscan_params* p);
+/* extract() of one cloud: xyz is the address of the first x, points stride_bytes apart (>= 12, a multiple of 4); doppler: one float per
+ * point doppler_stride_bytes apart, or NULL; both in device memory (on_device = 1) or both on the host.  *n_clusters = kept clusters K.
+ * n = 0: K = 0, status 0.  More than 2^24 points: APDGICP_ERR_UNSUPPORTED. */
+int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t stride_bytes, const float* doppler, int64_t doppler_stride_bytes, int on_device,
+                       int32_t* n_clusters);
+/* device memory, valid until the next run: one int32 per point, the rank (D7) of its kept primary cluster or -1 */
+int apdgicp_dbscan_labels(apdgicp_dbscan* h, const int32_t** device_labels, int64_t* n);
+int apdgicp_dbscan_copy_labels(apdgicp_dbscan* h, int32_t* labels, int64_t capacity);                       /* the same, to HOST memory */
+int apdgicp_dbscan_clusters(apdgicp_dbscan* h, apdgicp_dbscan_cluster* table, int64_t capacity);            /* K rows in rank order, HOST memory */
+/* the member lists as CSR, HOST memory: offsets [K + 1], indices [offsets[K]] (cluster r: indices[offsets[r] .. offsets[r + 1]), ascending;
+ * a point of D5 is listed by both clusters); *n_indices = offsets[K].  Any destination may be NULL; too small: APDGICP_ERR_INVALID_ARG. */
+int apdgicp_dbscan_members(apdgicp_dbscan* h, int32_t* offsets, int64_t offsets_capacity, int32_t* indices, int64_t indices_capacity, int64_t* n_indices);
+/* before the size filter, HOST memory, capacity >= n entries each, any may be NULL (for tests): cnt (D2), core 0 / 1, root (a core point's
+ * seed, else -1), primary (D4: the seed of the primary cluster, -1 noise) */
+int apdgicp_dbscan_debug(apdgicp_dbscan* h, int32_t* cnt, uint8_t* core, int32_t* root, int32_t* primary, int64_t capacity);
+/* For the measurement scripts.  _set_profiling(1): a run records events at its phase boundaries and waits a second time, at its end.
+ * _stats: kernel launches and host waits of the last run as counted by the host code that enqueued them, and (profiling on, else zeros) the
+ * device time between the boundaries in ms: {cells + sort + sorted copy, count, union + flatten, border, everything behind it -- rank sort,
+ * the wait, member lists, labels, table}.  Any destination may be NULL. */
+int apdgicp_dbscan_set_profiling(apdgicp_dbscan* h, int enable);
+int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, double phase_ms[5]);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #include "apd_vgicp_batch.hpp"
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
+#include "apd_dbscan.hpp"
 
 using namespace apd;
 
@@ -403,6 +404,36 @@ struct apdgicp_scan_context {
     if (stream) (void)hipStreamSynchronize(stream);
     if (h_out) (void)hipHostFree(h_out);
     for (DevBuf* b : {&desc, &ring_key, &sector_key, &col_norm, &stage, &hi1, &lo1, &inv1, &rec, &hi2, &lo2, &inv2, &out, &qtab.dev, &cand.dev}) b->release();
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_dbscan {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  apdgicp_dbscan_params prm;
+  VoxSortScratch sort;  // the three radix sorts of a run, one after the other
+  DevBuf stage, stage_dop, pts, dop, gkeys, spts, cnt, core, score, parent, root, seed, nextra, size, ncore, rank_of, cseed, csize, tsum, mcount, msum, offsets, members,
+      labels, table, scal;
+  int* h_scal = nullptr;  // pinned mirror of scal
+  int64_t n_last = 0, K_last = 0, M_last = 0;
+  bool ran = false;
+  int64_t launches = 0;   // of the last run (tests/measure/bench_dbscan.py)
+  bool profiling = false; // apdgicp_dbscan_set_profiling: events at the phase boundaries, one more wait at the end of a run
+  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double phase_ms[5] = {0, 0, 0, 0, 0};  // sort (cells, sort, sorted copy) / count / union + flatten / border / output
+  std::vector<DevBuf*> bufs() {
+    return {&stage, &stage_dop, &pts, &dop, &gkeys, &spts, &cnt, &core, &score, &parent, &root, &seed, &nextra, &size, &ncore, &rank_of, &cseed, &csize, &tsum, &mcount, &msum,
+            &offsets, &members, &labels, &table, &scal};
+  }
+  ~apdgicp_dbscan() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    if (h_scal) (void)hipHostFree(h_scal);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    sort.release();
+    for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -3946,6 +3977,305 @@ int apdgicp_scan_context_descriptors(apdgicp_scan_context* h, int32_t first, int
     APD_HIP(hipStreamSynchronize(h->stream));
     return 0;
   });
+}
+
+// ------------------------------------------------------------------ DBSCAN clustering (apd_dbscan.hpp)
+static_assert(sizeof(apdgicp_dbscan_cluster) == 80 && sizeof(DbCluster) == sizeof(apdgicp_dbscan_cluster) && offsetof(DbCluster, seed) == offsetof(apdgicp_dbscan_cluster, seed),
+              "DbCluster is the table row");
+static_assert(sizeof(apdgicp_dbscan_params) == 24, "apdgicp_dbscan_params layout");
+
+void apdgicp_dbscan_default_params(apdgicp_dbscan_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->eps = 0.0, p->min_pts = 1, p->min_cluster_size = 1, p->max_cluster_size = std::numeric_limits<int32_t>::max();  // DB:111-114
+}
+
+static int dbscan_check_params(const apdgicp_dbscan_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
+  if (!(p->eps >= 0.0) || !std::isfinite(p->eps)) return fail(APDGICP_ERR_INVALID_ARG, "eps must be finite and >= 0 (and > 0 to run)");
+  if (p->min_pts < 1) return fail(APDGICP_ERR_INVALID_ARG, "min_pts must be >= 1");
+  if (p->min_cluster_size < 1 || p->max_cluster_size < 1) return fail(APDGICP_ERR_INVALID_ARG, "min_cluster_size and max_cluster_size must be >= 1");
+  return 0;
+}
+
+int apdgicp_dbscan_create(const apdgicp_dbscan_params* p, int device, void* stream, apdgicp_dbscan** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_dbscan_params dflt;
+    apdgicp_dbscan_default_params(&dflt);
+    if (!p) p = &dflt;
+    APD_TRY(dbscan_check_params(p));
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_dbscan> h(new apdgicp_dbscan);
+    h->device = device, h->prm = *p;
+    if (stream) {
+      h->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+      h->own_stream = true;
+    }
+    APD_HIP(hipHostMalloc((void**)&h->h_scal, DB_WORDS * sizeof(int), hipHostMallocDefault));
+    memset(h->h_scal, 0, DB_WORDS * sizeof(int));
+    APD_TRY(h->scal.ensure(DB_WORDS * sizeof(int)));
+    *out = h.release();
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_destroy(apdgicp_dbscan* h) {
+  return guarded([&]() -> int {
+    if (h) (void)hipSetDevice(h->device);
+    delete h;
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_set_params(apdgicp_dbscan* h, const apdgicp_dbscan_params* p) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(dbscan_check_params(p));
+    h->prm = *p;
+    return 0;
+  });
+}
+
+// the stable LSD radix sort of apd_map.hpp over n (key, value) pairs, `passes` 8-bit digits from the bottom; the sorted pairs end in *ks / *vs
+static void dbscan_radix_sort(apdgicp_dbscan* h, int n, int passes, unsigned long long** ks, int** vs) {
+  VoxSortScratch& s = h->sort;
+  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
+  const int64_t entries = 256ll * nblk;
+  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
+  unsigned long long *ka = s.keys_a.as<unsigned long long>(), *kb = s.keys_b.as<unsigned long long>();
+  int *va = s.idx_a.as<int>(), *vb = s.idx_b.as<int>();
+  for (int p = 0; p < passes; p++) {
+    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, h->stream, ka, n, 8 * p, nblk, s.hist.as<int>());
+    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, h->stream, s.hist.as<int>(), (int)entries, s.rs_bsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, h->stream, s.rs_bsum.as<int>(), nsb, h->scal.as<int>() + DB_W_RADIX);
+    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, h->stream, ka, va, kb, vb, n, 8 * p, nblk, s.hist.as<int>(), s.rs_bsum.as<int>());
+    std::swap(ka, kb), std::swap(va, vb);
+  }
+  h->launches += 4 * passes;
+  *ks = ka, *vs = va;
+}
+static int bits_for(int64_t n) {  // the smallest b with n <= 2^b
+  int b = 0;
+  while ((1ll << b) < n) b++;
+  return b;
+}
+
+int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t stride_bytes, const float* doppler, int64_t doppler_stride_bytes, int on_device,
+                       int32_t* n_clusters) {
+  return guarded([&]() -> int {
+    if (!h || !n_clusters) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *n_clusters = 0;
+    h->ran = false, h->n_last = h->K_last = h->M_last = 0, h->launches = 0;
+    const apdgicp_dbscan_params& P = h->prm;
+    if (!(P.eps > 0.0)) return fail(APDGICP_ERR_INVALID_ARG, "eps (setClusterTolerance) must be > 0");
+    if (n < 0 || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (doppler && (doppler_stride_bytes < 4 || doppler_stride_bytes % 4)) return fail(APDGICP_ERR_INVALID_ARG, "doppler stride must be a multiple of 4 bytes and >= 4");
+    if (n > (1ll << 24)) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    if (n == 0) {
+      h->ran = true;
+      return 0;
+    }
+    APD_HIP(hipSetDevice(h->device));
+    const int ni = (int)n, nb = (ni + DB_BLK - 1) / DB_BLK, nt = (ni + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS);
+    const float *d_xyz = xyz, *d_dop = doppler;
+    if (!on_device) {
+      // (no wait: the copies are ordered behind the previous run's kernels by the stream; a buffer that grows is freed by hipFree, which waits)
+      APD_TRY(h->stage.ensure((size_t)n * stride_bytes));
+      APD_HIP(hipMemcpyAsync(h->stage.p, xyz, (size_t)(n - 1) * stride_bytes + 12, hipMemcpyHostToDevice, h->stream));
+      d_xyz = h->stage.as<float>();
+      if (doppler) {
+        APD_TRY(h->stage_dop.ensure((size_t)n * doppler_stride_bytes));
+        APD_HIP(hipMemcpyAsync(h->stage_dop.p, doppler, (size_t)(n - 1) * doppler_stride_bytes + 4, hipMemcpyHostToDevice, h->stream));
+        d_dop = h->stage_dop.as<float>();
+      }
+    }
+    APD_TRY(h->sort.ensure(ni));
+    APD_TRY(h->pts.ensure((size_t)n * 16));
+    APD_TRY(h->spts.ensure((size_t)n * 16));
+    APD_TRY(h->gkeys.ensure((size_t)n * 8));
+    for (DevBuf* b : {&h->dop, &h->cnt, &h->parent, &h->root, &h->seed, &h->nextra, &h->size, &h->ncore, &h->rank_of, &h->cseed, &h->csize, &h->mcount, &h->labels})
+      APD_TRY(b->ensure((size_t)n * 4));
+    APD_TRY(h->core.ensure((size_t)n));
+    APD_TRY(h->score.ensure((size_t)n));
+    APD_TRY(h->tsum.ensure((size_t)nt * 4));
+    APD_TRY(h->msum.ensure((size_t)nt * 4));
+    int* scal = h->scal.as<int>();
+    const double eps2 = P.eps * P.eps, cell = P.eps * (1.0 + 0x1p-20);
+    const int bits = bits_for(n), p1 = std::max(1, (2 * bits + 1 + 7) / 8);
+    const dim3 grid(nb), blk(DB_BLK);
+    hipStream_t st = h->stream;
+    APD_HIP(hipMemsetAsync(scal, 0, DB_WORDS * sizeof(int), st));
+    auto mark = [&](int k) { return h->profiling ? hipEventRecord(h->ev[k], st) : hipSuccess; };
+    APD_HIP(mark(0));
+    // the grid: cells, (cell, index) sorted, the sorted copy
+    hipLaunchKernelGGL(k_db_keys, grid, blk, 0, st, d_xyz, ni, (int)(stride_bytes / 4), d_dop, (int)(doppler_stride_bytes / 4), cell, h->pts.as<float4>(), h->dop.as<float>(),
+                       h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>(), scal);
+    unsigned long long* ks;
+    int* vs;
+    dbscan_radix_sort(h, ni, 8, &ks, &vs);
+    const unsigned long long* gk = h->gkeys.as<unsigned long long>();
+    const float4* sp = h->spts.as<float4>();
+    const unsigned char* sc = h->score.as<unsigned char>();
+    hipLaunchKernelGGL(k_db_gather, grid, blk, 0, st, ks, vs, h->pts.as<float4>(), ni, h->gkeys.as<unsigned long long>(), h->spts.as<float4>());
+    APD_HIP(mark(1));
+    // D1 - D5
+    hipLaunchKernelGGL(k_db_count, grid, blk, 0, st, gk, sp, ni, eps2, P.min_pts, h->cnt.as<int>(), h->core.as<unsigned char>(), h->score.as<unsigned char>(), h->parent.as<int>(),
+                       h->size.as<int>(), h->ncore.as<int>());
+    APD_HIP(mark(2));
+    hipLaunchKernelGGL(k_db_union, grid, blk, 0, st, gk, sp, sc, ni, eps2, h->parent.as<int>());
+    hipLaunchKernelGGL(k_db_flatten, grid, blk, 0, st, h->parent.as<int>(), h->core.as<unsigned char>(), ni, h->root.as<int>());
+    APD_HIP(mark(3));
+    hipLaunchKernelGGL(k_db_border, grid, blk, 0, st, gk, sp, sc, h->root.as<int>(), ni, eps2, h->seed.as<int>(), h->nextra.as<int>(), h->size.as<int>(), h->ncore.as<int>());
+    APD_HIP(mark(4));
+    // D6 / D7: kept seeds ranked by (size descending, seed ascending), the sizes scanned
+    hipLaunchKernelGGL(k_db_rank_keys, grid, blk, 0, st, h->core.as<unsigned char>(), h->root.as<int>(), h->size.as<int>(), ni, bits, P.min_cluster_size, P.max_cluster_size,
+                       h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>(), h->rank_of.as<int>(), scal);
+    dbscan_radix_sort(h, ni, p1, &ks, &vs);
+    hipLaunchKernelGGL(k_db_rank_table, grid, blk, 0, st, ks, h->size.as<int>(), ni, bits, scal, h->rank_of.as<int>(), h->cseed.as<int>(), h->csize.as<int>());
+    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nt), dim3(SCAN_BLK), 0, st, h->csize.as<int>(), ni, h->tsum.as<int>());
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, st, h->tsum.as<int>(), nt, scal + DB_W_M);
+    h->launches += 10;
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(h->h_scal, h->scal.p, DB_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    APD_HIP(hipStreamSynchronize(st));  // the one wait of the call
+    if (h->h_scal[DB_W_BAD] != 0)
+      return fail(APDGICP_ERR_UNSUPPORTED, "DBSCAN: point " + std::to_string(DB_BAD_BASE - h->h_scal[DB_W_BAD]) + " lies 2^20 cells or more from the origin (cell side " +
+                                               std::to_string(cell) + ")");
+    const int K = h->h_scal[DB_W_K];
+    const int64_t M = h->h_scal[DB_W_M];
+    if (K < 0 || K > ni || M < K || M > (1ll << 30)) return fail(APDGICP_ERR_INTERNAL, "DBSCAN: inconsistent cluster count");
+    if (K > 0) {
+      const int Mi = (int)M, p2 = std::max(1, (bits_for(K) + 7) / 8);
+      APD_TRY(h->sort.ensure(std::max(ni, Mi)));  // (nothing is in flight)
+      APD_TRY(h->offsets.ensure((size_t)(K + 1) * 4));
+      APD_TRY(h->members.ensure((size_t)M * 4));
+      APD_TRY(h->table.ensure((size_t)K * sizeof(DbCluster)));
+      hipLaunchKernelGGL(k_db_offsets, dim3((K + 1 + DB_BLK - 1) / DB_BLK), blk, 0, st, h->csize.as<int>(), h->tsum.as<int>(), K, Mi, h->offsets.as<int>());
+      hipLaunchKernelGGL(k_db_member_count, grid, blk, 0, st, gk, sp, sc, h->root.as<int>(), h->seed.as<int>(), h->nextra.as<int>(), h->rank_of.as<int>(), ni, eps2,
+                         h->mcount.as<int>());
+      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nt), dim3(SCAN_BLK), 0, st, h->mcount.as<int>(), ni, h->msum.as<int>());
+      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, st, h->msum.as<int>(), nt, scal + DB_W_M2);
+      hipLaunchKernelGGL(k_db_member_emit, grid, blk, 0, st, gk, sp, sc, h->root.as<int>(), h->seed.as<int>(), h->nextra.as<int>(), h->rank_of.as<int>(), h->mcount.as<int>(),
+                         h->msum.as<int>(), ni, eps2, Mi, h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>());
+      dbscan_radix_sort(h, Mi, p2, &ks, &vs);
+      APD_HIP(hipMemcpyAsync(h->members.p, vs, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(k_db_table, dim3(K), blk, 0, st, h->offsets.as<int>(), h->members.as<int>(), h->cseed.as<int>(), h->ncore.as<int>(), h->pts.as<float4>(),
+                         d_dop ? h->dop.as<float>() : (const float*)nullptr, ni, h->table.as<DbCluster>());
+      h->launches += 6;
+    }
+    hipLaunchKernelGGL(k_db_labels, grid, blk, 0, st, h->seed.as<int>(), h->rank_of.as<int>(), ni, h->labels.as<int>());
+    h->launches += 1;
+    APD_HIP(hipGetLastError());
+    if (h->profiling) {
+      APD_HIP(mark(5));
+      APD_HIP(hipEventSynchronize(h->ev[5]));
+      for (int k = 0; k < 5; k++) {
+        float ms = 0.f;
+        APD_HIP(hipEventElapsedTime(&ms, h->ev[k], h->ev[k + 1]));
+        h->phase_ms[k] = (double)ms;
+      }
+    }
+    h->n_last = n, h->K_last = K, h->M_last = K > 0 ? M : 0, h->ran = true;
+    *n_clusters = K;
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_labels(apdgicp_dbscan* h, const int32_t** device_labels, int64_t* n) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t cnt = h->ran ? h->n_last : 0;
+    if (device_labels) *device_labels = cnt ? h->labels.as<int32_t>() : nullptr;
+    if (n) *n = cnt;
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_copy_labels(apdgicp_dbscan* h, int32_t* labels, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t n = h->ran ? h->n_last : 0;
+    if (capacity < n || (n && !labels)) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer entries than the cloud has points");
+    if (!n) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipMemcpyAsync(labels, h->labels.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_clusters(apdgicp_dbscan* h, apdgicp_dbscan_cluster* table, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t K = h->ran ? h->K_last : 0;
+    if (capacity < K || (K && !table)) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer rows than there are clusters");
+    if (!K) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipMemcpyAsync(table, h->table.p, (size_t)K * sizeof(DbCluster), hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_members(apdgicp_dbscan* h, int32_t* offsets, int64_t offsets_capacity, int32_t* indices, int64_t indices_capacity, int64_t* n_indices) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t K = h->ran ? h->K_last : 0, M = h->ran ? h->M_last : 0;
+    if ((offsets && offsets_capacity < K + 1) || (indices && indices_capacity < M)) return fail(APDGICP_ERR_INVALID_ARG, "a destination holds fewer entries than the member lists");
+    if (n_indices) *n_indices = M;
+    if (!K) {
+      if (offsets) offsets[0] = 0;
+      return 0;
+    }
+    APD_HIP(hipSetDevice(h->device));
+    if (offsets) APD_HIP(hipMemcpyAsync(offsets, h->offsets.p, (size_t)(K + 1) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (indices) APD_HIP(hipMemcpyAsync(indices, h->members.p, (size_t)M * 4, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_debug(apdgicp_dbscan* h, int32_t* cnt, uint8_t* core, int32_t* root, int32_t* primary, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    const int64_t n = h->ran ? h->n_last : 0;
+    if ((cnt || core || root || primary) && capacity < n) return fail(APDGICP_ERR_INVALID_ARG, "a destination holds fewer entries than the cloud has points");
+    if (!n) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    if (cnt) APD_HIP(hipMemcpyAsync(cnt, h->cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (core) APD_HIP(hipMemcpyAsync(core, h->core.p, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (root) APD_HIP(hipMemcpyAsync(root, h->root.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (primary) APD_HIP(hipMemcpyAsync(primary, h->seed.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_set_profiling(apdgicp_dbscan* h, int enable) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(h->device));
+    for (hipEvent_t& e : h->ev)
+      if (enable && !e) APD_HIP(hipEventCreate(&e));
+    h->profiling = enable != 0;
+    return 0;
+  });
+}
+
+int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, double phase_ms[5]) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  if (launches) *launches = h->launches;
+  if (waits) *waits = h->launches ? (h->profiling ? 2 : 1) : 0;
+  for (int k = 0; k < 5 && phase_ms; k++) phase_ms[k] = h->profiling ? h->phase_ms[k] : 0.0;
+  return 0;
 }
 
 }  // extern "C"

@@ -114,6 +114,8 @@ SYMBOLS = [
     "apdgicp_ndt_default_params", "apdgicp_set_ndt", "apdgicp_get_ndt", "apdgicp_ndt_voxel_count", "apdgicp_ndt_get_voxels",
     "apdgicp_ndt_get_correspondences", "apdgicp_ndt_build_count",
     "apdgicp_batch_set_ndt", "apdgicp_batch_get_ndt", "apdgicp_batch_ndt_voxel_count", "apdgicp_batch_ndt_get_voxels", "apdgicp_batch_ndt_build_count",
+    "apdgicp_dbscan_default_params", "apdgicp_dbscan_create", "apdgicp_dbscan_destroy", "apdgicp_dbscan_set_params", "apdgicp_dbscan_run", "apdgicp_dbscan_labels",
+    "apdgicp_dbscan_copy_labels", "apdgicp_dbscan_clusters", "apdgicp_dbscan_members", "apdgicp_dbscan_debug", "apdgicp_dbscan_set_profiling", "apdgicp_dbscan_stats",
 ]
 
 _lib = None
@@ -304,6 +306,19 @@ def load_library(path: str | None = None):
     L.apdgicp_batch_ndt_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
     L.apdgicp_batch_ndt_get_voxels.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp, vp]
     L.apdgicp_batch_ndt_build_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_dbscan_default_params.argtypes = [vp]
+    L.apdgicp_dbscan_default_params.restype = None
+    L.apdgicp_dbscan_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.apdgicp_dbscan_destroy.argtypes = [vp]
+    L.apdgicp_dbscan_set_params.argtypes = [vp, vp]
+    L.apdgicp_dbscan_run.argtypes = [vp, vp, i64, i64, vp, i64, i32, C.POINTER(C.c_int32)]
+    L.apdgicp_dbscan_labels.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_dbscan_copy_labels.argtypes = [vp, vp, i64]
+    L.apdgicp_dbscan_clusters.argtypes = [vp, vp, i64]
+    L.apdgicp_dbscan_members.argtypes = [vp, vp, i64, vp, i64, C.POINTER(i64)]
+    L.apdgicp_dbscan_debug.argtypes = [vp, vp, vp, vp, vp, i64]
+    L.apdgicp_dbscan_set_profiling.argtypes = [vp, i32]
+    L.apdgicp_dbscan_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), vp]
     if path is None:
         _lib = L
     return L
