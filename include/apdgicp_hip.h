@@ -45,7 +45,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_set_vgicp and the apdgicp_vgicp_* calls (voxelized GICP as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle);
                                       still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle);
-                                      still 6 (additive): + apdgicp_batch_set_ndt / _get_ndt and the apdgicp_batch_ndt_* calls (NDT as a mode of the batch handle) */
+                                      still 6 (additive): + apdgicp_batch_set_ndt / _get_ndt and the apdgicp_batch_ndt_* calls (NDT as a mode of the batch handle);
+                                      still 6 (additive): + apdgicp_debug_live_buffers */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -215,6 +216,11 @@ int apdgicp_get_trace_step_norms(apdgicp_handle* h, int64_t capacity, double* no
 /* Debug: out[i] = atan2f(y[i], x[i]) as the kernels evaluate it on `device` (include/apd_atan2f.h: glibc's generic atan2f restated;
  * A:168,172-173 call the C library's float overload); host arrays.  For the bit-for-bit comparison with the host's evaluation. */
 int apdgicp_debug_atan2f(int device, const float* y, const float* x, float* out, int64_t n);
+/* Debug: how many device allocations (hipMalloc) and pinned host allocations (hipHostMalloc) the library's objects hold in this process right now,
+ * over all handles of every kind.  Every object frees what it holds when it is destroyed, so the counts after create ... destroy equal those
+ * before.  The two poll-record blocks of an engine (one per registration or batch handle, two once apdgicp_batch_align_enqueue has been used)
+ * are kept outside the counted owners and are not in pinned_buffers.  Either pointer may be NULL. */
+int apdgicp_debug_live_buffers(int64_t* device_buffers, int64_t* pinned_buffers);
 /* pcl::transformPointCloud(*input_, output, final_transformation_) (L:79): writes n xyz triples
  * `out_stride_bytes` apart into host memory */
 int apdgicp_transform_source(apdgicp_handle* h, const float T[16], float* out_xyz, int64_t n, int64_t out_stride_bytes);

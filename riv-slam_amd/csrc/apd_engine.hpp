@@ -26,30 +26,13 @@
 #include <dlfcn.h>
 
 #include "../../include/apdgicp_hip.h"
+#include "apd_devbuf.hpp"
 #include "apd_kernels.hpp"
 #include "apd_hostpack.hpp"
 
 namespace apd {
 
 static_assert(sizeof(ResultRec) == sizeof(apdgicp_result), "ResultRec must mirror apdgicp_result");
-
-inline thread_local std::string g_last_error;
-inline int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
-
-#define APD_HIP(expr)                                                                                         \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess)                                                                                     \
-      return fail(APDGICP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-  } while (0)
-#define APD_TRY(expr)          \
-  do {                         \
-    int rc_ = (expr);          \
-    if (rc_ < 0) return rc_;   \
-  } while (0)
 
 // roctx ranges over the host-side phases (pack / sort / k-NN covariances / optimiser ticks / poll), visible in
 // `rocprofv3 --marker-trace`.  The marker library is looked up at run time -- the copy already in the process (a profiler
@@ -86,83 +69,10 @@ struct roctx_range {
   roctx_range& operator=(const roctx_range&) = delete;
 };
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t bytes) {
-    if (bytes <= cap) return 0;
-    if (p) {
-      hipError_t e = hipFree(p);
-      (void)e;
-      p = nullptr;
-      cap = 0;
-    }
-    const size_t want = (bytes + 255) & ~size_t(255);
-    APD_HIP(hipMalloc(&p, want));
-    cap = want;
-    return 0;
-  }
-  void release() {
-    if (p) {
-      hipError_t e = hipFree(p);
-      (void)e;
-    }
-    p = nullptr;
-    cap = 0;
-  }
-  template <typename T>
-  T* as() const { return (T*)p; }
-};
-
 inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return v && *v ? atoi(v) : dflt;
 }
-
-// A small host->device table that is re-uploaded only when its contents change.  A changed table goes through one of two
-// pinned staging buffers and an asynchronous copy on the caller's stream -- stream order already keeps it behind the
-// kernels that still read the old contents -- and the host never waits for the GPU: a staging buffer is only rewritten
-// after the event recorded behind ITS last copy has fired (normally long ago).
-struct CachedTable {
-  DevBuf dev;
-  std::vector<char> host;  // last uploaded contents (for the comparison)
-  char* pin[2] = {nullptr, nullptr};
-  size_t pin_cap[2] = {0, 0};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int cur = 0;
-  ~CachedTable() {
-    for (int i = 0; i < 2; i++) {
-      if (ev[i]) (void)hipEventDestroy(ev[i]);
-      if (pin[i]) (void)hipHostFree(pin[i]);
-    }
-  }
-  int upload(const void* data, size_t bytes, hipStream_t stream) {
-    if (dev.p && host.size() == bytes && (bytes == 0 || memcmp(host.data(), data, bytes) == 0)) return 0;
-    host.assign((const char*)data, (const char*)data + bytes);
-    if (std::max<size_t>(bytes, 16) > dev.cap) APD_HIP(hipStreamSynchronize(stream));  // the old device buffer is about to be freed
-    APD_TRY(dev.ensure(std::max<size_t>(bytes, 16)));
-    if (!bytes) return 0;
-    cur ^= 1;
-    if (!ev[cur]) APD_HIP(hipEventCreateWithFlags(&ev[cur], hipEventDisableTiming));
-    else APD_HIP(hipEventSynchronize(ev[cur]));
-    if (bytes > pin_cap[cur]) {
-      if (pin[cur]) APD_HIP(hipHostFree(pin[cur]));
-      pin[cur] = nullptr, pin_cap[cur] = 0;
-      const size_t cap = std::max<size_t>(bytes * 2, 256);
-      APD_HIP(hipHostMalloc((void**)&pin[cur], cap, hipHostMallocDefault));
-      pin_cap[cur] = cap;
-    }
-    memcpy(pin[cur], data, bytes);
-    APD_HIP(hipMemcpyAsync(dev.p, pin[cur], bytes, hipMemcpyHostToDevice, stream));
-    APD_HIP(hipEventRecord(ev[cur], stream));
-    return 0;
-  }
-  template <typename T>
-  T* as() const { return (T*)dev.p; }
-  CachedTable() = default;
-  CachedTable(const CachedTable&) = delete;
-  CachedTable& operator=(const CachedTable&) = delete;
-};
 
 class Engine {
  public:
@@ -177,21 +87,13 @@ class Engine {
     uint64_t token = 0;
     uint64_t pts_gen = 0;            // Engine::pts_epoch when the slot's points were last set: names one setting of the points (0: none)
     // a host cloud of the tiled-sort size class stays in this pinned buffer until the sort has read it (TileJob::staged)
-    char* stage_p = nullptr;
-    char* stage_dev = nullptr;
-    size_t stage_cap = 0;
+    PinnedBuf stage;
+    char* stage_dev = nullptr;      // the same memory as the device addresses it
     bool staged = false;            // set_cloud left the points there, the next sort reads them
     bool stage_pending = false;     // a sort that reads the buffer has been enqueued ...
     hipEvent_t stage_wait = nullptr;  // ... in front of this event (the poll event of the align behind it; not owned)
     volatile int* stage_seq_word = nullptr;  // ... and of the poll that posts stage_seq_val (or a later number) here
     int stage_seq_val = 0;
-    void release_all() {
-      opts.release(), pts.release(), perm.release(), cbox.release(), gbox.release(), cov.release();
-      hipError_t e = hipSuccess;
-      if (stage_p) e = hipHostFree(stage_p);
-      (void)e;
-      stage_p = stage_dev = nullptr, stage_cap = 0, staged = stage_pending = false, stage_wait = nullptr, stage_seq_word = nullptr;
-    }
   };
 
   int device = 0;
@@ -263,7 +165,7 @@ class Engine {
   int* h_status = nullptr;   // inside h_poll (or, for check_errflag, at its start)
   bool results_on_host = false;
   const ResultRec* host_results() const { return results_on_host ? (const ResultRec*)h_poll : nullptr; }
-  double* h_probe = nullptr; // pinned, 48 doubles
+  PinnedBuf h_probe;         // 64 doubles
   hipEvent_t ev_poll = nullptr;
   // Two aligns in flight (apdgicp_batch_align_enqueue / _collect): everything an align leaves behind for its caller -- the
   // record buffers on both sides, the poll event, the timed-launch events -- exists twice; swap_slots() makes the other set
@@ -328,7 +230,7 @@ class Engine {
     memset(h_poll, 0, 65540 * sizeof(int) + kHostResults * sizeof(ResultRec));  // the sequence word the host spins on starts at 0
     h_status = (int*)h_poll;
     APD_HIP(hipHostGetDevicePointer((void**)&h_poll_dev, h_poll, 0));
-    APD_HIP(hipHostMalloc((void**)&h_probe, 64 * sizeof(double), hipHostMallocDefault));
+    APD_TRY(h_probe.ensure(64 * sizeof(double)));
     APD_HIP(hipEventCreateWithFlags(&ev_poll, hipEventDisableTiming));
     APD_TRY(d_errflag.ensure(sizeof(int)));
     APD_HIP(hipMemsetAsync(d_errflag.p, 0, sizeof(int), stream));
@@ -374,45 +276,23 @@ class Engine {
     hipError_t e;
     e = hipSetDevice(device);
     if (stream) e = hipStreamSynchronize(stream);
-    for (auto& c : clouds) c.release_all();
-    for (CachedTable* t : {&d_desc, &d_pairs, &d_guess, &d_ids, &d_packjobs, &d_sortjobs, &d_sortjobs_reg[0], &d_sortjobs_reg[1], &d_sortjobs_reg[2], &d_tilejobs[0], &d_tilejobs[1], &d_tilejobs[2], &d_active, &d_post}) t->dev.release();
-    d_tkeys.release();
-    for (DevBuf* b : {&d_state, &d_results, &d_errflag, &d_probe, &d_stage, &d_T, &d_trace,
-                      &d_keys, &d_box6, &d_stats, &b_ticket, &b_blkcost, &b_blkorder, &b_nnpart, &b_corr, &b_nnpt, &b_nnaux, &b_sqd, &b_maha, &b_blkpart, &b_errpart})
-      b->release();
-    if (bulk_host) e = hipHostFree(bulk_host);
-    if (bulk_ev) e = hipEventDestroy(bulk_ev);
-    bulk_dev.release();
+    if (pool.cstream) e = hipStreamSynchronize(pool.cstream);
+    for (auto st_ : gstreams) e = hipStreamSynchronize(st_);
+    // what is neither a DevBuf nor a PinnedBuf: the poll records of both slots (raw: swap_slots hands them over), events, streams.
+    // Every buffer is freed by its own destructor once this body has run -- behind the waits above.
     if (h_poll) e = hipHostFree(h_poll);
     if (alt.h_poll) e = hipHostFree(alt.h_poll);
-    if (alt.ev_poll) e = hipEventDestroy(alt.ev_poll);
-    alt.d_results.release();
+    for (hipEvent_t ev_ : {bulk_ev, alt.ev_poll, ev_poll, ev_main, ev_producer, h_stage[0].ev, h_stage[1].ev})
+      if (ev_) e = hipEventDestroy(ev_);
     for (auto& pr : alt.nn_events) e = hipEventDestroy(pr.first), e = hipEventDestroy(pr.second);
-    if (h_probe) e = hipHostFree(h_probe);
-    if (ev_poll) e = hipEventDestroy(ev_poll);
-    if (ev_main) e = hipEventDestroy(ev_main);
-    if (ev_producer) e = hipEventDestroy(ev_producer);
-    if (pool.cstream) e = hipStreamSynchronize(pool.cstream);
     for (Pool::List& li : pool.L)
       for (hipEvent_t ev_ : li.ev)
         if (ev_) e = hipEventDestroy(ev_);
     for (Pool::Timed& c : pool.timed) e = hipEventDestroy(c.e0), e = hipEventDestroy(c.e1);
-    for (PoolJob& j : pool.jobs) {
+    for (PoolJob& j : pool.jobs)
       if (j.ev_pro) e = hipEventDestroy(j.ev_pro);
-      if (j.pin) e = hipHostFree(j.pin);
-      j.d_recs.release();
-    }
-    for (DevBuf* b : {&pool.state, &pool.pairs, &pool.guess, &pool.results, &pool.ticket, &pool.nnpart, &pool.corr,
-                      &pool.nnpt, &pool.nnaux, &pool.sqd, &pool.maha, &pool.blkpart, &pool.errpart})
-      b->release();
-    for (Pool::List& li : pool.L) li.active.release(), li.nactive.release();
-    if (pool.host) e = hipHostFree(pool.host);
     if (pool.cstream) e = hipStreamDestroy(pool.cstream);
-    for (HostStage& hs : h_stage) {
-      if (hs.ev) e = hipEventDestroy(hs.ev);
-      if (hs.p) e = hipHostFree(hs.p);
-    }
-    for (auto st_ : gstreams) e = hipStreamSynchronize(st_), e = hipStreamDestroy(st_);
+    for (auto st_ : gstreams) e = hipStreamDestroy(st_);
     for (auto ev_ : gevents) e = hipEventDestroy(ev_);
     for (auto& pr : nn_events) e = hipEventDestroy(pr.first), e = hipEventDestroy(pr.second);
     if (own_stream && stream) e = hipStreamDestroy(stream);
@@ -468,8 +348,7 @@ class Engine {
   }
 
   struct HostStage {
-    char* p = nullptr;
-    size_t cap = 0;
+    PinnedBuf pin;
     hipEvent_t ev = nullptr;
   } h_stage[2];
   int h_stage_cur = 0;
@@ -506,15 +385,12 @@ class Engine {
         c.stage_pending = false, c.stage_wait = nullptr, c.stage_seq_word = nullptr;
       }
       const size_t need = ((size_t)n + 2) * 16;
-      if (need > c.stage_cap) {
-        if (c.stage_p) APD_HIP(hipHostFree(c.stage_p));
-        c.stage_p = c.stage_dev = nullptr, c.stage_cap = 0;
-        const size_t cap = std::max<size_t>(need * 5 / 4, 1 << 16);
-        APD_HIP(hipHostMalloc((void**)&c.stage_p, cap, hipHostMallocDefault));
-        APD_HIP(hipHostGetDevicePointer((void**)&c.stage_dev, c.stage_p, 0));
-        c.stage_cap = cap;
+      if (need > c.stage.cap) {
+        c.stage_dev = nullptr;
+        APD_TRY(c.stage.ensure(std::max<size_t>(need * 5 / 4, 1 << 16)));
+        APD_HIP(hipHostGetDevicePointer((void**)&c.stage_dev, c.stage.p, 0));
       }
-      pack_staged_host((HostF4*)c.stage_p, raw, n, stride_bytes);
+      pack_staged_host(c.stage.as<HostF4>(), raw, n, stride_bytes);
       c.staged = true;
     } else if (!on_device) {
       // Host clouds (the odometry nodelet hands over pcl::PointXYZI, 32 bytes a point): the three coordinates are packed into
@@ -524,19 +400,13 @@ class Engine {
       HostStage& hs = h_stage[h_stage_cur ^= 1];
       if (!hs.ev) APD_HIP(hipEventCreateWithFlags(&hs.ev, hipEventDisableTiming));
       else APD_HIP(hipEventSynchronize(hs.ev));
-      if ((size_t)n * 16 > hs.cap) {
-        if (hs.p) APD_HIP(hipHostFree(hs.p));
-        hs.p = nullptr, hs.cap = 0;
-        const size_t cap = std::max<size_t>((size_t)n * 16 * 5 / 4, 1 << 16);
-        APD_HIP(hipHostMalloc((void**)&hs.p, cap, hipHostMallocDefault));
-        hs.cap = cap;
-      }
-      float4* dst = (float4*)hs.p;
+      if ((size_t)n * 16 > hs.pin.cap) APD_TRY(hs.pin.ensure(std::max<size_t>((size_t)n * 16 * 5 / 4, 1 << 16)));
+      float4* dst = hs.pin.as<float4>();
       for (int64_t q = 0; q < n; q++) {
         const float* sp = (const float*)(raw + q * stride_bytes);
         dst[q] = make_float4(sp[0], sp[1], sp[2], 1.0f);
       }
-      APD_HIP(hipMemcpyAsync(c.opts.p, hs.p, (size_t)n * 16, hipMemcpyHostToDevice, cstream));
+      APD_HIP(hipMemcpyAsync(c.opts.p, hs.pin.p, (size_t)n * 16, hipMemcpyHostToDevice, cstream));
       APD_HIP(hipEventRecord(hs.ev, cstream));
     } else {
       hipLaunchKernelGGL(k_pack_points, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, cstream, raw, (long long)stride_bytes, (int)n, c.opts.as<float4>());
@@ -556,8 +426,7 @@ class Engine {
   // pack launch of set_clouds_device.  The single-cloud path lets the sort read a scan-sized cloud straight from pinned memory --
   // right for one frame (no copy in front of the first kernel), wrong for 64 clouds: the sort's blocks then sit on their compute
   // units waiting for PCIe (bench.py --host-clouds: 1.07 ms per step that way, 0.96 with the packing vectorised, see docs/experiments.md).
-  char* bulk_host = nullptr;
-  size_t bulk_cap = 0;
+  PinnedBuf bulk_host;
   hipEvent_t bulk_ev = nullptr;
   DevBuf bulk_dev;
   int set_clouds_host(int first, int count, const float* const* xyz, const int64_t* ns, int64_t stride_bytes) {
@@ -580,23 +449,18 @@ class Engine {
     for (int q = 0; q < count; q++) offs[q] = need, need += ((size_t)ns[q] * 12 + 15) & ~(size_t)15;
     if (!bulk_ev) APD_HIP(hipEventCreateWithFlags(&bulk_ev, hipEventDisableTiming));
     else APD_HIP(hipEventSynchronize(bulk_ev));  // the previous copy out of the pinned region (long done: a step ago on this handle)
-    if (need > bulk_cap) {
-      if (bulk_host) APD_HIP(hipHostFree(bulk_host));
-      bulk_host = nullptr, bulk_cap = 0;
-      APD_HIP(hipHostMalloc((void**)&bulk_host, need * 5 / 4, hipHostMallocDefault));
-      bulk_cap = need * 5 / 4;
-    }
+    if (need > bulk_host.cap) APD_TRY(bulk_host.ensure(need * 5 / 4));
     if (need > bulk_dev.cap) APD_HIP(hipStreamSynchronize(cstream));  // (the pack launch of the previous call may still read it)
     APD_TRY(bulk_dev.ensure(need));
     std::vector<const float*> dptr(count);
     for (int q = 0; q < count; q++) dptr[q] = (const float*)((char*)bulk_dev.p + offs[q]);
     int want = 1;
     HostPool* hp = shared_host_pool(&want);
-    const std::function<void(int)> f = [&](int i) { compact_xyz_host((float*)(bulk_host + offs[i]), (const char*)xyz[i], ns[i], stride_bytes); };
+    const std::function<void(int)> f = [&](int i) { compact_xyz_host((float*)(bulk_host.as<char>() + offs[i]), (const char*)xyz[i], ns[i], stride_bytes); };
     if (hp) hp->run(count, f);
     else
       for (int q = 0; q < count; q++) f(q);
-    APD_HIP(hipMemcpyAsync(bulk_dev.p, bulk_host, need, hipMemcpyHostToDevice, cstream));
+    APD_HIP(hipMemcpyAsync(bulk_dev.p, bulk_host.p, need, hipMemcpyHostToDevice, cstream));
     APD_HIP(hipEventRecord(bulk_ev, cstream));
     return set_clouds_device(first, count, dptr.data(), ns, 12);
   }
@@ -1472,8 +1336,7 @@ class Engine {
     std::vector<std::pair<int, int>> pair_ids;
     std::vector<ResultRec> recs;      // host copy of the records, taken when the batch completed
     hipEvent_t ev_pro = nullptr;      // behind the preparation of its clouds (cloud stream)
-    char* pin = nullptr;              // staging of the lane's pair descriptors and guesses
-    size_t pin_cap = 0;
+    PinnedBuf pin;                    // staging of the lane's pair descriptors and guesses
     int layout_gen = 0;               // Pool::layout_gen when the batch was enqueued: where its device records are
     DevBuf d_recs;                    // device copy of `recs` for a collect that comes after the pool was laid out anew
   };
@@ -1485,9 +1348,8 @@ class Engine {
     hipStream_t cstream = nullptr;
     DevBuf state, pairs, guess, results, ticket, nnpart, corr, nnpt, nnaux, sqd, maha, blkpart, errpart;
     Work work{};
-    char* host = nullptr;  // pinned: ResultRec[cap], then PoolHdr[kLists][kPoolRing]
-    char* host_dev = nullptr;
-    size_t host_cap = 0;
+    PinnedBuf host;        // ResultRec[cap], then PoolHdr[kLists][kPoolRing]
+    char* host_dev = nullptr;  // the same memory as the device addresses it
     PoolJob jobs[kPoolLanes];
     // TWO independent pair lists, each with its own tick stream, poll kernel, header ring and chunk numbering; a batch lives on
     // one of them (the less loaded one when it is enqueued).  Nothing ever waits across the two streams: the poll of a list is
@@ -1537,7 +1399,7 @@ class Engine {
   // batches of one handle that may be in flight at once (round 4, two lists: 8 / 16 / 24 / 32 in flight: 1.08 / 0.91 / 0.87 / 0.86 ms per 32 loop
   // pairs; round 3, one list: 8 / 12 / 16 / 24 / 32: 1.27 / 1.13 / 1.07 / 1.03 / 1.01)
   static int pool_lanes_cfg() { return std::max(1, std::min(kPoolLanes, env_int("APDGICP_POOL_LANES", 24))); }
-  PoolHdr* pool_hdr(int l, uint64_t seq) const { return (PoolHdr*)(pool.host + (size_t)pool.cap * sizeof(ResultRec)) + (size_t)l * kPoolRing + seq % kPoolRing; }
+  PoolHdr* pool_hdr(int l, uint64_t seq) const { return (PoolHdr*)(pool.host.as<char>() + (size_t)pool.cap * sizeof(ResultRec)) + (size_t)l * kPoolRing + seq % kPoolRing; }
   bool pool_busy() const {
     for (const PoolJob& j : pool.jobs)
       if (j.state == PoolJob::PENDING || j.state == PoolJob::RUNNING) return true;
@@ -1613,14 +1475,12 @@ class Engine {
     APD_TRY(pool.blkpart.ensure((size_t)cap * nblk * kRed * 8));
     APD_TRY(pool.errpart.ensure((size_t)cap * nblk * 8));
     const size_t host_bytes = (size_t)cap * sizeof(ResultRec) + (size_t)Pool::kLists * kPoolRing * sizeof(PoolHdr);
-    if (host_bytes > pool.host_cap) {
-      if (pool.host) APD_HIP(hipHostFree(pool.host));
-      pool.host = pool.host_dev = nullptr, pool.host_cap = 0;
-      APD_HIP(hipHostMalloc((void**)&pool.host, host_bytes, hipHostMallocDefault));
-      APD_HIP(hipHostGetDevicePointer((void**)&pool.host_dev, pool.host, 0));
-      pool.host_cap = host_bytes;
+    if (host_bytes > pool.host.cap) {
+      pool.host_dev = nullptr;
+      APD_TRY(pool.host.ensure(host_bytes));
+      APD_HIP(hipHostGetDevicePointer((void**)&pool.host_dev, pool.host.p, 0));
     }
-    memset(pool.host, 0, pool.host_cap);  // (also the sequence words: a header counts once its word equals the expected number, never 0)
+    memset(pool.host.p, 0, pool.host.cap);  // (also the sequence words: a header counts once its word equals the expected number, never 0)
     for (Pool::List& li : pool.L) {
       APD_HIP(hipMemsetAsync(li.nactive.p, 0, sizeof(int), stream));
       APD_HIP(hipMemsetAsync(li.active.p, 0xff, (size_t)cap * sizeof(int), stream));
@@ -1785,7 +1645,7 @@ class Engine {
       PoolJob& j = pool.jobs[ln];
       if (j.state != PoolJob::RUNNING || j.list != l || j.admit_seq > seq || h.lane_left[ln] != 0) continue;
       j.recs.resize(j.np);
-      memcpy(j.recs.data(), (const ResultRec*)pool.host + (size_t)ln * pool.segcap, (size_t)j.np * sizeof(ResultRec));
+      memcpy(j.recs.data(), pool.host.as<const ResultRec>() + (size_t)ln * pool.segcap, (size_t)j.np * sizeof(ResultRec));
       pool_job_finished(j);
     }
     return 0;
@@ -1930,14 +1790,9 @@ class Engine {
     // descriptors and guesses of the lane's pairs: staged in the lane's pinned buffer (its last reader, the copy of the lane's
     // previous batch, is long done), copied in stream order in front of the chunk that admits them
     const size_t bytes = (size_t)n * (sizeof(PairDesc) + sizeof(Rigid));
-    if (bytes > j.pin_cap) {
-      if (j.pin) APD_HIP(hipHostFree(j.pin));
-      j.pin = nullptr, j.pin_cap = 0;
-      APD_HIP(hipHostMalloc((void**)&j.pin, bytes * 2, hipHostMallocDefault));
-      j.pin_cap = bytes * 2;
-    }
-    PairDesc* hp = (PairDesc*)j.pin;
-    Rigid* hg = (Rigid*)(j.pin + (size_t)n * sizeof(PairDesc));
+    if (bytes > j.pin.cap) APD_TRY(j.pin.ensure(bytes * 2));
+    PairDesc* hp = j.pin.as<PairDesc>();
+    Rigid* hg = (Rigid*)(j.pin.as<char>() + (size_t)n * sizeof(PairDesc));
     j.pair_ids.resize(n);
     for (int64_t i = 0; i < n; i++) {
       const int s = pairs[i].source_cloud, t = pairs[i].target_cloud;
@@ -2000,14 +1855,14 @@ class Engine {
     APD_TRY(launch_linearize(whole(), H && b ? 1 : 0));
     hipLaunchKernelGGL(k_probe_reduce, dim3(1), dim3(64), 0, stream, d_desc.as<CloudDesc>(), d_pairs.as<PairDesc>(), d_state.as<PairState>(), work,
                        d_probe.as<double>(), 0);
-    APD_HIP(hipMemcpyAsync(h_probe, d_probe.p, 44 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    APD_HIP(hipMemcpyAsync(h_probe.p, d_probe.p, 44 * sizeof(double), hipMemcpyDeviceToHost, stream));
     APD_HIP(hipStreamSynchronize(stream));
     if (H && b) {
-      memcpy(H, h_probe, 36 * sizeof(double));
-      memcpy(b, h_probe + 36, 6 * sizeof(double));
+      memcpy(H, h_probe.p, 36 * sizeof(double));
+      memcpy(b, h_probe.as<double>() + 36, 6 * sizeof(double));
     }
-    if (cost) *cost = h_probe[42];
-    if (matched) *matched = (int)h_probe[43];
+    if (cost) *cost = h_probe.as<double>()[42];
+    if (matched) *matched = (int)h_probe.as<double>()[43];
     return 0;
   }
 
@@ -2018,9 +1873,9 @@ class Engine {
     APD_TRY(launch_error(whole(), false));
     hipLaunchKernelGGL(k_probe_reduce, dim3(1), dim3(64), 0, stream, d_desc.as<CloudDesc>(), d_pairs.as<PairDesc>(), d_state.as<PairState>(), work,
                        d_probe.as<double>(), 1);
-    APD_HIP(hipMemcpyAsync(h_probe, d_probe.p, 44 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    APD_HIP(hipMemcpyAsync(h_probe.p, d_probe.p, 44 * sizeof(double), hipMemcpyDeviceToHost, stream));
     APD_HIP(hipStreamSynchronize(stream));
-    *cost = h_probe[42];
+    *cost = h_probe.as<double>()[42];
     return 0;
   }
 };

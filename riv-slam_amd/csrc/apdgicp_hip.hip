@@ -42,9 +42,6 @@ struct VoxSortScratch {
     APD_TRY(rs_bsum.ensure(nsb * 4));
     return bsum.ensure(nhb * 4);
   }
-  void release() {
-    for (DevBuf* b : {&keys_a, &keys_b, &idx_a, &idx_b, &hist, &rs_bsum, &bsum}) b->release();
-  }
 };
 
 // The buffers of one voxel map, voxels in ascending key order (vraw: NDT only).  What the map was made from stays with its owner, per mode.
@@ -56,9 +53,6 @@ struct VoxMapBufs {
     APD_TRY(vmean.ensure(voxels * 24));
     if (raw) APD_TRY(vraw.ensure(voxels * 48));
     return vcov.ensure(voxels * 48);
-  }
-  void release() {
-    for (DevBuf* b : {&vkeys, &vcount, &vmean, &vraw, &vcov}) b->release();
   }
   VgMap map(int nv) const { return VgMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv}; }
   VgbMap map(const int* nv_word) const { return VgbMap{vkeys.as<unsigned long long>(), vcount.as<int>(), vmean.as<double>(), vcov.as<double>(), nv_word}; }
@@ -88,10 +82,6 @@ struct VgState {
   double T_lin[12];
   VoxMapBufs buf;
   DevBuf scal, inv_t, inv_s, corr, part, T, out;
-  void release() {
-    buf.release();
-    for (DevBuf* b : {&scal, &inv_t, &inv_s, &corr, &part, &T, &out}) b->release();
-  }
   VgMap map() const { return buf.map((int)n_vox); }
 };
 
@@ -105,10 +95,6 @@ struct NdState {
     int64_t id = 0;            // which build this is (NdState::builds when it was made): names the map for the frozen state
     int nv = 0;
     VoxMapBufs buf;
-    void release() {
-      buf.release();
-      built = false, nv = 0;
-    }
     VgMap map() const { return buf.map(nv); }
   };
   bool on = false;
@@ -126,25 +112,15 @@ struct NdState {
   void reset_final_H() {
     for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
   }
-  bool allocated() const { return T.p || maps[0].buf.vkeys.p || maps[1].buf.vkeys.p; }
-  void release() {
-    for (Map& m : maps) m.release();
-    for (DevBuf* b : {&scal, &corr, &part, &T, &out}) b->release();
-  }
 };
 
 struct apdgicp_handle {
-  Engine eng;
-  VgState vg;  // (released by ~apdgicp_handle, while the engine's stream still exists)
-  NdState nd;  // (likewise)
+  Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
+  VgState vg;   // (freed by its members' destructors, behind the wait of ~apdgicp_handle)
+  NdState nd;   // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two are exclusive
   ~apdgicp_handle() {
-    if (sort.keys_a.p || vg.T.p || vg.inv_s.p || nd.allocated()) {
-      if (eng.stream) (void)hipStreamSynchronize(eng.stream);
-      vg.release();
-      nd.release();
-      sort.release();
-    }
+    if (eng.stream) (void)hipStreamSynchronize(eng.stream);  // the voxel kernels run there; the members are freed once this body has run
   }
   uint64_t cloud_epoch = 0, cloud_gen[2] = {0, 0};  // cloud_gen[slot]: which setting of points the slot holds (0: none); swapped with the clouds
   bool pair_ready = false;   // work buffers / descriptors match the current source+target
@@ -168,11 +144,6 @@ struct VgbState {
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
     DevBuf inv;
     VoxMapBufs buf;            // sized for nv <= n
-    void release() {
-      buf.release();
-      inv.release();
-      map_built = false, inv_pts_gen = 0, nv = 0;
-    }
   };
   bool on = false;
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
@@ -182,10 +153,9 @@ struct VgbState {
   int scal_slots = 0;
   DevBuf corr, part;
   CachedTable pairs;
-  void release() {
-    for (Slot& sl : slots) sl.release();
+  void release() {  // apdgicp_batch_clear: the maps go with the clouds
     slots.clear();
-    for (DevBuf* b : {&scal, &corr, &part, &pairs.dev}) b->release();
+    scal.release(), corr.release(), part.release(), pairs.dev.release();
     scal_slots = 0;
   }
 };
@@ -199,10 +169,6 @@ struct NdbState {
     double res = 0.0;
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
     VoxMapBufs buf;            // sized for nv <= n
-    void release() {
-      buf.release();
-      built = false, nv = 0;
-    }
   };
   bool on = false;
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
@@ -212,10 +178,9 @@ struct NdbState {
   int scal_slots = 0;
   DevBuf corr, part;
   CachedTable pairs;
-  void release() {
-    for (Slot& sl : slots) sl.release();
+  void release() {  // apdgicp_batch_clear: the maps go with the clouds
     slots.clear();
-    for (DevBuf* b : {&scal, &corr, &part, &pairs.dev}) b->release();
+    scal.release(), corr.release(), part.release(), pairs.dev.release();
     scal_slots = 0;
   }
 };
@@ -224,33 +189,34 @@ struct NdbState {
 // pinned words the host reads, the events of the last two chunks.
 struct DeviceLoop {
   DevBuf done;
-  int* h_words = nullptr;      // pinned: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
-  size_t h_words_cap = 0;
+  PinnedBuf h_words;           // ints: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
   hipEvent_t ev[2] = {nullptr, nullptr};
   int chunk = 0;               // ticks per enqueued chunk (create time: APDGICP_VGB_CHUNK, default kVgbChunk)
   int last_ticks = 0;
-  void release() {
-    done.release();
-    if (h_words) (void)hipHostFree(h_words);
-    h_words = nullptr, h_words_cap = 0;
+  void drop_events() {
     for (hipEvent_t& e : ev) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
     }
   }
+  void release() {  // apdgicp_batch_clear
+    done.release(), h_words.release();
+    drop_events();
+  }
+  ~DeviceLoop() { drop_events(); }
 };
 
 struct apdgicp_batch {
-  Engine eng;
-  VgbState vg;  // (released by ~apdgicp_batch, while the engine's stream still exists)
+  Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
+  VgbState vg;  // (freed by its members' destructors, behind the wait of ~apdgicp_batch)
   NdbState nd;  // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two never run together
-  DeviceLoop loop;      // (likewise)
+  DeviceLoop loop;      // (likewise; its events by its own destructor)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
-  void release_voxel_modes() {
+  void release_voxel_modes() {  // apdgicp_batch_clear
     vg.release();
     nd.release();
-    sort.release();
+    sort = VoxSortScratch{};
     loop.release();
   }
   ~apdgicp_batch() {
@@ -258,7 +224,6 @@ struct apdgicp_batch {
       (void)hipSetDevice(eng.device);
       (void)hipStreamSynchronize(eng.stream);
     }
-    release_voxel_modes();
   }
 };
 
@@ -268,12 +233,10 @@ struct apdgicp_submap {
   bool own_stream = false;
   DevBuf stage, cat, keys, pos, bsum, out, scal;  // scal: box6[6], total, err
   CachedTable jobs;
-  int* h_scal = nullptr;  // pinned mirror of {total, err}
+  PinnedBuf h_scal;  // mirror of {total, err}: 2 ints
   int64_t n_last = 0;
   bool last_is_cat = false;  // no downsampling: the result is the concatenation itself
   ~apdgicp_submap() {
-    if (h_scal) (void)hipHostFree(h_scal);
-    for (DevBuf* b : {&stage, &cat, &keys, &pos, &bsum, &out, &scal, &jobs.dev}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -286,7 +249,7 @@ struct apdgicp_scan_filter {
   apdgicp_submap* vox = nullptr;  // step 2 with a leaf: the voxel grid of the submap target, on this object's stream
   Engine* eng = nullptr;          // step 3: packs, sorts and boxes the cloud of step 2 like a registration cloud (created when first needed)
   DevBuf stage, gated, dense, stat, kept, out, bsum, scal;  // scal: int counts[4] {gate, compaction, output, -}, double {mean, stddev, thr}
-  char* h_scal = nullptr;         // pinned mirror of scal + the engine's error flag
+  PinnedBuf h_scal;               // mirror of scal + the engine's error flag
   const float* result = nullptr;
   int64_t counts[4] = {0, 0, 0, 0};
   int64_t n_stat = 0;
@@ -295,8 +258,6 @@ struct apdgicp_scan_filter {
     if (stream) (void)hipStreamSynchronize(stream);
     delete eng;
     delete vox;
-    if (h_scal) (void)hipHostFree(h_scal);
-    for (DevBuf* b : {&stage, &gated, &dense, &stat, &kept, &out, &bsum, &scal}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -308,17 +269,13 @@ struct apdgicp_ego_velocity {
   apdgicp_ego_velocity_params prm;
   DevBuf stage, rows_all, valid, rows, src, bsum, words, vk, n_in, samples, rec;
   DevBuf in_row, in_xyzi, in_dop, in_src, out_row, out_xyzi, out_dop, out_src;
-  EgoRecord* h_rec = nullptr;  // pinned mirror of rec
+  PinnedBuf h_rec;  // mirror of rec: one EgoRecord
   int64_t n_last = 0;
   int K_last = 0, S_last = 0;
   bool ran = false;
-  std::vector<DevBuf*> bufs() {
-    return {&stage, &rows_all, &valid, &rows, &src, &bsum, &words, &vk, &n_in, &samples, &rec, &in_row, &in_xyzi, &in_dop, &in_src, &out_row, &out_xyzi, &out_dop, &out_src};
-  }
+  EgoRecord* record() { return h_rec.as<EgoRecord>(); }
   ~apdgicp_ego_velocity() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (h_rec) (void)hipHostFree(h_rec);
-    for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -331,20 +288,14 @@ struct apdgicp_floor {
   Engine* eng = nullptr;  // the normal filter: packs, sorts and boxes the clipped cloud like a registration cloud (created when first needed)
   DevBuf stage, tilted, mask, clip, clip_src, stat, filt, filt_src, bsum, words, coef, bad, n_in, samples, rec, state;
   DevBuf in_xyzi, in_src, in_row, under_xyzi, under_src;
-  char* h_rec = nullptr;  // pinned mirror of rec + the engine's error flag
+  PinnedBuf h_rec;  // mirror of rec + the engine's error flag
   int64_t n_last = 0;
   int K_last = 0;
   bool ran = false, stat_valid = false;
-  FloorRecord* record() { return (FloorRecord*)h_rec; }
-  std::vector<DevBuf*> bufs() {
-    return {&stage, &tilted, &mask, &clip, &clip_src, &stat, &filt, &filt_src, &bsum, &words, &coef, &bad, &n_in, &samples, &rec, &state,
-            &in_xyzi, &in_src, &in_row, &under_xyzi, &under_src};
-  }
+  FloorRecord* record() { return h_rec.as<FloorRecord>(); }
   ~apdgicp_floor() {
     if (stream) (void)hipStreamSynchronize(stream);
     delete eng;
-    if (h_rec) (void)hipHostFree(h_rec);
-    for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -361,7 +312,7 @@ struct apdgicp_map_cloud {
   std::vector<Keyframe> kfs;
   DevBuf stage, pushed, keys_a, keys_b, hist, rs_bsum, bsum, bmin, out, state;
   CachedTable jobs;
-  MapState* h_state = nullptr;  // pinned mirror of state
+  PinnedBuf h_state;  // mirror of state: one MapState
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   apdgicp_map_cloud_stats info;
   const float* result = nullptr;
@@ -373,11 +324,8 @@ struct apdgicp_map_cloud {
   }
   ~apdgicp_map_cloud() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (Keyframe& k : kfs) k.pts.release();
-    if (h_state) (void)hipHostFree(h_state);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&stage, &pushed, &keys_a, &keys_b, &hist, &rs_bsum, &bsum, &bmin, &out, &state, &jobs.dev}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -391,8 +339,7 @@ struct apdgicp_scan_context {
   DevBuf desc, ring_key, sector_key, col_norm;
   DevBuf stage, hi1, lo1, inv1, rec, hi2, lo2, inv2, out;
   CachedTable qtab, cand;
-  ScRec* h_out = nullptr;  // pinned
-  size_t h_out_cap = 0;
+  PinnedBuf h_out;  // ScRec records
   std::vector<uint32_t> seen;  // per id: the call that listed it last (duplicate check)
   uint32_t epoch = 0;
   ScDb db() const { return ScDb{desc.as<float>(), ring_key.as<float>(), sector_key.as<double>(), col_norm.as<double>()}; }
@@ -402,8 +349,6 @@ struct apdgicp_scan_context {
   }
   ~apdgicp_scan_context() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (h_out) (void)hipHostFree(h_out);
-    for (DevBuf* b : {&desc, &ring_key, &sector_key, &col_norm, &stage, &hi1, &lo1, &inv1, &rec, &hi2, &lo2, &inv2, &out, &qtab.dev, &cand.dev}) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -416,24 +361,17 @@ struct apdgicp_dbscan {
   VoxSortScratch sort;  // the three radix sorts of a run, one after the other
   DevBuf stage, stage_dop, pts, dop, gkeys, spts, cnt, core, score, parent, root, seed, nextra, size, ncore, rank_of, cseed, csize, tsum, mcount, msum, offsets, members,
       labels, table, scal;
-  int* h_scal = nullptr;  // pinned mirror of scal
+  PinnedBuf h_scal;  // mirror of scal: DB_WORDS ints
   int64_t n_last = 0, K_last = 0, M_last = 0;
   bool ran = false;
   int64_t launches = 0;   // of the last run (tests/measure/bench_dbscan.py)
   bool profiling = false; // apdgicp_dbscan_set_profiling: events at the phase boundaries, one more wait at the end of a run
   hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double phase_ms[5] = {0, 0, 0, 0, 0};  // sort (cells, sort, sorted copy) / count / union + flatten / border / output
-  std::vector<DevBuf*> bufs() {
-    return {&stage, &stage_dop, &pts, &dop, &gkeys, &spts, &cnt, &core, &score, &parent, &root, &seed, &nextra, &size, &ncore, &rank_of, &cseed, &csize, &tsum, &mcount, &msum,
-            &offsets, &members, &labels, &table, &scal};
-  }
   ~apdgicp_dbscan() {
     if (stream) (void)hipStreamSynchronize(stream);
-    if (h_scal) (void)hipHostFree(h_scal);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
-    sort.release();
-    for (DevBuf* b : bufs()) b->release();
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -589,14 +527,14 @@ int ensure_corr_part(Engine& e, DevBuf& corr, DevBuf& part, size_t corr_bytes, s
 int reduce_and_read(Engine& e, const DevBuf& part, DevBuf& out, int nblk, int offset, double* H, double* b, double* cost, int* matched) {
   hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, part.as<double>(), nblk, offset, out.as<double>());
   APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe, out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(e.h_probe.p, out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   if (H && b) {
-    memcpy(H, e.h_probe, 36 * sizeof(double));
-    memcpy(b, e.h_probe + 36, 6 * sizeof(double));
+    memcpy(H, e.h_probe.p, 36 * sizeof(double));
+    memcpy(b, e.h_probe.as<double>() + 36, 6 * sizeof(double));
   }
-  if (cost) *cost = e.h_probe[42];
-  if (matched) *matched = (int)std::min(e.h_probe[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
+  if (cost) *cost = e.h_probe.as<double>()[42];
+  if (matched) *matched = (int)std::min(e.h_probe.as<double>()[43], 2147483647.0);  // (apdgicp_result::n_matched is an int32: saturates, see the header)
   return 0;
 }
 
@@ -920,14 +858,10 @@ constexpr int kVgbChunk = 4;  // ticks enqueued per look at the done counter (do
 
 int device_loop_ensure_words(apdgicp_batch* b, size_t ints) {
   DeviceLoop& l = b->loop;
-  if (l.h_words && ints <= l.h_words_cap) return 0;
+  if (ints * sizeof(int) <= l.h_words.cap) return 0;
   APD_HIP(hipStreamSynchronize(b->eng.stream));
-  if (l.h_words) APD_HIP(hipHostFree(l.h_words));
-  l.h_words = nullptr, l.h_words_cap = 0;
-  const size_t cap = std::max<size_t>(ints * 2, 1024);
-  APD_HIP(hipHostMalloc((void**)&l.h_words, cap * sizeof(int), hipHostMallocDefault));
-  memset(l.h_words, 0, cap * sizeof(int));
-  l.h_words_cap = cap;
+  APD_TRY(l.h_words.ensure(std::max<size_t>(ints * 2, 1024) * sizeof(int)));
+  memset(l.h_words.p, 0, l.h_words.cap);
   return 0;
 }
 
@@ -953,11 +887,11 @@ int batch_build_maps(apdgicp_batch* b, const std::vector<int>& slots, const char
   APD_TRY(b->sort.ensure(nmax));
   // (a slot with an offending point has key 0 there: its voxels are wrong and never used -- the align fails below before any pair runs)
   for (int t : todo) APD_TRY(launch(t));
-  int* hw = b->loop.h_words + 4;
+  int* hw = b->loop.h_words.as<int>() + 4;
   APD_HIP(hipMemcpyAsync(hw, scal.as<int>() + 4 * (size_t)lo, (size_t)(hi - lo + 1) * 16, hipMemcpyDeviceToHost, e.stream));
-  if (errflag) APD_HIP(hipMemcpyAsync(b->loop.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  if (errflag) APD_HIP(hipMemcpyAsync(b->loop.h_words.as<int>() + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
-  if (errflag) *errflag = b->loop.h_words[2];
+  if (errflag) *errflag = b->loop.h_words.as<int>()[2];
   int rc = 0;
   for (int t : todo) {
     const int* w = hw + 4 * (size_t)(t - lo);
@@ -981,8 +915,7 @@ int batch_ensure_slot_words(Engine& e, DevBuf& scal, int& scal_slots) {
   APD_TRY(grown.ensure((size_t)cap * 16));
   APD_HIP(hipStreamSynchronize(e.stream));
   if (scal_slots) APD_HIP(hipMemcpy(grown.p, scal.p, (size_t)scal_slots * 16, hipMemcpyDeviceToDevice));
-  scal.release();
-  scal = grown;
+  scal = std::move(grown);
   scal_slots = cap;
   return 0;
 }
@@ -1019,7 +952,7 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
     APD_HIP(hipGetLastError());
     ticks += todo;
     // the done counter as of this chunk, mirrored into the pinned word of the chunk's parity
-    APD_HIP(hipMemcpyAsync(v.h_words + (nchunks & 1), v.done.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipMemcpyAsync(v.h_words.as<int>() + (nchunks & 1), v.done.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
     APD_HIP(hipEventRecord(v.ev[nchunks & 1], e.stream));
     nchunks++;
     return 0;
@@ -1032,18 +965,18 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
     for (int waited = 0;; waited++) {
       if (ticks < bound) APD_TRY(enqueue_chunk());  // (one chunk ahead while the host waits for the one before)
       APD_HIP(hipEventSynchronize(v.ev[waited & 1]));
-      if (v.h_words[waited & 1] >= np || waited + 1 >= nchunks) break;
+      if (v.h_words.as<int>()[waited & 1] >= np || waited + 1 >= nchunks) break;
     }
   }
   // the covariance kernels' error flag (deferred by setup_pairs) with the final wait
-  APD_HIP(hipMemcpyAsync(v.h_words + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(v.h_words.as<int>() + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   for (Engine::Cloud& c : e.clouds) c.stage_pending = false, c.stage_wait = nullptr, c.stage_seq_word = nullptr;  // (every sort has run)
   e.n_stage_pending = 0;
   v.last_ticks = (int)ticks;
   e.last_ticks = (int)ticks;
-  if (v.h_words[2]) {
-    const int flag = v.h_words[2];
+  if (v.h_words.as<int>()[2]) {
+    const int flag = v.h_words.as<int>()[2];
     APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
     return fail(APDGICP_ERR_INTERNAL, Engine::errflag_text(flag));
   }
@@ -1940,18 +1873,19 @@ int apdgicp_debug_atan2f(int device, const float* y, const float* x, float* out,
     DevBuf buf;
     APD_TRY(buf.ensure((size_t)n * 12));
     float* dy = buf.as<float>();
-    int rc = 0;
-    hipError_t he = hipMemcpy(dy, y, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(dy + n, x, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (he == hipSuccess) {
-      hipLaunchKernelGGL(k_debug_atan2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dy, dy + n, dy + 2 * n, (long long)n);
-      he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpy(out, dy + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) rc = fail(APDGICP_ERR_HIP, hipGetErrorString(he));
-    buf.release();
-    return rc;
+    APD_HIP(hipMemcpy(dy, y, (size_t)n * 4, hipMemcpyHostToDevice));
+    APD_HIP(hipMemcpy(dy + n, x, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_debug_atan2f, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, dy, dy + n, dy + 2 * n, (long long)n);
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpy(out, dy + 2 * n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return 0;
   });
+}
+
+int apdgicp_debug_live_buffers(int64_t* device_buffers, int64_t* pinned_buffers) {
+  if (device_buffers) *device_buffers = DevBuf::live.load();
+  if (pinned_buffers) *pinned_buffers = PinnedBuf::live.load();
+  return 0;
 }
 
 int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
@@ -2012,10 +1946,10 @@ static int nn_range_stats(apdgicp_handle* h, const float T[16], double max_range
   APD_HIP(hipMemsetAsync(e.d_probe.p, 0, 2 * sizeof(double), e.stream));
   hipLaunchKernelGGL(k_fitness, dim3((unsigned)e.work.nblk_max, 1), dim3(LIN_BLK), 0, e.stream, e.d_desc.as<CloudDesc>(), e.d_pairs.as<PairDesc>(), e.work,
                      max_range2, e.d_probe.as<double>(), strict);
-  APD_HIP(hipMemcpyAsync(e.h_probe, e.d_probe.p, 2 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(e.h_probe.p, e.d_probe.p, 2 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   h->have_corr = false;  // the nn partials were overwritten at another pose
-  *sum = e.h_probe[0], *cnt = e.h_probe[1];
+  *sum = e.h_probe.as<double>()[0], *cnt = e.h_probe.as<double>()[1];
   return 0;
 }
 
@@ -2101,7 +2035,7 @@ int apdgicp_get_points(apdgicp_handle* h, int which, float* out_xyz, int64_t n) 
     if (n != c.n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the cloud size");
     APD_HIP(hipSetDevice(e.device));
     if (c.staged) {  // a scan-sized host cloud still waiting in its pinned buffer for the sort: the float4 copy is right there
-      const float4* p = (const float4*)c.stage_p;
+      const float4* p = c.stage.as<const float4>();
       for (int64_t i = 0; i < n; i++) out_xyz[3 * i] = p[i].x, out_xyz[3 * i + 1] = p[i].y, out_xyz[3 * i + 2] = p[i].z;
       return 0;
     }
@@ -2177,8 +2111,7 @@ int apdgicp_batch_clear(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   APD_TRY(b->eng.pool_leave());
   APD_HIP(hipStreamSynchronize(b->eng.stream));
-  for (auto& c : b->eng.clouds) c.release_all();
-  b->eng.clouds.clear();
+  b->eng.clouds.clear();  // (frees every slot's buffers)
   b->eng.clouds_written();
   b->release_voxel_modes();  // (V8 / N10: every slot's map and inverse permutation go with the clouds)
   return 0;
@@ -2513,7 +2446,7 @@ int apdgicp_submap_create(int device, void* stream, apdgicp_submap** out) {
       }
       s->own_stream = true;
     }
-    if (hipHostMalloc((void**)&s->h_scal, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess || s->scal.ensure(8 * sizeof(int)) < 0) {
+    if (s->h_scal.ensure(2 * sizeof(int)) < 0 || s->scal.ensure(8 * sizeof(int)) < 0) {
       delete s;
       return fail(APDGICP_ERR_HIP, "allocation failed");
     }
@@ -2611,9 +2544,9 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
     hipLaunchKernelGGL(k_vox_centroids, dim3((np2 + 255) / 256), dim3(256), 0, s->stream, keys, s->cat.as<float4>(), s->pos.as<int>(),
                        s->bsum.as<int>(), np2, s->out.as<float4>(), n);
     APD_HIP(hipGetLastError());
-    APD_HIP(hipMemcpyAsync(s->h_scal, d_total, 2 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    APD_HIP(hipMemcpyAsync(s->h_scal.p, d_total, 2 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
     APD_HIP(hipStreamSynchronize(s->stream));
-    if (s->h_scal[1] == 5) {
+    if (s->h_scal.as<int>()[1] == 5) {
       // pcl::VoxelGrid::applyFilter (filters/impl/voxel_grid.hpp): "Leaf size is too small for the input dataset. Integer indices would
       // overflow." is a WARNING there and the output is the input cloud, unfiltered -- so is it here: the assembled (transformed,
       // concatenated) cloud itself, the same line on stderr, success; apdgicp_last_error() holds the message.
@@ -2624,8 +2557,8 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
       *n_out = n;
       return 0;
     }
-    if (s->h_scal[1]) return fail(APDGICP_ERR_INTERNAL, "voxel filter failed");
-    s->n_last = s->h_scal[0], s->last_is_cat = false;
+    if (s->h_scal.as<int>()[1]) return fail(APDGICP_ERR_INTERNAL, "voxel filter failed");
+    s->n_last = s->h_scal.as<int>()[0], s->last_is_cat = false;
     *n_out = s->n_last;
     return 0;
   });
@@ -2698,7 +2631,7 @@ int apdgicp_scan_filter_create(const apdgicp_scan_filter_params* p, int device, 
       APD_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
       f->own_stream = true;
     }
-    APD_HIP(hipHostMalloc((void**)&f->h_scal, 64, hipHostMallocDefault));
+    APD_TRY(f->h_scal.ensure(64));
     APD_TRY(f->scal.ensure(64));
     APD_TRY(apdgicp_submap_create(device, f->stream, &f->vox));
     *out = f.release();
@@ -2751,7 +2684,7 @@ int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n,
     }
     int* d_counts = f->scal.as<int>();
     double* d_thr = (double*)(f->scal.as<char>() + 16);
-    int* h_counts = (int*)f->h_scal;
+    int* h_counts = f->h_scal.as<int>();
     APD_TRY(f->gated.ensure((size_t)n * 16));
     APD_TRY(f->bsum.ensure((size_t)((n + FLT_BLK - 1) / FLT_BLK) * 4));
     APD_HIP(hipMemsetAsync(f->scal.p, 0, 64, f->stream));
@@ -2776,8 +2709,8 @@ int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n,
       step2 = f->dense.as<float4>();
     }
     auto read_back = [&](bool with_engine_flag) -> int {
-      APD_HIP(hipMemcpyAsync(f->h_scal, f->scal.p, 40, hipMemcpyDeviceToHost, f->stream));
-      if (with_engine_flag) APD_HIP(hipMemcpyAsync(f->h_scal + 40, f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+      APD_HIP(hipMemcpyAsync(f->h_scal.p, f->scal.p, 40, hipMemcpyDeviceToHost, f->stream));
+      if (with_engine_flag) APD_HIP(hipMemcpyAsync(f->h_scal.as<char>() + 40, f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
       APD_HIP(hipStreamSynchronize(f->stream));
       return 0;
     };
@@ -2835,12 +2768,12 @@ int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n,
     if (statistical) hipLaunchKernelGGL(k_flt_threshold, dim3(1), dim3(FLT_BLK), 0, f->stream, stat, n2, P.stddev_mul, d_thr);
     APD_TRY((scan_filter_compact<1>(f, step2, stat, r2, statistical ? d_thr + 2 : nullptr, n2, f->out.as<float4>(), f->kept.as<unsigned char>(), d_counts + 2)));
     APD_TRY(read_back(true));
-    const int flag = *(int*)(f->h_scal + 40);
+    const int flag = *(int*)(f->h_scal.as<char>() + 40);
     if (flag) {
       APD_HIP(hipMemsetAsync(E.d_errflag.p, 0, sizeof(int), f->stream));
       return fail(APDGICP_ERR_INTERNAL, "outlier filter k-NN: " + Engine::errflag_text(flag));
     }
-    const double* h_thr = (const double*)(f->h_scal + 16);
+    const double* h_thr = (const double*)(f->h_scal.as<char>() + 16);
     f->n_stat = n2;
     if (statistical) f->mean = h_thr[0], f->stddev = h_thr[1], f->thr = h_thr[2];
     else f->thr = r2;
@@ -2959,8 +2892,8 @@ int apdgicp_ego_velocity_create(const apdgicp_ego_velocity_params* p, int device
       APD_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
       e->own_stream = true;
     }
-    APD_HIP(hipHostMalloc((void**)&e->h_rec, sizeof(EgoRecord), hipHostMallocDefault));
-    memset(e->h_rec, 0, sizeof(EgoRecord));
+    APD_TRY(e->h_rec.ensure(sizeof(EgoRecord)));
+    memset(e->h_rec.p, 0, sizeof(EgoRecord));
     APD_TRY(e->rec.ensure(sizeof(EgoRecord)));
     APD_TRY(e->vk.ensure((size_t)EGO_MAX_K * 3 * sizeof(double)));
     APD_TRY(e->n_in.ensure((size_t)EGO_MAX_K * sizeof(int)));
@@ -2995,7 +2928,7 @@ int apdgicp_ego_velocity_run(apdgicp_ego_velocity* e, const float* pts, int64_t 
     memset(result, 0, sizeof(*result));
     result->best_in = result->best_out = -1;
     e->ran = false, e->n_last = 0;
-    memset(e->h_rec, 0, sizeof(EgoRecord));
+    memset(e->h_rec.p, 0, sizeof(EgoRecord));
     if (n < 0 || (n > 0 && !pts)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
     if (stride_bytes < 20 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 20");
     for (int64_t off : {intensity_offset_bytes, doppler_offset_bytes})
@@ -3067,10 +3000,10 @@ int apdgicp_ego_velocity_run(apdgicp_ego_velocity* e, const float* pts, int64_t 
                        e->out_dop.as<float>(), e->out_src.as<int>());
     hipLaunchKernelGGL(k_ego_lsq, dim3(1), dim3(EGO_BLK), 0, e->stream, rows, e->in_row.as<int>(), D, rec);
     APD_HIP(hipGetLastError());
-    APD_HIP(hipMemcpyAsync(e->h_rec, e->rec.p, sizeof(EgoRecord), hipMemcpyDeviceToHost, e->stream));
+    APD_HIP(hipMemcpyAsync(e->h_rec.p, e->rec.p, sizeof(EgoRecord), hipMemcpyDeviceToHost, e->stream));
     APD_HIP(hipStreamSynchronize(e->stream));  // the one wait of the call
-    memcpy(result, e->h_rec, sizeof(*result));
-    if (e->h_rec->mode != EGO_MODE_RANSAC) result->best_in = result->best_out = -1;
+    memcpy(result, e->h_rec.p, sizeof(*result));
+    if (e->record()->mode != EGO_MODE_RANSAC) result->best_in = result->best_out = -1;
     result->K = K;
     e->n_last = n, e->ran = true;
     return 0;
@@ -3079,7 +3012,7 @@ int apdgicp_ego_velocity_run(apdgicp_ego_velocity* e, const float* pts, int64_t 
 
 static int ego_cloud(apdgicp_ego_velocity* e, int which, const float** xyzi, const float** dop, const int32_t** index, int64_t* n) {
   if (!e || which < 0 || which > 1) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
-  const int64_t cnt = e->ran ? (which ? e->h_rec->n_outlier : e->h_rec->n_inlier) : 0;
+  const int64_t cnt = e->ran ? (which ? e->record()->n_outlier : e->record()->n_inlier) : 0;
   if (xyzi) *xyzi = cnt ? (which ? e->out_xyzi : e->in_xyzi).as<float>() : nullptr;
   if (dop) *dop = cnt ? (which ? e->out_dop : e->in_dop).as<float>() : nullptr;
   if (index) *index = cnt ? (which ? e->out_src : e->in_src).as<int32_t>() : nullptr;
@@ -3127,16 +3060,16 @@ int apdgicp_ego_velocity_debug(apdgicp_ego_velocity* e, uint8_t* valid, int64_t 
                                int64_t samples_capacity, float* selected_abs_v) {
   return guarded([&]() -> int {
     if (!e) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    const int m = e->ran ? e->h_rec->m : 0;
+    const int m = e->ran ? e->record()->m : 0;
     if (e->ran && ((valid && valid_capacity < e->n_last) || (rows && rows_capacity < m) ||
-                   (samples && e->h_rec->mode == EGO_MODE_RANSAC && samples_capacity < (int64_t)e->K_last * e->S_last)))
+                   (samples && e->record()->mode == EGO_MODE_RANSAC && samples_capacity < (int64_t)e->K_last * e->S_last)))
       return fail(APDGICP_ERR_INVALID_ARG, "a destination holds fewer entries than the last run produced");
-    if (selected_abs_v) memcpy(selected_abs_v, &e->h_rec->sel_bits, 4);
+    if (selected_abs_v) memcpy(selected_abs_v, &e->record()->sel_bits, 4);
     if (!e->ran) return 0;
     APD_HIP(hipSetDevice(e->device));
     if (valid) APD_HIP(hipMemcpyAsync(valid, e->valid.p, (size_t)e->n_last, hipMemcpyDeviceToHost, e->stream));
     if (rows && m) APD_HIP(hipMemcpyAsync(rows, e->rows.p, (size_t)m * 32, hipMemcpyDeviceToHost, e->stream));
-    if (samples && e->h_rec->mode == EGO_MODE_RANSAC)
+    if (samples && e->record()->mode == EGO_MODE_RANSAC)
       APD_HIP(hipMemcpyAsync(samples, e->samples.p, (size_t)e->K_last * e->S_last * sizeof(int), hipMemcpyDeviceToHost, e->stream));
     APD_HIP(hipStreamSynchronize(e->stream));
     return 0;
@@ -3194,8 +3127,8 @@ int apdgicp_floor_create(const apdgicp_floor_params* p, int device, void* stream
       APD_HIP(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
       f->own_stream = true;
     }
-    APD_HIP(hipHostMalloc((void**)&f->h_rec, sizeof(FloorRecord) + 16, hipHostMallocDefault));
-    memset(f->h_rec, 0, sizeof(FloorRecord) + 16);
+    APD_TRY(f->h_rec.ensure(sizeof(FloorRecord) + 16));
+    memset(f->h_rec.p, 0, sizeof(FloorRecord) + 16);
     APD_TRY(f->rec.ensure(sizeof(FloorRecord)));
     APD_TRY(f->state.ensure(sizeof(FloorState)));
     APD_TRY(f->coef.ensure((size_t)FLOOR_MAX_K * sizeof(float4)));
@@ -3244,7 +3177,7 @@ int apdgicp_floor_run(apdgicp_floor* f, const float* xyz, int64_t n, int64_t str
     memset(result, 0, sizeof(*result));
     result->winner = -1;
     f->ran = false, f->stat_valid = false, f->n_last = 0;
-    memset(f->h_rec, 0, sizeof(FloorRecord) + 16);
+    memset(f->h_rec.p, 0, sizeof(FloorRecord) + 16);
     if (n < 0 || (n > 0 && !xyz)) return fail(APDGICP_ERR_INVALID_ARG, "bad cloud");
     if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
     if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
@@ -3303,7 +3236,7 @@ int apdgicp_floor_run(apdgicp_floor* f, const float* xyz, int64_t n, int64_t str
     // 2. the normal filter: the exact k-NN of the registration over the clipped cloud, whose size the host has to know
     bool searched = false;
     if (P.use_normal_filtering) {
-      APD_HIP(hipMemcpyAsync(f->h_rec, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
+      APD_HIP(hipMemcpyAsync(f->h_rec.p, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
       APD_HIP(hipStreamSynchronize(f->stream));
       const int nc = f->record()->n_clipped;
       D.nf_mode = nc >= P.normal_k ? FLOOR_NF_STAT : FLOOR_NF_NONE;
@@ -3344,10 +3277,10 @@ int apdgicp_floor_run(apdgicp_floor* f, const float* xyz, int64_t n, int64_t str
     hipLaunchKernelGGL(k_floor_emit_scatter, dim3(nb), dim3(FLOOR_BLK), 0, f->stream, filt, f->filt_src.as<int>(), d_in, ni, stride, ioff, D, rec, st, bsum + 2 * nb,
                        bsum + 3 * nb, f->in_xyzi.as<float4>(), f->in_src.as<int>(), f->in_row.as<int>(), f->under_xyzi.as<float4>(), f->under_src.as<int>());
     APD_HIP(hipGetLastError());
-    APD_HIP(hipMemcpyAsync(f->h_rec, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
-    if (searched) APD_HIP(hipMemcpyAsync(f->h_rec + sizeof(FloorRecord), f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
+    APD_HIP(hipMemcpyAsync(f->h_rec.p, f->rec.p, sizeof(FloorRecord), hipMemcpyDeviceToHost, f->stream));
+    if (searched) APD_HIP(hipMemcpyAsync(f->h_rec.as<char>() + sizeof(FloorRecord), f->eng->d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, f->stream));
     APD_HIP(hipStreamSynchronize(f->stream));  // the wait for the result record
-    const int flag = *(int*)(f->h_rec + sizeof(FloorRecord));
+    const int flag = *(int*)(f->h_rec.as<char>() + sizeof(FloorRecord));
     if (flag) {
       APD_HIP(hipMemsetAsync(f->eng->d_errflag.p, 0, sizeof(int), f->stream));
       return fail(APDGICP_ERR_INTERNAL, "normal filter k-NN: " + Engine::errflag_text(flag));
@@ -3450,7 +3383,7 @@ int apdgicp_map_cloud_create(int device, void* stream, apdgicp_map_cloud** out) 
       APD_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
       m->own_stream = true;
     }
-    APD_HIP(hipHostMalloc((void**)&m->h_state, sizeof(MapState), hipHostMallocDefault));
+    APD_TRY(m->h_state.ensure(sizeof(MapState)));
     APD_TRY(m->state.ensure(sizeof(MapState)));
     for (hipEvent_t& e : m->ev) APD_HIP(hipEventCreate(&e));
     *out = m.release();
@@ -3496,12 +3429,9 @@ int apdgicp_map_cloud_add_keyframe(apdgicp_map_cloud* m, const float* xyz, int64
         APD_HIP(hipStreamSynchronize(m->stream));  // the caller's memory is free again when the call returns
         return 0;
       }();
-      if (rc < 0) {
-        kf.pts.release();
-        return rc;
-      }
+      if (rc < 0) return rc;
     }
-    m->kfs.push_back(kf);
+    m->kfs.push_back(std::move(kf));
     *id = (int32_t)(m->kfs.size() - 1);
     return 0;
   });
@@ -3512,8 +3442,7 @@ int apdgicp_map_cloud_clear(apdgicp_map_cloud* m) {
     if (!m) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_HIP(hipSetDevice(m->device));
     APD_HIP(hipStreamSynchronize(m->stream));
-    for (auto& k : m->kfs) k.pts.release();
-    m->kfs.clear();
+    m->kfs.clear();  // (frees every keyframe's points)
     m->forget();
     return 0;
   });
@@ -3547,7 +3476,7 @@ int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const 
     MapState* st = m->state.as<MapState>();
     auto fetch_state = [&]() -> int {
       APD_HIP(hipGetLastError());
-      APD_HIP(hipMemcpyAsync(m->h_state, st, sizeof(MapState), hipMemcpyDeviceToHost, m->stream));
+      APD_HIP(hipMemcpyAsync(m->h_state.p, st, sizeof(MapState), hipMemcpyDeviceToHost, m->stream));
       APD_HIP(hipStreamSynchronize(m->stream));
       return 0;
     };
@@ -3568,7 +3497,7 @@ int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const 
                        m->pushed.as<float4>(), st);
     APD_HIP(hipEventRecord(m->ev[1], m->stream));
     APD_TRY(fetch_state());
-    const MapState& h = *m->h_state;
+    const MapState& h = *m->h_state.as<MapState>();
     const int n_pushed = h.n_pushed, n_fin = h.n_finite;
     m->info.n_pushed = n_pushed, m->info.n_finite = n_fin;
     if (resolution <= 0.0) {  // M2
@@ -3708,25 +3637,13 @@ int sc_reserve(apdgicp_scan_context* h) {
   const size_t per[4] = {R * S * 4, R * 4, S * 8, S * 8};
   DevBuf* old[4] = {&h->desc, &h->ring_key, &h->sector_key, &h->col_norm};
   DevBuf fresh[4];
-  for (int b = 0; b < 4; b++) {
-    const int rc = fresh[b].ensure(per[b] * ncap);
-    if (rc < 0) {
-      for (DevBuf& f : fresh) f.release();
-      return rc;
-    }
-  }
+  for (int b = 0; b < 4; b++) APD_TRY(fresh[b].ensure(per[b] * ncap));
   hipError_t e = hipSuccess;
   for (int b = 0; b < 4 && e == hipSuccess; b++)
     if (h->size) e = hipMemcpyAsync(fresh[b].p, old[b]->p, per[b] * h->size, hipMemcpyDeviceToDevice, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) {
-    for (DevBuf& f : fresh) f.release();
-    return fail(APDGICP_ERR_HIP, std::string("scan context: growing the database: ") + hipGetErrorString(e));
-  }
-  for (int b = 0; b < 4; b++) {
-    old[b]->release();
-    *old[b] = fresh[b];
-  }
+  if (e != hipSuccess) return fail(APDGICP_ERR_HIP, std::string("scan context: growing the database: ") + hipGetErrorString(e));
+  for (int b = 0; b < 4; b++) *old[b] = std::move(fresh[b]);
   h->cap = ncap;
   return 0;
 }
@@ -3911,11 +3828,8 @@ int apdgicp_scan_context_detect_batch(apdgicp_scan_context* h, int32_t n_queries
       APD_TRY(h->lo2.ensure(total * 4));
       APD_TRY(h->inv2.ensure(total * 4));
       APD_TRY(h->out.ensure((size_t)total_out * sizeof(ScRec)));
-      if ((size_t)total_out > h->h_out_cap) {
-        if (h->h_out) APD_HIP(hipHostFree(h->h_out));
-        h->h_out = nullptr, h->h_out_cap = 0;
-        APD_HIP(hipHostMalloc((void**)&h->h_out, (size_t)total_out * 2 * sizeof(ScRec), hipHostMallocDefault));
-        h->h_out_cap = (size_t)total_out * 2;
+      if ((size_t)total_out * sizeof(ScRec) > h->h_out.cap) {
+        APD_TRY(h->h_out.ensure((size_t)total_out * 2 * sizeof(ScRec)));
       }
       const ScQuery* dq = h->qtab.dev.as<ScQuery>();
       const int* dc = h->cand.dev.as<int>();
@@ -3934,17 +3848,17 @@ int apdgicp_scan_context_detect_batch(apdgicp_scan_context* h, int32_t n_queries
       hipLaunchKernelGGL(k_sc_emit, dim3((unsigned)((max_out + SC_BLK - 1) / SC_BLK), nq), dim3(SC_BLK), 0, h->stream, dq, h->inv2.as<int>(), h->rec.as<ScRec>(),
                          h->out.as<ScRec>());
       APD_HIP(hipGetLastError());
-      APD_HIP(hipMemcpyAsync(h->h_out, h->out.p, (size_t)total_out * sizeof(ScRec), hipMemcpyDeviceToHost, h->stream));
+      APD_HIP(hipMemcpyAsync(h->h_out.p, h->out.p, (size_t)total_out * sizeof(ScRec), hipMemcpyDeviceToHost, h->stream));
       APD_HIP(hipStreamSynchronize(h->stream));  // the call's one wait
     }
     for (int q = 0; q < n_queries; q++) {
       const ScQuery& Q = qs[(size_t)q];
       n_matches[q] = Q.m_out;
-      if (Q.m_out) memcpy(matches + (size_t)q * top_k, h->h_out + Q.out_base, (size_t)Q.m_out * sizeof(ScRec));
+      if (Q.m_out) memcpy(matches + (size_t)q * top_k, h->h_out.as<ScRec>() + Q.out_base, (size_t)Q.m_out * sizeof(ScRec));
       int loop = -1;
       float yaw = 0.f;
       if (Q.m_out) {
-        const ScRec& m = h->h_out[Q.out_base];
+        const ScRec& m = h->h_out.as<ScRec>()[Q.out_base];
         if (m.distance < p.dist_thresh) loop = m.id;  // SC:359-361
         yaw = (float)((double)(float)(m.shift * ((p.azimuth_max - p.azimuth_min) / (double)S)) * 3.14159265358979323846 / 180.0);  // SC:374, :18-21
       }
@@ -4018,8 +3932,8 @@ int apdgicp_dbscan_create(const apdgicp_dbscan_params* p, int device, void* stre
       APD_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
       h->own_stream = true;
     }
-    APD_HIP(hipHostMalloc((void**)&h->h_scal, DB_WORDS * sizeof(int), hipHostMallocDefault));
-    memset(h->h_scal, 0, DB_WORDS * sizeof(int));
+    APD_TRY(h->h_scal.ensure(DB_WORDS * sizeof(int)));
+    memset(h->h_scal.p, 0, DB_WORDS * sizeof(int));
     APD_TRY(h->scal.ensure(DB_WORDS * sizeof(int)));
     *out = h.release();
     return 0;
@@ -4144,13 +4058,13 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
     hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, st, h->tsum.as<int>(), nt, scal + DB_W_M);
     h->launches += 10;
     APD_HIP(hipGetLastError());
-    APD_HIP(hipMemcpyAsync(h->h_scal, h->scal.p, DB_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
+    APD_HIP(hipMemcpyAsync(h->h_scal.p, h->scal.p, DB_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
     APD_HIP(hipStreamSynchronize(st));  // the one wait of the call
-    if (h->h_scal[DB_W_BAD] != 0)
-      return fail(APDGICP_ERR_UNSUPPORTED, "DBSCAN: point " + std::to_string(DB_BAD_BASE - h->h_scal[DB_W_BAD]) + " lies 2^20 cells or more from the origin (cell side " +
+    if (h->h_scal.as<int>()[DB_W_BAD] != 0)
+      return fail(APDGICP_ERR_UNSUPPORTED, "DBSCAN: point " + std::to_string(DB_BAD_BASE - h->h_scal.as<int>()[DB_W_BAD]) + " lies 2^20 cells or more from the origin (cell side " +
                                                std::to_string(cell) + ")");
-    const int K = h->h_scal[DB_W_K];
-    const int64_t M = h->h_scal[DB_W_M];
+    const int K = h->h_scal.as<int>()[DB_W_K];
+    const int64_t M = h->h_scal.as<int>()[DB_W_M];
     if (K < 0 || K > ni || M < K || M > (1ll << 30)) return fail(APDGICP_ERR_INTERNAL, "DBSCAN: inconsistent cluster count");
     if (K > 0) {
       const int Mi = (int)M, p2 = std::max(1, (bits_for(K) + 7) / 8);

@@ -83,7 +83,7 @@ assert RESULT_DTYPE.itemsize == C.sizeof(Result) == 96
 # every symbol include/apdgicp_hip.h declares (tests check that the library exports all of them)
 SYMBOLS = [
     "apdgicp_abi_version", "apdgicp_source_stamp", "apdgicp_build_flags", "apdgicp_last_error", "apdgicp_device_count", "apdgicp_default_params",
-    "apdgicp_set_trace", "apdgicp_get_trace", "apdgicp_get_trace_step_norms", "apdgicp_debug_atan2f", "apdgicp_nearest_neighbours", "apdgicp_nearest_neighbours_of", "apdgicp_get_points",
+    "apdgicp_set_trace", "apdgicp_get_trace", "apdgicp_get_trace_step_norms", "apdgicp_debug_atan2f", "apdgicp_debug_live_buffers", "apdgicp_nearest_neighbours", "apdgicp_nearest_neighbours_of", "apdgicp_get_points",
     "apdgicp_create", "apdgicp_destroy", "apdgicp_set_params", "apdgicp_get_params",
     "apdgicp_set_source", "apdgicp_set_target", "apdgicp_clear_source", "apdgicp_clear_target",
     "apdgicp_swap_source_and_target", "apdgicp_compute_covariances", "apdgicp_get_covariances",
@@ -190,6 +190,7 @@ def load_library(path: str | None = None):
     L.apdgicp_get_trace.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(i64), i64, vp, C.POINTER(i64)]
     L.apdgicp_get_trace_step_norms.argtypes = [vp, i64, vp, C.POINTER(i64)]
     L.apdgicp_debug_atan2f.argtypes = [i32, vp, vp, vp, i64]
+    L.apdgicp_debug_live_buffers.argtypes = [C.POINTER(i64), C.POINTER(i64)]
     L.apdgicp_nearest_neighbours.argtypes = [vp, vp, vp, vp, i64]
     L.apdgicp_nearest_neighbours_of.argtypes = [vp, vp, i64, i64, vp, vp]
     L.apdgicp_get_points.argtypes = [vp, i32, vp, i64]

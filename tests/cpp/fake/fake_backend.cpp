@@ -128,7 +128,13 @@ hipError_t hipEventDestroy(hipEvent_t e) {
   return hipSuccess;
 }
 static std::atomic<long> g_live_allocs{0};
+static std::atomic<long> g_allocs_until_failure{-1};  // fake_fail_allocations_after (tests/cpp/fake/test_devbuf.cpp): < 0 never
 hipError_t hipMalloc(void** p, size_t bytes) {
+  if (g_allocs_until_failure.load() >= 0 && g_allocs_until_failure.fetch_sub(1) <= 0) {
+    g_allocs_until_failure = 0;
+    *p = nullptr;
+    return hipErrorUnknown;
+  }
   *p = std::malloc(bytes ? bytes : 1);
   g_live_allocs++;
   return *p ? hipSuccess : hipErrorUnknown;
@@ -157,6 +163,8 @@ hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKin
   return hipSuccess;
 }
 long fake_live_allocations() { return g_live_allocs.load(); }
+void fake_fail_allocations_after(long n) { g_allocs_until_failure = n; }  // the next n succeed, every later one fails; n < 0: none fails
+const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "fake error"; }
 }
 
 // ------------------------------------------------------------------ RCCL

@@ -1,4 +1,4 @@
-// TEST-ONLY stand-in for the slice of <hip/hip_runtime_api.h> that riv-slam_amd/cpp/sharded_batch_hip.hpp calls, so that the aligner's HOST
+// TEST-ONLY stand-in for the slice of <hip/hip_runtime_api.h> that riv-slam_amd/cpp/sharded_batch_hip.hpp and riv-slam_amd/csrc/apd_devbuf.hpp call, so that the aligner's HOST
 // logic -- worker threads, queues, slots, late gathers, abort -- runs on the CPU box under ThreadSanitizer / AddressSanitizer
 // (tests/test_sanitizers.py).  Never shipped, never on the include path of a product build.  Semantics kept: streams are in-order
 // queues with an executor thread each (they make progress on their own, like device queues), events mark a position in a stream, "device"
@@ -12,6 +12,7 @@ typedef struct fakeStream* hipStream_t;
 typedef struct fakeEvent* hipEvent_t;
 enum hipMemcpyKind { hipMemcpyHostToHost = 0, hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 };
 enum { hipStreamNonBlocking = 1, hipEventDisableTiming = 2, hipHostMallocDefault = 0 };
+const char* hipGetErrorString(hipError_t e);
 hipError_t hipSetDevice(int device);
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned flags);
 hipError_t hipStreamSynchronize(hipStream_t s);

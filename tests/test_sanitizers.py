@@ -4,7 +4,7 @@ No sanitizer runs on the GPU box (not available there); what can race or overrun
 apdgicp_* calls, so a test-only, link-time fake of those three call families (tests/cpp/fake/, never shipped) lets the real
 `ShardedBatchAlignerHip` -- worker threads, queues, slots, late gathers, abort_all -- run the schedule of tests/cpp/test_multi_device.cpp on
 four fake devices; the engine's own host code that needs no HIP at all (riv-slam_amd/csrc/apd_hostpack.hpp: packing host clouds, the
-process-wide thread pool) is compiled as it is.  Also: the sanitizer build of the ORACLE (oracle/Makefile) runs a registration."""
+process-wide thread pool; riv-slam_amd/csrc/apd_devbuf.hpp: the owners of device and pinned memory) is compiled as it is.  Also: the sanitizer build of the ORACLE (oracle/Makefile) runs a registration."""
 import os
 import shutil
 import subprocess
@@ -61,6 +61,16 @@ def test_host_cloud_packing_and_the_host_pool_under_sanitizers(san):
     exe = _compile([os.path.join(FAKE, "test_hostpack.cpp")], os.path.join(OUT, "hostpack_" + san.split(",")[0]), san,
                    [os.path.join(ROOT, "riv-slam_amd", "csrc")], need_clang=True)
     _run(exe, {"TSAN_OPTIONS": "halt_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+
+
+def test_buffer_owners_under_sanitizers():
+    """riv-slam_amd/csrc/apd_devbuf.hpp as the library compiles it, against the fake runtime (its hipMalloc is malloc, so a double free or a use
+    after free is a report and fake_live_allocations() counts leaks): DevBuf, PinnedBuf and CachedTable::dev through ensure / release / moves /
+    std::swap, a vector of owners resized up and down, the four-buffer growth of the scan-context database with an allocation failing half way."""
+    exe = _compile([os.path.join(FAKE, "test_devbuf.cpp"), os.path.join(FAKE, "fake_backend.cpp")], os.path.join(OUT, "devbuf_address"), "address,undefined",
+                   [os.path.join(FAKE, "include"), os.path.join(ROOT, "include"), os.path.join(ROOT, "riv-slam_amd", "csrc")])
+    rep = _run(exe, {"ASAN_OPTIONS": "detect_leaks=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    assert "live_allocations 0 device 0 pinned 0" in rep
 
 
 def test_the_oracle_runs_clean_under_address_sanitizer(tmp_path):
