@@ -46,7 +46,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_batch_set_vgicp / _get_vgicp and the apdgicp_batch_vgicp_* calls (voxelized GICP as a mode of the batch handle);
                                       still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_ndt / _get_ndt and the apdgicp_batch_ndt_* calls (NDT as a mode of the batch handle);
-                                      still 6 (additive): + apdgicp_debug_live_buffers */
+                                      still 6 (additive): + apdgicp_debug_live_buffers;
+                                      still 6 (additive): + the apdgicp_scan_ingest_* object (power gate and packing of a radar message, IMU deskew, frame transform) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -714,7 +715,7 @@ int apdgicp_scan_filter_scores(apdgicp_scan_filter* f, float* stat, uint8_t* kep
  *      returns true on every path (E:302): success = 1 whenever the inlier list is not empty; sigma_in_bounds says whether
  *      diag C >= 0 and sigma < max_sigma_* held (if diag C < 0, sigma holds diag C as in the reference).
  *   use_ransac = 0 (E:138-142): every valid row is an inlier, step 6 alone.
- * Not part of this object: deskewing (:792), bdcSvd.  The radius filter on the outlier cloud (:766-774) is the scan filter with
+ * Not part of this object: bdcSvd; deskewing (:792) is apdgicp_scan_ingest_deskew below, which takes _inliers' device pointer.  The radius filter on the outlier cloud (:766-774) is the scan filter with
  * APDGICP_OUTLIER_RADIUS, its clustering into moving objects apdgicp_dbscan_* below; both take the device pointers of _outliers. */
 typedef struct {
   float min_dist;                             /* EH:32 ; default 0.1 */
@@ -1096,6 +1097,79 @@ int apdgicp_dbscan_debug(apdgicp_dbscan* h, int32_t* cnt, uint8_t* core, int32_t
  * the wait, member lists, labels, table}.  Any destination may be NULL. */
 int apdgicp_dbscan_set_profiling(apdgicp_dbscan* h, int enable);
 int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, double phase_ms[5]);
+
+/* ------------------------------------------------------------------ scan ingest and deskew: the two ends of cloud_callback
+ * What PreprocessingNodelet::cloud_callback ("P:" = radar_graph_slam/apps/preprocessing_nodelet.cpp) does to the message before the
+ * ego-velocity estimate (P:667-697; the hugin callback P:497-506) and to src_cloud between that estimate and distance_filter
+ * (deskewing P:914-975, the base-link transform P:796-810).  With this object every per-point step of the callback is on the device:
+ *   _run -> apdgicp_ego_velocity_run on the rows -> its inliers (or the rows) -> _deskew -> apdgicp_scan_filter_run -> apdgicp_set_source.
+ *   I1. Lanes (P:667-683, P:497-506).  A point's x, y, z are three consecutive floats at xyz + i * xyz_stride_bytes; intensity (the
+ *       message's "Power") and doppler are one float each at their own base and stride.  geometry_msgs::Point32[] plus channels[2] /
+ *       channels[0]: strides 12 / 4 / 4.  A sensor_msgs::PointCloud2 or any array of structures: all strides = point_step, the bases
+ *       offset by the field offsets.  Strides are multiples of 4, >= 12 / 4 / 4.  Input order is kept.  on_device = 0: the lanes are
+ *       staged by copies on the object's stream without a wait (one copy when they are fields of one array of structures).
+ *   I2. Gate (P:670-673), gate = 1.  A point is kept iff power > power_threshold (fp32; a NaN power fails) and none of x, y, z equals
+ *       +infinity.  The reference's `== NAN` tests are never true: a NaN coordinate is kept.  -infinity is kept.  gate = 0 (P:497-506):
+ *       every point is kept.
+ *   I3. Pre-transform (P:477-480), applied to the kept points.  pre_transform == NULL: none.  Otherwise x, y, z become rows 0..2 of the
+ *       column-major 4x4 times (x, y, z, 1) in fp32: (r0 x + r1 y) + (r2 z + t), or ((r0 x + r1 y) + r2 z) + t with
+ *       APDGICP_FLAG_XF_LINEAR_CHAIN in params.flags -- the order of apdgicp_params.flags and of M1 of the map cloud.  Eigen's own order
+ *       is not pinned by the reference tree.
+ *   I4. Output of _run.  n_out rows of 32 bytes {x, y, z, intensity, doppler, 0, 0, 0}: what apdgicp_ego_velocity_run(..., stride 32,
+ *       intensity offset 12, doppler offset 16, on_device = 1) accepts, and apdgicp_scan_filter_run, apdgicp_set_source and
+ *       apdgicp_dbscan_run likewise.  Beside the rows one int32 per row: the point's index in the message.  One host wait per run, for
+ *       n_out.  n = 0: n_out = 0, status 0.  At most 2^24 points (indices are int32, the block counts are scanned by one block);
+ *       above: APDGICP_ERR_UNSUPPORTED.
+ *   I5. Deskew (P:951-972), per point i of n in the order of the input cloud (the rows of _run, the ego-velocity inlier cloud, any
+ *       xyzi cloud), v = its (x, y, z):
+ *         a_k = -(float)ang_vel[k];  dt = (scan_period * (double)i) / (double)n;  h = dt / 2.0;
+ *         q = ((float)(h * (double)a_x), (float)(h * (double)a_y), (float)(h * (double)a_z)), qw = 1.0f;
+ *         Quaternionf::inverse():  n2 = (qx qx + qy qy) + (qz qz + qw qw), each product rounded on its own, no FMA; with
+ *           APDGICP_FLAG_XF_LINEAR_CHAIN ((qx qx + qy qy) + qz qz) + qw qw.  n2 > 0: c = (-qx / n2, -qy / n2, -qz / n2), cw = qw / n2
+ *           (IEEE divisions); otherwise (a NaN rate) c = 0, cw = 0: Eigen's zero quaternion.
+ *         Quaternion::_transformVector, literally (the quaternion is not of unit length):  uv = c x v;  uv = uv + uv;
+ *           out = (v + cw * uv) + (c x uv)  with  a x b = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x),
+ *           everything fp32 without contraction.
+ *       The intensity is copied.  ang_vel == NULL (imu_queue.empty(), P:916): the cloud passes through bit for bit.  Eigen's reduction
+ *       order for squaredNorm() is not pinned by the reference tree (the two orders above are those of the two Eigen generations named
+ *       at XF_LINEAR_CHAIN).  Which message of the IMU queue supplies ang_vel (P:939-949) is host bookkeeping: select_imu of the
+ *       Python package, ScanIngestHip::selectImu.
+ *   I6. Frame transform (P:796-810), behind the deskew in the same launch.  T == NULL: none; otherwise as I3.
+ *   I7. Output of _deskew.  n rows {x, y, z, intensity} of 16 bytes: what apdgicp_scan_filter_run(on_device = 1) and
+ *       apdgicp_set_source accept; valid until the next _deskew.  No host wait: n is the caller's.  A consumer on another stream orders
+ *       itself behind the launch with _synchronize (or shares the object's stream).  The call is legal on the rows the same object's
+ *       _run produced and on any other device or host cloud.
+ * Not part of this object: the polar message (cloud_callback_scan), the ranges / predicted_ranges topics (P:660-700), the colour
+ * cloud (P:921-937), the distance histogram (P:818-828), underfloor_filter (its result is unused, P:816). */
+typedef struct {
+  float power_threshold;   /* "power_threshold", P:107 ; default 0 */
+  int32_t gate;            /* 1 (default): I2 ; 0: every point is kept (P:497-506) */
+  int32_t flags;           /* 0 or APDGICP_FLAG_XF_LINEAR_CHAIN (I3, I5, I6) */
+  int32_t reserved;        /* 0 */
+} apdgicp_scan_ingest_params;
+typedef struct apdgicp_scan_ingest apdgicp_scan_ingest;
+void apdgicp_scan_ingest_default_params(apdgicp_scan_ingest_params* p);
+/* `stream` may be NULL (the object creates its own) or a hipStream_t of the caller; params NULL: the defaults */
+int apdgicp_scan_ingest_create(const apdgicp_scan_ingest_params* p, int device, void* stream, apdgicp_scan_ingest** out);
+int apdgicp_scan_ingest_destroy(apdgicp_scan_ingest* h);
+int apdgicp_scan_ingest_set_params(apdgicp_scan_ingest* h, const apdgicp_scan_ingest_params* p);
+/* I1 .. I4 of one message; the three lanes all in device memory (on_device = 1) or all on the host; pre_transform: float[16] column-major or NULL */
+int apdgicp_scan_ingest_run(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t xyz_stride_bytes, const float* intensity, int64_t intensity_stride_bytes,
+                            const float* doppler, int64_t doppler_stride_bytes, int on_device, const float* pre_transform, int64_t* n_out);
+/* the rows of the last run and their message indices in device memory, valid until the next run; any pointer but h may be NULL */
+int apdgicp_scan_ingest_points(apdgicp_scan_ingest* h, const float** device_rows, const int32_t** device_index, int64_t* n);
+/* the same to HOST memory: rows [8 * capacity] floats, index [capacity]; either may be NULL */
+int apdgicp_scan_ingest_copy(apdgicp_scan_ingest* h, float* rows, int32_t* index, int64_t capacity);
+/* I5 .. I7: xyz / n / stride_bytes / intensity_offset_bytes (< 0: none, 0 is kept) / on_device as in apdgicp_scan_filter_run;
+ * ang_vel: double[3] (the IMU message's angular_velocity, HOST memory) or NULL; T: float[16] column-major (HOST memory) or NULL */
+int apdgicp_scan_ingest_deskew(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device,
+                               const double* ang_vel, double scan_period, const float* T);
+/* the cloud of the last deskew in device memory (I7); any pointer but h may be NULL */
+int apdgicp_scan_ingest_deskewed(apdgicp_scan_ingest* h, const float** device_xyzi, int64_t* n);
+int apdgicp_scan_ingest_deskewed_copy(apdgicp_scan_ingest* h, float* xyzi, int64_t capacity);   /* the same to HOST memory, [4 * capacity] floats; waits */
+int apdgicp_scan_ingest_synchronize(apdgicp_scan_ingest* h);                                      /* waits for the object's stream (I7) */
+/* kernel launches and host waits of the last _run or _deskew as counted by the host code that enqueued them (for the measurement scripts) */
+int apdgicp_scan_ingest_stats(apdgicp_scan_ingest* h, int64_t* launches, int64_t* waits);
 
 #ifdef __cplusplus
 }

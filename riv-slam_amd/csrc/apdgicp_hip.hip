@@ -18,6 +18,7 @@
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
 #include "apd_dbscan.hpp"
+#include "apd_ingest.hpp"
 
 using namespace apd;
 
@@ -372,6 +373,22 @@ struct apdgicp_dbscan {
     if (stream) (void)hipStreamSynchronize(stream);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
+    if (own_stream && stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+struct apdgicp_scan_ingest {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  apdgicp_scan_ingest_params prm;
+  DevBuf stage_xyz, stage_int, stage_dop, rows, index, bsum, scal;  // run: the staged lanes of a host message, the output, scal: int n_out
+  DevBuf stage_cloud, desk;                                           // deskew: the staged host cloud, the output
+  PinnedBuf h_scal;                                                   // mirror of scal
+  int64_t n_rows = 0, n_desk = 0;
+  int64_t launches = 0, waits = 0;  // of the last run / deskew (tests/measure/bench_scan_ingest.py)
+  ~apdgicp_scan_ingest() {
+    if (stream) (void)hipStreamSynchronize(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -4189,6 +4206,239 @@ int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, d
   if (launches) *launches = h->launches;
   if (waits) *waits = h->launches ? (h->profiling ? 2 : 1) : 0;
   for (int k = 0; k < 5 && phase_ms; k++) phase_ms[k] = h->profiling ? h->phase_ms[k] : 0.0;
+  return 0;
+}
+
+// ------------------------------------------------------------------ scan ingest and deskew (apd_ingest.hpp)
+static_assert(sizeof(apdgicp_scan_ingest_params) == 16, "apdgicp_scan_ingest_params layout");
+
+void apdgicp_scan_ingest_default_params(apdgicp_scan_ingest_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->power_threshold = 0.f, p->gate = 1;  // preprocessing_nodelet.cpp:107
+}
+
+static int ingest_check_params(const apdgicp_scan_ingest_params* p) {
+  if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
+  if (p->gate != 0 && p->gate != 1) return fail(APDGICP_ERR_INVALID_ARG, "gate must be 0 or 1");
+  if (p->flags & ~APDGICP_FLAG_XF_LINEAR_CHAIN) return fail(APDGICP_ERR_INVALID_ARG, "flags: only APDGICP_FLAG_XF_LINEAR_CHAIN is read by this object");
+  return 0;
+}
+
+int apdgicp_scan_ingest_create(const apdgicp_scan_ingest_params* p, int device, void* stream, apdgicp_scan_ingest** out) {
+  return guarded([&]() -> int {
+    if (!out) return fail(APDGICP_ERR_INVALID_ARG, "out is null");
+    *out = nullptr;
+    apdgicp_scan_ingest_params dflt;
+    apdgicp_scan_ingest_default_params(&dflt);
+    if (!p) p = &dflt;
+    APD_TRY(ingest_check_params(p));
+    int count = 0;
+    APD_HIP(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(APDGICP_ERR_INVALID_ARG, "device index out of range");
+    APD_HIP(hipSetDevice(device));
+    std::unique_ptr<apdgicp_scan_ingest> h(new apdgicp_scan_ingest);
+    h->device = device, h->prm = *p;
+    if (stream) {
+      h->stream = (hipStream_t)stream;
+    } else {
+      APD_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+      h->own_stream = true;
+    }
+    APD_TRY(h->h_scal.ensure(16));
+    memset(h->h_scal.p, 0, 16);
+    APD_TRY(h->scal.ensure(16));
+    *out = h.release();
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_destroy(apdgicp_scan_ingest* h) {
+  return guarded([&]() -> int {
+    if (h) (void)hipSetDevice(h->device);
+    delete h;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_set_params(apdgicp_scan_ingest* h, const apdgicp_scan_ingest_params* p) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(ingest_check_params(p));
+    h->prm = *p;
+    return 0;
+  });
+}
+
+static IngestXf ingest_xf(const float* colmajor16, int flags) {
+  IngestXf X;
+  memset(&X, 0, sizeof(X));
+  X.linear = (flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;
+  if (colmajor16) {
+    X.on = 1;
+    for (int r = 0; r < 3; r++)
+      for (int c = 0; c < 4; c++) X.m[4 * r + c] = colmajor16[r + 4 * c];
+  }
+  return X;
+}
+
+int apdgicp_scan_ingest_run(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t xyz_stride_bytes, const float* intensity, int64_t intensity_stride_bytes,
+                            const float* doppler, int64_t doppler_stride_bytes, int on_device, const float* pre_transform, int64_t* n_out) {
+  return guarded([&]() -> int {
+    if (!h || !n_out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *n_out = 0;
+    h->n_rows = 0, h->launches = h->waits = 0;
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative number of points");
+    if (n > 0 && (!xyz || !intensity || !doppler)) return fail(APDGICP_ERR_INVALID_ARG, "a lane of the message is null");
+    if (xyz_stride_bytes < 12 || xyz_stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "xyz stride must be a multiple of 4 bytes and >= 12");
+    if (intensity_stride_bytes < 4 || intensity_stride_bytes % 4 || doppler_stride_bytes < 4 || doppler_stride_bytes % 4)
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity / doppler stride must be a multiple of 4 bytes and >= 4");
+    if (n > ING_MAX_N) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    const int ni = (int)n, nb = (ni + ING_BLK - 1) / ING_BLK;
+    IngestLanes L;
+    L.xyz = (const char*)xyz, L.intensity = (const char*)intensity, L.doppler = (const char*)doppler;
+    L.xyz_stride = xyz_stride_bytes, L.intensity_stride = intensity_stride_bytes, L.doppler_stride = doppler_stride_bytes;
+    if (!on_device) {
+      // (no wait: the copies are ordered behind the previous run's kernels by the stream; a buffer that grows is freed by hipFree, which waits)
+      const char* base[3] = {L.xyz, L.intensity, L.doppler};
+      const int64_t stride[3] = {xyz_stride_bytes, intensity_stride_bytes, doppler_stride_bytes}, width[3] = {12, 4, 4};
+      const char* lo = std::min(base[0], std::min(base[1], base[2]));
+      const char* hi = std::max(base[0] + width[0], std::max(base[1] + width[1], base[2] + width[2]));
+      if (n >= 2 && stride[0] == stride[1] && stride[1] == stride[2] && hi - lo <= stride[0]) {
+        // one array of structures: the three lanes overlap from the second point on, so [lo, last byte) is the caller's; one copy
+        const size_t bytes = (size_t)(n - 1) * stride[0] + (size_t)(hi - lo);
+        APD_TRY(h->stage_xyz.ensure(bytes));
+        APD_HIP(hipMemcpyAsync(h->stage_xyz.p, lo, bytes, hipMemcpyHostToDevice, h->stream));
+        L.xyz = h->stage_xyz.as<char>() + (base[0] - lo), L.intensity = h->stage_xyz.as<char>() + (base[1] - lo), L.doppler = h->stage_xyz.as<char>() + (base[2] - lo);
+      } else {
+        DevBuf* st[3] = {&h->stage_xyz, &h->stage_int, &h->stage_dop};
+        const char** lane[3] = {&L.xyz, &L.intensity, &L.doppler};
+        for (int k = 0; k < 3; k++) {
+          const size_t bytes = (size_t)(n - 1) * stride[k] + width[k];
+          APD_TRY(st[k]->ensure(bytes));
+          APD_HIP(hipMemcpyAsync(st[k]->p, base[k], bytes, hipMemcpyHostToDevice, h->stream));
+          *lane[k] = st[k]->as<char>();
+        }
+      }
+    }
+    APD_TRY(h->rows.ensure((size_t)n * 32));
+    APD_TRY(h->index.ensure((size_t)n * 4));
+    APD_TRY(h->bsum.ensure((size_t)nb * sizeof(int)));
+    const apdgicp_scan_ingest_params& P = h->prm;
+    const IngestXf X = ingest_xf(pre_transform, P.flags);
+    int* bsum = h->bsum.as<int>();
+    hipLaunchKernelGGL(k_ing_count, dim3(nb), dim3(ING_BLK), 0, h->stream, L, ni, P.gate, P.power_threshold, bsum);
+    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, h->stream, bsum, nb, h->scal.as<int>());
+    hipLaunchKernelGGL(k_ing_scatter, dim3(nb), dim3(ING_BLK), 0, h->stream, L, ni, P.gate, P.power_threshold, X, bsum, h->rows.as<float4>(), h->index.as<int>());
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(h->h_scal.p, h->scal.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));  // the one wait of the call
+    h->launches = 3, h->waits = 1;
+    h->n_rows = *h->h_scal.as<int>();
+    *n_out = h->n_rows;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_points(apdgicp_scan_ingest* h, const float** device_rows, const int32_t** device_index, int64_t* n) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (device_rows) *device_rows = h->n_rows ? h->rows.as<float>() : nullptr;
+    if (device_index) *device_index = h->n_rows ? h->index.as<int32_t>() : nullptr;
+    if (n) *n = h->n_rows;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_copy(apdgicp_scan_ingest* h, float* rows, int32_t* index, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (capacity < h->n_rows) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer rows than the last run produced");
+    if (!h->n_rows || (!rows && !index)) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    if (rows) APD_HIP(hipMemcpyAsync(rows, h->rows.p, (size_t)h->n_rows * 32, hipMemcpyDeviceToHost, h->stream));
+    if (index) APD_HIP(hipMemcpyAsync(index, h->index.p, (size_t)h->n_rows * 4, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_deskew(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t stride_bytes, int64_t intensity_offset_bytes, int on_device,
+                               const double* ang_vel, double scan_period, const float* T) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    h->n_desk = 0, h->launches = h->waits = 0;
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative number of points");
+    if (n > 0 && !xyz) return fail(APDGICP_ERR_INVALID_ARG, "the cloud is null");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (intensity_offset_bytes >= 0 && (intensity_offset_bytes % 4 || intensity_offset_bytes + 4 > stride_bytes))
+      return fail(APDGICP_ERR_INVALID_ARG, "intensity offset outside the point");
+    if (n > ING_MAX_N) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    const char* d_in = (const char*)xyz;
+    if (!on_device) {
+      // (no wait, as in run)
+      const size_t used = (size_t)std::max<int64_t>(12, intensity_offset_bytes >= 0 ? intensity_offset_bytes + 4 : 12);
+      const size_t bytes = (size_t)(n - 1) * stride_bytes + used;
+      APD_TRY(h->stage_cloud.ensure(bytes));
+      APD_HIP(hipMemcpyAsync(h->stage_cloud.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+      d_in = h->stage_cloud.as<char>();
+    }
+    APD_TRY(h->desk.ensure((size_t)n * 16));
+    DeskewParams D;
+    memset(&D, 0, sizeof(D));
+    D.scan_period = scan_period;
+    if (ang_vel) {
+      D.on = 1;
+      for (int k = 0; k < 3; k++) D.a[k] = -(float)ang_vel[k];  // ang_v *= -1 (:951-952)
+    }
+    const IngestXf X = ingest_xf(T, h->prm.flags);
+    hipLaunchKernelGGL(k_ing_deskew, dim3((unsigned)((n + ING_DESKEW_BLK - 1) / ING_DESKEW_BLK)), dim3(ING_DESKEW_BLK), 0, h->stream, d_in, (int)n, (long long)stride_bytes,
+                       intensity_offset_bytes >= 0 ? (int)(intensity_offset_bytes / 4) : -1, D, X, h->desk.as<float4>());
+    APD_HIP(hipGetLastError());
+    h->launches = 1, h->waits = 0;
+    h->n_desk = n;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_deskewed(apdgicp_scan_ingest* h, const float** device_xyzi, int64_t* n) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (device_xyzi) *device_xyzi = h->n_desk ? h->desk.as<float>() : nullptr;
+    if (n) *n = h->n_desk;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_deskewed_copy(apdgicp_scan_ingest* h, float* xyzi, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h || (!xyzi && capacity > 0)) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (capacity < h->n_desk) return fail(APDGICP_ERR_INVALID_ARG, "destination holds fewer points than the deskewed cloud");
+    if (!h->n_desk) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipMemcpyAsync(xyzi, h->desk.p, (size_t)h->n_desk * 16, hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_synchronize(apdgicp_scan_ingest* h) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_stats(apdgicp_scan_ingest* h, int64_t* launches, int64_t* waits) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  if (launches) *launches = h->launches;
+  if (waits) *waits = h->waits;
   return 0;
 }
 

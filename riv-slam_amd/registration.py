@@ -116,6 +116,9 @@ SYMBOLS = [
     "apdgicp_batch_set_ndt", "apdgicp_batch_get_ndt", "apdgicp_batch_ndt_voxel_count", "apdgicp_batch_ndt_get_voxels", "apdgicp_batch_ndt_build_count",
     "apdgicp_dbscan_default_params", "apdgicp_dbscan_create", "apdgicp_dbscan_destroy", "apdgicp_dbscan_set_params", "apdgicp_dbscan_run", "apdgicp_dbscan_labels",
     "apdgicp_dbscan_copy_labels", "apdgicp_dbscan_clusters", "apdgicp_dbscan_members", "apdgicp_dbscan_debug", "apdgicp_dbscan_set_profiling", "apdgicp_dbscan_stats",
+    "apdgicp_scan_ingest_default_params", "apdgicp_scan_ingest_create", "apdgicp_scan_ingest_destroy", "apdgicp_scan_ingest_set_params", "apdgicp_scan_ingest_run",
+    "apdgicp_scan_ingest_points", "apdgicp_scan_ingest_copy", "apdgicp_scan_ingest_deskew", "apdgicp_scan_ingest_deskewed", "apdgicp_scan_ingest_deskewed_copy",
+    "apdgicp_scan_ingest_synchronize", "apdgicp_scan_ingest_stats",
 ]
 
 _lib = None
@@ -320,6 +323,19 @@ def load_library(path: str | None = None):
     L.apdgicp_dbscan_debug.argtypes = [vp, vp, vp, vp, vp, i64]
     L.apdgicp_dbscan_set_profiling.argtypes = [vp, i32]
     L.apdgicp_dbscan_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), vp]
+    L.apdgicp_scan_ingest_default_params.argtypes = [vp]
+    L.apdgicp_scan_ingest_default_params.restype = None
+    L.apdgicp_scan_ingest_create.argtypes = [vp, i32, vp, C.POINTER(vp)]
+    L.apdgicp_scan_ingest_destroy.argtypes = [vp]
+    L.apdgicp_scan_ingest_set_params.argtypes = [vp, vp]
+    L.apdgicp_scan_ingest_run.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, i32, vp, C.POINTER(i64)]
+    L.apdgicp_scan_ingest_points.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_scan_ingest_copy.argtypes = [vp, vp, vp, i64]
+    L.apdgicp_scan_ingest_deskew.argtypes = [vp, vp, i64, i64, i64, i32, vp, dbl, vp]
+    L.apdgicp_scan_ingest_deskewed.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.apdgicp_scan_ingest_deskewed_copy.argtypes = [vp, vp, i64]
+    L.apdgicp_scan_ingest_synchronize.argtypes = [vp]
+    L.apdgicp_scan_ingest_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     if path is None:
         _lib = L
     return L
