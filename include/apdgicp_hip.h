@@ -922,14 +922,13 @@ int apdgicp_floor_debug(apdgicp_floor* f, uint8_t* clip_mask, int64_t mask_capac
  *      intensity 0 (the reference pushes a default-constructed point).
  *   M6: no keyframes: APDGICP_ERR_INVALID_ARG (the reference returns nullptr); no finite pushed point: n_out = 0, status 0; more than
  *      2^31 - 1 input points: APDGICP_ERR_UNSUPPORTED; a resolution that is NaN or infinite: APDGICP_ERR_INVALID_ARG.
- * Nothing per point goes to the host.  The distinct keys come from a stable radix sort of the interleaved keys (environment
- * APDGICP_MAP_SORT=bitonic at create time: the bitonic sort of the submap assembler instead, for measurements).  The calls wait for
+ * Nothing per point goes to the host.  The distinct keys come from a stable radix sort of the interleaved keys.  The calls wait for
  * their own work. */
 typedef struct {
   int64_t n_input, n_pushed, n_finite, n_out;   /* points of the keyframes given, M1's cloud, its finite points, the output */
   double min[3], max[3];                        /* M3's final box (zeros without an octree) */
   int32_t depth, rounds;                        /* octree depth; points after the first that made the box grow */
-  int32_t sort_passes, sort_kind;               /* radix passes (8-bit digits over 3 * depth bits); 0 = radix, 1 = bitonic */
+  int32_t sort_passes, sort_kind;               /* radix passes (8-bit digits over 3 * depth bits); always 0 (the radix sort) */
   float stage_ms[4];                            /* device time of the last generate: M1, M3, keys + sort, heads + centres */
 } apdgicp_map_cloud_stats;
 typedef struct apdgicp_map_cloud apdgicp_map_cloud;

@@ -599,8 +599,7 @@ class Engine {
     for (int id : large) {  // generic path: keys in global memory, one launch per bitonic stage
       Cloud& c = clouds[id];
       const int n = c.n;
-      int np2 = VOX_TILE;
-      while (np2 < n) np2 <<= 1;
+      const int np2 = bitonic_padded_size(n);
       APD_HIP(hipStreamSynchronize(cstream));
       APD_TRY(d_keys.ensure((size_t)np2 * 8));
       APD_TRY(d_box6.ensure(6 * sizeof(int)));
@@ -613,12 +612,7 @@ class Engine {
       const int mbits = std::min(21, (64 - idx_bits) / 3);
       hipLaunchKernelGGL(k_morton_keys, dim3((np2 + 255) / 256), dim3(256), 0, cstream, c.opts.as<float4>(), n, np2, d_box6.as<int>(),
                          d_keys.as<unsigned long long>(), mbits, idx_bits);
-      hipLaunchKernelGGL(k_bitonic_tile_sort, dim3(np2 / VOX_TILE), dim3(1024), 0, cstream, d_keys.as<unsigned long long>());
-      for (int k = 2 * VOX_TILE; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j >= VOX_TILE; j >>= 1)
-          hipLaunchKernelGGL(k_bitonic_global, dim3((np2 / 2 + 255) / 256), dim3(256), 0, cstream, d_keys.as<unsigned long long>(), np2, k, j);
-        hipLaunchKernelGGL(k_bitonic_tile_merge, dim3(np2 / VOX_TILE), dim3(1024), 0, cstream, d_keys.as<unsigned long long>(), k);
-      }
+      enqueue_bitonic_sort(cstream, d_keys.as<unsigned long long>(), np2);
       hipLaunchKernelGGL(k_gather_sorted, dim3((n + 255) / 256), dim3(256), 0, cstream, d_keys.as<unsigned long long>(), c.opts.as<float4>(), n,
                          c.pts.as<float4>(), c.perm.as<int>(), idx_bits);
       const int nch = (n + 15) / 16, ngr = (n + kGroupPts - 1) / kGroupPts;

@@ -25,8 +25,8 @@
 //     is past the depth limit anyway; PCL shifts an int by the depth and breaks near 31, here a depth above 21 is refused (the
 //     interleaved key stays within 63 bits; at 0.05 m depth 21 is a cube of 104 km).
 // The distinct keys come from a stable LSD radix sort of the interleaved u64 keys (8-bit digits over the 3 * depth significant bits:
-// k_map_rs_hist / k_map_scan_tiles / k_scan_bsum / k_map_rs_scatter) or, for comparison (APDGICP_MAP_SORT=bitonic), from the bitonic sort
-// of apd_sort.hpp.  No floating-point atomics; integer counts use atomicAdd.  Every pointer of this file is a kernel argument.
+// k_map_rs_hist / k_map_scan_tiles / k_scan_bsum / k_map_rs_scatter).  No floating-point atomics; integer counts use atomicAdd.  Every
+// pointer of this file is a kernel argument.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,7 +45,6 @@ constexpr int MAP_RS_ITEMS = 16;          // ... each owning 16 rounds of 64 con
 constexpr int MAP_RS_TILE = MAP_RS_BLK * MAP_RS_ITEMS;
 constexpr int MAP_NONE = 2147483647;
 constexpr double MAP_EPS = 1.1920928955078125e-07;  // std::numeric_limits<float>::epsilon()
-constexpr unsigned long long MAP_PAD_KEY = ~0ull;   // bitonic padding (a real key has at most 63 bits)
 
 struct MapJob {  // one keyframe of a generate call
   const float4* pts;
@@ -254,10 +253,6 @@ __global__ __launch_bounds__(MAP_BLK) void k_map_keys(const float4* pushed, doub
   for (int w = 0; w < wave; w++) before += wsum[w];
   if (ok) keys[mbcnt_add(m, before)] = key;
 }
-__global__ void k_map_pad(unsigned long long* keys, int n, int np2) {  // the bitonic sort wants a power of two
-  const int i = n + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < np2) keys[i] = MAP_PAD_KEY;
-}
 
 // ---- the stable LSD radix sort, one 8-bit digit per pass.  A block owns MAP_RS_TILE consecutive keys.
 // pass part 1: hist[digit * nblk + block] = keys of the block with that digit
@@ -356,7 +351,7 @@ __global__ __launch_bounds__(MAP_RS_BLK) void k_map_rs_scatter_pairs(const unsig
 
 // ---- M5: the first key of every run of equal keys is a voxel; count, scan (k_scan_bsum -> n_out), centres
 __device__ __forceinline__ bool map_head(const unsigned long long* keys, long long i, int n) {
-  return i < n && keys[i] != MAP_PAD_KEY && (i == 0 || keys[i - 1] != keys[i]);
+  return i < n && (i == 0 || keys[i - 1] != keys[i]);
 }
 __global__ __launch_bounds__(MAP_BLK) void k_map_heads(const unsigned long long* keys, int n, int* bsum) {
   __shared__ int wsum[MAP_BLK / 64];

@@ -492,6 +492,20 @@ __global__ __launch_bounds__(1024) void k_bitonic_tile_merge(unsigned long long*
   tile_steps(t, base, k, VOX_TILE >> 1, tid);
   for (int q = tid; q < VOX_TILE; q += 1024) keys[base + q] = t[q];
 }
+// host: the size this sort wants for n keys (the smallest power of two >= n, at least one tile; the caller pads with keys that sort last) ...
+inline int bitonic_padded_size(int n) {
+  int np2 = VOX_TILE;
+  while (np2 < n) np2 <<= 1;
+  return np2;
+}
+// ... and the whole sort of keys[0 .. np2), ascending, enqueued on stream: never waits
+inline void enqueue_bitonic_sort(hipStream_t stream, unsigned long long* keys, int np2) {
+  hipLaunchKernelGGL(k_bitonic_tile_sort, dim3(np2 / VOX_TILE), dim3(1024), 0, stream, keys);
+  for (int k = 2 * VOX_TILE; k <= np2; k <<= 1) {
+    for (int j = k >> 1; j >= VOX_TILE; j >>= 1) hipLaunchKernelGGL(k_bitonic_global, dim3((np2 / 2 + 255) / 256), dim3(256), 0, stream, keys, np2, k, j);
+    hipLaunchKernelGGL(k_bitonic_tile_merge, dim3(np2 / VOX_TILE), dim3(1024), 0, stream, keys, k);
+  }
+}
 
 __global__ void k_gather_sorted(const unsigned long long* keys, const float4* pts, int n, float4* spts, int* perm, int idx_bits) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;

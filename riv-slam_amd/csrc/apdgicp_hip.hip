@@ -22,26 +22,76 @@
 
 using namespace apd;
 
-// The scratch of one voxel-map build (k_vg_keys, the radix sort of apd_map.hpp, k_map_heads): one per handle, used by whichever voxel mode is
-// on.  Builds follow each other in stream order.
-struct VoxSortScratch {
-  DevBuf keys_a, keys_b, idx_a, idx_b, hist, rs_bsum, bsum;
-  // sized for a cloud of n points.  With `grows` given it only says whether that would replace a buffer and replaces none: the caller waits
-  // for the stream first, then calls again without.
-  int ensure(int n, bool* grows = nullptr) {
-    const int64_t entries = 256ll * ((n + MAP_RS_TILE - 1) / MAP_RS_TILE);
-    const size_t nsb = (size_t)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS)), nhb = (size_t)(n + MAP_BLK - 1) / MAP_BLK;
+// Exclusive scan of v[0 .. n) in place, enqueued on stream: tiles of SCAN_BLK * SCAN_ITEMS, then their sums (tile_sums: one int per tile, left
+// scanned); *total = the sum of all.
+static int scan_tiles(int64_t n) { return (int)((n + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS)); }
+static void enqueue_exclusive_scan(hipStream_t stream, int* v, int n, int* tile_sums, int* total) {
+  const int nt = scan_tiles(n);
+  hipLaunchKernelGGL(k_map_scan_tiles, dim3(nt), dim3(SCAN_BLK), 0, stream, v, n, tile_sums);
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, stream, tile_sums, nt, total);
+}
+
+// The stable LSD radix sort of apd_map.hpp, 8 bits per pass, over u64 keys or (key, int) pairs.  The caller sizes the scratch (ensure), writes
+// the keys into keys_a (pairs: their values into val_a) in stream order and enqueues the passes (enqueue_radix_sort).
+struct RadixDims {
+  int nblk, entries, nsb;  // blocks of MAP_RS_TILE keys; histogram entries of a pass; scan tiles of that histogram
+};
+static RadixDims radix_dims(int n) {
+  const int nblk = (int)(((int64_t)n + MAP_RS_TILE - 1) / MAP_RS_TILE);
+  return RadixDims{nblk, 256 * nblk, scan_tiles(256ll * nblk)};
+}
+struct RadixScratch {
+  DevBuf keys_a, keys_b, val_a, val_b, hist, tile_sums;  // tile_sums: nsb ints, then the word that takes the total of a pass's scan (nobody reads it)
+  // sized for n keys (pairs: and n values).  With `grows` given it only says whether that would replace a buffer and replaces none: the caller
+  // waits for the stream first, then calls again without.
+  int ensure(int n, bool pairs, bool* grows = nullptr) {
+    const RadixDims d = radix_dims(n);
+    const size_t kb = (size_t)n * 8, vb = pairs ? (size_t)n * 4 : 0, hb = (size_t)d.entries * 4, tb = ((size_t)d.nsb + 1) * 4;
     if (grows) {
-      *grows = (size_t)n * 8 > keys_a.cap || (size_t)entries * 4 > hist.cap || nsb * 4 > rs_bsum.cap || nhb * 4 > bsum.cap;
+      *grows = kb > keys_a.cap || kb > keys_b.cap || vb > val_a.cap || vb > val_b.cap || hb > hist.cap || tb > tile_sums.cap;
       return 0;
     }
-    APD_TRY(keys_a.ensure((size_t)n * 8));
-    APD_TRY(keys_b.ensure((size_t)n * 8));
-    APD_TRY(idx_a.ensure((size_t)n * 4));
-    APD_TRY(idx_b.ensure((size_t)n * 4));
-    APD_TRY(hist.ensure((size_t)entries * 4));
-    APD_TRY(rs_bsum.ensure(nsb * 4));
-    return bsum.ensure(nhb * 4);
+    APD_TRY(keys_a.ensure(kb));
+    APD_TRY(keys_b.ensure(kb));
+    APD_TRY(val_a.ensure(vb));
+    APD_TRY(val_b.ensure(vb));
+    APD_TRY(hist.ensure(hb));
+    return tile_sums.ensure(tb);
+  }
+};
+struct RadixSorted {  // where the sorted keys and values ended (vals: null without pairs), and the launches that took
+  unsigned long long* keys;
+  int* vals;
+  int launches;
+};
+// `passes` passes from bit 0 over the n keys in s.keys_a, s sized for n (and for pairs) by the caller.  Enqueues only, never waits.
+static RadixSorted enqueue_radix_sort(hipStream_t stream, RadixScratch& s, int n, int passes, bool pairs) {
+  const RadixDims d = radix_dims(n);
+  unsigned long long *ka = s.keys_a.as<unsigned long long>(), *kb = s.keys_b.as<unsigned long long>();
+  int *va = pairs ? s.val_a.as<int>() : nullptr, *vb = pairs ? s.val_b.as<int>() : nullptr, *hist = s.hist.as<int>(), *sums = s.tile_sums.as<int>();
+  for (int p = 0; p < passes; p++) {
+    hipLaunchKernelGGL(k_map_rs_hist, dim3(d.nblk), dim3(MAP_RS_BLK), 0, stream, ka, n, 8 * p, d.nblk, hist);
+    enqueue_exclusive_scan(stream, hist, d.entries, sums, sums + d.nsb);
+    if (pairs) hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(d.nblk), dim3(MAP_RS_BLK), 0, stream, ka, va, kb, vb, n, 8 * p, d.nblk, hist, sums);
+    else hipLaunchKernelGGL(k_map_rs_scatter, dim3(d.nblk), dim3(MAP_RS_BLK), 0, stream, ka, kb, n, 8 * p, d.nblk, hist, sums);
+    std::swap(ka, kb), std::swap(va, vb);
+  }
+  return RadixSorted{ka, va, 4 * passes};
+}
+
+// The scratch of one voxel-map build (k_vg_keys, the pair sort, k_map_heads): one per handle, used by whichever voxel mode is on.  Builds
+// follow each other in stream order.  bsum: the head count of every block of MAP_BLK sorted keys.
+struct VoxSortScratch {
+  RadixScratch radix;
+  DevBuf bsum;
+  int ensure(int n, bool* grows = nullptr) {  // (grows: as RadixScratch::ensure)
+    const size_t hb = (size_t)(n + MAP_BLK - 1) / MAP_BLK * 4;
+    APD_TRY(radix.ensure(n, true, grows));
+    if (grows) {
+      *grows = *grows || hb > bsum.cap;
+      return 0;
+    }
+    return bsum.ensure(hb);
   }
 };
 
@@ -309,9 +359,9 @@ struct apdgicp_map_cloud {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  bool bitonic = false;  // APDGICP_MAP_SORT=bitonic at create time
   std::vector<Keyframe> kfs;
-  DevBuf stage, pushed, keys_a, keys_b, hist, rs_bsum, bsum, bmin, out, state;
+  RadixScratch sort;  // of the voxel keys (keys only)
+  DevBuf stage, pushed, bsum, bmin, out, state;
   CachedTable jobs;
   PinnedBuf h_state;  // mirror of state: one MapState
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -320,8 +370,7 @@ struct apdgicp_map_cloud {
   int64_t n_last = 0;
   void forget() {
     result = nullptr, n_last = 0;
-    memset(&info, 0, sizeof(info));
-    info.sort_kind = bitonic ? 1 : 0;
+    memset(&info, 0, sizeof(info));  // (sort_kind: always 0, the radix sort)
   }
   ~apdgicp_map_cloud() {
     if (stream) (void)hipStreamSynchronize(stream);
@@ -359,7 +408,7 @@ struct apdgicp_dbscan {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   apdgicp_dbscan_params prm;
-  VoxSortScratch sort;  // the three radix sorts of a run, one after the other
+  RadixScratch sort;  // the three pair sorts of a run, one after the other
   DevBuf stage, stage_dop, pts, dop, gkeys, spts, cnt, core, score, parent, root, seed, nextra, size, ncore, rank_of, cseed, csize, tsum, mcount, msum, offsets, members,
       labels, table, scal;
   PinnedBuf h_scal;  // mirror of scal: DB_WORDS ints
@@ -464,24 +513,13 @@ struct VoxSorted {  // what enqueue_voxel_sort leaves for k_vg_voxels / k_ndt_vo
 // The build chain up to the voxel kernel, on s (sized for n by the caller).  Enqueues only, never waits: the four scal words reset, the voxel
 // keys of pts[0 .. n) (scal[0]: the first point that has none), the (key, index) pairs sorted, the voxels counted (scal[1]).
 int enqueue_voxel_sort(hipStream_t stream, VoxSortScratch& s, const float4* pts, int n, double resolution, int* scal, VoxSorted* sorted) {
-  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-  const int64_t entries = 256ll * nblk;
-  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
   const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK), nb256 = (unsigned)((n + 255) / 256);
   APD_HIP(hipMemsetAsync(scal, 0x7f, 16, stream));
-  unsigned long long *ks = s.keys_a.as<unsigned long long>(), *kd = s.keys_b.as<unsigned long long>();
-  int *is = s.idx_a.as<int>(), *id = s.idx_b.as<int>();
-  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, stream, pts, n, resolution, ks, is, scal);
-  for (int p = 0; p < 8; p++) {  // 63 key bits, 8 per pass
-    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, stream, ks, n, 8 * p, nblk, s.hist.as<int>());
-    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, stream, s.hist.as<int>(), (int)entries, s.rs_bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, stream, s.rs_bsum.as<int>(), nsb, scal + 2);
-    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, stream, ks, is, kd, id, n, 8 * p, nblk, s.hist.as<int>(), s.rs_bsum.as<int>());
-    std::swap(ks, kd), std::swap(is, id);
-  }
-  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, stream, ks, n, s.bsum.as<int>());
+  hipLaunchKernelGGL(k_vg_keys, dim3(nb256), dim3(256), 0, stream, pts, n, resolution, s.radix.keys_a.as<unsigned long long>(), s.radix.val_a.as<int>(), scal);
+  const RadixSorted r = enqueue_radix_sort(stream, s.radix, n, 8, true);  // 63 key bits, 8 per pass
+  hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, stream, r.keys, n, s.bsum.as<int>());
   hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, stream, s.bsum.as<int>(), (int)nhb, scal + 1);
-  *sorted = VoxSorted{ks, is, nhb};
+  *sorted = VoxSorted{r.keys, r.vals, nhb};
   return 0;
 }
 
@@ -2535,8 +2573,7 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
     }
     if (!(leaf[1] > 0.f) || !(leaf[2] > 0.f)) return fail(APDGICP_ERR_INVALID_ARG, "leaf sizes must be positive");
     const float il[3] = {1.f / leaf[0], 1.f / leaf[1], 1.f / leaf[2]};  // inverse_leaf_size_ = Array4f::Ones() / leaf_size_
-    int np2 = VOX_TILE;
-    while (np2 < n) np2 <<= 1;
+    const int np2 = bitonic_padded_size(n);
     const int nsb = (np2 + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS);
     APD_TRY(s->keys.ensure((size_t)np2 * 8));
     APD_TRY(s->pos.ensure((size_t)np2 * 4));
@@ -2550,12 +2587,7 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
     hipLaunchKernelGGL(k_vox_bbox, dim3(std::min((n + 255) / 256, 256)), dim3(256), 0, s->stream, s->cat.as<float4>(), n, box6);
     unsigned long long* keys = s->keys.as<unsigned long long>();
     hipLaunchKernelGGL(k_vox_keys, dim3((np2 + 255) / 256), dim3(256), 0, s->stream, s->cat.as<float4>(), n, np2, box6, il[0], il[1], il[2], keys, d_err);
-    hipLaunchKernelGGL(k_bitonic_tile_sort, dim3(np2 / VOX_TILE), dim3(1024), 0, s->stream, keys);
-    for (int k = 2 * VOX_TILE; k <= np2; k <<= 1) {
-      for (int j = k >> 1; j >= VOX_TILE; j >>= 1)
-        hipLaunchKernelGGL(k_bitonic_global, dim3((np2 / 2 + 255) / 256), dim3(256), 0, s->stream, keys, np2, k, j);
-      hipLaunchKernelGGL(k_bitonic_tile_merge, dim3(np2 / VOX_TILE), dim3(1024), 0, s->stream, keys, k);
-    }
+    enqueue_bitonic_sort(s->stream, keys, np2);
     hipLaunchKernelGGL(k_vox_heads, dim3(nsb), dim3(SCAN_BLK), 0, s->stream, keys, np2, s->pos.as<int>(), s->bsum.as<int>());
     hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, s->stream, s->bsum.as<int>(), nsb, d_total);
     hipLaunchKernelGGL(k_vox_centroids, dim3((np2 + 255) / 256), dim3(256), 0, s->stream, keys, s->cat.as<float4>(), s->pos.as<int>(),
@@ -3391,8 +3423,6 @@ int apdgicp_map_cloud_create(int device, void* stream, apdgicp_map_cloud** out) 
     APD_HIP(hipSetDevice(device));
     std::unique_ptr<apdgicp_map_cloud> m(new apdgicp_map_cloud);
     m->device = device;
-    const char* sort = getenv("APDGICP_MAP_SORT");
-    m->bitonic = sort && !strcmp(sort, "bitonic");
     m->forget();
     if (stream) {
       m->stream = (hipStream_t)stream;
@@ -3546,52 +3576,18 @@ int apdgicp_map_cloud_generate(apdgicp_map_cloud* m, int32_t n_keyframes, const 
     // ---- M4 + the sort
     const int n = n_fin;
     const unsigned npb = (unsigned)(((int64_t)n_pushed + MAP_BLK - 1) / MAP_BLK);
-    int n_sorted = n;
-    unsigned long long* keys = nullptr;
-    if (m->bitonic) {
-      int64_t np2 = VOX_TILE;
-      while (np2 < n) np2 <<= 1;
-      if (np2 > (1ll << 30)) return fail(APDGICP_ERR_UNSUPPORTED, "too many points for the bitonic sort");
-      APD_TRY(m->keys_a.ensure((size_t)np2 * 8));
-      keys = m->keys_a.as<unsigned long long>();
-      hipLaunchKernelGGL(k_map_keys, dim3(npb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), resolution, st, keys);
-      if (np2 > n) hipLaunchKernelGGL(k_map_pad, dim3((unsigned)((np2 - n + 255) / 256)), dim3(256), 0, m->stream, keys, n, (int)np2);
-      hipLaunchKernelGGL(k_bitonic_tile_sort, dim3((unsigned)(np2 / VOX_TILE)), dim3(1024), 0, m->stream, keys);
-      for (int64_t k = 2 * VOX_TILE; k <= np2; k <<= 1) {
-        for (int64_t j = k >> 1; j >= VOX_TILE; j >>= 1)
-          hipLaunchKernelGGL(k_bitonic_global, dim3((unsigned)((np2 / 2 + 255) / 256)), dim3(256), 0, m->stream, keys, (int)np2, (int)k, (int)j);
-        hipLaunchKernelGGL(k_bitonic_tile_merge, dim3((unsigned)(np2 / VOX_TILE)), dim3(1024), 0, m->stream, keys, (int)k);
-      }
-      n_sorted = (int)np2;
-    } else {
-      const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-      const int64_t entries = 256ll * nblk;
-      const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-      APD_TRY(m->keys_a.ensure((size_t)n * 8));
-      APD_TRY(m->keys_b.ensure((size_t)n * 8));
-      APD_TRY(m->hist.ensure((size_t)entries * 4));
-      APD_TRY(m->rs_bsum.ensure((size_t)nsb * 4));
-      unsigned long long *src = m->keys_a.as<unsigned long long>(), *dst = m->keys_b.as<unsigned long long>();
-      hipLaunchKernelGGL(k_map_keys, dim3(npb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), resolution, st, src);
-      const int passes = (3 * depth + 7) / 8;
-      for (int p = 0; p < passes; p++) {
-        hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, m->stream, src, n, 8 * p, nblk, m->hist.as<int>());
-        hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, m->stream, m->hist.as<int>(), (int)entries, m->rs_bsum.as<int>());
-        hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, m->stream, m->rs_bsum.as<int>(), nsb, &st->pad_[0]);
-        hipLaunchKernelGGL(k_map_rs_scatter, dim3(nblk), dim3(MAP_RS_BLK), 0, m->stream, src, dst, n, 8 * p, nblk, m->hist.as<int>(), m->rs_bsum.as<int>());
-        std::swap(src, dst);
-      }
-      keys = src;
-      m->info.sort_passes = passes;
-    }
+    APD_TRY(m->sort.ensure(n, false));  // (nothing is in flight: the state was just read)
+    hipLaunchKernelGGL(k_map_keys, dim3(npb), dim3(MAP_BLK), 0, m->stream, m->pushed.as<float4>(), resolution, st, m->sort.keys_a.as<unsigned long long>());
+    m->info.sort_passes = (3 * depth + 7) / 8;
+    const unsigned long long* keys = enqueue_radix_sort(m->stream, m->sort, n, m->info.sort_passes, false).keys;
     APD_HIP(hipEventRecord(m->ev[3], m->stream));
     // ---- M5
-    const unsigned nhb = (unsigned)((n_sorted + MAP_BLK - 1) / MAP_BLK);
+    const unsigned nhb = (unsigned)((n + MAP_BLK - 1) / MAP_BLK);
     APD_TRY(m->bsum.ensure((size_t)nhb * 4));
     APD_TRY(m->out.ensure((size_t)n * 16));
-    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n_sorted, m->bsum.as<int>());
+    hipLaunchKernelGGL(k_map_heads, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n, m->bsum.as<int>());
     hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, m->stream, m->bsum.as<int>(), (int)nhb, &st->n_out);
-    hipLaunchKernelGGL(k_map_centres, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n_sorted, m->bsum.as<int>(), resolution, st, m->out.as<float4>(), n);
+    hipLaunchKernelGGL(k_map_centres, dim3(nhb), dim3(MAP_BLK), 0, m->stream, keys, n, m->bsum.as<int>(), resolution, st, m->out.as<float4>(), n);
     APD_HIP(hipEventRecord(m->ev[4], m->stream));
     APD_TRY(fetch_state());
     stage_times(4);
@@ -3974,24 +3970,6 @@ int apdgicp_dbscan_set_params(apdgicp_dbscan* h, const apdgicp_dbscan_params* p)
   });
 }
 
-// the stable LSD radix sort of apd_map.hpp over n (key, value) pairs, `passes` 8-bit digits from the bottom; the sorted pairs end in *ks / *vs
-static void dbscan_radix_sort(apdgicp_dbscan* h, int n, int passes, unsigned long long** ks, int** vs) {
-  VoxSortScratch& s = h->sort;
-  const int nblk = (n + MAP_RS_TILE - 1) / MAP_RS_TILE;
-  const int64_t entries = 256ll * nblk;
-  const int nsb = (int)((entries + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS));
-  unsigned long long *ka = s.keys_a.as<unsigned long long>(), *kb = s.keys_b.as<unsigned long long>();
-  int *va = s.idx_a.as<int>(), *vb = s.idx_b.as<int>();
-  for (int p = 0; p < passes; p++) {
-    hipLaunchKernelGGL(k_map_rs_hist, dim3(nblk), dim3(MAP_RS_BLK), 0, h->stream, ka, n, 8 * p, nblk, s.hist.as<int>());
-    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nsb), dim3(SCAN_BLK), 0, h->stream, s.hist.as<int>(), (int)entries, s.rs_bsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, h->stream, s.rs_bsum.as<int>(), nsb, h->scal.as<int>() + DB_W_RADIX);
-    hipLaunchKernelGGL(k_map_rs_scatter_pairs, dim3(nblk), dim3(MAP_RS_BLK), 0, h->stream, ka, va, kb, vb, n, 8 * p, nblk, s.hist.as<int>(), s.rs_bsum.as<int>());
-    std::swap(ka, kb), std::swap(va, vb);
-  }
-  h->launches += 4 * passes;
-  *ks = ka, *vs = va;
-}
 static int bits_for(int64_t n) {  // the smallest b with n <= 2^b
   int b = 0;
   while ((1ll << b) < n) b++;
@@ -4015,7 +3993,7 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
       return 0;
     }
     APD_HIP(hipSetDevice(h->device));
-    const int ni = (int)n, nb = (ni + DB_BLK - 1) / DB_BLK, nt = (ni + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS);
+    const int ni = (int)n, nb = (ni + DB_BLK - 1) / DB_BLK, nt = scan_tiles(ni);
     const float *d_xyz = xyz, *d_dop = doppler;
     if (!on_device) {
       // (no wait: the copies are ordered behind the previous run's kernels by the stream; a buffer that grows is freed by hipFree, which waits)
@@ -4028,7 +4006,7 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
         d_dop = h->stage_dop.as<float>();
       }
     }
-    APD_TRY(h->sort.ensure(ni));
+    APD_TRY(h->sort.ensure(ni, true));
     APD_TRY(h->pts.ensure((size_t)n * 16));
     APD_TRY(h->spts.ensure((size_t)n * 16));
     APD_TRY(h->gkeys.ensure((size_t)n * 8));
@@ -4048,14 +4026,17 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
     APD_HIP(mark(0));
     // the grid: cells, (cell, index) sorted, the sorted copy
     hipLaunchKernelGGL(k_db_keys, grid, blk, 0, st, d_xyz, ni, (int)(stride_bytes / 4), d_dop, (int)(doppler_stride_bytes / 4), cell, h->pts.as<float4>(), h->dop.as<float>(),
-                       h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>(), scal);
-    unsigned long long* ks;
-    int* vs;
-    dbscan_radix_sort(h, ni, 8, &ks, &vs);
+                       h->sort.keys_a.as<unsigned long long>(), h->sort.val_a.as<int>(), scal);
+    auto sort_pairs = [&](int count, int passes) {  // what k_db_keys / k_db_rank_keys / k_db_member_emit left in keys_a / val_a
+      const RadixSorted r = enqueue_radix_sort(st, h->sort, count, passes, true);
+      h->launches += r.launches;
+      return r;
+    };
+    RadixSorted r = sort_pairs(ni, 8);
     const unsigned long long* gk = h->gkeys.as<unsigned long long>();
     const float4* sp = h->spts.as<float4>();
     const unsigned char* sc = h->score.as<unsigned char>();
-    hipLaunchKernelGGL(k_db_gather, grid, blk, 0, st, ks, vs, h->pts.as<float4>(), ni, h->gkeys.as<unsigned long long>(), h->spts.as<float4>());
+    hipLaunchKernelGGL(k_db_gather, grid, blk, 0, st, r.keys, r.vals, h->pts.as<float4>(), ni, h->gkeys.as<unsigned long long>(), h->spts.as<float4>());
     APD_HIP(mark(1));
     // D1 - D5
     hipLaunchKernelGGL(k_db_count, grid, blk, 0, st, gk, sp, ni, eps2, P.min_pts, h->cnt.as<int>(), h->core.as<unsigned char>(), h->score.as<unsigned char>(), h->parent.as<int>(),
@@ -4068,11 +4049,10 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
     APD_HIP(mark(4));
     // D6 / D7: kept seeds ranked by (size descending, seed ascending), the sizes scanned
     hipLaunchKernelGGL(k_db_rank_keys, grid, blk, 0, st, h->core.as<unsigned char>(), h->root.as<int>(), h->size.as<int>(), ni, bits, P.min_cluster_size, P.max_cluster_size,
-                       h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>(), h->rank_of.as<int>(), scal);
-    dbscan_radix_sort(h, ni, p1, &ks, &vs);
-    hipLaunchKernelGGL(k_db_rank_table, grid, blk, 0, st, ks, h->size.as<int>(), ni, bits, scal, h->rank_of.as<int>(), h->cseed.as<int>(), h->csize.as<int>());
-    hipLaunchKernelGGL(k_map_scan_tiles, dim3(nt), dim3(SCAN_BLK), 0, st, h->csize.as<int>(), ni, h->tsum.as<int>());
-    hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, st, h->tsum.as<int>(), nt, scal + DB_W_M);
+                       h->sort.keys_a.as<unsigned long long>(), h->sort.val_a.as<int>(), h->rank_of.as<int>(), scal);
+    r = sort_pairs(ni, p1);
+    hipLaunchKernelGGL(k_db_rank_table, grid, blk, 0, st, r.keys, h->size.as<int>(), ni, bits, scal, h->rank_of.as<int>(), h->cseed.as<int>(), h->csize.as<int>());
+    enqueue_exclusive_scan(st, h->csize.as<int>(), ni, h->tsum.as<int>(), scal + DB_W_M);
     h->launches += 10;
     APD_HIP(hipGetLastError());
     APD_HIP(hipMemcpyAsync(h->h_scal.p, h->scal.p, DB_WORDS * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -4085,19 +4065,18 @@ int apdgicp_dbscan_run(apdgicp_dbscan* h, const float* xyz, int64_t n, int64_t s
     if (K < 0 || K > ni || M < K || M > (1ll << 30)) return fail(APDGICP_ERR_INTERNAL, "DBSCAN: inconsistent cluster count");
     if (K > 0) {
       const int Mi = (int)M, p2 = std::max(1, (bits_for(K) + 7) / 8);
-      APD_TRY(h->sort.ensure(std::max(ni, Mi)));  // (nothing is in flight)
+      APD_TRY(h->sort.ensure(std::max(ni, Mi), true));  // (nothing is in flight)
       APD_TRY(h->offsets.ensure((size_t)(K + 1) * 4));
       APD_TRY(h->members.ensure((size_t)M * 4));
       APD_TRY(h->table.ensure((size_t)K * sizeof(DbCluster)));
       hipLaunchKernelGGL(k_db_offsets, dim3((K + 1 + DB_BLK - 1) / DB_BLK), blk, 0, st, h->csize.as<int>(), h->tsum.as<int>(), K, Mi, h->offsets.as<int>());
       hipLaunchKernelGGL(k_db_member_count, grid, blk, 0, st, gk, sp, sc, h->root.as<int>(), h->seed.as<int>(), h->nextra.as<int>(), h->rank_of.as<int>(), ni, eps2,
                          h->mcount.as<int>());
-      hipLaunchKernelGGL(k_map_scan_tiles, dim3(nt), dim3(SCAN_BLK), 0, st, h->mcount.as<int>(), ni, h->msum.as<int>());
-      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, st, h->msum.as<int>(), nt, scal + DB_W_M2);
+      enqueue_exclusive_scan(st, h->mcount.as<int>(), ni, h->msum.as<int>(), scal + DB_W_M2);
       hipLaunchKernelGGL(k_db_member_emit, grid, blk, 0, st, gk, sp, sc, h->root.as<int>(), h->seed.as<int>(), h->nextra.as<int>(), h->rank_of.as<int>(), h->mcount.as<int>(),
-                         h->msum.as<int>(), ni, eps2, Mi, h->sort.keys_a.as<unsigned long long>(), h->sort.idx_a.as<int>());
-      dbscan_radix_sort(h, Mi, p2, &ks, &vs);
-      APD_HIP(hipMemcpyAsync(h->members.p, vs, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+                         h->msum.as<int>(), ni, eps2, Mi, h->sort.keys_a.as<unsigned long long>(), h->sort.val_a.as<int>());
+      r = sort_pairs(Mi, p2);
+      APD_HIP(hipMemcpyAsync(h->members.p, r.vals, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
       hipLaunchKernelGGL(k_db_table, dim3(K), blk, 0, st, h->offsets.as<int>(), h->members.as<int>(), h->cseed.as<int>(), h->ncore.as<int>(), h->pts.as<float4>(),
                          d_dop ? h->dop.as<float>() : (const float*)nullptr, ni, h->table.as<DbCluster>());
       h->launches += 6;

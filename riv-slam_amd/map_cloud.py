@@ -93,10 +93,10 @@ class MapCloudGenerator:
 
     def info(self) -> dict:
         """counts (n_input, n_pushed, n_finite, n_out), the octree's depth, final box (min, max: float64[3]) and growth rounds, the sort
-        (sort_passes, sort_kind: "radix" / "bitonic") and the device time of the last generate per stage (stage_ms: transform + gate, box
+        (sort_passes, sort_kind: always "radix") and the device time of the last generate per stage (stage_ms: transform + gate, box
         replay, keys + sort, heads + centres)"""
         r = MapCloudInfo()
         _check(self.L.apdgicp_map_cloud_info(self.h, C.byref(r)))
         return dict(n_input=r.n_input, n_pushed=r.n_pushed, n_finite=r.n_finite, n_out=r.n_out, min=np.array(r.min, dtype=np.float64),
                     max=np.array(r.max, dtype=np.float64), depth=r.depth, rounds=r.rounds, sort_passes=r.sort_passes,
-                    sort_kind="bitonic" if r.sort_kind else "radix", stage_ms=np.array(r.stage_ms, dtype=np.float32))
+                    sort_kind="radix", stage_ms=np.array(r.stage_ms, dtype=np.float32))

@@ -2,9 +2,8 @@
 (tests/map_cloud_np.py: trajectory_keyframes), 64 x 8192 and 1024 x 8192 points, at map_cloud_resolution = 0.05, with the clouds resident:
 only generate() is timed.  Protocol: 5 warm-up calls, then 30 timed calls per configuration (wall clock around a call that ends with the
 host holding n_out), median with p10 / p90, the device otherwise idle; per stage the median of the device times the library takes with
-events around its own launches (transform + gate, box replay with its host round trips, keys + sort, heads + centres).  Both sorts: the
-radix sort (the product) and the bitonic sort of the submap assembler (APDGICP_MAP_SORT=bitonic, read when a generator is created).  For
-scale only: the numpy restatement (tests/map_cloud_np.py) on the small case.
+events around its own launches (transform + gate, box replay with its host round trips, keys + sort, heads + centres).  For scale only:
+the numpy restatement (tests/map_cloud_np.py) on the small case.
 usage: python tests/measure/bench_map_cloud.py [out.json] [--keyframes K ...] [--runs R]"""
 import importlib
 import json
@@ -37,31 +36,22 @@ def main():
     for K in counts:
         clouds, poses = M.trajectory_keyframes(scene, K, 8192, 7, origin=(250.0, -120.0, 3.0))
         case = {"keyframes": K}
-        ref = None
-        for sort in ("radix", "bitonic"):
-            os.environ["APDGICP_MAP_SORT"] = sort
-            gen = mc.MapCloudGenerator()
-            for c in clouds:
-                gen.add_keyframe(c)
-            stage = []
+        gen = mc.MapCloudGenerator()
+        for c in clouds:
+            gen.add_keyframe(c)
+        stage = []
 
-            def once():
-                n = gen.generate(poses, None, 0.05)
-                stage.append(gen.info()["stage_ms"])
-                return n
-            case[sort] = timed(once, runs=runs, warm=5)
-            med = np.median(np.array(stage[-runs:]), axis=0)
-            case[sort]["stage_ms"] = {k: float(v) for k, v in zip(STAGES, med)}
-            info = gen.info()
-            assert info["sort_kind"] == sort
-            case.update(n_input=info["n_input"], n_pushed=info["n_pushed"], n_out=info["n_out"], depth=info["depth"], rounds=info["rounds"])
-            if sort == "radix":
-                case["radix_passes"] = info["sort_passes"]
-                ref = gen.to_numpy()
-            else:
-                case["sorts_agree"] = bool(np.array_equal(ref.view(np.uint32), gen.to_numpy().view(np.uint32)))
-            del gen
-        os.environ.pop("APDGICP_MAP_SORT", None)
+        def once():
+            n = gen.generate(poses, None, 0.05)
+            stage.append(gen.info()["stage_ms"])
+            return n
+        case["radix"] = timed(once, runs=runs, warm=5)
+        med = np.median(np.array(stage[-runs:]), axis=0)
+        case["radix"]["stage_ms"] = {k: float(v) for k, v in zip(STAGES, med)}
+        info = gen.info()
+        case.update(n_input=info["n_input"], n_pushed=info["n_pushed"], n_out=info["n_out"], depth=info["depth"], rounds=info["rounds"],
+                    radix_passes=info["sort_passes"])
+        del gen
         if K <= 64:
             case["numpy_restatement"] = timed(lambda: M.generate(clouds, poses, 0.05), runs=3, warm=1)
         print(json.dumps(case), flush=True)

@@ -272,6 +272,23 @@ def test_blobs_with_noise_and_equal_sizes(mods):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [4095, 4096, 4097])
+def test_blobs_around_one_radix_tile(mods, n):
+    """24 blobs of 150 points + uniform noise around 4096 points, the tile of the radix sort: the cell sort and the rank sort run over one tile
+    (4095, 4096) or two (4097); the member sort runs over M != n pairs"""
+    _, db = mods
+    rng = np.random.default_rng(11)
+    centres = rng.uniform(-20, 20, (24, 3))
+    pts = np.concatenate([c + 0.3 * rng.normal(size=(150, 3)) for c in centres])
+    pts = np.concatenate([pts, rng.uniform(-25, 25, (n - len(pts), 3))]).astype(F32)
+    pts = pts[rng.permutation(n)]
+    ref, got = check(db, pts, 0.4, min_pts=4, min_cluster_size=5, max_cluster_size=400)
+    M = len(got["idx"])
+    print("clusters:", len(ref["clusters"]), "members:", M)
+    assert len(ref["clusters"]) >= 12 and 12 * 100 <= M < n
+
+
+@pytest.mark.gpu
 def test_non_finite_rows_in_the_middle(mods):
     _, db = mods
     rng = np.random.default_rng(13)

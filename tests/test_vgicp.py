@@ -193,7 +193,7 @@ def _scene_cloud(n, seed=21):
 
 
 @gpu
-@pytest.mark.parametrize("n", (20, 63, 64, 65, 257, 4099))
+@pytest.mark.parametrize("n", (20, 63, 64, 65, 257, 4099, 65537))  # 65537: 17 radix tiles, the scanned histogram of the pair sort spans two scan tiles
 def test_voxel_map_bit_for_bit(vg, n):
     cloud = _scene_cloud(n)
     g = vg.FastVGICP()
