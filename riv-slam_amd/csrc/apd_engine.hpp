@@ -29,6 +29,7 @@
 #include "apd_devbuf.hpp"
 #include "apd_kernels.hpp"
 #include "apd_hostpack.hpp"
+#include "apd_streams.hpp"
 
 namespace apd {
 
@@ -72,6 +73,47 @@ struct roctx_range {
 inline int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
   return v && *v ? atoi(v) : dflt;
+}
+
+// The registry of apd_streams.hpp bound to HIP: every stream an engine creates itself (main stream, group streams, the pool's cloud
+// stream) comes from here and goes back here.  The current device is the engine's (every entry point sets it).  Never destroyed:
+// handles may outlive the statics of this library at process exit.
+inline int engine_streams(StreamSlots** out) {
+  static StreamSlots* const reg = []() -> StreamSlots* {
+    StreamClass cls;
+    if (!parse_stream_class(getenv("APDGICP_STREAM_CLASS"), StreamClass::Low, &cls)) return nullptr;
+    StreamSlots::Backend be;
+    be.create = [](int, StreamClass c, void** o) -> int {
+      hipStream_t s = nullptr;
+      if (c == StreamClass::Normal) {
+        APD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      } else {
+        int least = 0, greatest = 0;  // numerically: the greatest priority is the smaller number
+        APD_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        APD_HIP(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, c == StreamClass::Low ? least : greatest));
+      }
+      *o = (void*)s;
+      return 0;
+    };
+    be.destroy = [](int, void* s) { (void)hipStreamDestroy((hipStream_t)s); };
+    be.has_priorities = [](int) {
+      int least = 0, greatest = 0;
+      return hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
+    };
+    return new StreamSlots(std::move(be), cls, hw_queue_limit(getenv("GPU_MAX_HW_QUEUES")));
+  }();
+  if (!reg) return fail(APDGICP_ERR_INVALID_ARG, "APDGICP_STREAM_CLASS must be normal, low or high");
+  *out = reg;
+  return 0;
+}
+inline int engine_stream_create(int device, hipStream_t* s) {
+  StreamSlots* reg = nullptr;
+  APD_TRY(engine_streams(&reg));
+  return reg->acquire(device, (void**)s);
+}
+inline void engine_stream_destroy(hipStream_t s) {
+  StreamSlots* reg = nullptr;
+  if (engine_streams(&reg) == 0) reg->release((void*)s);
 }
 
 class Engine {
@@ -222,7 +264,7 @@ class Engine {
     if (strm) {
       stream = (hipStream_t)strm;
     } else {
-      APD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+      APD_TRY(engine_stream_create(device, &stream));
       own_stream = true;
     }
     cstream = stream;
@@ -259,12 +301,13 @@ class Engine {
   // The streams of pair groups 1 .. n-1 (group 0 uses the main stream) are created when a batch first needs them, not with the
   // engine: the runtime deals streams onto its hardware queues in creation order, and the never-used group streams of
   // one-group handles pushed the main streams of four handles onto colliding queues (bench: 1.06 -> 0.93 ms per step with
-  // four handles once the main streams sat on queues of their own).
+  // four handles once the main streams sat on queues of their own).  They also take slots of the stream registry, which
+  // places only the first GPU_MAX_HW_QUEUES engine streams of a device on queues of their own (apd_streams.hpp).
   int ensure_group_streams(int ng) {
     while ((int)gstreams.size() + 1 < ng) {
       hipStream_t st_;
       hipEvent_t ev_;
-      APD_HIP(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
+      APD_TRY(engine_stream_create(device, &st_));
       APD_HIP(hipEventCreateWithFlags(&ev_, hipEventDisableTiming));
       gstreams.push_back(st_);
       gevents.push_back(ev_);
@@ -291,11 +334,11 @@ class Engine {
     for (Pool::Timed& c : pool.timed) e = hipEventDestroy(c.e0), e = hipEventDestroy(c.e1);
     for (PoolJob& j : pool.jobs)
       if (j.ev_pro) e = hipEventDestroy(j.ev_pro);
-    if (pool.cstream) e = hipStreamDestroy(pool.cstream);
-    for (auto st_ : gstreams) e = hipStreamDestroy(st_);
+    if (pool.cstream) engine_stream_destroy(pool.cstream);
+    for (auto st_ : gstreams) engine_stream_destroy(st_);
     for (auto ev_ : gevents) e = hipEventDestroy(ev_);
     for (auto& pr : nn_events) e = hipEventDestroy(pr.first), e = hipEventDestroy(pr.second);
-    if (own_stream && stream) e = hipStreamDestroy(stream);
+    if (own_stream && stream) engine_stream_destroy(stream);
     (void)e;
   }
 
@@ -1404,9 +1447,9 @@ class Engine {
     if (pool.on) return 0;
     APD_HIP(hipStreamSynchronize(stream));  // whatever the clouds went through on the main stream so far
     if (!pool.cstream) {
-      // one cloud stream at the default priority on every CU (round 6, docs/experiments.md, C4 shard: a second cloud stream 0.892 against
+      // one cloud stream, in the class of the other engine streams (apd_streams.hpp), on every CU (round 6, docs/experiments.md, C4 shard: a second cloud stream 0.892 against
       // 0.851 ms per batch; the lowest priority 0.852, confined to 192 / 128 / 96 CUs 0.859 / 0.907 / 1.031 against 0.846)
-      APD_HIP(hipStreamCreateWithFlags(&pool.cstream, hipStreamNonBlocking));
+      APD_TRY(engine_stream_create(device, &pool.cstream));
       for (Pool::List& li : pool.L)
         for (int i = 0; i < kPoolRing; i++) APD_HIP(hipEventCreateWithFlags(&li.ev[i], hipEventDisableTiming));
       APD_TRY(ensure_group_streams(Pool::kLists + 1));  // gstreams[l - 1]: list l; gstreams[kLists - 1]: the slice stream of a list that ticks alone
