@@ -603,11 +603,43 @@ int apdgicp_batch_debug_block_timeline(apdgicp_batch* b, unsigned long long* out
  * (scan_matching_odometry_nodelet.cpp:606-618): the clouds of the last <= max_submap_frames keyframes are
  * transformed by their poses relative to the newest keyframe (pcl::transformPointCloud with a Matrix4d),
  * concatenated, and downsampled by downsample() (:412-422) -- pcl::VoxelGrid with the configured leaf
- * (preprocessing_nodelet.cpp:137-144, "VOXELGRID").  Everything stays on the device; the result can be handed to
- * apdgicp_set_target / apdgicp_batch_set_cloud as a device pointer (16-byte stride). */
+ * (preprocessing_nodelet.cpp:137-144, "VOXELGRID") or, after apdgicp_submap_set_downsample_method, pcl::ApproximateVoxelGrid
+ * ("APPROX_VOXELGRID", :145-149; scan_matching_odometry_nodelet.cpp:156-160).  Everything stays on the device; the result can be
+ * handed to apdgicp_set_target / apdgicp_batch_set_cloud as a device pointer (16-byte stride).
+ *
+ * APPROX_VOXELGRID: pcl::ApproximateVoxelGrid<PointXYZI>::applyFilter, PCL 1.10, filters/impl/approximate_voxel_grid.hpp, "as
+ * published" like the exact grid.  A table of histsize_ = 512 entries {ix, iy, iz, count, centroid}, all reset at the start of every
+ * call; downsample_all_data_ = true (the default, which the reference never changes): the centroid is {x, y, z, intensity}.
+ *   AV1. inv[a] = 1.0f / leaf[a] in fp32 (Array3f::Ones() / leaf_size_).
+ *   AV2. Voxel index, for point cp in input order: ix = (int)floorf(x * inv[0]), iy, iz likewise; the product is one fp32 multiply
+ *        rounded on its own.  A value that an int cannot hold (beyond +-2^31, an infinite product of finite factors, NaN) becomes
+ *        INT_MIN, as the reference's x86-64 build converts it -- on the positive side too.
+ *   AV3. hash = (ix * 7171 + iy * 3079 + iz * 4231) & 511, in unsigned arithmetic (two's complement: ix = -1, iy = iz = 0 gives 509).
+ *   AV4. Eviction.  If entry `hash` has count > 0 and another (ix, iy, iz), it is flushed: centroid / (float)count -- a true fp32
+ *        division per component, Eigen >= 3.3 -- becomes the next output point, count and centroid are zeroed.  Then, in every case,
+ *        the entry takes (ix, iy, iz), count++ and centroid += {x, y, z, intensity}: fp32 additions in input order.
+ *   AV5. Final flush.  After the last point the entries with count > 0 are flushed in ascending entry index.
+ *   AV6. Consequences: a voxel can be emitted more than once (evicted, then revisited); the output is not sorted by voxel; n_out lies
+ *        between the number of occupied voxels and n; there is no bounding box and no leaf that is "too small".
+ *   AV7. Deviations.  A point with a non-finite x, y or z takes no part (PCL's class has undefined behaviour there; in the reference
+ *        the range gate has removed such points before the grid, here the gate leaves them as NaN holes: skipping them is the same
+ *        thing).  Eigen 3.2's `v /= s`, which multiplies by the reciprocal, is not built.
+ * The device does not run the loop: it sorts the points by hash (stable, so input order survives inside an entry), takes every maximal
+ * stretch of one voxel inside a hash as one stay in the entry, places the evicted stays by a scan over the points that evicted them
+ * and the remaining ones behind them in entry order, and adds every stay's points in input order (apd_approx_voxel.hpp).  The bytes
+ * are the loop's (tests/approx_voxel_np.py restates it literally).  At most 2^27 points, like the exact grid.  15 kernel launches and one
+ * wait (for n_out) per call, whatever n.  Measured on an MI355X (profiles/approx_voxel.json, tests/measure/bench_approx_voxel.py; device
+ * input, leaf 0.1, median ms per assemble; the ranges are those of several sessions, which differ by about 10 %): 0.08 - 0.09 at 512
+ * points, 0.09 - 0.10 at 8 192, 0.11 - 0.13 at 100 000, against 0.08 / 0.09 - 0.10 / 0.19 - 0.21 for VOXELGRID on the same clouds in the
+ * same process; the whole scan filter at 8 192 points is 0.20 - 0.22 with either.  Both are launch and wait latency up to a scan's size.
+ * No bar was set. */
+typedef enum { APDGICP_DOWNSAMPLE_VOXELGRID = 0, APDGICP_DOWNSAMPLE_APPROX_VOXELGRID = 1 } apdgicp_downsample_method;
 typedef struct apdgicp_submap apdgicp_submap;
 int apdgicp_submap_create(int device, void* stream, apdgicp_submap** out);
 int apdgicp_submap_destroy(apdgicp_submap* s);
+/* Which filter downsample() is (an apdgicp_downsample_method): stays on the object until set again, VOXELGRID after create.  A NULL
+ * object or an unknown method: APDGICP_ERR_INVALID_ARG.  A NULL leaf or leaf[0] <= 0 still means NONE, whatever the method. */
+int apdgicp_submap_set_downsample_method(apdgicp_submap* s, int method);
 /* xyz[c]: first coordinate of cloud c (n_points[c] points, stride_bytes apart, host or device memory as on_device says);
  * intensity_offset_bytes: distance from a point's x to its intensity field (16 for pcl::PointXYZI), < 0: none (0 is kept);
  * rel_poses: n_clouds x 16 doubles, column-major 4x4 (keyframes[i].odom^-1 * keyframes.back().odom, :609), NULL = identity;
@@ -632,7 +664,8 @@ int apdgicp_submap_copy(apdgicp_submap* s, float* dst_xyzi, int64_t capacity_poi
  *   2. downsample (:850-866): leaf[0] > 0: pcl::VoxelGrid ("VOXELGRID", :137-144) through the kernels of apdgicp_submap_assemble --
  *      one point per occupied voxel in ascending voxel index, a leaf too small for the extent returns the cloud unfiltered with the
  *      same warning (non-finite points are dropped from it here, in input order); leaf[0] <= 0: pcl::removeNaNFromPointCloud (:852-857),
- *      order kept.  APPROX_VOXELGRID is not offered.
+ *      order kept.  downsample_method APPROX_VOXELGRID (:145-149) with leaf[0] > 0: pcl::ApproximateVoxelGrid instead, AV1 .. AV7 above
+ *      (one point per stay of a voxel in its table entry, in eviction order and then entry order; never "too small").
  *   3. outlier_removal (:868-879) on the cloud of step 2, whose order the output keeps.  d2 = the fp32 squared distance in FLANN
  *      L2_Simple order, neighbours in rank order, the first one the point itself (or a duplicate) at 0:
  *        STATISTICAL (:167-175, pcl::StatisticalOutlierRemoval): k = mean_k + 1; score = (float)(sum_{r=1..mean_k} (double)sqrtf(d2[r]) / mean_k)
@@ -658,7 +691,7 @@ typedef struct {
   double stddev_mul;             /* "statistical_stddev", :169 ; default 1.0 */
   double radius;                 /* "radius_radius", :177 ; default 0.8 */
   float leaf[3];                 /* "downsample_resolution", :138 ; default 0.1 each; leaf[0] <= 0: "downsample_method" NONE */
-  int32_t reserved;              /* 0 */
+  int32_t downsample_method;     /* apdgicp_downsample_method, "downsample_method", :137-156 ; default VOXELGRID (0); anything else: INVALID_ARG */
 } apdgicp_scan_filter_params;
 typedef struct apdgicp_scan_filter apdgicp_scan_filter;
 void apdgicp_scan_filter_default_params(apdgicp_scan_filter_params* p);                       /* the nodelet's defaults, :137-205 */

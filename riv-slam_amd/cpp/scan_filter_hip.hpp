@@ -42,10 +42,12 @@ class ScanFilterHip {
   void setDistanceFarThresh(double v) { prm_.far = v, dirty_ = true; }
   void setZLowThresh(double v) { prm_.z_low = v, dirty_ = true; }
   void setZHighThresh(double v) { prm_.z_high = v, dirty_ = true; }
-  // "downsample_method" (VOXELGRID / NONE; APPROX_VOXELGRID is not offered: it falls to NONE with a warning, like an unknown name at
-  // :150-156) and "downsample_resolution" (:137-138)
+  // "downsample_method" (VOXELGRID / APPROX_VOXELGRID / NONE; an unknown name falls to NONE with a warning, like :150-156) and
+  // "downsample_resolution" (:137-138)
   void setDownsampleMethod(const std::string& m) {
-    voxelgrid_ = m == "VOXELGRID";
+    const bool approx = m == "APPROX_VOXELGRID";
+    voxelgrid_ = approx || m == "VOXELGRID";
+    prm_.downsample_method = approx ? APDGICP_DOWNSAMPLE_APPROX_VOXELGRID : APDGICP_DOWNSAMPLE_VOXELGRID;
     if (!voxelgrid_ && m != "NONE") std::fprintf(stderr, "[ScanFilterHip] downsample_method %s is not offered: no downsampling\n", m.c_str());
     dirty_ = true;
   }

@@ -19,6 +19,7 @@
 #include "apd_ndt_batch.hpp"
 #include "apd_dbscan.hpp"
 #include "apd_ingest.hpp"
+#include "apd_approx_voxel.hpp"
 
 using namespace apd;
 
@@ -285,6 +286,9 @@ struct apdgicp_submap {
   DevBuf stage, cat, keys, pos, bsum, out, scal;  // scal: box6[6], total, err
   CachedTable jobs;
   PinnedBuf h_scal;  // mirror of {total, err}: 2 ints
+  int method = APDGICP_DOWNSAMPLE_VOXELGRID;  // apdgicp_submap_set_downsample_method: sticky
+  RadixScratch av_sort;                       // APPROX_VOXELGRID (apd_approx_voxel.hpp): the (hash, point) pair sort,
+  DevBuf av_evict, av_tiles, av_head, av_words;  // the eviction flags and their scan, the run heads, AV_WORDS ints
   int64_t n_last = 0;
   bool last_is_cat = false;  // no downsampling: the result is the concatenation itself
   ~apdgicp_submap() {
@@ -2515,6 +2519,42 @@ int apdgicp_submap_destroy(apdgicp_submap* s) {
   return 0;
 }
 
+int apdgicp_submap_set_downsample_method(apdgicp_submap* s, int method) {
+  if (!s) return fail(APDGICP_ERR_INVALID_ARG, "submap is null");
+  if (method != APDGICP_DOWNSAMPLE_VOXELGRID && method != APDGICP_DOWNSAMPLE_APPROX_VOXELGRID) return fail(APDGICP_ERR_INVALID_ARG, "unknown downsample method");
+  s->method = method;
+  return 0;
+}
+
+// AV1 .. AV7: pcl::ApproximateVoxelGrid of the n points of s->cat into s->out, one wait (for n_out)
+static int submap_approx_voxel(apdgicp_submap* s, int n, const float il[3], int64_t* n_out) {
+  const int nt = scan_tiles(n), nb = (n + AV_BLK - 1) / AV_BLK;
+  APD_TRY(s->av_sort.ensure(n, true));
+  APD_TRY(s->av_evict.ensure((size_t)n * 4));
+  APD_TRY(s->av_tiles.ensure((size_t)nt * 4));
+  APD_TRY(s->av_head.ensure((size_t)n));
+  APD_TRY(s->av_words.ensure(AV_WORDS * sizeof(int)));
+  APD_TRY(s->out.ensure((size_t)n * 16));
+  const float4* cat = s->cat.as<float4>();
+  int *evict = s->av_evict.as<int>(), *tiles = s->av_tiles.as<int>(), *words = s->av_words.as<int>();
+  unsigned char* head = s->av_head.as<unsigned char>();
+  hipLaunchKernelGGL(k_av_keys, dim3(nb), dim3(AV_BLK), 0, s->stream, cat, n, il[0], il[1], il[2], s->av_sort.keys_a.as<unsigned long long>(),
+                     s->av_sort.val_a.as<int>(), evict, words);
+  const RadixSorted r = enqueue_radix_sort(s->stream, s->av_sort, n, AV_SORT_PASSES, true);
+  hipLaunchKernelGGL(k_av_heads, dim3(nb), dim3(AV_BLK), 0, s->stream, r.keys, r.vals, cat, n, il[0], il[1], il[2], head, evict, words);
+  enqueue_exclusive_scan(s->stream, evict, n, tiles, words);  // words[0] = evictions
+  hipLaunchKernelGGL(k_av_occ, dim3(1), dim3(SCAN_BLK), 0, s->stream, words);
+  hipLaunchKernelGGL(k_av_centroids, dim3(nb), dim3(AV_BLK), 0, s->stream, r.keys, r.vals, head, cat, evict, tiles, words, n, s->out.as<float4>(), n);
+  APD_HIP(hipGetLastError());
+  APD_HIP(hipMemcpyAsync(s->h_scal.p, words + 1, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  APD_HIP(hipStreamSynchronize(s->stream));
+  const int total = s->h_scal.as<int>()[0];
+  if (total < 0 || total > n) return fail(APDGICP_ERR_INTERNAL, "approximate voxel filter failed");
+  s->n_last = total, s->last_is_cat = false;  // (AV6: no bounding box, no leaf that is too small)
+  *n_out = total;
+  return 0;
+}
+
 int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* xyz, const int64_t* n_points, int64_t stride_bytes,
                             int64_t intensity_offset_bytes, int on_device, const double* rel_poses, const float* leaf, int64_t* n_out) {
   return guarded([&]() -> int {
@@ -2573,6 +2613,7 @@ int apdgicp_submap_assemble(apdgicp_submap* s, int n_clouds, const void* const* 
     }
     if (!(leaf[1] > 0.f) || !(leaf[2] > 0.f)) return fail(APDGICP_ERR_INVALID_ARG, "leaf sizes must be positive");
     const float il[3] = {1.f / leaf[0], 1.f / leaf[1], 1.f / leaf[2]};  // inverse_leaf_size_ = Array4f::Ones() / leaf_size_
+    if (s->method == APDGICP_DOWNSAMPLE_APPROX_VOXELGRID) return submap_approx_voxel(s, n, il, n_out);
     const int np2 = bitonic_padded_size(n);
     const int nsb = (np2 + SCAN_BLK * SCAN_ITEMS - 1) / (SCAN_BLK * SCAN_ITEMS);
     APD_TRY(s->keys.ensure((size_t)np2 * 8));
@@ -2646,6 +2687,8 @@ void apdgicp_scan_filter_default_params(apdgicp_scan_filter_params* p) {
 static int scan_filter_check_params(const apdgicp_scan_filter_params* p) {
   if (!p) return fail(APDGICP_ERR_INVALID_ARG, "params is null");
   if (p->leaf[0] > 0.f && (!(p->leaf[1] > 0.f) || !(p->leaf[2] > 0.f))) return fail(APDGICP_ERR_INVALID_ARG, "leaf sizes must be positive");
+  if (p->downsample_method != APDGICP_DOWNSAMPLE_VOXELGRID && p->downsample_method != APDGICP_DOWNSAMPLE_APPROX_VOXELGRID)
+    return fail(APDGICP_ERR_INVALID_ARG, "unknown downsample method");
   if (p->outlier_method == APDGICP_OUTLIER_STATISTICAL) {
     if (p->mean_k < 1) return fail(APDGICP_ERR_INVALID_ARG, "mean_k must be >= 1");
     if (p->mean_k + 1 > KNN_NC) return fail(APDGICP_ERR_UNSUPPORTED, "mean_k above 31");
@@ -2749,6 +2792,7 @@ int apdgicp_scan_filter_run(apdgicp_scan_filter* f, const float* xyz, int64_t n,
     if (P.leaf[0] > 0.f) {
       const void* src = f->gated.p;
       int64_t nn = n, nv = 0;
+      APD_TRY(apdgicp_submap_set_downsample_method(f->vox, P.downsample_method));
       APD_TRY(apdgicp_submap_assemble(f->vox, 1, &src, &nn, 16, 12, 1, nullptr, P.leaf, &nv));
       if (!f->vox->last_is_cat) step2 = f->vox->out.as<float4>(), n2 = (int)nv;  // (else: leaf too small, PCL returns its input: compacted below)
     }

@@ -96,6 +96,7 @@ SYMBOLS = [
     "apdgicp_batch_align_async", "apdgicp_batch_pump", "apdgicp_batch_is_pooled", "apdgicp_batch_fitness", "apdgicp_batch_synchronize", "apdgicp_batch_copy_results", "apdgicp_batch_set_profiling",
     "apdgicp_batch_align_enqueue", "apdgicp_batch_align_collect", "apdgicp_batch_set_pair_groups", "apdgicp_batch_last_nn_time", "apdgicp_batch_last_nn_profile", "apdgicp_batch_last_ticks", "apdgicp_batch_last_nn_kernel", "apdgicp_batch_debug_stats", "apdgicp_batch_debug_block_timeline", "apdgicp_batch_pool_counters",
     "apdgicp_submap_create", "apdgicp_submap_destroy", "apdgicp_submap_assemble", "apdgicp_submap_points", "apdgicp_submap_copy",
+    "apdgicp_submap_set_downsample_method",
     "apdgicp_scan_filter_default_params", "apdgicp_scan_filter_create", "apdgicp_scan_filter_destroy", "apdgicp_scan_filter_set_params",
     "apdgicp_scan_filter_run", "apdgicp_scan_filter_points", "apdgicp_scan_filter_copy", "apdgicp_scan_filter_stage_counts", "apdgicp_scan_filter_scores",
     "apdgicp_ego_velocity_default_params", "apdgicp_ego_velocity_create", "apdgicp_ego_velocity_destroy", "apdgicp_ego_velocity_set_params",
@@ -231,6 +232,7 @@ def load_library(path: str | None = None):
     L.apdgicp_submap_assemble.argtypes = [vp, i32, vp, vp, i64, i64, i32, vp, vp, C.POINTER(i64)]
     L.apdgicp_submap_points.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     L.apdgicp_submap_copy.argtypes = [vp, vp, i64, i32]
+    L.apdgicp_submap_set_downsample_method.argtypes = [vp, i32]
     L.apdgicp_scan_filter_default_params.argtypes = [vp]
     L.apdgicp_scan_filter_default_params.restype = None
     L.apdgicp_scan_filter_create.argtypes = [vp, i32, vp, C.POINTER(vp)]

@@ -1,6 +1,6 @@
 """Scan preprocessing on the GPU: what PreprocessingNodelet::cloud_callback does to every scan before it becomes a registration
 source (radar_graph_slam/apps/preprocessing_nodelet.cpp:812-815) -- distance_filter (:881-889), downsample
-(:850-866, pcl::VoxelGrid) and outlier_removal (:868-879, pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval) -- with the
+(:850-866, pcl::VoxelGrid or pcl::ApproximateVoxelGrid) and outlier_removal (:868-879, pcl::StatisticalOutlierRemoval / pcl::RadiusOutlierRemoval) -- with the
 scan entering the device once and leaving as the device-resident cloud setInputSource accepts.  Host side of
 include/apdgicp_hip.h's apdgicp_scan_filter_* entry points.
 """
@@ -14,6 +14,13 @@ from .registration import DevicePoints, _check, _cloud_arg, _ptr, load_library
 
 OUTLIER_NONE, OUTLIER_STATISTICAL, OUTLIER_RADIUS = 0, 1, 2
 _METHODS = {"NONE": OUTLIER_NONE, "STATISTICAL": OUTLIER_STATISTICAL, "RADIUS": OUTLIER_RADIUS}
+DOWNSAMPLE_VOXELGRID, DOWNSAMPLE_APPROX_VOXELGRID = 0, 1
+_DOWNSAMPLE_METHODS = {"VOXELGRID": DOWNSAMPLE_VOXELGRID, "APPROX_VOXELGRID": DOWNSAMPLE_APPROX_VOXELGRID}
+
+
+def downsample_method_number(method) -> int:
+    """apdgicp_downsample_method of a name ("VOXELGRID" / "APPROX_VOXELGRID") or a number (passed on: the library checks it)"""
+    return _DOWNSAMPLE_METHODS[method.upper()] if isinstance(method, str) else int(method)
 
 
 class ScanFilterParams(C.Structure):
@@ -30,13 +37,14 @@ class ScanFilterParams(C.Structure):
         ("stddev_mul", C.c_double),
         ("radius", C.c_double),
         ("leaf", C.c_float * 3),
-        ("reserved", C.c_int32),
+        ("downsample_method", C.c_int32),
     ]
 
 
 def default_filter_params(**kw) -> ScanFilterParams:
     """The nodelet's defaults (preprocessing_nodelet.cpp:137-205): gate 1 .. 100 m / -5 .. 20 m, VOXELGRID 0.1, STATISTICAL 20 / 1.0
-    (RADIUS: 0.8 / 2).  leaf: a float, three floats or None (no downsampling); outlier_method: a name or a number."""
+    (RADIUS: 0.8 / 2).  leaf: a float, three floats or None (no downsampling); outlier_method: a name or a number;
+    downsample_method: "VOXELGRID" (the default), "APPROX_VOXELGRID" or a number."""
     p = ScanFilterParams()
     load_library().apdgicp_scan_filter_default_params(C.byref(p))
     for k, v in kw.items():
@@ -46,6 +54,8 @@ def default_filter_params(**kw) -> ScanFilterParams:
             v = (C.c_float * 3)(*(np.broadcast_to(np.asarray(0.0 if v is None else v, dtype=np.float32), (3,)).tolist()))
         elif k == "outlier_method" and isinstance(v, str):
             v = _METHODS[v.upper()]
+        elif k == "downsample_method":
+            v = downsample_method_number(v)
         setattr(p, k, v)
     return p
 

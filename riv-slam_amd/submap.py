@@ -1,8 +1,8 @@
 """Scan-to-submap target assembly on the GPU: the step in front of registration_s2m->setInputTarget
 in scan-to-map mode (/root/reference/radar_graph_slam/apps/scan_matching_odometry_nodelet.cpp:606-618) --
 transform the clouds of the last `max_submap_frames` keyframes into the newest keyframe's frame,
-concatenate, downsample() (:412-422, pcl::VoxelGrid with `downsample_resolution`,
-preprocessing_nodelet.cpp:137-144) and make the result the registration target, without the
+concatenate, downsample() (:412-422, pcl::VoxelGrid or pcl::ApproximateVoxelGrid with `downsample_resolution`,
+preprocessing_nodelet.cpp:137-149) and make the result the registration target, without the
 submap ever leaving the device.  Host side of include/apdgicp_hip.h's apdgicp_submap_* entry points.
 """
 from __future__ import annotations
@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from .registration import DevicePoints, _check, _cloud_arg, _ptr, load_library
+from .scan_filter import downsample_method_number
 
 POINT_XYZI_INTENSITY_OFFSET = 16  # pcl::PointXYZI: {x, y, z, pad, intensity, pad[3]} -- 32 bytes per point
 
@@ -31,11 +32,13 @@ class SubmapAssembler:
         except Exception:
             pass
 
-    def assemble(self, clouds, rel_poses=None, leaf=None, intensity_column: int | None = 3) -> int:
+    def assemble(self, clouds, rel_poses=None, leaf=None, intensity_column: int | None = 3, method="VOXELGRID") -> int:
         """clouds: list of [n, >=3] float32 arrays (numpy, or torch CUDA tensors -- all in the same memory space and with
         the same row stride); rel_poses: list of 4x4 (row-major numpy, double); leaf: float, 3 floats or None (no
-        downsampling); intensity_column: column that holds the intensity (None or a column the clouds do not have: 0 is kept).
+        downsampling); intensity_column: column that holds the intensity (None or a column the clouds do not have: 0 is kept);
+        method: downsample_method, "VOXELGRID", "APPROX_VOXELGRID" (include/apdgicp_hip.h, AV1 .. AV7) or a number.
         Returns the number of points of the assembled cloud."""
+        _check(self.L.apdgicp_submap_set_downsample_method(self.h, downsample_method_number(method)))
         args = [_cloud_arg(c) for c in clouds]
         stride, dev = args[0][2], args[0][3]
         if any(a[2] != stride or a[3] != dev for a in args):
@@ -72,6 +75,15 @@ class SubmapAssembler:
         return out
 
 
+def approx_voxel_downsample(cloud, leaf, assembler: SubmapAssembler | None = None, intensity_column: int | None = 3) -> DevicePoints:
+    """pcl::ApproximateVoxelGrid of ONE cloud, no poses: what fast_apdgicp's align.cpp:136-147 and kitti.cpp:81 do to source and target
+    before registration.  Returns the device-resident result (what setInputSource / setInputTarget accept), which lives in `assembler`
+    (a new one when None; the result keeps it alive) until its next assemble."""
+    a = assembler if assembler is not None else SubmapAssembler()
+    a.assemble([cloud], None, leaf, intensity_column, method="APPROX_VOXELGRID")
+    return a.points()
+
+
 def relative_poses(odoms, newest=None):
     """rel_pose_i = odom_i^-1 * odom_newest (scan_matching_odometry_nodelet.cpp:609), 4x4 doubles"""
     newest = np.asarray(odoms[-1] if newest is None else newest, dtype=np.float64)
@@ -79,7 +91,7 @@ def relative_poses(odoms, newest=None):
 
 
 def update_submap_target(registration, keyframe_clouds, keyframe_odoms, max_submap_frames: int, leaf, assembler: SubmapAssembler,
-                         intensity_column: int | None = 3) -> int:
+                         intensity_column: int | None = 3, method="VOXELGRID") -> int:
     """The `if (enable_scan_to_map)` block at :606-618.  keyframe_clouds / keyframe_odoms include the keyframe that was
     just pushed (keyframes.back()); like the reference loop, the submap is built from the keyframes BEFORE it:
     i in [max(0, size - max_submap_frames), size - 1).  Sets the result as `registration`'s target and returns its size
@@ -90,7 +102,7 @@ def update_submap_target(registration, keyframe_clouds, keyframe_odoms, max_subm
     if not idx:
         return 0
     poses = relative_poses([keyframe_odoms[i] for i in idx], keyframe_odoms[-1])
-    n = assembler.assemble([keyframe_clouds[i] for i in idx], poses, leaf, intensity_column)
+    n = assembler.assemble([keyframe_clouds[i] for i in idx], poses, leaf, intensity_column, method)
     if n:
         registration.setInputTarget(assembler.points())
     return n
