@@ -47,7 +47,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_set_ndt / _get_ndt and the apdgicp_ndt_* calls (NDT, P2D and D2D, as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_ndt / _get_ndt and the apdgicp_batch_ndt_* calls (NDT as a mode of the batch handle);
                                       still 6 (additive): + apdgicp_debug_live_buffers;
-                                      still 6 (additive): + the apdgicp_scan_ingest_* object (power gate and packing of a radar message, IMU deskew, frame transform) */
+                                      still 6 (additive): + the apdgicp_scan_ingest_* object (power gate and packing of a radar message, IMU deskew, frame transform);
+                                      still 6 (additive): + apdgicp_set_icp / _get_icp and the apdgicp_icp_* calls (point-to-point ICP as a mode of the registration handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -464,6 +465,90 @@ int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32
 int apdgicp_ndt_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_rows);
 /* Debug: how many voxel maps (of either cloud) this handle has built in this mode (the tests of the cache rules read it) */
 int apdgicp_ndt_build_count(apdgicp_handle* h, int64_t* n_builds);
+
+/* ------------------------------------------------------------------ point-to-point ICP as a mode of the handle
+ * pcl::IterativeClosestPoint, the ICP branch of select_registration_method() (registrations.cpp:71-78).  PCL is not under the reference tree, so
+ * nothing below can be cited by line: the source is PCL 1.10 "as published", unpinned like the filters (DESIGN.md sections 4 and 5) --
+ * registration/impl/icp.hpp, correspondence_estimation.hpp, default_convergence_criteria.hpp and transformation_estimation_svd.hpp with
+ * Eigen >= 3.3's umeyama.  The kernels (riv-slam_amd/csrc/apd_icp.hpp) and the restatement the tests compare with (tests/icp_np.py) follow
+ * this list:
+ *   IC1. Working cloud.  W0 = guess * source, or the source itself when the guess is the identity.  Each iteration replaces W by T_k * W in
+ *        fp32, in place; the order of T * p is the handle's: pairwise by default, APDGICP_FLAG_XF_LINEAR_CHAIN otherwise.  W is never
+ *        recomputed from the source.  Non-finite source points take no part: they have no match, are nobody's reciprocal neighbour, and
+ *        come back as NaN from apdgicp_icp_get_working_cloud.
+ *   IC2. Forward correspondences.  For every point of W its nearest target point with the fp32 squared distance in the engine's L2_Simple
+ *        order ((dx dx + dy dy) + dz dz over d = target - W); a tie resolves to the lowest target index.  A point is rejected iff
+ *        (double)d2 > max_correspondence_distance^2, the product taken in fp64; equality is kept.
+ *   IC3. Reciprocal correspondences (use_reciprocal_correspondences).  A forward match (i, j) is kept iff the nearest point of W to target[j]
+ *        is i, and that distance also passes the gate of IC2.  Same fp32 arithmetic (the same expression, so the reciprocal distance of a
+ *        kept pair is the forward one); a tie resolves to the lowest index of W in the caller's order.  The stored distance is the forward one.
+ *   IC4. Minimum.  Fewer than min_correspondences (default 3) matches give state NO_CORRESPONDENCES; the loop stops with converged = 0 and
+ *        T = the product so far, which is the guess if this happens at the first iteration.
+ *   IC5. Estimation (Umeyama without scaling).  pm, qm = the means of the matched W points and target points; Sigma = (1/n) sum (q - qm)(p - pm)^T,
+ *        Sigma = U D V^T, S = diag(1, 1, sign(det U det V)), R = U S V^T, t = qm - R pm.  Everything in fp64 from the fp32 coordinates, two
+ *        passes, sums in a fixed order (lanes by a fixed tree, waves and blocks in index order).  T_k is the fp32 rounding of the result; a
+ *        non-finite T_k stops the loop with converged = 0.  STATED DEVIATION: PCL sums in fp32 in Eigen's vectorised order, which cannot be
+ *        pinned.  The SVD is a one-sided Jacobi iteration, not Eigen's JacobiSVD; with fewer than two non-zero singular values R is not
+ *        unique (Sigma = 0 gives R = I).
+ *   IC6. Accumulation.  final = T_k * final as an fp32 4x4 product, each element ((a0 b0 + a1 b1) + a2 b2) + a3 b3 without contraction
+ *        (STATED DEVIATION: Eigen's order for this product is its own).  nr_iterations is then incremented, so in this mode
+ *        apdgicp_result.iterations is a COUNT, not a zero-based index.
+ *   IC7. Convergence (DefaultConvergenceCriteria), in this order: iterations >= max_iterations -> ITERATIONS, converged = 1.  With
+ *        cos = 0.5 (T00 + T11 + T22 - 1) and t2 = T03^2 + T13^2 + T23^2 of T_k in fp64 the step is similar if cos >= rot_thr and
+ *        t2 <= transformation_epsilon (NOT squared, as there); rot_thr = rotation_epsilon if rotation_epsilon > 0, else
+ *        1 - transformation_epsilon -> TRANSFORM.  mse = the fp64 mean of the kept fp32 d2; |mse - prev| < mse_threshold_absolute (default
+ *        1e-12) -> ABS_MSE; |mse - prev| / prev < euclidean_fitness_epsilon (default -DBL_MAX: never) -> REL_MSE.  Each of the three tests
+ *        fires only once iterations_similar_transforms >= max_similar_transforms (default 0), otherwise it counts the iteration as similar;
+ *        the counter is incremented when the iteration was similar and reset otherwise.  prev starts at DBL_MAX.
+ *   IC8. Result.  T = final; final_cost = the mse of the last iteration's matches (0 without a match); n_matched = the last count (saturating);
+ *        iterations = n_linearize = the iteration count; n_compute_error = 0, lm_failed = 0.  apdgicp_icp_convergence_state reads the state.
+ *        After an align W has had every T_k of the trace applied.
+ *   IC9. Mode rules.  apdgicp_set_icp, apdgicp_set_vgicp and apdgicp_set_ndt are exclusive: switching one on switches the others off, as in
+ *        N9.  No covariances are computed, clouds of any size >= 1 are accepted.  apdgicp_linearize, apdgicp_compute_error,
+ *        apdgicp_get_final_hessian (and apdgicp_get_correspondences / apdgicp_get_mahalanobis) answer APDGICP_ERR_UNSUPPORTED;
+ *        apdgicp_align_host_loop runs the same loop as apdgicp_align.  apdgicp_fitness_score, apdgicp_inlier_fraction,
+ *        apdgicp_nearest_neighbours*, apdgicp_transform_source, swap and clear keep working.  With the mode off the handle's APD / GICP
+ *        results are bit for bit what they were.
+ *   IC10. Determinism.  The same inputs give the same bytes on every run; no floating-point atomics.
+ * Not built: batch handles, the loop verifier and the sharded path in this mode; correspondence rejectors; point-to-plane; PCL's own GICP / NDT. */
+typedef enum {
+  APDGICP_ICP_NOT_CONVERGED = 0,
+  APDGICP_ICP_ITERATIONS = 1,
+  APDGICP_ICP_TRANSFORM = 2,
+  APDGICP_ICP_ABS_MSE = 3,
+  APDGICP_ICP_REL_MSE = 4,
+  APDGICP_ICP_NO_CORRESPONDENCES = 5
+} apdgicp_icp_state;   /* DefaultConvergenceCriteria::ConvergenceState, same numeric values */
+typedef struct {
+  int32_t enable;                          /* apdgicp_set_icp: non-zero switches the mode on, 0 stores the parameters and switches it off */
+  int32_t use_reciprocal_correspondences;  /* setUseReciprocalCorrespondences ; default 0 */
+  int32_t min_correspondences;             /* min_number_correspondences_ ; default 3 ; >= 1 */
+  int32_t max_similar_transforms;          /* setMaximumIterationsSimilarTransforms ; default 0 ; >= 0 */
+  double euclidean_fitness_epsilon;        /* setEuclideanFitnessEpsilon ; default -DBL_MAX (never) */
+  double rotation_epsilon;                 /* setTransformationRotationEpsilon ; default 0: 1 - transformation_epsilon is used */
+  double mse_threshold_absolute;           /* DefaultConvergenceCriteria::setAbsoluteMSE ; default 1e-12 */
+} apdgicp_icp_params;
+/* max_iterations, transformation_epsilon, max_correspondence_distance and flags stay in apdgicp_params, where pcl::Registration keeps them */
+void apdgicp_icp_default_params(apdgicp_icp_params* p);   /* enable = 1 and the defaults above */
+/* p != NULL with p->enable: the mode on with these parameters (voxelized GICP and NDT off); NULL or enable = 0: back to what apdgicp_params says */
+int apdgicp_set_icp(apdgicp_handle* h, const apdgicp_icp_params* p);
+int apdgicp_get_icp(const apdgicp_handle* h, apdgicp_icp_params* p, int* enabled);   /* either output may be NULL */
+/* The per-iteration probe, this mode's linearize: W = T * source (the source itself when T is the identity), then IC2 .. IC5.  T_out = T_k
+ * (column-major; the identity when IC4 or a non-finite result refused the estimate), *n_corr the matches, *mse their fp64 mean d2, and
+ * sums[16] the reduction: [0] sum d2; [1..3] sum p; [4..6] sum q; [7..15] sum (q - qm)(p - pm)^T row-major (row: q, column: p) -- NOT
+ * divided by n; p runs over the matched points of W, q over their target points.  Any output may be NULL.  Nothing is accumulated (no IC6 / IC7). */
+int apdgicp_icp_estimate(apdgicp_handle* h, const float T[16], float T_out[16], int64_t* n_corr, double* mse, double sums[16]);
+/* the matches of the last estimate or of the last iteration of the last align, in the caller's source order: target index or -1 for a
+ * rejected point; sq_dist the forward fp32 d2 of every finite point whether kept or not (NaN for a non-finite one).  n = the source size. */
+int apdgicp_icp_get_correspondences(apdgicp_handle* h, int32_t* match, float* sq_dist, int64_t n);
+/* W in the caller's order, n x 3 floats */
+int apdgicp_icp_get_working_cloud(apdgicp_handle* h, float* xyz, int64_t n);
+/* the iterations of the last align, one entry each (the first min(capacity, *n_iterations) are written; any array may be NULL): T_k,
+ * the matches, their mse, iterations_similar_transforms after the iteration.  An iteration stopped by IC4 has T_k = identity. */
+int apdgicp_icp_get_trace(apdgicp_handle* h, int64_t capacity, float* T_k16, int64_t* n_corr, double* mse, int32_t* similar, int64_t* n_iterations);
+int apdgicp_icp_convergence_state(apdgicp_handle* h, int32_t* state);   /* apdgicp_icp_state of the last align (NOT_CONVERGED before any) */
+/* Debug: launches and host waits of the last align in this mode (tests/measure/bench_icp.py) */
+int apdgicp_icp_debug_counts(apdgicp_handle* h, int64_t* launches, int64_t* waits);
 
 /* ------------------------------------------------------------------ batched registrations
  * Independent (source, target) pairs -- loop-closure candidates (loop_detector.cpp:222-236,404-423)

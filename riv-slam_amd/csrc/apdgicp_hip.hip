@@ -17,6 +17,7 @@
 #include "apd_vgicp_batch.hpp"
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
+#include "apd_icp.hpp"
 #include "apd_dbscan.hpp"
 #include "apd_ingest.hpp"
 #include "apd_approx_voxel.hpp"
@@ -166,10 +167,30 @@ struct NdState {
   }
 };
 
+// apdgicp_set_icp: the working cloud W (in the source's curve order), its boxes, the matches and the record of the last iteration
+// (include/apdgicp_hip.h, IC1 .. IC10).  The forward search runs through the engine's own buffers (Work::nnpt / sqd).
+struct IcState {
+  bool on = false;
+  apdgicp_icp_params prm{1, 0, 3, 0, -std::numeric_limits<double>::max(), 0.0, 1e-12};
+  bool brute = false;          // APDGICP_ICP_RECIP_MODE=brute (read when the handle is created): the reciprocal search without its boxes
+  bool have = false;           // W / match / dsq describe source points have_src_gen (n_have of them) against target points have_tgt_gen
+  uint64_t have_src_gen = 0, have_tgt_gen = 0;
+  int n_have = 0;
+  int state = APDGICP_ICP_NOT_CONVERGED;
+  int64_t launches = 0, waits = 0;  // of the last align
+  std::vector<float> tr_T;     // the trace of the last align: 16 floats per iteration
+  std::vector<int64_t> tr_n;
+  std::vector<double> tr_mse;
+  std::vector<int32_t> tr_sim;
+  DevBuf W, cbox, gbox, beaten, match, dsq, part, sum1, rec, dT;
+  PinnedBuf h_rec;             // mirror of rec: one IcpRecord
+};
+
 struct apdgicp_handle {
   Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
   VgState vg;   // (freed by its members' destructors, behind the wait of ~apdgicp_handle)
   NdState nd;   // (likewise)
+  IcState ic;   // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two are exclusive
   ~apdgicp_handle() {
     if (eng.stream) (void)hipStreamSynchronize(eng.stream);  // the voxel kernels run there; the members are freed once this body has run
@@ -462,13 +483,14 @@ int ensure_pair(apdgicp_handle* h, const float* guess16 = nullptr) {
   Engine& e = h->eng;
   if (e.clouds.size() < 2 || e.clouds[kSrc].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "source cloud is not set");
   if (e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
-  if (h->pair_ready && e.clouds[kSrc].cov_valid && e.clouds[kTgt].cov_valid) return 0;
+  const bool need_cov = !h->ic.on;  // IC9: the ICP mode searches only, clouds of any size
+  if (h->pair_ready && (!need_cov || (e.clouds[kSrc].cov_valid && e.clouds[kTgt].cov_valid))) return 0;
   apdgicp_pair p;
   p.source_cloud = kSrc;
   p.target_cloud = kTgt;
   if (guess16) memcpy(p.guess, guess16, sizeof(p.guess));
   else identity16(p.guess);
-  APD_TRY(e.setup_pairs(&p, 1, true));
+  APD_TRY(e.setup_pairs(&p, 1, true, false, need_cov));
   h->pair_ready = true;
   h->have_corr = false;
   return 0;
@@ -911,6 +933,180 @@ int nd_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   h->have_corr = false;  // (the APD kernels' correspondences are not what this mode wrote)
   return rc;
 }
+
+// ---- point-to-point ICP (include/apdgicp_hip.h IC1 .. IC10; kernels: apd_icp.hpp)
+bool is_identity16(const float* T) {
+  for (int q = 0; q < 16; q++)
+    if (T[q] != ((q % 5 == 0) ? 1.f : 0.f)) return false;
+  return true;
+}
+
+// Both clouds sorted, the engine's one-pair search set up with W in place of the sorted source at the identity pose, W0 = T * source
+// written, the record started at `final0`.  The handle's own pair is set up again by whoever needs it next.
+int ic_begin(apdgicp_handle* h, const float* T16, const float* final0) {
+  Engine& e = h->eng;
+  IcState& v = h->ic;
+  v.have = false;
+  h->pair_ready = false;  // (a pair table left by an earlier call may name a W that is replaced below)
+  APD_TRY(ensure_pair(h));
+  const Engine::Cloud& s = e.clouds[kSrc];
+  const int n = s.n, nblk = (n + IC_BLK - 1) / IC_BLK;
+  const size_t nch = ((size_t)n + kChunk - 1) / kChunk, ngr = ((size_t)n + kGroupPts - 1) / kGroupPts;
+  if ((size_t)n * 16 > v.W.cap || nch * sizeof(Box) > v.cbox.cap || ngr * sizeof(Box) > v.gbox.cap || (size_t)n > v.beaten.cap || (size_t)n * 4 > v.match.cap ||
+      (size_t)n * 4 > v.dsq.cap || (size_t)nblk * IC_R2 * 8 > v.part.cap)
+    APD_HIP(hipStreamSynchronize(e.stream));
+  APD_TRY(v.W.ensure((size_t)n * 16));
+  APD_TRY(v.cbox.ensure(nch * sizeof(Box)));
+  APD_TRY(v.gbox.ensure(ngr * sizeof(Box)));
+  APD_TRY(v.beaten.ensure((size_t)n));
+  APD_TRY(v.match.ensure((size_t)n * 4));
+  APD_TRY(v.dsq.ensure((size_t)n * 4));
+  APD_TRY(v.part.ensure((size_t)nblk * IC_R2 * 8));
+  APD_TRY(v.sum1.ensure(IC_R1 * 8));
+  APD_TRY(v.rec.ensure(sizeof(IcpRecord)));
+  APD_TRY(v.dT.ensure(16 * sizeof(float)));
+  APD_TRY(v.h_rec.ensure(sizeof(IcpRecord)));
+  PairDesc pd = e.h_pairs[0];
+  pd.s.pts = v.W.as<float4>();
+  APD_TRY(e.d_pairs.upload(&pd, sizeof(pd), e.stream));
+  h->pair_ready = false, h->have_corr = false;
+  const double I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  APD_HIP(hipMemcpyAsync(e.d_T.p, I16, sizeof(I16), hipMemcpyHostToDevice, e.stream));
+  hipLaunchKernelGGL(k_set_probe, dim3(1), dim3(1), 0, e.stream, e.d_state.as<PairState>(), e.d_T.as<double>(), (int)ST_NEED_LIN, 0);  // (n_lin = 0: every search is cold)
+  IcpRecord r0;
+  memset(&r0, 0, sizeof(r0));
+  for (int q = 0; q < 16; q++) r0.T_k[q] = (q % 5 == 0) ? 1.f : 0.f;
+  memcpy(r0.final_T, final0, sizeof(r0.final_T));
+  r0.prev_mse = std::numeric_limits<double>::max();
+  APD_HIP(hipMemcpyAsync(v.rec.p, &r0, sizeof(r0), hipMemcpyHostToDevice, e.stream));  // (pageable source: staged before the call returns)
+  const bool ident = is_identity16(T16);
+  if (!ident) APD_HIP(hipMemcpyAsync(v.dT.p, T16, 16 * sizeof(float), hipMemcpyHostToDevice, e.stream));
+  hipLaunchKernelGGL(k_icp_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, s.pts.as<float4>(), n, ident ? nullptr : v.dT.as<float>(),
+                     (e.params.flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0, v.W.as<float4>());
+  APD_HIP(hipGetLastError());
+  v.launches += 2;
+  return 0;
+}
+
+IcpConsts ic_consts(const apdgicp_handle* h, int accumulate) {
+  const apdgicp_params& p = h->eng.params;
+  const apdgicp_icp_params& q = h->ic.prm;
+  IcpConsts c;
+  c.thr2 = p.max_correspondence_distance * p.max_correspondence_distance;
+  c.trans_eps = p.transformation_epsilon;
+  c.rot_thr = q.rotation_epsilon > 0.0 ? q.rotation_epsilon : 1.0 - p.transformation_epsilon;
+  c.mse_abs = q.mse_threshold_absolute, c.mse_rel = q.euclidean_fitness_epsilon;
+  c.max_iterations = p.max_iterations, c.min_corr = q.min_correspondences, c.max_similar = q.max_similar_transforms, c.accumulate = accumulate;
+  return c;
+}
+
+// IC2 .. IC7 over the W that is there: the searches, the two reduction passes, the step; the record comes home behind ONE wait
+int ic_iteration(apdgicp_handle* h, const IcpConsts& c) {
+  Engine& e = h->eng;
+  IcState& v = h->ic;
+  const Engine::Cloud &s = e.clouds[kSrc];
+  const int n = s.n, nblk = (n + IC_BLK - 1) / IC_BLK;
+  float4* W = v.W.as<float4>();
+  APD_TRY(e.launch_nn(e.whole()));
+  APD_TRY(e.launch_linearize(e.whole(), 0));  // (the per-point pass that settles the exact index: Work::nnpt, Work::sqd)
+  v.launches += 2;
+  const bool recip = v.prm.use_reciprocal_correspondences != 0;
+  if (recip) {
+    const int nch = (n + kChunk - 1) / kChunk, ngr = (n + kGroupPts - 1) / kGroupPts;
+    if (!v.brute) {
+      hipLaunchKernelGGL(k_boxes, dim3((unsigned)((nch + 255) / 256)), dim3(256), 0, e.stream, W, n, (int)kChunk, v.cbox.as<Box>(), nch);
+      hipLaunchKernelGGL(k_boxes, dim3((unsigned)((ngr + 255) / 256)), dim3(256), 0, e.stream, W, n, (int)kGroupPts, v.gbox.as<Box>(), ngr);
+      hipLaunchKernelGGL(k_icp_recip<true>, dim3((unsigned)nblk), dim3(IC_BLK), 0, e.stream, W, n, s.perm.as<int>(), v.cbox.as<Box>(), v.gbox.as<Box>(), e.work.nnpt,
+                         e.work.sqd, c.thr2, v.beaten.as<unsigned char>());
+      v.launches += 3;
+    } else {
+      hipLaunchKernelGGL(k_icp_recip<false>, dim3((unsigned)nblk), dim3(IC_BLK), 0, e.stream, W, n, s.perm.as<int>(), v.cbox.as<Box>(), v.gbox.as<Box>(), e.work.nnpt,
+                         e.work.sqd, c.thr2, v.beaten.as<unsigned char>());
+      v.launches += 1;
+    }
+  }
+  hipLaunchKernelGGL(k_icp_pairs, dim3((unsigned)nblk), dim3(IC_BLK), 0, e.stream, W, n, e.work.nnpt, e.work.sqd, recip ? v.beaten.as<unsigned char>() : nullptr, c.thr2,
+                     v.match.as<int>(), v.dsq.as<float>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_icp_sums, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, (int)IC_R1, v.sum1.as<double>());
+  hipLaunchKernelGGL(k_icp_cross, dim3((unsigned)nblk), dim3(IC_BLK), 0, e.stream, W, n, e.work.nnpt, v.match.as<int>(), v.sum1.as<double>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_icp_step, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), nblk, v.sum1.as<double>(), v.rec.as<IcpRecord>(), c);
+  APD_HIP(hipGetLastError());
+  v.launches += 4;
+  APD_HIP(hipMemcpyAsync(v.h_rec.p, v.rec.p, sizeof(IcpRecord), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  v.waits += 1;
+  return 0;
+}
+
+void ic_mark_have(apdgicp_handle* h) {
+  IcState& v = h->ic;
+  v.have = true, v.have_src_gen = h->cloud_gen[kSrc], v.have_tgt_gen = h->cloud_gen[kTgt], v.n_have = h->eng.clouds[kSrc].n;
+}
+
+int ic_estimate(apdgicp_handle* h, const float T[16], float T_out[16], int64_t* n_corr, double* mse, double sums[16]) {
+  float I[16];
+  identity16(I);
+  APD_TRY(ic_begin(h, T, I));
+  APD_TRY(ic_iteration(h, ic_consts(h, 0)));
+  const IcpRecord& r = *h->ic.h_rec.as<IcpRecord>();
+  if (T_out) memcpy(T_out, r.T_k, sizeof(r.T_k));
+  if (n_corr) *n_corr = r.n_corr;
+  if (mse) *mse = r.mse;
+  if (sums) memcpy(sums, r.sums, sizeof(r.sums));
+  ic_mark_have(h);
+  return 0;
+}
+
+int ic_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  Engine& e = h->eng;
+  IcState& v = h->ic;
+  float g[16];
+  if (guess) memcpy(g, guess, sizeof(g));
+  else identity16(g);
+  v.tr_T.clear(), v.tr_n.clear(), v.tr_mse.clear(), v.tr_sim.clear();
+  v.launches = v.waits = 0;
+  v.state = APDGICP_ICP_NOT_CONVERGED;
+  APD_TRY(ic_begin(h, g, g));
+  const IcpConsts c = ic_consts(h, 1);
+  const int n = e.clouds[kSrc].n, xf = (e.params.flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;
+  const IcpRecord& r = *v.h_rec.as<IcpRecord>();
+  for (;;) {
+    APD_TRY(ic_iteration(h, c));
+    v.tr_T.insert(v.tr_T.end(), r.T_k, r.T_k + 16);
+    v.tr_n.push_back(r.n_corr), v.tr_mse.push_back(r.mse), v.tr_sim.push_back(r.similar);
+    if (r.estimated) {  // IC1: W = T_k * W, T_k read from the device record (after the last iteration too: W ends as PCL's output cloud)
+      hipLaunchKernelGGL(k_icp_transform, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, v.W.as<float4>(), n, v.rec.as<IcpRecord>(), xf);
+      APD_HIP(hipGetLastError());
+      v.launches += 1;
+    }
+    if (r.stop) break;
+  }
+  APD_HIP(hipStreamSynchronize(e.stream));
+  v.state = r.state;
+  memcpy(out->T, r.final_T, sizeof(out->T));
+  out->final_cost = r.mse;
+  out->converged = r.converged;
+  out->iterations = r.iterations;
+  out->n_linearize = r.iterations;
+  out->n_compute_error = 0;
+  out->lm_failed = 0;
+  out->n_matched = (int)std::min<long long>(r.n_corr, 2147483647ll);
+  h->trace_from_host_loop = true;  // (apdgicp_get_trace: this align left no optimiser trace)
+  h->tr_lambda.clear(), h->tr_rho.clear(), h->tr_y0.clear(), h->tr_yi.clear(), h->tr_dnorm.clear(), h->tr_poses.clear();
+  ic_mark_have(h);
+  return 0;
+}
+
+int check_icp_params(const apdgicp_icp_params* p) {
+  if (!p) return 0;
+  if (p->min_correspondences < 1) return fail(APDGICP_ERR_INVALID_ARG, "ICP: min_correspondences must be at least 1");
+  if (p->max_similar_transforms < 0) return fail(APDGICP_ERR_INVALID_ARG, "ICP: max_similar_transforms must not be negative");
+  if (std::isnan(p->euclidean_fitness_epsilon) || std::isnan(p->rotation_epsilon) || std::isnan(p->mse_threshold_absolute))
+    return fail(APDGICP_ERR_INVALID_ARG, "ICP: a threshold is not a number");
+  return 0;
+}
+
+const char* const kIcNoLinearize = "point-to-point ICP has no linearisation: apdgicp_icp_estimate is this mode's probe";
 
 // ---- the voxel modes on a batch handle: what voxelized GICP (V8 .. V12) and NDT (N10 .. N15) share
 constexpr int kVgbChunk = 4;  // ticks enqueued per look at the done counter (docs/experiments.md, "VGICP batch: chunk length")
@@ -1385,6 +1581,8 @@ int apdgicp_create(const apdgicp_params* p, int device, void* stream, apdgicp_ha
       return rc;
     }
     h->eng.clouds.resize(2);
+    const char* recip_mode = getenv("APDGICP_ICP_RECIP_MODE");
+    h->ic.brute = recip_mode && std::string(recip_mode) == "brute";
     *out = h;
     return 0;
   });
@@ -1498,6 +1696,7 @@ int apdgicp_set_covariances(apdgicp_handle* h, int which, const double* in, int6
 int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], double b[6], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
     if (h->nd.on) return nd_linearize(h, T, H, b, cost, nullptr);
     if (h->vg.on) return vg_linearize(h, T, H, b, cost, nullptr);
     APD_TRY(ensure_pair(h));
@@ -1510,6 +1709,7 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
 int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T || !cost) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
     if (h->nd.on) return nd_error(h, T, cost);
     if (h->vg.on) return vg_error(h, T, cost);
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
@@ -1520,6 +1720,7 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
 int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int64_t n) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps its own correspondences: apdgicp_icp_get_correspondences");
     if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
     Engine& e = h->eng;
@@ -1541,6 +1742,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
 int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps no per-point Mahalanobis matrices");
     if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT keeps no per-point Mahalanobis matrices");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP keeps no per-point Mahalanobis matrices");
     Engine& e = h->eng;
@@ -1567,6 +1769,7 @@ int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
 int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->ic.on) return ic_align(h, guess, out);
     if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
     float g[16];
@@ -1602,6 +1805,7 @@ int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out)
 int apdgicp_align_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (h->ic.on) return ic_align(h, guess, out);
     if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
     APD_TRY(ensure_pair(h));
@@ -1634,6 +1838,7 @@ int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
   v.prm = *p;
   v.on = true;
   h->nd.on = false;  // N9: the two modes are exclusive
+  h->ic.on = false;  // IC9: likewise
   return 0;
 }
 
@@ -1708,6 +1913,127 @@ int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
   v.prm = *p;
   v.on = true;
   h->vg.on = false;  // N9: the two modes are exclusive
+  h->ic.on = false;  // IC9: likewise
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ point-to-point ICP
+void apdgicp_icp_default_params(apdgicp_icp_params* p) {
+  if (!p) return;
+  p->enable = 1;
+  p->use_reciprocal_correspondences = 0;   // pcl::IterativeClosestPoint: use_reciprocal_correspondence_(false)
+  p->min_correspondences = 3;              // pcl::Registration: min_number_correspondences_(3)
+  p->max_similar_transforms = 0;           // DefaultConvergenceCriteria: max_iterations_similar_transforms_(0)
+  p->euclidean_fitness_epsilon = -std::numeric_limits<double>::max();  // pcl::Registration: euclidean_fitness_epsilon_
+  p->rotation_epsilon = 0.0;               // pcl::Registration: transformation_rotation_epsilon_(0.0)
+  p->mse_threshold_absolute = 1e-12;       // DefaultConvergenceCriteria: mse_threshold_absolute_(1e-12)
+}
+
+int apdgicp_set_icp(apdgicp_handle* h, const apdgicp_icp_params* p) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  IcState& v = h->ic;
+  APD_TRY(check_icp_params(p));
+  if (p) v.prm = *p;
+  const bool on = p && p->enable != 0;
+  if (on != v.on) h->have_corr = false, h->pair_ready = false;  // (the pair of the other side was set up with / without covariances)
+  if (!on) {
+    v.on = false;
+    return 0;
+  }
+  v.on = true, v.have = false;
+  v.state = APDGICP_ICP_NOT_CONVERGED;
+  h->vg.on = false, h->nd.on = false;  // IC9: the three modes are exclusive
+  return 0;
+}
+
+int apdgicp_get_icp(const apdgicp_handle* h, apdgicp_icp_params* p, int* enabled) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (p) {
+    *p = h->ic.prm;
+    p->enable = h->ic.on ? 1 : 0;
+  }
+  if (enabled) *enabled = h->ic.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_icp_estimate(apdgicp_handle* h, const float T[16], float T_out[16], int64_t* n_corr, double* mse, double sums[16]) {
+  return guarded([&]() -> int {
+    if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (!h->ic.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_set_icp)");
+    return ic_estimate(h, T, T_out, n_corr, mse, sums);
+  });
+}
+
+// the last estimate / align must still describe the clouds the handle holds
+static int ic_check_have(apdgicp_handle* h, int64_t n) {
+  const IcState& v = h->ic;
+  if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_set_icp)");
+  if (!v.have || v.have_src_gen != h->cloud_gen[kSrc] || v.have_tgt_gen != h->cloud_gen[kTgt] || h->eng.clouds[kSrc].n != v.n_have)
+    return fail(APDGICP_ERR_NO_INPUT, "no estimate or align of the clouds the handle holds now");
+  if (n != v.n_have) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
+  return 0;
+}
+
+int apdgicp_icp_get_correspondences(apdgicp_handle* h, int32_t* match, float* sq_dist, int64_t n) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    APD_TRY(ic_check_have(h, n));
+    Engine& e = h->eng;
+    IcState& v = h->ic;
+    APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(e.d_stage.ensure((size_t)n * 8));
+    int* d_c = e.d_stage.as<int>();
+    float* d_s = (float*)(d_c + n);
+    hipLaunchKernelGGL(k_icp_export, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, v.match.as<int>(), v.dsq.as<float>(), e.clouds[kSrc].perm.as<int>(),
+                       e.clouds[kTgt].perm.as<int>(), (int)n, d_c, d_s);
+    APD_HIP(hipGetLastError());
+    if (match) APD_HIP(hipMemcpyAsync(match, d_c, n * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    if (sq_dist) APD_HIP(hipMemcpyAsync(sq_dist, d_s, n * sizeof(float), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    return 0;
+  });
+}
+
+int apdgicp_icp_get_working_cloud(apdgicp_handle* h, float* xyz, int64_t n) {
+  return guarded([&]() -> int {
+    if (!h || !xyz) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(ic_check_have(h, n));
+    Engine& e = h->eng;
+    APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(e.d_stage.ensure((size_t)n * 12));
+    hipLaunchKernelGGL(k_icp_export_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, h->ic.W.as<float4>(), e.clouds[kSrc].perm.as<int>(), (int)n,
+                       e.d_stage.as<float>());
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(xyz, e.d_stage.p, (size_t)n * 12, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    return 0;
+  });
+}
+
+int apdgicp_icp_get_trace(apdgicp_handle* h, int64_t capacity, float* T_k16, int64_t* n_corr, double* mse, int32_t* similar, int64_t* n_iterations) {
+  return guarded([&]() -> int {
+    if (!h || !n_iterations || capacity < 0) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    const IcState& v = h->ic;
+    *n_iterations = (int64_t)v.tr_n.size();
+    const int64_t m = std::min<int64_t>(*n_iterations, capacity);
+    if (m && T_k16) memcpy(T_k16, v.tr_T.data(), m * 16 * sizeof(float));
+    if (m && n_corr) memcpy(n_corr, v.tr_n.data(), m * sizeof(int64_t));
+    if (m && mse) memcpy(mse, v.tr_mse.data(), m * sizeof(double));
+    if (m && similar) memcpy(similar, v.tr_sim.data(), m * sizeof(int32_t));
+    return 0;
+  });
+}
+
+int apdgicp_icp_convergence_state(apdgicp_handle* h, int32_t* state) {
+  if (!h || !state) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *state = h->ic.state;
+  return 0;
+}
+
+int apdgicp_icp_debug_counts(apdgicp_handle* h, int64_t* launches, int64_t* waits) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (launches) *launches = h->ic.launches;
+  if (waits) *waits = h->ic.waits;
   return 0;
 }
 
@@ -1951,6 +2277,7 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
   return guarded([&]() -> int {
     if (!h || !H) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     Engine& e = h->eng;
+    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
     if (h->nd.on) {  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
       memcpy(H, h->nd.final_H, 36 * sizeof(double));
       return 0;
