@@ -1783,13 +1783,13 @@ __device__ __forceinline__ unsigned long long dist_key(float d, int orig) { retu
 //   A  lane = (query, 1/L of the work): tau = k-th smallest of 32 strided class minima over the KQ_WIN sorted neighbours
 //      around the wave, read straight from L1 (k distinct points lie within tau, so it bounds the k-th neighbour distance);
 //      the L lanes of a query split the 32 classes (L = 4: sorted in place by a network over (lane, register)).  Group
-//      masks: lane g keeps the box of group g in registers and tests it against one query per trip, broadcast through
-//      SGPRs -- the ballot is that query's mask;
+//      masks: lane g keeps the box of group g in registers and tests it against one query per trip, read from the query's
+//      record in LDS (KnnRec: a read from a wave-uniform address is a broadcast) -- the ballot is that query's mask;
 //   B  lane = candidate: every group some query needs is loaded ONCE (2 candidates per lane, coalesced); for each query
-//      that needs it (uniform loop, query broadcast by readlane) the 128 keys (distance bits << 32 | original index) are
+//      that needs it (uniform loop, the query's record read from LDS) the 128 keys (distance bits << 32 | original index) are
 //      compared with the query's tau and the hits are compacted into its LDS list with ballot / popcount -- no divergence.
 //      A full list is tightened in place to its k smallest keys (tau only decreases, nothing of the final answer is
-//      dropped); the query state (tau, count) is kept identical in the L lanes;
+//      dropped); the query state (tau, count) lives in the record: a tightening writes tau back, a hit step the count;
 //   C  lane = (query, 1/L): each lane sorts its share of the list in REGISTERS, the k neighbours come out of an L-way merge
 //      (a DPP butterfly over the heads per round, no LDS reads inside the rounds; u64 order == the reference's (distance,
 //      index) order); gather of the k points, moments in fp64 relative to the query (exact differences) as four partial
@@ -1811,7 +1811,18 @@ __host__ __device__ constexpr int knn_coop_cap(int lanes_per_query) { return lan
 #define APD_KNN_KEEP 40
 #endif
 constexpr int KQ_KEEP = APD_KNN_KEEP;  // a full list is tightened to between k and this many entries (32 / 40 / 48: 0.409 / 0.404 / 0.406 ms)
-__host__ __device__ constexpr int knn_coop_lds_bytes(int qpw) { return qpw * (knn_coop_cap(64 / qpw) + 1) * 8; }  // lists only (boxes in registers, window from L1)
+// What a step of phase B needs of its query, kept in LDS in front of the lists: a read from a wave-uniform address is a broadcast done by the
+// LDS pipe, which this kernel leaves nearly idle -- as five v_readlane per step it was paid in vector issue slots, which bind the batch.
+// 24 bytes, 8-byte aligned (ds_read2_b64 + ds_read_b64 from ONE address register); tau = (tau_hi << 32) | tau_lo where the u64 compare wants it.
+struct KnnRec {
+  float qx, qy;
+  unsigned long long tau;  // the bound as a key; a padding or finished query: high word = bits of -1.f, no key is below it as a float bound
+  float qz;
+  int cnt;                 // entries in the query's list
+};
+static_assert(sizeof(KnnRec) == 24 && alignof(KnnRec) == 8, "record layout");
+// lists + records (boxes in registers, window from L1); 4 lanes per query: 16 x (61 x 8 + 24) = 8192 bytes, 20 one-wave blocks fill a CU's 160 KB
+__host__ __device__ constexpr int knn_coop_lds_bytes(int qpw) { return qpw * ((knn_coop_cap(64 / qpw) + 1) * 8 + (int)sizeof(KnnRec)); }
 
 template <int CTRL>
 __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
@@ -1884,8 +1895,10 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   constexpr int QPW = 64 / L, NCL = KNN_NC / L, KQ_CAP = knn_coop_cap(L), KQ_STRIDE = KQ_CAP + 1, EPL = KQ_CAP / L;  // queries per wave, classes and list entries per lane
   static_assert(L == 4 || L == 8 || L == 16, "L lanes per query");
   static_assert(KQ_CAP % L == 0 && KQ_CAP <= 64 && KQ_WIN % KNN_NC == 0, "layout");
-  unsigned long long* lst = knn_smem;                            // [query][slot], padded row
-  float* cml = (float*)knn_smem;                                 // phase A only: [query][33] class minima (the lists are still empty)
+  // the records come first: within reach of the 8-bit offsets of ds_read2_b64 from the wave's base
+  KnnRec* rec = (KnnRec*)knn_smem;                               // [query], written once after phase A; phase B keeps tau and cnt there
+  unsigned long long* lst = knn_smem + QPW * sizeof(KnnRec) / 8;  // [query][slot], padded row
+  float* cml = (float*)lst;                                      // phase A only: [query][33] class minima (the lists are still empty)
   const int n = c.n;
   const int base = (int)bx * QPW;
   if (base >= n) return;
@@ -1904,7 +1917,6 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   const Box nobox{inf, inf, inf, inf, inf, inf};
   Box mybox = G(c.gbox)[min(lane, ngroups - 1)];
   if (lane >= ngroups) mybox = nobox;  // lane g keeps the box of group gb0 + g in registers: no LDS copy
-  int cnt = 0;  // entries in this query's list (same value in its L lanes)
   wave_lds_fence();  // (the wave's own LDS region: no block barrier -- eight independent waves share a block in k_knn_and_search)
   float tau_q = inf;  // (L == 4) the k-th smallest class minimum
   {
@@ -2075,7 +2087,9 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
     if (s == k - 1) tau_d = cm[s];
   }
   if (!valid) tau_d = -1.f;
-  unsigned tau_hi = __float_as_uint(tau_d), tau_lo = 0xFFFFFFFFu;  // tau key = (tau_hi << 32) | tau_lo
+  // (the L lanes of a query store the same record to the same address: no exec-mask region; LDS operations of a wave complete in order,
+  // so every later read sees it)
+  rec[slot] = KnnRec{q.x, q.y, ((unsigned long long)__float_as_uint(tau_d) << 32) | 0xFFFFFFFFull, q.z, 0};
 
   if (stats) { const long long t = clock64(); tA += t - tm, tm = t; }
   // ---- B
@@ -2090,9 +2104,8 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
     unsigned long long sany = 0;
 #pragma unroll
     for (int qi = 0; qi < QPW; qi++) {
-      const float qx = readlane_f(q.x, qi * L), qy = readlane_f(q.y, qi * L), qz = readlane_f(q.z, qi * L);
-      const float td = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)tau_hi, qi * L));
-      sany |= __ballot(lb_point_box(sbx, qx, qy, qz) <= td);
+      const KnnRec r = rec[qi];
+      sany |= __ballot(lb_point_box(sbx, r.qx, r.qy, r.qz) <= __uint_as_float((unsigned)(r.tau >> 32)));
     }
     smask &= sany;
   }
@@ -2103,17 +2116,16 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
       mybox = G(c.gbox)[min(gb0 + lane, ngroups - 1)];
       if (gb0 + lane >= ngroups) mybox = nobox;
     }
-    // group masks, one query per trip: lane g tests ITS box against the query broadcast through SGPRs, the ballot IS the
+    // group masks, one query per trip: lane g tests ITS box against the query's record (a broadcast read), the ballot IS the
     // query's mask (a finished or padding query has tau = -1 and gets none); gany = groups some query of this wave needs
     unsigned long long gany = 0;
     int gneed_lo = 0, gneed_hi = 0;
     static_for<0, QPW>([&](auto qi_) {
       constexpr int qi = decltype(qi_)::value;
-      const float qx = readlane_f(q.x, qi * L), qy = readlane_f(q.y, qi * L), qz = readlane_f(q.z, qi * L);
-      const float td = __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)tau_hi, qi * L));
+      const KnnRec r = rec[qi];
       // (a lane without a group holds the all-infinite box: its bound is +inf, no `lane < nb` needed -- as a condition it became
       // a branch around the bound in every one of the QPW trips)
-      const unsigned long long mq = __ballot(lb_point_box(mybox, qx, qy, qz) <= td);
+      const unsigned long long mq = __ballot(lb_point_box(mybox, r.qx, r.qy, r.qz) <= __uint_as_float((unsigned)(r.tau >> 32)));
       gany |= mq;
       // only the query's owner lane reads its mask (qm below): two v_writelane instead of a select per lane and trip, whose QPW
       // lane masks the compiler kept in 2 QPW scalar registers for the whole kernel
@@ -2179,7 +2191,12 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
       while (qm) {
         const int qq = __builtin_ctzll(qm);  // owner lane of the query
         asm("s_bitset0_b64 %0, %1" : "+s"(qm) : "s"(qq));
-        const float qx = readlane_f(q.x, qq), qy = readlane_f(q.y, qq), qz = readlane_f(q.z, qq);
+        // (read at the top of the step, behind every write of the step before: the same query may close one group and open the next)
+        // (qq is a multiple of L: one scalar multiply where 24 / L is whole)
+        KnnRec* rq = sizeof(KnnRec) % L == 0 ? (KnnRec*)((char*)rec + qq * (int)(sizeof(KnnRec) / L)) : rec + qq / L;
+        // (q.z and the count as ONE 8-byte read: asked for on its own, the count is fetched in the hit path, a second trip to LDS)
+        const unsigned long long zc = *(const unsigned long long*)&rq->qz;
+        const float qx = rq->qx, qy = rq->qy, qz = __uint_as_float((unsigned)zc);
 #if defined(APD_PROBE_SALU) || defined(APD_PROBE_VALU)
         {  // issue probe (tools/probe_issue.sh, docs/experiments.md): n extra independent scalar / vector instructions per step
           int t_ = 0;
@@ -2192,18 +2209,18 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
 #endif
         }
 #endif
-        unsigned long long tk = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(tau_hi, qq) << 32) |
-                                (unsigned long long)(unsigned)__builtin_amdgcn_readlane(tau_lo, qq);  // readlane returns int: no sign extension
+        unsigned long long tk = rq->tau;
         const v2f ddx = cx - qx, ddy = cy - qy, ddz = cz - qz;  // (sqdist1's operations in sqdist1's order, per candidate)
         v2f dd = ddx * ddx;
         dd = dd + ddy * ddy;
         dd = dd + ddz * ddz;
         const unsigned long long k0 = ((unsigned long long)__float_as_uint(dd.x) << 32) | o0;
         const unsigned long long k1 = ((unsigned long long)__float_as_uint(dd.y) << 32) | o1;
-        unsigned long long* row = lst + (qq / L) * KQ_STRIDE;
+        unsigned long long* row = KQ_STRIDE * 8 % L == 0 ? (unsigned long long*)((char*)lst + qq * (KQ_STRIDE * 8 / L)) : lst + (qq / L) * KQ_STRIDE;
         unsigned long long m0 = __ballot(k0 <= tk), m1 = __ballot(k1 <= tk);
         if ((m0 | m1) == 0) continue;  // the box passed the test, none of its 128 points does
-        int cntq = __builtin_amdgcn_readlane(cnt, qq);
+        // (a value read from LDS is per-lane data to the compiler: readfirstlane keeps the count, and the branch on it, scalar)
+        int cntq = __builtin_amdgcn_readfirstlane((int)(unsigned)(zc >> 32));
         if (cntq + __popcll(m0) + __popcll(m1) > KQ_CAP) {
           // List full: tau becomes a key of rank k .. KQ_KEEP among (stored keys U this group's hits); only keys <= tau survive.
           // tau only decreases and stays >= the k-th smallest key seen, so nothing of the final answer is ever dropped, and at
@@ -2214,7 +2231,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
           const unsigned long long keep = __ballot(mine <= tk);
           if (mine <= tk) row[__popcll(keep & ((1ull << lane) - 1ull))] = mine;
           cntq = __popcll(keep);
-          if (owner == qq) tau_hi = (unsigned)(tk >> 32), tau_lo = (unsigned)tk;
+          rq->tau = tk;  // (every lane, the same value: the query's next step, in this group's successor, reads it)
           m0 = __ballot(k0 <= tk), m1 = __ballot(k1 <= tk);
           n_compact++;
           if (cntq + (int)__popcll(m0) + (int)__popcll(m1) > KQ_CAP) {  // impossible by construction (<= KQ_KEEP now); never silently wrong
@@ -2229,7 +2246,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
         // builds two ANDs and two bit counts per key).
         row[lane_select(m0, mbcnt_add(m0, cntq), KQ_CAP)] = k0;
         row[lane_select(m1, mbcnt_add(m1, n0), KQ_CAP)] = k1;
-        if (owner == qq) cnt = total;
+        rq->cnt = total;
       }
     }
   }
@@ -2249,6 +2266,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
   // round used to scan all EPL register entries of every lane: 86 instructions against 20.
   unsigned long long e[EPL];
   unsigned long long* row = lst + slot * KQ_STRIDE;
+  const int cnt = rec[slot].cnt;
 #pragma unroll
   for (int t = 0; t < EPL; t++) {
     const int a = sub + L * t;
