@@ -55,6 +55,10 @@ class LoopVerifierHip {
   /// registration_method = NDT: the candidates are registered with NDT, P2D or D2D (apdgicp_batch_set_ndt, N10 .. N15 of the C header); switches
   /// voxelized GICP off, as setVGICP switches this off; nullptr: back to APD-GICP / plain GICP as the parameters say
   int setNDT(const apdgicp_ndt_params* p) { return batch_ ? apdgicp_batch_set_ndt(batch_, p) : APDGICP_ERR_HIP; }
+  /// registration_method = ICP: the candidates are registered with point-to-point ICP (apdgicp_batch_set_icp, IC11 .. IC16 of the C header), every
+  /// record byte-equal to IterativeClosestPointHip's for the same candidate; switches voxelized GICP and NDT off, as they switch this off;
+  /// nullptr or enable = 0: back to APD-GICP / plain GICP as the parameters say
+  int setICP(const apdgicp_icp_params* p) { return batch_ ? apdgicp_batch_set_icp(batch_, p) : APDGICP_ERR_HIP; }
 
   /// guesses: n_candidates x 16 floats, column-major ((new_keyframe_estimate^-1 * candidate_estimate) with guess(2,3) = 0,
   /// loop_detector.cpp:405-411), or nullptr for the identity (:225).  Returns 0 or a negative apdgicp_status.

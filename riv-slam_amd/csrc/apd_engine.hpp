@@ -979,7 +979,9 @@ class Engine {
     w.xf_linear = (params.flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;  // (read at launch time: set_params may come between aligns)
     return w;
   }
-  const PairDesc* t_pairs() const { return in_pool ? pool.pairs.as<PairDesc>() : d_pairs.as<PairDesc>(); }
+  // ICP on a batch handle (IC12): while set, the searches read this table -- d_pairs with every pair's W in place of its sorted source
+  const PairDesc* pairs_override = nullptr;
+  const PairDesc* t_pairs() const { return in_pool ? pool.pairs.as<PairDesc>() : pairs_override ? pairs_override : d_pairs.as<PairDesc>(); }
   PairState* t_state() const { return in_pool ? pool.state.as<PairState>() : d_state.as<PairState>(); }
   int t_npairs() const { return in_pool ? pool.cap : npairs; }
   int t_nmax_src() const { return in_pool ? pool.nmax_src : nmax_src; }

@@ -19,6 +19,8 @@
 // Reductions: a wave's values through the DPP tree of apd_kernels.hpp (wave_sum_to_lane63), waves through LDS in wave order, blocks in block
 // order.  No floating-point atomics.  Compiled without contraction: written order is evaluated order.  Every pointer is a kernel argument.
 // Launches per iteration: 2 (search) + 3 (pairs, sums, cross) + 1 (step) + 1 (transform), + 3 with reciprocal correspondences; none depends on n.
+// Every kernel body is a device function (icp_init_point .. icp_step_wave): the batch handle's kernels (apd_icp_batch.hpp, IC11 .. IC16) call the
+// same ones with the pair in the grid, which is what makes a batch pair's bytes the single handle's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,9 +55,8 @@ struct IcpRecord {
   int iterations, similar, state, converged, stop, estimated;
 };
 
-__global__ void k_icp_init(const float4* src /* sorted */, int n, const float* T16 /* column-major, device; null: W0 = source */, int xf_linear, float4* W) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+// IC1 for one point: W0[i] = T * src[i] (null T: the source itself), .w = 1 for a finite point, else {0, 0, 0, 0}
+__device__ __forceinline__ void icp_init_point(const float4* src /* sorted */, const float* T16 /* column-major, device; null: W0 = source */, int xf_linear, float4* W, int i) {
   const float4 p = src[i];
   const bool ok = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);
   float x = p.x, y = p.y, z = p.z;
@@ -66,14 +67,24 @@ __global__ void k_icp_init(const float4* src /* sorted */, int n, const float* T
   W[i] = ok ? make_float4(x, y, z, 1.f) : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
-__global__ void k_icp_transform(float4* W, int n, const IcpRecord* rec, int xf_linear) {
+__global__ void k_icp_init(const float4* src /* sorted */, int n, const float* T16 /* column-major, device; null: W0 = source */, int xf_linear, float4* W) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float* T = rec->T_k;
+  icp_init_point(src, T16, xf_linear, W, i);
+}
+
+// IC1 for one point: W[i] = T_k * W[i] in place
+__device__ __forceinline__ void icp_transform_point(float4* W, const float* T /* column-major, device */, int xf_linear, int i) {
   const float4 p = W[i];
   if (p.w == 0.f) return;
   const float r0[4] = {T[0], T[4], T[8], T[12]}, r1[4] = {T[1], T[5], T[9], T[13]}, r2[4] = {T[2], T[6], T[10], T[14]};
   W[i] = make_float4(xf_row(r0, p.x, p.y, p.z, xf_linear), xf_row(r1, p.x, p.y, p.z, xf_linear), xf_row(r2, p.x, p.y, p.z, xf_linear), 1.f);
+}
+
+__global__ void k_icp_transform(float4* W, int n, const IcpRecord* rec, int xf_linear) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  icp_transform_point(W, rec->T_k, xf_linear, i);
 }
 
 // forward match of sorted source position i as the engine's search left it: target index (sorted) or -1, after validity and the gate
@@ -83,10 +94,11 @@ __device__ __forceinline__ int icp_forward(const float4 w, const float4 nn, floa
 }
 
 // beaten[i] = 1: some point of W other than i is the nearest point of W to i's forward match (IC3)
+// (the body of block bx of k_icp_recip: taken by whole blocks)
 template <bool PRUNED>
-__global__ __launch_bounds__(IC_BLK) void k_icp_recip(const float4* W, int n, const int* perm, const Box* cbox, const Box* gbox, const float4* nnpt, const float* sqd,
-                                                      double thr2, unsigned char* beaten) {
-  const int tid = threadIdx.x, i = blockIdx.x * IC_BLK + tid;
+__device__ __forceinline__ void icp_recip_block(const float4* W, int n, const int* perm, const Box* cbox, const Box* gbox, const float4* nnpt, const float* sqd, double thr2,
+                                                unsigned char* beaten, int bx) {
+  const int tid = threadIdx.x, i = bx * IC_BLK + tid;
   const bool in = i < n;
   const float4 w = in ? W[i] : make_float4(0.f, 0.f, 0.f, 0.f);
   const float4 q = in ? nnpt[i] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
@@ -138,6 +150,12 @@ __global__ __launch_bounds__(IC_BLK) void k_icp_recip(const float4* W, int n, co
   if (in) beaten[i] = lost ? 1 : 0;
 }
 
+template <bool PRUNED>
+__global__ __launch_bounds__(IC_BLK) void k_icp_recip(const float4* W, int n, const int* perm, const Box* cbox, const Box* gbox, const float4* nnpt, const float* sqd,
+                                                      double thr2, unsigned char* beaten) {
+  icp_recip_block<PRUNED>(W, n, perm, cbox, gbox, nnpt, sqd, thr2, beaten, (int)blockIdx.x);
+}
+
 // wave -> LDS -> the block's row: R sums of this block in wave order
 template <int R>
 __device__ __forceinline__ void icp_block_row(double (&v)[R], double* lds, int tid, double* row) {
@@ -150,10 +168,11 @@ __device__ __forceinline__ void icp_block_row(double (&v)[R], double* lds, int t
   }
 }
 
-__global__ __launch_bounds__(IC_BLK) void k_icp_pairs(const float4* W, int n, const float4* nnpt, const float* sqd, const unsigned char* beaten /* or null */, double thr2,
-                                                      int* match, float* dsq, double* part) {
+// (the body of block bx of k_icp_pairs: taken by whole blocks)
+__device__ __forceinline__ void icp_pairs_block(const float4* W, int n, const float4* nnpt, const float* sqd, const unsigned char* beaten /* or null */, double thr2, int* match,
+                                                float* dsq, double* part, int bx) {
   __shared__ double lds[(IC_BLK / 64) * IC_R1];
-  const int tid = threadIdx.x, i = blockIdx.x * IC_BLK + tid;
+  const int tid = threadIdx.x, i = bx * IC_BLK + tid;
   double v[IC_R1] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (i < n) {
     const float4 w = W[i], q = nnpt[i];
@@ -164,21 +183,30 @@ __global__ __launch_bounds__(IC_BLK) void k_icp_pairs(const float4* W, int n, co
     dsq[i] = w.w != 0.f ? d : __builtin_nanf("");
     if (j >= 0) v[0] = (double)d, v[1] = (double)w.x, v[2] = (double)w.y, v[3] = (double)w.z, v[4] = (double)q.x, v[5] = (double)q.y, v[6] = (double)q.z, v[7] = 1.0;
   }
-  icp_block_row<IC_R1>(v, lds, tid, part + (size_t)blockIdx.x * IC_R1);
+  icp_block_row<IC_R1>(v, lds, tid, part + (size_t)bx * IC_R1);
+}
+
+__global__ __launch_bounds__(IC_BLK) void k_icp_pairs(const float4* W, int n, const float4* nnpt, const float* sqd, const unsigned char* beaten /* or null */, double thr2,
+                                                      int* match, float* dsq, double* part) {
+  icp_pairs_block(W, n, nnpt, sqd, beaten, thr2, match, dsq, part, (int)blockIdx.x);
 }
 
 // out[r] = the rows' column r added in block order from 0.0 (one block of 64, R <= 64)
-__global__ __launch_bounds__(64) void k_icp_sums(const double* part, int nblk, int R, double* out) {
-  const int r = threadIdx.x;
+__device__ __forceinline__ void icp_sums_lane(const double* part, int nblk, int R, double* out, int r) {
   if (r >= R) return;
   double s = 0.0;
   for (int b = 0; b < nblk; b++) s += part[(size_t)b * R + r];
   out[r] = s;
 }
 
-__global__ __launch_bounds__(IC_BLK) void k_icp_cross(const float4* W, int n, const float4* nnpt, const int* match, const double* sum1, double* part) {
+__global__ __launch_bounds__(64) void k_icp_sums(const double* part, int nblk, int R, double* out) {
+  icp_sums_lane(part, nblk, R, out, (int)threadIdx.x);
+}
+
+// (the body of block bx of k_icp_cross: taken by whole blocks)
+__device__ __forceinline__ void icp_cross_block(const float4* W, int n, const float4* nnpt, const int* match, const double* sum1, double* part, int bx) {
   __shared__ double lds[(IC_BLK / 64) * IC_R2];
-  const int tid = threadIdx.x, i = blockIdx.x * IC_BLK + tid;
+  const int tid = threadIdx.x, i = bx * IC_BLK + tid;
   double v[IC_R2] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   const double cnt = sum1[7];
   if (i < n && cnt > 0.0 && match[i] >= 0) {
@@ -187,7 +215,11 @@ __global__ __launch_bounds__(IC_BLK) void k_icp_cross(const float4* W, int n, co
     const double qx = (double)q.x - sum1[4] / cnt, qy = (double)q.y - sum1[5] / cnt, qz = (double)q.z - sum1[6] / cnt;
     v[0] = qx * px, v[1] = qx * py, v[2] = qx * pz, v[3] = qy * px, v[4] = qy * py, v[5] = qy * pz, v[6] = qz * px, v[7] = qz * py, v[8] = qz * pz;
   }
-  icp_block_row<IC_R2>(v, lds, tid, part + (size_t)blockIdx.x * IC_R2);
+  icp_block_row<IC_R2>(v, lds, tid, part + (size_t)bx * IC_R2);
+}
+
+__global__ __launch_bounds__(IC_BLK) void k_icp_cross(const float4* W, int n, const float4* nnpt, const int* match, const double* sum1, double* part) {
+  icp_cross_block(W, n, nnpt, match, sum1, part, (int)blockIdx.x);
 }
 
 // IC5: R = U S V^T of the 3x3 A (row-major) by a one-sided Jacobi SVD: columns of G = A V are rotated until they are orthogonal, their norms
@@ -311,7 +343,8 @@ APD_HD void icp_step_record(IcpRecord& rec, const double* sum1, const double* cr
   rec.stop = 0;
 }
 
-__global__ __launch_bounds__(64) void k_icp_step(const double* part2, int nblk, const double* sum1, IcpRecord* rec, IcpConsts c) {
+// one wave: the nine cross sums in block order from 0.0, then IC4 .. IC7 in lane 0, which is the only lane to return true (the record is written)
+__device__ __forceinline__ bool icp_step_wave(const double* part2, int nblk, const double* sum1, IcpRecord* rec, const IcpConsts& c) {
   __shared__ double cross[IC_R2];
   const int r = threadIdx.x;
   if (r < IC_R2) {
@@ -320,10 +353,15 @@ __global__ __launch_bounds__(64) void k_icp_step(const double* part2, int nblk, 
     cross[r] = s;
   }
   __syncthreads();
-  if (r != 0) return;
+  if (r != 0) return false;
   IcpRecord l = *rec;
   icp_step_record(l, sum1, cross, c);
   *rec = l;
+  return true;
+}
+
+__global__ __launch_bounds__(64) void k_icp_step(const double* part2, int nblk, const double* sum1, IcpRecord* rec, IcpConsts c) {
+  (void)icp_step_wave(part2, nblk, sum1, rec, c);
 }
 
 // getters: the caller's indexing

@@ -517,9 +517,8 @@ __global__ void k_gather_sorted(const unsigned long long* keys, const float4* pt
   spts[s] = q;
 }
 
-__global__ void k_boxes(const float4* spts, int n, int pts_per_box, Box* out, int nboxes) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nboxes) return;
+// box c of spts[0 .. n): min / max of its pts_per_box points
+__device__ __forceinline__ void box_of_points(const float4* spts, int n, int pts_per_box, Box* out, int c) {
   const float inf = __builtin_inff();
   Box b{inf, inf, inf, -inf, -inf, -inf};
   for (int e = 0; e < pts_per_box; e++) {
@@ -531,6 +530,12 @@ __global__ void k_boxes(const float4* spts, int n, int pts_per_box, Box* out, in
     }
   }
   out[c] = b;
+}
+
+__global__ void k_boxes(const float4* spts, int n, int pts_per_box, Box* out, int nboxes) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nboxes) return;
+  box_of_points(spts, n, pts_per_box, out, c);
 }
 
 // Third level for large clouds (n > SORT_LDS_MAX_N): one box per kSuperGroups consecutive group boxes (8192 sorted points),

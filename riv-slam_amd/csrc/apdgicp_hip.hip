@@ -18,6 +18,7 @@
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
 #include "apd_icp.hpp"
+#include "apd_icp_batch.hpp"
 #include "apd_dbscan.hpp"
 #include "apd_ingest.hpp"
 #include "apd_approx_voxel.hpp"
@@ -258,14 +259,36 @@ struct NdbState {
   }
 };
 
-// The device optimiser loop of a batch handle (V12 / N15), whichever voxel mode runs it: the done counter the step kernels count into, the
+// apdgicp_batch_set_icp (include/apdgicp_hip.h, IC11 .. IC16): per align the working clouds of all pairs (one buffer, a slice per pair), their
+// boxes, matches, block rows and records.  Nothing is kept per cloud slot.  The state of the device loop is the handle's (apdgicp_batch::loop).
+struct IcbState {
+  bool on = false;
+  apdgicp_icp_params prm{1, 0, 3, 0, -std::numeric_limits<double>::max(), 0.0, 1e-12};
+  bool brute = false;          // APDGICP_ICP_RECIP_MODE=brute (read when the handle is created), as on the single handle
+  // what the getters may read: the last align in this mode, while no cloud slot has been written since (epoch: Engine::pts_epoch at the align)
+  bool have = false;
+  uint64_t have_epoch = 0;
+  std::vector<int> src, tgt, n_src;      // per pair of that align: slots and source size
+  std::vector<size_t> w_off;             // ... and where its W starts (points)
+  int nstride = 0, trace_cap = 0;
+  int64_t launches = 0, waits = 0, ticks = 0;  // of the last align
+  DevBuf W, cbox, gbox, beaten, match, dsq, part, sum1, rec, aux, trace, guess;
+  CachedTable pairs, nn_pairs;  // IcbPair per pair; the engine's PairDesc with W as the source
+  void release() {  // apdgicp_batch_clear
+    have = false;
+    W.release(), cbox.release(), gbox.release(), beaten.release(), match.release(), dsq.release(), part.release(), sum1.release(), rec.release(), aux.release(),
+        trace.release(), guess.release(), pairs.dev.release(), nn_pairs.dev.release();
+  }
+};
+
+// The device optimiser loop of a batch handle (V12 / N15 / IC15), whichever mode runs it: the done counter the step kernels count into, the
 // pinned words the host reads, the events of the last two chunks.
 struct DeviceLoop {
   DevBuf done;
   PinnedBuf h_words;           // ints: [0, 2) the done counter as of the last two chunks, [2] the error flag, [4 ...) the scal words of a build
   hipEvent_t ev[2] = {nullptr, nullptr};
   int chunk = 0;               // ticks per enqueued chunk (create time: APDGICP_VGB_CHUNK, default kVgbChunk)
-  int last_ticks = 0;
+  int last_ticks = 0, last_chunks = 0, last_waits = 0;  // of the last run (waits: event and stream waits of the host)
   void drop_events() {
     for (hipEvent_t& e : ev) {
       if (e) (void)hipEventDestroy(e);
@@ -283,12 +306,14 @@ struct apdgicp_batch {
   Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
   VgbState vg;  // (freed by its members' destructors, behind the wait of ~apdgicp_batch)
   NdbState nd;  // (likewise)
+  IcbState ic;  // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two never run together
   DeviceLoop loop;      // (likewise; its events by its own destructor)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
   void release_voxel_modes() {  // apdgicp_batch_clear
     vg.release();
     nd.release();
+    ic.release();
     sort = VoxSortScratch{};
     loop.release();
   }
@@ -988,9 +1013,7 @@ int ic_begin(apdgicp_handle* h, const float* T16, const float* final0) {
   return 0;
 }
 
-IcpConsts ic_consts(const apdgicp_handle* h, int accumulate) {
-  const apdgicp_params& p = h->eng.params;
-  const apdgicp_icp_params& q = h->ic.prm;
+IcpConsts ic_consts(const apdgicp_params& p, const apdgicp_icp_params& q, int accumulate) {
   IcpConsts c;
   c.thr2 = p.max_correspondence_distance * p.max_correspondence_distance;
   c.trans_eps = p.transformation_epsilon;
@@ -999,6 +1022,7 @@ IcpConsts ic_consts(const apdgicp_handle* h, int accumulate) {
   c.max_iterations = p.max_iterations, c.min_corr = q.min_correspondences, c.max_similar = q.max_similar_transforms, c.accumulate = accumulate;
   return c;
 }
+IcpConsts ic_consts(const apdgicp_handle* h, int accumulate) { return ic_consts(h->eng.params, h->ic.prm, accumulate); }
 
 // IC2 .. IC7 over the W that is there: the searches, the two reduction passes, the step; the record comes home behind ONE wait
 int ic_iteration(apdgicp_handle* h, const IcpConsts& c) {
@@ -1188,19 +1212,19 @@ int device_loop_prepare(apdgicp_batch* b) {
 // V10 / V12 / N13 / N15: the optimiser loop of every pair of the engine's list (setup_pairs done, device_loop_prepare done) on the device.
 // launch_tick() enqueues the two launches of one tick on the engine's stream.  Ticks go out in chunks, one chunk ahead of the pinned word the
 // host looks at; returns with the device records complete and the deferred error flag read.
-template <class Tick>
-int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
+// launch_init() enqueues what builds every pair's state and zeroes the done counter; bound: the ticks after which every pair has finished (0:
+// no tick runs, the records are those of the initial states -- the voxel modes only).
+template <class Init, class Tick>
+int device_loop_run(apdgicp_batch* b, long long bound, Init&& launch_init, Tick&& launch_tick) {
   Engine& e = b->eng;
   DeviceLoop& v = b->loop;
   const int np = e.npairs;
-  const apdgicp_params& p = e.params;
   PairState* st = e.d_state.as<PairState>();
   ResultRec* recs = e.d_results.as<ResultRec>();
-  hipLaunchKernelGGL(k_vgb_init, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, e.stream, st, e.d_guess.as<Rigid>(), np, p.max_iterations, v.done.as<int>());
-  const long long bound = p.max_iterations <= 0 ? 0 : (p.optimizer == APDGICP_OPT_GN ? (long long)p.max_iterations : (long long)p.max_iterations * (1 + (long long)std::max(0, p.lm_max_iterations)));
+  launch_init();
   const int chunk = std::max(1, v.chunk);
   long long ticks = 0;
-  int nchunks = 0;
+  int nchunks = 0, waits = 0;
   auto enqueue_chunk = [&]() -> int {
     const int todo = (int)std::min<long long>(chunk, bound - ticks);
     for (int q = 0; q < todo; q++) launch_tick();
@@ -1220,6 +1244,7 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
     for (int waited = 0;; waited++) {
       if (ticks < bound) APD_TRY(enqueue_chunk());  // (one chunk ahead while the host waits for the one before)
       APD_HIP(hipEventSynchronize(v.ev[waited & 1]));
+      waits++;
       if (v.h_words.as<int>()[waited & 1] >= np || waited + 1 >= nchunks) break;
     }
   }
@@ -1229,6 +1254,7 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
   for (Engine::Cloud& c : e.clouds) c.stage_pending = false, c.stage_wait = nullptr, c.stage_seq_word = nullptr;  // (every sort has run)
   e.n_stage_pending = 0;
   v.last_ticks = (int)ticks;
+  v.last_chunks = nchunks, v.last_waits = waits + 1;
   e.last_ticks = (int)ticks;
   if (v.h_words.as<int>()[2]) {
     const int flag = v.h_words.as<int>()[2];
@@ -1237,6 +1263,21 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
   }
   e.poses_of_align = true;
   return 0;
+}
+
+// the voxel modes: V10's state machine from the guesses, its tick bound
+template <class Tick>
+int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
+  Engine& e = b->eng;
+  const apdgicp_params& p = e.params;
+  const long long bound = p.max_iterations <= 0 ? 0 : (p.optimizer == APDGICP_OPT_GN ? (long long)p.max_iterations : (long long)p.max_iterations * (1 + (long long)std::max(0, p.lm_max_iterations)));
+  return device_loop_run(
+      b, bound,
+      [&]() {
+        hipLaunchKernelGGL(k_vgb_init, dim3((unsigned)((e.npairs + 63) / 64)), dim3(64), 0, e.stream, e.d_state.as<PairState>(), e.d_guess.as<Rigid>(), e.npairs,
+                           p.max_iterations, b->loop.done.as<int>());
+      },
+      launch_tick);
 }
 
 // ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
@@ -1449,8 +1490,128 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   });
 }
 
+// ---- point-to-point ICP on a batch handle (include/apdgicp_hip.h IC11 .. IC16; kernels: apd_icp_batch.hpp)
+constexpr int kIcbTraceCap = 1024;  // a pair's trace keeps its first this many iterations (the count goes on)
+
+// IC13 / IC15: the loop of every pair on the device; returns with the device records complete
+int icb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
+  Engine& e = b->eng;
+  IcbState& v = b->ic;
+  v.have = false;
+  if (n_pairs > 65535) return fail(APDGICP_ERR_INVALID_ARG, "point-to-point ICP: at most 65535 pairs per align (the pair is a grid dimension)");
+  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
+  APD_TRY(e.setup_pairs(pairs, n_pairs, true, /*pipeline_cov=*/false, /*need_cov=*/false));  // clouds sorted, no covariances, the search buffers
+  e.results_on_host = false;
+  const int np = e.npairs, nstride = e.work.nstride, nblk_max = (e.nmax_src + IC_BLK - 1) / IC_BLK;
+  const size_t nch_max = ((size_t)e.nmax_src + kChunk - 1) / kChunk, ngr_max = ((size_t)e.nmax_src + kGroupPts - 1) / kGroupPts;
+  const long long bound = std::max(1, e.params.max_iterations);  // (max_iterations <= 1 still runs one iteration, as the single handle does)
+  const int trace_cap = (int)std::min<long long>(bound, kIcbTraceCap);
+  v.src.resize(np), v.tgt.resize(np), v.n_src.resize(np), v.w_off.resize(np);
+  size_t total = 0;
+  for (int i = 0; i < np; i++) {
+    v.src[i] = e.h_pairs[i].src, v.tgt[i] = e.h_pairs[i].tgt, v.n_src[i] = e.clouds[v.src[i]].n;
+    v.w_off[i] = total;
+    total += (size_t)v.n_src[i];
+  }
+  const bool recip = v.prm.use_reciprocal_correspondences != 0;
+  struct Want {
+    DevBuf* buf;
+    size_t bytes;
+  };
+  const Want wants[] = {{&v.W, total * 16},
+                        {&v.cbox, recip ? (size_t)np * nch_max * sizeof(Box) : 0},
+                        {&v.gbox, recip ? (size_t)np * ngr_max * sizeof(Box) : 0},
+                        {&v.beaten, recip ? (size_t)np * nstride : 0},
+                        {&v.match, (size_t)np * nstride * 4},
+                        {&v.dsq, (size_t)np * nstride * 4},
+                        {&v.part, (size_t)np * nblk_max * IC_R2 * 8},
+                        {&v.sum1, (size_t)np * IC_R1 * 8},
+                        {&v.rec, (size_t)np * sizeof(IcpRecord)},
+                        {&v.aux, (size_t)np * sizeof(IcbAux)},
+                        {&v.trace, (size_t)np * trace_cap * sizeof(IcbTrace)},
+                        {&v.guess, (size_t)np * 16 * sizeof(float)}};
+  bool grows = false;
+  for (const Want& w : wants) grows |= w.bytes > w.buf->cap;
+  if (grows) APD_HIP(hipStreamSynchronize(e.stream));  // (getters of the last align may still read the old buffers)
+  for (const Want& w : wants) APD_TRY(w.buf->ensure(w.bytes));
+  v.nstride = nstride, v.trace_cap = trace_cap;
+  std::vector<IcbPair> tab(np);
+  std::vector<PairDesc> nn(np);
+  for (int i = 0; i < np; i++) {
+    const Engine::Cloud& s = e.clouds[v.src[i]];
+    float4* W = v.W.as<float4>() + v.w_off[i];
+    tab[i] = IcbPair{s.pts.as<float4>(), s.perm.as<int>(), W, recip ? v.cbox.as<Box>() + (size_t)i * nch_max : nullptr, recip ? v.gbox.as<Box>() + (size_t)i * ngr_max : nullptr,
+                     s.n, 0};
+    nn[i] = e.h_pairs[i];
+    nn[i].s.pts = W;  // IC12: the search sees W itself at the identity pose
+  }
+  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(IcbPair), e.stream));
+  APD_TRY(v.nn_pairs.upload(nn.data(), nn.size() * sizeof(PairDesc), e.stream));
+  APD_HIP(hipMemcpyAsync(v.guess.p, e.h_guesses.data(), (size_t)np * 16 * sizeof(float), hipMemcpyHostToDevice, e.stream));  // (pageable source: staged before the call returns)
+  APD_TRY(device_loop_prepare(b));
+  const IcpConsts c = ic_consts(e.params, v.prm, 1);
+  const int xf = (e.params.flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;
+  // the engine's search with this mode's inputs, for the length of this call: W as the source, the distances kept, no keeping, no timing
+  struct SearchScope {
+    Engine& e;
+    float* sqd;
+    bool profile;
+    int active;
+    ~SearchScope() { e.pairs_override = nullptr, e.work.sqd = sqd, e.profile_nn = profile, e.cur_active = active; }
+  } scope{e, e.work.sqd, e.profile_nn, e.cur_active};
+  e.pairs_override = v.nn_pairs.as<PairDesc>();
+  e.work.sqd = e.b_sqd.as<float>();
+  e.profile_nn = false, e.cur_active = 0;
+  const IcbTab t{v.pairs.as<IcbPair>(), e.d_state.as<PairState>(), v.rec.as<IcpRecord>(), v.aux.as<IcbAux>(), v.trace.as<IcbTrace>(), e.work.nnpt, e.work.sqd,
+                 v.match.as<int>(), v.dsq.as<float>(), v.beaten.as<unsigned char>(), v.part.as<double>(), v.sum1.as<double>(), nstride, nblk_max, trace_cap, 0};
+  ResultRec* recs = e.d_results.as<ResultRec>();
+  int* done = b->loop.done.as<int>();
+  const dim3 grid_pts((unsigned)nblk_max, (unsigned)np), grid_w((unsigned)((e.nmax_src + 255) / 256), (unsigned)np);
+  int tick = 0, rc_tick = 0;
+  const int per_tick = 2 + (recip ? (v.brute ? 1 : 3) : 0) + 5;
+  const int rc = device_loop_run(
+      b, bound,
+      [&]() {
+        hipLaunchKernelGGL(k_icb_init, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, e.stream, t, v.guess.as<float>(), np, done);
+        hipLaunchKernelGGL(k_icb_winit, grid_w, dim3(256), 0, e.stream, t.pairs, v.guess.as<float>(), xf);
+      },
+      [&]() {
+        if (rc_tick == 0) rc_tick = e.launch_nn(e.whole());
+        if (rc_tick == 0) rc_tick = e.launch_linearize(e.whole(), 0);  // (the per-point pass that settles the exact index: Work::nnpt, Work::sqd)
+        if (recip && !v.brute) {
+          hipLaunchKernelGGL(k_icb_boxes, dim3((unsigned)((nch_max + 255) / 256), (unsigned)np), dim3(256), 0, e.stream, t, 0);
+          hipLaunchKernelGGL(k_icb_boxes, dim3((unsigned)((ngr_max + 255) / 256), (unsigned)np), dim3(256), 0, e.stream, t, 1);
+          hipLaunchKernelGGL(k_icb_recip<true>, grid_pts, dim3(IC_BLK), 0, e.stream, t, c.thr2);
+        } else if (recip) {
+          hipLaunchKernelGGL(k_icb_recip<false>, grid_pts, dim3(IC_BLK), 0, e.stream, t, c.thr2);
+        }
+        hipLaunchKernelGGL(k_icb_pairs, grid_pts, dim3(IC_BLK), 0, e.stream, t, recip ? 1 : 0, c.thr2);
+        hipLaunchKernelGGL(k_icb_sums, dim3((unsigned)np), dim3(64), 0, e.stream, t);
+        hipLaunchKernelGGL(k_icb_cross, grid_pts, dim3(IC_BLK), 0, e.stream, t);
+        hipLaunchKernelGGL(k_icb_step, dim3((unsigned)np), dim3(64), 0, e.stream, t, c, tick, recs, done);
+        hipLaunchKernelGGL(k_icb_transform, grid_w, dim3(256), 0, e.stream, t, tick, xf);  // IC1: once per iteration, the last included
+        tick++;
+      });
+  APD_TRY(rc);
+  APD_TRY(rc_tick);
+  v.ticks = b->loop.last_ticks, v.waits = b->loop.last_waits;
+  v.launches = 2 + (int64_t)v.ticks * per_tick;
+  v.have = true, v.have_epoch = e.pts_epoch;
+  return 0;
+}
+
+// the last align in this mode must still describe the slots as they are
+int icb_check_have(apdgicp_batch* b, int64_t pair) {
+  const IcbState& v = b->ic;
+  if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_batch_set_icp)");
+  if (!v.have || v.have_epoch != b->eng.pts_epoch) return fail(APDGICP_ERR_NO_INPUT, "no align in this mode of the clouds the handle holds now");
+  if (pair < 0 || pair >= (int64_t)v.src.size()) return fail(APDGICP_ERR_INVALID_ARG, "pair is not one of the last align");
+  return 0;
+}
+
 const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 const char* const kNdbNoPipeline = "NDT on a batch handle (apdgicp_batch_set_ndt) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+const char* const kIcbNoPipeline = "point-to-point ICP on a batch handle (apdgicp_batch_set_icp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 
 // what the single and the batch setters refuse (null: nothing to check -- the mode is being switched off)
 int check_vgicp_params(const apdgicp_vgicp_params* p) {
@@ -2094,10 +2255,11 @@ int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on && !b->nd.on) APD_TRY(batch_enter_device_loop_mode(b));
+    if (!v.on && !b->nd.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.prm = *p;
     v.on = true;
     b->nd.on = false;  // N15: the two modes are exclusive
+    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
     return 0;
   });
 }
@@ -2143,10 +2305,11 @@ int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on && !b->vg.on) APD_TRY(batch_enter_device_loop_mode(b));
+    if (!v.on && !b->vg.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.prm = *p;
     v.on = true;
     b->vg.on = false;  // N15: the two modes are exclusive
+    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
     return 0;
   });
 }
@@ -2478,6 +2641,8 @@ int apdgicp_batch_create(const apdgicp_params* p, int device, void* stream, apdg
     }
     b->eng.profile_nn = env_int("APDGICP_PROFILE_NN", 0) != 0;
     b->eng.keep_maha = false;  // no batch entry point reads the Mahalanobis matrices back
+    const char* recip_mode = getenv("APDGICP_ICP_RECIP_MODE");
+    b->ic.brute = recip_mode && std::string(recip_mode) == "brute";
     *out = b;
     return 0;
   });
@@ -2557,6 +2722,11 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
       if (d_results) *d_results = b->eng.d_results.p;
       return 0;
     }
+    if (b->ic.on) {  // point-to-point ICP: likewise (IC15)
+      APD_TRY(icb_align(b, pairs, n_pairs));
+      if (d_results) *d_results = b->eng.d_results.p;
+      return 0;
+    }
     if (b->eng.pool_eligible()) {  // Levenberg-Marquardt: through the pair pool (complete on return, like every LM run)
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
@@ -2574,6 +2744,7 @@ int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int
     if (!b || !pairs || !ticket) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
+    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_eligible()) return e.pool_enqueue(pairs, n_pairs, ticket);
     APD_TRY(e.ensure_alt_slot());
@@ -2592,13 +2763,14 @@ int apdgicp_batch_pump(apdgicp_batch* b) {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
+    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
     return b->eng.pool.on ? b->eng.pool_pump(false) : 0;
   });
 }
 
 int apdgicp_batch_is_pooled(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-  if (b->vg.on || b->nd.on) return 0;
+  if (b->vg.on || b->nd.on || b->ic.on) return 0;
   return b->eng.pool_eligible() ? Engine::pool_lanes_cfg() : 0;
 }
 
@@ -2607,6 +2779,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
+    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_find(ticket)) return e.pool_collect(ticket, d_results, host_results);
     const bool previous = ticket + 1 == e.align_seq;
@@ -2633,7 +2806,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
 int apdgicp_batch_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, apdgicp_result* results) {
   return guarded([&]() -> int {
     if (!results) return fail(APDGICP_ERR_INVALID_ARG, "results is null");
-    if (b && pairs && !b->vg.on && !b->nd.on && b->eng.pool_eligible()) {
+    if (b && pairs && !b->vg.on && !b->nd.on && !b->ic.on && b->eng.pool_eligible()) {
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
       return b->eng.pool_collect(ticket, nullptr, results);
@@ -2671,6 +2844,14 @@ int apdgicp_batch_fitness(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n
         T = pool_T.data();
         same_pairs = false;
       }
+    }
+    if (!T && b->ic.on && same_pairs && e.poses_of_align) {  // IC16: the poses of an ICP align are its records' (the pair state holds the identity)
+      std::vector<ResultRec> recs((size_t)n_pairs);
+      APD_HIP(hipMemcpyAsync(recs.data(), e.d_results.p, recs.size() * sizeof(ResultRec), hipMemcpyDeviceToHost, e.stream));
+      APD_HIP(hipStreamSynchronize(e.stream));
+      pool_T.resize((size_t)n_pairs * 16);
+      for (int64_t i = 0; i < n_pairs; i++) memcpy(&pool_T[(size_t)i * 16], recs[i].T, 16 * sizeof(float));
+      T = pool_T.data();
     }
     // (the state's poses are the align's only until somebody else writes them: an explicit-pose call on the same list does)
     if (!T && !(same_pairs && e.poses_of_align)) return fail(APDGICP_ERR_NO_INPUT, "T == NULL needs a previous align of the same pair list");
@@ -2744,6 +2925,120 @@ int apdgicp_batch_last_nn_time(apdgicp_batch* b, double* total_ms, int64_t* laun
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (total_ms) *total_ms = b->eng.last_nn_ms;
   if (launches) *launches = b->eng.last_nn_launches;
+  return 0;
+}
+
+int apdgicp_batch_set_icp(apdgicp_batch* b, const apdgicp_icp_params* p) {
+  return guarded([&]() -> int {
+    // (the parameters first: what is wrong with them does not depend on the handle)
+    APD_TRY(check_icp_params(p));
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    IcbState& v = b->ic;
+    if (p) v.prm = *p;
+    if (!p || !p->enable) {
+      if (v.on) b->eng.poses_of_align = false;  // (the engine's pair state holds this mode's identity poses, not an align's)
+      v.on = false;
+      return 0;
+    }
+    if (!v.on && !b->vg.on && !b->nd.on) APD_TRY(batch_enter_device_loop_mode(b));
+    v.on = true, v.have = false;
+    b->vg.on = false, b->nd.on = false;  // IC16: the three modes are exclusive
+    return 0;
+  });
+}
+
+int apdgicp_batch_get_icp(const apdgicp_batch* b, apdgicp_icp_params* p, int* enabled) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (p) {
+    *p = b->ic.prm;
+    p->enable = b->ic.on ? 1 : 0;
+  }
+  if (enabled) *enabled = b->ic.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_batch_icp_states(apdgicp_batch* b, int32_t* states, int64_t n_pairs) {
+  return guarded([&]() -> int {
+    if (!b || !states) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(icb_check_have(b, 0));
+    IcbState& v = b->ic;
+    if (n_pairs != (int64_t)v.src.size()) return fail(APDGICP_ERR_INVALID_ARG, "n_pairs does not match the last align");
+    std::vector<IcpRecord> recs((size_t)n_pairs);
+    APD_HIP(hipMemcpyAsync(recs.data(), v.rec.p, recs.size() * sizeof(IcpRecord), hipMemcpyDeviceToHost, b->eng.stream));
+    APD_HIP(hipStreamSynchronize(b->eng.stream));
+    for (int64_t i = 0; i < n_pairs; i++) states[i] = recs[i].state;
+    return 0;
+  });
+}
+
+int apdgicp_batch_icp_get_correspondences(apdgicp_batch* b, int64_t pair, int32_t* match, float* sq_dist, int64_t n) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    APD_TRY(icb_check_have(b, pair));
+    Engine& e = b->eng;
+    IcbState& v = b->ic;
+    if (n != v.n_src[pair]) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the pair's source size");
+    APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(e.d_stage.ensure((size_t)n * 8));
+    int* d_c = e.d_stage.as<int>();
+    float* d_s = (float*)(d_c + n);
+    const size_t o = (size_t)pair * v.nstride;
+    hipLaunchKernelGGL(k_icp_export, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, v.match.as<int>() + o, v.dsq.as<float>() + o,
+                       e.clouds[v.src[pair]].perm.as<int>(), e.clouds[v.tgt[pair]].perm.as<int>(), (int)n, d_c, d_s);
+    APD_HIP(hipGetLastError());
+    if (match) APD_HIP(hipMemcpyAsync(match, d_c, n * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    if (sq_dist) APD_HIP(hipMemcpyAsync(sq_dist, d_s, n * sizeof(float), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    return 0;
+  });
+}
+
+int apdgicp_batch_icp_get_working_cloud(apdgicp_batch* b, int64_t pair, float* xyz, int64_t n) {
+  return guarded([&]() -> int {
+    if (!b || !xyz) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(icb_check_have(b, pair));
+    Engine& e = b->eng;
+    IcbState& v = b->ic;
+    if (n != v.n_src[pair]) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the pair's source size");
+    APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(e.d_stage.ensure((size_t)n * 12));
+    hipLaunchKernelGGL(k_icp_export_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, v.W.as<float4>() + v.w_off[pair], e.clouds[v.src[pair]].perm.as<int>(), (int)n,
+                       e.d_stage.as<float>());
+    APD_HIP(hipGetLastError());
+    APD_HIP(hipMemcpyAsync(xyz, e.d_stage.p, (size_t)n * 12, hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    return 0;
+  });
+}
+
+int apdgicp_batch_icp_get_trace(apdgicp_batch* b, int64_t pair, int64_t capacity, float* T_k16, int64_t* n_corr, double* mse, int32_t* similar, int64_t* n_iterations) {
+  return guarded([&]() -> int {
+    if (!b || !n_iterations || capacity < 0) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    APD_TRY(icb_check_have(b, pair));
+    Engine& e = b->eng;
+    IcbState& v = b->ic;
+    IcbAux aux;
+    std::vector<IcbTrace> tr((size_t)v.trace_cap);
+    APD_HIP(hipMemcpyAsync(&aux, v.aux.as<IcbAux>() + pair, sizeof(aux), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipMemcpyAsync(tr.data(), v.trace.as<IcbTrace>() + (size_t)pair * v.trace_cap, tr.size() * sizeof(IcbTrace), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    *n_iterations = aux.n_trace;
+    const int64_t m = std::min<int64_t>(std::min<int64_t>(aux.n_trace, v.trace_cap), capacity);
+    for (int64_t k = 0; k < m; k++) {
+      if (T_k16) memcpy(T_k16 + 16 * k, tr[k].T_k, 16 * sizeof(float));
+      if (n_corr) n_corr[k] = tr[k].n_corr;
+      if (mse) mse[k] = tr[k].mse;
+      if (similar) similar[k] = tr[k].similar;
+    }
+    return 0;
+  });
+}
+
+int apdgicp_batch_icp_debug_counts(apdgicp_batch* b, int64_t* launches, int64_t* waits, int64_t* ticks) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (launches) *launches = b->ic.launches;
+  if (waits) *waits = b->ic.waits;
+  if (ticks) *ticks = b->ic.ticks;
   return 0;
 }
 

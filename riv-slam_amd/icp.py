@@ -1,6 +1,6 @@
 """Point-to-point ICP (pcl::IterativeClosestPoint, the ICP branch of select_registration_method(), registrations.cpp:71-78) as a mode of the
 registration handle: `ICP` is `registration.FastAPDGICP` with apdgicp_set_icp switched on and PCL's setters.  Semantics: the list
-IC1 .. IC10 in include/apdgicp_hip.h.
+IC1 .. IC10 in include/apdgicp_hip.h.  `BatchICP` is the same mode on a batch handle (IC11 .. IC16): every pair's loop runs on the device.
 
 There is NO CPU fallback: without the HIP library or a GPU every call raises.
 """
@@ -143,3 +143,135 @@ class ICP(reg.FastAPDGICP):
         a, b = C.c_int64(), C.c_int64()
         _check(self.L.apdgicp_icp_debug_counts(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+
+def _rows(cloud) -> int:
+    return int(cloud.n) if isinstance(cloud, reg.DevicePoints) else int(cloud.shape[0])
+
+
+class BatchICP(reg.BatchAPDGICP):
+    """Many independent point-to-point ICP registrations on one GPU: a batch handle with apdgicp_batch_set_icp on (IC11 .. IC16).  Clouds,
+    align, align_async / synchronize and fitness are the base class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is;
+    align_enqueue / align_collect raise (one batch at a time).  A pair's record, state, trace, correspondences and working cloud are
+    byte-identical to what `ICP` returns for the same pair.  `params` None: PCL's defaults (pcl_params()).  `disable()` hands the handle
+    back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params or pcl_params(), device, stream)
+        self.iparams = default_icp_params()
+        self._rows, self._last_pairs = {}, []
+        self._push_icp()
+
+    def _push_icp(self):
+        _check(self.L.apdgicp_batch_set_icp(self.b, C.byref(self.iparams)))
+
+    _set = ICP._set
+    setUseReciprocalCorrespondences = ICP.setUseReciprocalCorrespondences
+    setEuclideanFitnessEpsilon = ICP.setEuclideanFitnessEpsilon
+    setTransformationRotationEpsilon = ICP.setTransformationRotationEpsilon
+    setMinCorrespondences = ICP.setMinCorrespondences
+    setMaximumIterationsSimilarTransforms = ICP.setMaximumIterationsSimilarTransforms
+    setAbsoluteMSE = ICP.setAbsoluteMSE
+
+    def _set_param(self, field: str, value):
+        setattr(self.params, field, value)
+        self.set_params(self.params)
+
+    def setMaximumIterations(self, n: int):
+        self._set_param("max_iterations", int(n))
+
+    def setTransformationEpsilon(self, eps: float):
+        self._set_param("transformation_epsilon", float(eps))
+
+    def setMaxCorrespondenceDistance(self, d: float):
+        self._set_param("max_correspondence_distance", float(d))
+
+    def get_icp(self):
+        """(IcpParams, enabled) as the library holds them."""
+        p, on = IcpParams(), C.c_int()
+        _check(self.L.apdgicp_batch_get_icp(self.b, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def disable(self):
+        _check(self.L.apdgicp_batch_set_icp(self.b, None))
+
+    def enable(self):
+        self.iparams.enable = 1
+        self._push_icp()
+
+    def enabled(self) -> bool:
+        return self.get_icp()[1]
+
+    # the sizes of the slots and the pairs of the last align: what the per-pair getters size their outputs by
+    def clear(self):
+        super().clear()
+        self._rows.clear()
+
+    def add_cloud(self, cloud) -> int:
+        idx = super().add_cloud(cloud)
+        self._rows[idx] = _rows(cloud)
+        return idx
+
+    def set_cloud(self, index: int, cloud) -> int:
+        idx = super().set_cloud(index, cloud)
+        self._rows[idx] = _rows(cloud)
+        return idx
+
+    def set_clouds(self, first_index: int, clouds, producer_wait: bool = True):
+        packed = clouds if isinstance(clouds, tuple) and clouds and clouds[0] == "packed_clouds" else self.pack_clouds(clouds)
+        super().set_clouds(first_index, packed, producer_wait)
+        for k in range(packed[5]):
+            self._rows[first_index + k] = int(packed[2][k])
+
+    def _remember(self, pairs):
+        self._last_pairs = [(int(p.source_cloud), int(p.target_cloud)) for p in pairs] if isinstance(pairs, C.Array) else [(int(s), int(t)) for s, t in pairs]
+
+    def align(self, pairs, guesses=None):
+        self._remember(pairs)
+        return super().align(pairs, guesses)
+
+    def align_async(self, pairs, guesses=None):
+        self._remember(pairs)
+        return super().align_async(pairs, guesses)
+
+    def _n_of(self, pair: int) -> int:
+        if not 0 <= pair < len(self._last_pairs):
+            return 0   # (the library refuses the pair)
+        return self._rows.get(self._last_pairs[pair][0], 0)
+
+    def states(self) -> np.ndarray:
+        """apdgicp_icp_state of every pair of the last align, int32."""
+        out = np.empty(len(self._last_pairs), dtype=np.int32)
+        _check(self.L.apdgicp_batch_icp_states(self.b, _ptr(out), len(out)))
+        return out
+
+    def correspondences(self, pair: int):
+        """(match, sq_dist) of the last iteration of pair `pair` of the last align, as ICP.correspondences()."""
+        n = self._n_of(pair)
+        match = np.empty(n, dtype=np.int32)
+        sqd = np.empty(n, dtype=np.float32)
+        _check(self.L.apdgicp_batch_icp_get_correspondences(self.b, int(pair), _ptr(match), _ptr(sqd), n))
+        return match, sqd
+
+    def working_cloud(self, pair: int) -> np.ndarray:
+        """W of pair `pair` after the last align in the source's order, [n, 3] float32."""
+        n = self._n_of(pair)
+        out = np.empty((n, 3), dtype=np.float32)
+        _check(self.L.apdgicp_batch_icp_get_working_cloud(self.b, int(pair), _ptr(out), n))
+        return out
+
+    def trace(self, pair: int):
+        """The iterations of pair `pair` of the last align, as ICP.trace()."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_icp_get_trace(self.b, int(pair), 0, None, None, None, None, C.byref(n)))
+        k = n.value
+        Tk, nc, mse, sim = np.zeros((k, 16), dtype=np.float32), np.zeros(k, dtype=np.int64), np.zeros(k), np.zeros(k, dtype=np.int32)
+        if k:
+            _check(self.L.apdgicp_batch_icp_get_trace(self.b, int(pair), k, _ptr(Tk), _ptr(nc), _ptr(mse), _ptr(sim), C.byref(n)))
+        return {"T_k": Tk.reshape(k, 4, 4).transpose(0, 2, 1).copy(), "n_corr": nc, "mse": mse, "similar": sim}
+
+    def debug_counts(self):
+        """(launches, waits, ticks) of the last align (tests/measure/bench_icp_batch.py)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.L.apdgicp_batch_icp_debug_counts(self.b, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value

@@ -117,6 +117,8 @@ SYMBOLS = [
     "apdgicp_batch_set_ndt", "apdgicp_batch_get_ndt", "apdgicp_batch_ndt_voxel_count", "apdgicp_batch_ndt_get_voxels", "apdgicp_batch_ndt_build_count",
     "apdgicp_icp_default_params", "apdgicp_set_icp", "apdgicp_get_icp", "apdgicp_icp_estimate", "apdgicp_icp_get_correspondences",
     "apdgicp_icp_get_working_cloud", "apdgicp_icp_get_trace", "apdgicp_icp_convergence_state", "apdgicp_icp_debug_counts",
+    "apdgicp_batch_set_icp", "apdgicp_batch_get_icp", "apdgicp_batch_icp_states", "apdgicp_batch_icp_get_correspondences", "apdgicp_batch_icp_get_working_cloud",
+    "apdgicp_batch_icp_get_trace", "apdgicp_batch_icp_debug_counts",
     "apdgicp_dbscan_default_params", "apdgicp_dbscan_create", "apdgicp_dbscan_destroy", "apdgicp_dbscan_set_params", "apdgicp_dbscan_run", "apdgicp_dbscan_labels",
     "apdgicp_dbscan_copy_labels", "apdgicp_dbscan_clusters", "apdgicp_dbscan_members", "apdgicp_dbscan_debug", "apdgicp_dbscan_set_profiling", "apdgicp_dbscan_stats",
     "apdgicp_scan_ingest_default_params", "apdgicp_scan_ingest_create", "apdgicp_scan_ingest_destroy", "apdgicp_scan_ingest_set_params", "apdgicp_scan_ingest_run",
@@ -319,6 +321,13 @@ def load_library(path: str | None = None):
     L.apdgicp_icp_get_trace.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
     L.apdgicp_icp_convergence_state.argtypes = [vp, C.POINTER(C.c_int32)]
     L.apdgicp_icp_debug_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_batch_set_icp.argtypes = [vp, vp]
+    L.apdgicp_batch_get_icp.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_batch_icp_states.argtypes = [vp, vp, i64]
+    L.apdgicp_batch_icp_get_correspondences.argtypes = [vp, i64, vp, vp, i64]
+    L.apdgicp_batch_icp_get_working_cloud.argtypes = [vp, i64, vp, i64]
+    L.apdgicp_batch_icp_get_trace.argtypes = [vp, i64, i64, vp, vp, vp, vp, C.POINTER(i64)]
+    L.apdgicp_batch_icp_debug_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
     L.apdgicp_batch_set_ndt.argtypes = [vp, vp]
     L.apdgicp_batch_get_ndt.argtypes = [vp, vp, C.POINTER(i32)]
     L.apdgicp_batch_ndt_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
