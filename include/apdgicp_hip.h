@@ -49,7 +49,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_debug_live_buffers;
                                       still 6 (additive): + the apdgicp_scan_ingest_* object (power gate and packing of a radar message, IMU deskew, frame transform);
                                       still 6 (additive): + apdgicp_set_icp / _get_icp and the apdgicp_icp_* calls (point-to-point ICP as a mode of the registration handle);
-                                      still 6 (additive): + apdgicp_batch_set_icp / _get_icp and the apdgicp_batch_icp_* calls (point-to-point ICP as a mode of the batch handle) */
+                                      still 6 (additive): + apdgicp_batch_set_icp / _get_icp and the apdgicp_batch_icp_* calls (point-to-point ICP as a mode of the batch handle);
+                                      still 6 (additive): + apdgicp_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the registration handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -363,6 +364,90 @@ int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coord
 int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_source);
 /* Debug: how many times this handle has built a voxel map (the tests of the cache rules read it) */
 int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds);
+
+/* ------------------------------------------------------------------ FAST_VGICP_CUDA as a mode of the handle
+ * fast_gicp::FastVGICPCuda, the FAST_VGICP_CUDA branch of select_registration_method() (registrations.cpp:51-61).  Not the algorithm of
+ * the FAST_VGICP mode above: its PLANE regularisation REMOVES every point whose neighbourhood is line-like from both clouds, k is fixed at
+ * 20, and it owns the DIRECT_RADIUS neighbour search.  Citation keys, paths under fast_apdgicp/:
+ *   VCI: include/fast_gicp/gicp/impl/fast_vgicp_cuda_impl.hpp      VC: src/fast_gicp/cuda/fast_vgicp_cuda.cu
+ *   CE:  src/fast_gicp/cuda/covariance_estimation.cu               CR: src/fast_gicp/cuda/covariance_regularization.cu
+ *   GV:  src/fast_gicp/cuda/gaussian_voxelmap.cu                   FC: src/fast_gicp/cuda/find_voxel_correspondences.cu
+ *   CD:  src/fast_gicp/cuda/compute_derivatives.cu
+ * The kernels (riv-slam_amd/csrc/apd_vgicp_cuda.hpp) and the restatement the tests compare with (tests/vgicp_cuda_np.py) follow this list:
+ *   VC1. Neighbours.  k = 20 always (VCI:38: setCorrespondenceRandomness is a no-op); apdgicp_params::k_correspondences is not read.
+ *        CPU_PARALLEL_KDTREE (the default, VCI:27) and GPU_BRUTEFORCE both mean the engine's exact k-NN, the point itself included, the
+ *        neighbours in rank order: ascending fp32 squared distance, ties by ascending original index (the engine's key order).
+ *        GPU_RBF_KERNEL: APDGICP_ERR_UNSUPPORTED.  A cloud of fewer than 20 points: APDGICP_ERR_TOO_FEW_POINTS.
+ *   VC2. Raw covariance (CE:26-34).  S1 = sum p, S2 = sum p p^T (six unique entries) over the 20 neighbours in rank order: fp64 sums started
+ *        at 0, p the fp64 value of the fp32 point, every product rounded before it is added.  mean = S1 / 20, C_rc = S2_rc / 20 - mean_r mean_c.
+ *        This is the reference's expression in absolute coordinates, not the query-relative form of apdgicp_compute_covariances.
+ *   VC3. Regularisation (CR:91-117), from the eigen-decomposition the rest of the library uses (cyclic Jacobi), eigenvalues
+ *        lambda0 <= lambda1 <= lambda2.
+ *        PLANE (the default, VCI:26): the point is KEPT iff lambda1 > 0.1 lambda2 in fp64 (CR:26-31; false for a NaN, which drops the point);
+ *        a kept point's covariance is V diag(1e-3, 1, 1) V^T, the 1e-3 on lambda0's vector, each entry the sum of its three products in
+ *        the order lambda2's, lambda1's, lambda0's vector (with orthonormal V the reference's V D V^-1).
+ *        MIN_EIG (CR:73-87): V diag(max(lambda, 1e-3)) V^T as N3.  No filter.
+ *        FROBENIUS (CR:63-71): C' = C + 1e-3 I, the result (C'^-1 / ||C'^-1||_F)^-1.  No filter.
+ *        NONE and NORMALIZED_MIN_EIG (the reference prints "unimplemented" and goes on with raw covariances): APDGICP_ERR_UNSUPPORTED.
+ *   VC4. The filter compacts.  With PLANE the kept points, in the caller's order, ARE the cloud of this mode, for source and target alike
+ *        (CR:104-109 replaces the points): correspondences, rows, the voxel map and n_matched see kept points only.  kept_index[j] = the
+ *        original index of kept point j; n_kept and kept_index are readable (apdgicp_vgicp_cuda_kept).  Flags, a block scan, a scatter; no
+ *        atomics.  Preparing a cloud (k-NN, VC2, VC3, compaction) costs one host wait.  Zero kept points on either side is legal: VC9.
+ *   VC5. Voxel map (GV:229-252, :154-167): V1 .. V3 above, ADDITIVE, over the kept target points and their VC3 covariances -- bit-equal to
+ *        what the FAST_VGICP mode builds from those points and covariances.
+ *   VC6. Offsets (VC:42-95).  DIRECT1 / DIRECT7 / DIRECT27 in V5's order.  DIRECT_RADIUS(r): for i, j, k from -ceil(r) to ceil(r), k
+ *        fastest, the offset (i, j, k) is kept iff sqrt(i^2 + j^2 + k^2) <= r + 1e-3 in fp64 (so r = 1.0 holds DIRECT7's offsets in
+ *        another order).  r must be finite with 0 <= r <= 4: 1 offset at r = 0 and 0.5, 7 at 1.0, 19 at 1.5, 33 at 2.0, 81 at 2.5, 123 at
+ *        3.0, 257 at 4.0; anything else is APDGICP_ERR_INVALID_ARG.  search_radius is read only with DIRECT_RADIUS.  V2's rule holds for
+ *        offsets of this size: a source coordinate up to 2^20 + 3 is still offered to the per-offset range test |c + o| < 2^20, made on
+ *        exact integers before the key is packed.
+ *   VC7. Correspondences and cost (FC:55-60, CD:50-92): V4 / V5 over the kept source, every hit of an offset a term, M = (C_voxel + R C_A
+ *        R^T)^-1, w = sqrt(count), e = mean - q, J = [skew(q) | -I]; terms in offset order, lanes, waves and blocks in V5's fixed order.
+ *   VC8. Frozen state (VC:276-284): V6 over the stored indices, n_kept x n_offsets int32, point-major, -1 = miss.
+ *   VC9. Degenerate cases: V7.  No correspondence at a linearize inside align (also: no kept point on either side) ends the loop with
+ *        converged = 0, lm_failed = 0, n_matched = 0, T = the pose so far.  max_correspondence_distance and the APD flags are not read.
+ *   VC10. Mode rules.  apdgicp_set_vgicp_cuda is exclusive with apdgicp_set_vgicp, _set_ndt and _set_icp: switching one on switches the others
+ *        off; NULL returns to what apdgicp_params says.  The prepared cloud (kept list + covariances) is cached by the identity of the
+ *        cloud's points and the regularisation, the map by that plus the resolution; apdgicp_swap_source_and_target swaps the prepared
+ *        clouds and the map is rebuilt (VC:97-107).  The mode's covariances live in buffers of their own: the covariances of
+ *        apdgicp_compute_covariances / _set_covariances are neither read nor written.  With the mode off a handle does exactly what one that
+ *        never had it on does.  apdgicp_linearize / _compute_error run these kernels; apdgicp_align and apdgicp_align_host_loop run the
+ *        host-driven loop over them as in the FAST_VGICP mode (trace, final Hessian, apdgicp_result).  fitness_score, nearest_neighbours*,
+ *        transform_source and get_points are unchanged, over the whole cloud; apdgicp_get_correspondences / _get_mahalanobis return
+ *        APDGICP_ERR_UNSUPPORTED.
+ * Deviations from the reference, all of them: (a) fp64 in a written order where the reference is fp32 with float atomics (GV:107-113) and
+ * thrust::transform_reduce (CD:161-176) in no defined order; (b) q by V4 in fp64 (FC:55-60 casts to fp32); (c) the exact voxel set -- the
+ * reference's hash table may drop up to 1 % of the points (GV:276); (d) voxels in key order, indices stored point-major (the reference:
+ * offset-major, compacted, undefined order); (e) a Jacobi eigen-decomposition for Eigen's closed form; (f) NONE / NORMALIZED_MIN_EIG refused;
+ * (g) the resolution is the one that was set: a GaussianVoxelMap of the reference keeps the resolution it was first built with (VC:257-263),
+ * and computeTransformation overwrites the core's resolution with a member that setResolution never writes (VCI:41-43, 145) -- neither quirk
+ * is reproduced; (h) GPU_RBF_KERNEL is not offered. */
+typedef enum { APDGICP_VGICP_CUDA_DIRECT_RADIUS = 3 } apdgicp_vgicp_cuda_search;   /* beside APDGICP_VGICP_DIRECT1 / 7 / 27 = 0 / 1 / 2 */
+typedef enum { APDGICP_NN_CPU_PARALLEL_KDTREE = 0, APDGICP_NN_GPU_BRUTEFORCE = 1, APDGICP_NN_GPU_RBF_KERNEL = 2 } apdgicp_nn_method;   /* NearestNeighborMethod, cuda/fast_vgicp_cuda.cuh */
+typedef struct {
+  double resolution;         /* setResolution ; default 1.0, VCI:24 ; finite and > 0 */
+  int32_t neighbor_search;   /* 0 / 1 / 2 = DIRECT1 / 7 / 27, 3 = DIRECT_RADIUS ; default DIRECT1, VC:28 */
+  double search_radius;      /* DIRECT_RADIUS only, in voxels ; default 1.5, VC:29 ; finite, 0 <= r <= 4 */
+  int32_t regularization;    /* apdgicp_regularization ; default PLANE, VCI:26 */
+  int32_t nn_method;         /* apdgicp_nn_method ; default CPU_PARALLEL_KDTREE, VCI:27 */
+} apdgicp_vgicp_cuda_params;
+void apdgicp_vgicp_cuda_default_params(apdgicp_vgicp_cuda_params* p);
+/* p != NULL: the mode on with these parameters (checked first: a refused setting changes nothing); NULL: mode off */
+int apdgicp_set_vgicp_cuda(apdgicp_handle* h, const apdgicp_vgicp_cuda_params* p);
+int apdgicp_get_vgicp_cuda(const apdgicp_handle* h, apdgicp_vgicp_cuda_params* p, int* enabled);   /* either output may be NULL */
+/* VC6: the offset list of p, n x 3 int32 in offset order.  Needs no handle and no device.  *n = the number of offsets; out_n3 may be NULL
+ * (it holds up to 257 x 3 values). */
+int apdgicp_vgicp_cuda_offsets(const apdgicp_vgicp_cuda_params* p, int32_t* out_n3, int64_t* n);
+/* VC4: the kept list of cloud `which` (prepared if it is not): *n_kept, and kept_index (may be NULL; capacity >= n_kept otherwise) */
+int apdgicp_vgicp_cuda_kept(apdgicp_handle* h, int which, int64_t* n_kept, int32_t* kept_index, int64_t capacity);
+/* VC2 / VC3 per KEPT point of cloud `which`, host memory, either may be NULL: raw (n_kept x 6: xx, xy, xz, yy, yz, zz) and regularised
+ * (n_kept x 9); capacity >= n_kept */
+int apdgicp_vgicp_cuda_get_covariances(apdgicp_handle* h, int which, double* raw_n6, double* reg_n9, int64_t capacity);
+/* as apdgicp_vgicp_voxel_count / _get_voxels / _get_correspondences / _build_count; correspondences: n_kept(source) x n_offsets */
+int apdgicp_vgicp_cuda_voxel_count(apdgicp_handle* h, int64_t* n_voxels);
+int apdgicp_vgicp_cuda_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9);
+int apdgicp_vgicp_cuda_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_kept_source);
+int apdgicp_vgicp_cuda_build_count(apdgicp_handle* h, int64_t* n_builds);
 
 /* ------------------------------------------------------------------ NDT (P2D / D2D) as a mode of the handle
  * fast_gicp::NDTCuda, the NDT the reference tree holds (the factory's own NDT_OMP fallback, registrations.cpp:101-134, is pclomp, whose

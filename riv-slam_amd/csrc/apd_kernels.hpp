@@ -1887,11 +1887,16 @@ __device__ __forceinline__ unsigned long long group_or_u64(unsigned long long v)
 // The rank-ordered keys of the merge carry the fp32 squared distance in their high word, so both come out of the rounds themselves.
 //   KNN_EPI_NORMALZ  stat_out[original index] = (float)(|u_z| / |u|), u = the eigenvector of the smallest eigenvalue (sym3_eig) of the
 //                    unregularised covariance KNN_EPI_COV forms: the verticality of the point's surface normal (apd_floor.hpp).
-constexpr int KNN_EPI_COV = 0, KNN_EPI_MEANDIST = 1, KNN_EPI_KTH = 2, KNN_EPI_NORMALZ = 3;
+//   KNN_EPI_RAWSUM   raw_out[6 * original index ..] = the covariance of covariance_estimation.cu:26-34 (VC2 of include/apdgicp_hip.h): S1 = sum p,
+//                    S2 = sum p p^T over the k neighbours IN RANK ORDER by one lane, fp64 sums started at 0, every product rounded before it is
+//                    added, mean = S1 / k, C_rc = S2_rc / k - mean_r mean_c -- absolute coordinates, not relative to the query as KNN_EPI_COV.
+//                    c.cov is neither read nor written.
+constexpr int KNN_EPI_COV = 0, KNN_EPI_MEANDIST = 1, KNN_EPI_KTH = 2, KNN_EPI_NORMALZ = 3, KNN_EPI_RAWSUM = 4;
 template <int L, int EPI = KNN_EPI_COV>
 __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned bx, int lane, unsigned long long* knn_smem, int k, int reg, int* err_flag,
                                                   unsigned long long* stats, int raw /* 1: store the population covariance, k_regularize_covs follows */,
-                                                  float* stat_out = nullptr /* EPI != KNN_EPI_COV: one float per point, original index order */) {
+                                                  float* stat_out = nullptr /* EPI 1 .. 3: one float per point, original index order */,
+                                                  double* raw_out = nullptr /* KNN_EPI_RAWSUM: xx, xy, xz, yy, yz, zz per point, original index order */) {
   constexpr int QPW = 64 / L, NCL = KNN_NC / L, KQ_CAP = knn_coop_cap(L), KQ_STRIDE = KQ_CAP + 1, EPL = KQ_CAP / L;  // queries per wave, classes and list entries per lane
   static_assert(L == 4 || L == 8 || L == 16, "L lanes per query");
   static_assert(KQ_CAP % L == 0 && KQ_CAP <= 64 && KQ_WIN % KNN_NC == 0, "layout");
@@ -2329,7 +2334,7 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
             atomicExch(err_flag, 2);
             bk = (unsigned long long)(unsigned)i;  // keeps the gathers in range
           }
-          if constexpr (EPI == KNN_EPI_COV || EPI == KNN_EPI_NORMALZ) {
+          if constexpr (EPI == KNN_EPI_COV || EPI == KNN_EPI_NORMALZ || EPI == KNN_EPI_RAWSUM) {
             if (sub == u) mysel[t] = (int)(unsigned)bk;
           } else if constexpr (EPI == KNN_EPI_MEANDIST) {  // (every lane of the query adds the same numbers in the same order)
             if (t * L + u >= 1) stat_sum += (double)sqrtf(__uint_as_float((unsigned)(bk >> 32)));
@@ -2369,6 +2374,21 @@ __device__ __forceinline__ void knn_cov_coop_wave(const CloudDesc& c, unsigned b
     if (r < k) nbl[3 * r] = nbv[t].x, nbl[3 * r + 1] = nbv[t].y, nbl[3 * r + 2] = nbv[t].z;
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if constexpr (EPI == KNN_EPI_RAWSUM) {  // one lane per query walks the ranks: the written order IS the order
+    if (sub != 0 || !valid) return;
+    double s1x = 0.0, s1y = 0.0, s1z = 0.0, sxx = 0.0, sxy = 0.0, sxz = 0.0, syy = 0.0, syz = 0.0, szz = 0.0;
+    for (int r = 0; r < k; r++) {
+      const double x = (double)nbl[3 * r], y = (double)nbl[3 * r + 1], z = (double)nbl[3 * r + 2];
+      s1x += x, s1y += y, s1z += z;
+      sxx += x * x, sxy += x * y, sxz += x * z, syy += y * y, syz += y * z, szz += z * z;
+    }
+    const double fk = (double)k;
+    const double mx = s1x / fk, my = s1y / fk, mz = s1z / fk;
+    double* o = raw_out + 6 * (size_t)G(c.perm)[i];
+    o[0] = sxx / fk - mx * mx, o[1] = sxy / fk - mx * my, o[2] = sxz / fk - mx * mz;
+    o[3] = syy / fk - my * my, o[4] = syz / fk - my * mz, o[5] = szz / fk - mz * mz;
+    return;
+  }
   // moments (Mom9): lanes 0..3 of the query take one partial sum each, two quad butterflies add them up in the common order
   // (the operands of an addition swap between partner lanes: the same bits)
   Mom9 mp;

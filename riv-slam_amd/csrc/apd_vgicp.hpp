@@ -148,22 +148,38 @@ __device__ __forceinline__ void vg_block_sums(double* acc, double* red /* [VG_BL
   }
 }
 
+// Where the offsets of a linearize come from.  REACH: the largest |component| an offset can have.
+struct VgModeOffsets {  // V5: DIRECT1 / 7 / 27, computed from k
+  static constexpr int REACH = 1;
+  int mode;
+  __device__ __forceinline__ void get(int k, int& ox, int& oy, int& oz) const { vg_offset(mode, k, ox, oy, oz); }
+};
+struct VgTableOffsets {  // VC6 (apd_vgicp_cuda.hpp): a table of 3 ints per offset in device memory, read at a wave-uniform index
+  static constexpr int REACH = 4;
+  const int* tab;
+  __device__ __forceinline__ void get(int k, int& ox, int& oy, int& oz) const { ox = tab[3 * k], oy = tab[3 * k + 1], oz = tab[3 * k + 2]; }
+};
+
 // V4 / V5: source point i of a linearize at pose T -- its noff voxel indices to corr, its terms onto the 29 sums `acc`.  The one per-point body of
-// k_vg_linearize and of the batch tick (apd_vgicp_batch.hpp): the same operations in the same written order wherever it is called from.
-__device__ __forceinline__ void vg_linearize_point(const float4* opts, const double* cov_src, const int* inv_src, int n, const VgMap& map, const Rigid& T, double res,
-                                                   int mode, int noff, int want_Hb, int* corr, int i, double* acc) {
+// k_vg_linearize, of the batch tick (apd_vgicp_batch.hpp) and of k_vc_linearize (apd_vgicp_cuda.hpp): the same operations in the same written
+// order wherever it is called from.
+template <class Offsets>
+__device__ __forceinline__ void vg_linearize_point_of(const float4* opts, const double* cov_src, const int* inv_src, int n, const VgMap& map, const Rigid& T, double res,
+                                                      const Offsets& offs, int noff, int want_Hb, int* corr, int i, double* acc) {
   const float4 p = opts[i];
   const double x = (double)p.x, y = (double)p.y, z = (double)p.z;
   const double vx = vg_xf_row(T, 0, x, y, z), vy = vg_xf_row(T, 1, x, y, z), vz = vg_xf_row(T, 2, x, y, z);
   const double cx = vg_coord(vx, res), cy = vg_coord(vy, res), cz = vg_coord(vz, res);
-  // a coordinate this far out cannot come back into range with an offset of one; also catches a q that is not finite
-  const bool inr = fabs(cx) <= (double)VG_LIM && fabs(cy) <= (double)VG_LIM && fabs(cz) <= (double)VG_LIM;
+  // A coordinate c with |c| > 2^20 + REACH - 1 cannot come back into range (|c + o| < 2^20) with any offset, |o| <= REACH: such a point
+  // misses everything, and so does a q that is not finite.  Inside that bound c + o is exact in an int, and the test per offset below is V2's.
+  // (REACH = 1: the bound is 2^20 itself.)
+  const bool inr = fabs(cx) <= (double)(VG_LIM + Offsets::REACH - 1) && fabs(cy) <= (double)(VG_LIM + Offsets::REACH - 1) && fabs(cz) <= (double)(VG_LIM + Offsets::REACH - 1);
   const int ix = inr ? (int)cx : 0, iy = inr ? (int)cy : 0, iz = inr ? (int)cz : 0;
   Sym3 RCA{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool have_rca = false;
   for (int k = 0; k < noff; k++) {
     int ox, oy, oz;
-    vg_offset(mode, k, ox, oy, oz);
+    offs.get(k, ox, oy, oz);
     const int ax = ix + ox, ay = iy + oy, az = iz + oz;
     int v = -1;
     if (inr && abs(ax) < VG_LIM && abs(ay) < VG_LIM && abs(az) < VG_LIM) v = vg_find(map, vg_pack(ax, ay, az));  // V2: the range test comes first
@@ -216,6 +232,10 @@ __device__ __forceinline__ void vg_linearize_point(const float4* opts, const dou
     acc[25] += w * -mey;
     acc[26] += w * -mez;
   }
+}
+__device__ __forceinline__ void vg_linearize_point(const float4* opts, const double* cov_src, const int* inv_src, int n, const VgMap& map, const Rigid& T, double res,
+                                                   int mode, int noff, int want_Hb, int* corr, int i, double* acc) {
+  vg_linearize_point_of(opts, cov_src, inv_src, n, map, T, res, VgModeOffsets{mode}, noff, want_Hb, corr, i, acc);
 }
 
 // T2[0..12): the pose, row-major 3x4.  corr: n x noff voxel indices (-1: miss), written here.

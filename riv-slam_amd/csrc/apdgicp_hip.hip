@@ -15,6 +15,7 @@
 #include "apd_scan_context.hpp"
 #include "apd_vgicp.hpp"
 #include "apd_vgicp_batch.hpp"
+#include "apd_vgicp_cuda.hpp"
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
 #include "apd_icp.hpp"
@@ -139,6 +140,44 @@ struct VgState {
   VgMap map() const { return buf.map((int)n_vox); }
 };
 
+// apdgicp_set_vgicp_cuda: per cloud the prepared cloud (kept points, their covariances, their original indices), the voxel map of the
+// prepared target and the frozen state of the last linearize (include/apdgicp_hip.h, VC1 .. VC10).  The scratch of a map build is the
+// handle's (apdgicp_handle::sort).
+struct VcState {
+  struct Prepared {              // VC1 .. VC4 of one cloud: a pure function of (points, regularisation), cached by identity
+    bool ready = false;
+    uint64_t pts_gen = 0;        // apdgicp_handle::cloud_gen of the points it was made from
+    int reg = 0;
+    int64_t id = 0;              // which preparation this is (VcState::preps when it was made): names it for the map and the frozen state
+    int n = 0, n_kept = 0;
+    DevBuf raw, reg6, flag, bsum, kpts, kcov, kept, ident;  // raw / reg6 / flag: per point of the cloud; the rest per kept point
+  };
+  bool on = false;
+  apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
+  Prepared pc[2];                // [source, target]; swapped with the clouds
+  int64_t preps = 0;
+  bool map_built = false;        // the map: prepared target map_prep_id at map_res
+  int64_t map_prep_id = 0;
+  double map_res = 0.0;
+  int64_t n_vox = 0, builds = 0;
+  std::vector<int32_t> offs;     // VC6: the table behind d_offs (3 ints per offset), and what it was made from
+  int offs_search = -1;
+  double offs_radius = 0.0;
+  bool have_lin = false;         // corr / T_lin: a linearize of prepared source lin_src_id against map number lin_build
+  int64_t lin_src_id = 0, lin_build = 0;
+  int n_src_lin = 0, noff_lin = 0;
+  double T_lin[12];
+  double final_H[36];            // of the last align in this mode (identity until then), on the host like NdState's
+  VoxMapBufs buf;
+  CachedTable d_offs;
+  DevBuf scal, corr, part, T, out;
+  VgMap map() const { return buf.map((int)n_vox); }
+  VcState() { reset_final_H(); }
+  void reset_final_H() {
+    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
+  }
+};
+
 // apdgicp_set_ndt: the voxel maps of target and source and the frozen state of the last linearize (include/apdgicp_hip.h, N1 .. N9).  The
 // scratch of a map build is the handle's (apdgicp_handle::sort).
 struct NdState {
@@ -190,6 +229,7 @@ struct IcState {
 struct apdgicp_handle {
   Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
   VgState vg;   // (freed by its members' destructors, behind the wait of ~apdgicp_handle)
+  VcState vc;   // (likewise)
   NdState nd;   // (likewise)
   IcState ic;   // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two are exclusive
@@ -851,6 +891,207 @@ int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return host_loop(
       h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vg_linearize(h, T, H, b, y0, m); },
       [&](const double* T, double* yi) { return vg_error(h, T, yi); }, true);
+}
+
+// ---- FAST_VGICP_CUDA (include/apdgicp_hip.h VC1 .. VC10; kernels: apd_vgicp_cuda.hpp)
+int check_vgicp_cuda_params(const apdgicp_vgicp_cuda_params* p) {
+  if (!p) return 0;
+  if (!(p->resolution > 0.0) || !std::isfinite(p->resolution)) return fail(APDGICP_ERR_INVALID_ARG, "FAST_VGICP_CUDA: the resolution must be finite and positive");
+  if (p->neighbor_search < APDGICP_VGICP_DIRECT1 || p->neighbor_search > APDGICP_VGICP_CUDA_DIRECT_RADIUS)
+    return fail(APDGICP_ERR_INVALID_ARG, "FAST_VGICP_CUDA: unknown neighbour search method");
+  if (p->neighbor_search == APDGICP_VGICP_CUDA_DIRECT_RADIUS && !(std::isfinite(p->search_radius) && p->search_radius >= 0.0 && p->search_radius <= (double)VC_MAX_RADIUS))
+    return fail(APDGICP_ERR_INVALID_ARG, "FAST_VGICP_CUDA: the DIRECT_RADIUS radius must be finite with 0 <= r <= 4 (voxels)");
+  if (p->regularization == APDGICP_REG_NONE || p->regularization == APDGICP_REG_NORMALIZED_MIN_EIG)
+    return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA: NONE and NORMALIZED_MIN_EIG are unimplemented in the reference (it goes on with raw covariances) and not offered");
+  if (p->regularization != APDGICP_REG_MIN_EIG && p->regularization != APDGICP_REG_PLANE && p->regularization != APDGICP_REG_FROBENIUS)
+    return fail(APDGICP_ERR_INVALID_ARG, "FAST_VGICP_CUDA: unknown regularization method");
+  if (p->nn_method == APDGICP_NN_GPU_RBF_KERNEL) return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA: GPU_RBF_KERNEL covariances are not offered");
+  if (p->nn_method != APDGICP_NN_CPU_PARALLEL_KDTREE && p->nn_method != APDGICP_NN_GPU_BRUTEFORCE)
+    return fail(APDGICP_ERR_INVALID_ARG, "FAST_VGICP_CUDA: unknown nearest neighbour method");
+  return 0;
+}
+
+// VC6: the offsets of p (checked by the caller), 3 ints each
+void vc_offsets(const apdgicp_vgicp_cuda_params& p, std::vector<int32_t>& out) {
+  out.clear();
+  auto push = [&](int i, int j, int k) { out.push_back(i), out.push_back(j), out.push_back(k); };
+  if (p.neighbor_search == APDGICP_VGICP_DIRECT1) {
+    push(0, 0, 0);
+  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT7) {  // VC:55-64
+    push(0, 0, 0), push(1, 0, 0), push(-1, 0, 0), push(0, 1, 0), push(0, -1, 0), push(0, 0, 1), push(0, 0, -1);
+  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT27) {  // VC:66-75
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 3; k++) push(i - 1, j - 1, k - 1);
+  } else {  // VC:77-90
+    const int range = (int)std::ceil(p.search_radius);
+    for (int i = -range; i <= range; i++)
+      for (int j = -range; j <= range; j++)
+        for (int k = -range; k <= range; k++)
+          if (std::sqrt((double)(i * i + j * j + k * k)) <= p.search_radius + 1e-3) push(i, j, k);
+  }
+}
+
+// VC1 .. VC4: the prepared cloud `which`.  One wait: the kept count and the error flag come back together.
+int vc_prepare_cloud(apdgicp_handle* h, int which) {
+  Engine& e = h->eng;
+  VcState& v = h->vc;
+  if (e.clouds.size() < 2 || e.clouds[which].n <= 0) return fail(APDGICP_ERR_NO_INPUT, std::string(cloud_name(which)) + " cloud is not set");
+  VcState::Prepared& pc = v.pc[which];
+  if (pc.ready && pc.pts_gen == h->cloud_gen[which] && pc.reg == v.prm.regularization) return 0;
+  if (e.clouds[which].n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "cloud has fewer points than k_correspondences");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet)
+  const Engine::Cloud& c = e.clouds[which];
+  const int n = c.n, nb = (n + VC_BLK - 1) / VC_BLK;
+  pc.ready = false;
+  v.have_lin = false;
+  const size_t b48 = (size_t)n * 48, b16 = (size_t)n * 16, b4 = (size_t)n * 4;
+  if (b48 > pc.raw.cap || b48 > pc.reg6.cap || (size_t)n > pc.flag.cap || (size_t)nb * 4 > pc.bsum.cap || b16 > pc.kpts.cap || b48 > pc.kcov.cap || b4 > pc.kept.cap ||
+      b4 > pc.ident.cap || 32 > v.scal.cap)
+    APD_HIP(hipStreamSynchronize(e.stream));  // (a buffer about to be replaced may still be read)
+  APD_TRY(pc.raw.ensure(b48));
+  APD_TRY(pc.reg6.ensure(b48));
+  APD_TRY(pc.flag.ensure((size_t)n));
+  APD_TRY(pc.bsum.ensure((size_t)nb * 4));
+  APD_TRY(pc.kpts.ensure(b16));
+  APD_TRY(pc.kcov.ensure(b48));
+  APD_TRY(pc.kept.ensure(b4));
+  APD_TRY(pc.ident.ensure(b4));
+  APD_TRY(v.scal.ensure(32));  // ints: [0, 4) a map build, [4] n_kept of a preparation
+  APD_TRY(e.d_ids.upload(&which, sizeof(int), e.cstream));
+  const CloudDesc* desc = e.d_desc.as<CloudDesc>();
+  const int* ids = e.d_ids.as<int>();
+  int* eflag = e.d_errflag.as<int>();
+  unsigned long long* stats = e.d_stats.as<unsigned long long>();
+  double* raw = pc.raw.as<double>();
+  const int qpw = n >= 100000 ? 16 : n >= 40000 ? 8 : 4;  // (as Engine::launch_knn)
+  const dim3 grid((unsigned)((n + qpw - 1) / qpw), 1u);
+  if (qpw == 16) hipLaunchKernelGGL(k_vc_knn_raw<4>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
+  else if (qpw == 8) hipLaunchKernelGGL(k_vc_knn_raw<8>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
+  else hipLaunchKernelGGL(k_vc_knn_raw<16>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
+  int* d_total = v.scal.as<int>() + 4;
+  hipLaunchKernelGGL(k_vc_regularize, dim3(nb), dim3(VC_BLK), 0, e.stream, raw, n, (int)v.prm.regularization, pc.flag.as<unsigned char>(), pc.reg6.as<double>(), pc.bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, pc.bsum.as<int>(), nb, d_total);
+  hipLaunchKernelGGL(k_vc_scatter, dim3(nb), dim3(VC_BLK), 0, e.stream, c.opts.as<float4>(), pc.reg6.as<double>(), pc.flag.as<unsigned char>(), n, pc.bsum.as<int>(), d_total,
+                     pc.kpts.as<float4>(), pc.kcov.as<double>(), pc.kept.as<int>(), pc.ident.as<int>());
+  APD_HIP(hipGetLastError());
+  int* hw = e.h_probe.as<int>();
+  APD_HIP(hipMemcpyAsync(hw, d_total, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(hw + 1, eflag, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (hw[1]) {
+    const int flag = hw[1];
+    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+    return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA k-NN: " + Engine::errflag_text(flag));
+  }
+  if (hw[0] < 0 || hw[0] > n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept count");
+  pc.n = n, pc.n_kept = hw[0];
+  pc.pts_gen = h->cloud_gen[which], pc.reg = v.prm.regularization, pc.id = ++v.preps;
+  pc.ready = true;
+  return 0;
+}
+
+// VC5: the voxel map of the prepared target
+int vc_build_map(apdgicp_handle* h) {
+  Engine& e = h->eng;
+  VcState& v = h->vc;
+  APD_TRY(vc_prepare_cloud(h, kTgt));
+  const VcState::Prepared& t = v.pc[kTgt];
+  if (v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution) return 0;
+  v.map_built = v.have_lin = false;
+  int nv = 0;
+  if (t.n_kept > 0) {
+    const int n = t.n_kept;
+    APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
+    APD_TRY(h->sort.ensure(n));
+    VoxSorted s;
+    APD_TRY(enqueue_voxel_sort(e.stream, h->sort, t.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>(), &s));
+    APD_HIP(hipGetLastError());
+    int hs[4];
+    APD_HIP(hipMemcpyAsync(hs, v.scal.p, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    if (hs[0] != kVgBadNone) {  // VC4: the message names the point by its index in the caller's cloud
+      int orig = -1;
+      if (hs[0] >= 0 && hs[0] < n) APD_HIP(hipMemcpy(&orig, t.kept.as<int>() + hs[0], sizeof(int), hipMemcpyDeviceToHost));
+      return voxel_key_range_error("FAST_VGICP_CUDA: target point " + std::to_string(orig), v.prm.resolution);
+    }
+    if (hs[1] < 1 || hs[1] > n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent voxel count");
+    nv = hs[1];
+    APD_TRY(v.buf.ensure((size_t)nv, false));
+    hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, h->sort.bsum.as<int>(), t.kpts.as<float4>(), t.kcov.as<double>(), t.ident.as<int>(),
+                       v.buf.vkeys.as<unsigned long long>(), v.buf.vcount.as<int>(), v.buf.vmean.as<double>(), v.buf.vcov.as<double>(), nv);
+    APD_HIP(hipGetLastError());
+  }
+  v.n_vox = nv;
+  v.map_built = true, v.map_prep_id = t.id, v.map_res = v.prm.resolution;
+  v.builds++;
+  return 0;
+}
+
+// both prepared clouds, the map and the offset table: everything k_vc_linearize reads
+int vc_prepare(apdgicp_handle* h) {
+  VcState& v = h->vc;
+  APD_TRY(vc_prepare_cloud(h, kSrc));
+  APD_TRY(vc_build_map(h));
+  if (v.offs.empty() || v.offs_search != v.prm.neighbor_search || v.offs_radius != v.prm.search_radius) {
+    vc_offsets(v.prm, v.offs);
+    v.offs_search = v.prm.neighbor_search, v.offs_radius = v.prm.search_radius;
+  }
+  return v.d_offs.upload(v.offs.data(), v.offs.size() * sizeof(int32_t), h->eng.stream);
+}
+
+int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
+  APD_TRY(vc_prepare(h));
+  Engine& e = h->eng;
+  VcState& v = h->vc;
+  const VcState::Prepared& s = v.pc[kSrc];
+  const int n = s.n_kept, noff = (int)(v.offs.size() / 3), nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)n * noff * 4, (size_t)nblk * VG_RED * 8));
+  APD_TRY(v.T.ensure(24 * sizeof(double)));
+  APD_TRY(v.out.ensure(64 * sizeof(double)));
+  colmajor_to_rows12(T16, v.T_lin);
+  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  const int want = H && b ? 1 : 0;
+  if (nblk > 0)
+    hipLaunchKernelGGL(k_vc_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), v.T.as<double>(),
+                       v.prm.resolution, v.d_offs.as<int>(), noff, want, v.corr.as<int>(), v.part.as<double>());
+  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));  // (no kept source point: no block rows, every sum 0)
+  v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
+  v.lin_src_id = s.id, v.lin_build = v.builds;
+  return 0;
+}
+
+// VC8: the frozen state must still describe what the handle holds
+bool vc_frozen_ok(const apdgicp_handle* h) {
+  const VcState& v = h->vc;
+  const VcState::Prepared &s = v.pc[kSrc], &t = v.pc[kTgt];
+  return v.have_lin && s.ready && s.pts_gen == h->cloud_gen[kSrc] && s.reg == v.prm.regularization && s.id == v.lin_src_id && s.n_kept == v.n_src_lin && t.ready &&
+         t.pts_gen == h->cloud_gen[kTgt] && t.reg == v.prm.regularization && v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution && v.lin_build == v.builds;
+}
+
+int vc_error(apdgicp_handle* h, const double* T16, double* cost) {
+  Engine& e = h->eng;
+  VcState& v = h->vc;
+  if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds, regularisation and voxel map the handle holds now");
+  const VcState::Prepared& s = v.pc[kSrc];
+  const int n = s.n_kept, noff = v.noff_lin, nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_HIP(hipSetDevice(e.device));
+  double t24[24];
+  colmajor_to_rows12(T16, t24);
+  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
+  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  if (nblk > 0)
+    hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), v.T.as<double>(), noff,
+                       v.corr.as<int>(), v.part.as<double>());
+  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
+}
+
+int vc_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  APD_TRY(vc_prepare(h));
+  return host_loop(
+      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vc_linearize(h, T, H, b, y0, m); },
+      [&](const double* T, double* yi) { return vc_error(h, T, yi); }, true, h->vc.final_H);
 }
 
 // ---- NDT (include/apdgicp_hip.h N1 .. N9; kernels: apd_ndt.hpp)
@@ -1807,6 +2048,8 @@ int apdgicp_swap_source_and_target(apdgicp_handle* h) {
   std::swap(h->cloud_gen[kSrc], h->cloud_gen[kTgt]);
   std::swap(h->nd.maps[kSrc], h->nd.maps[kTgt]);  // NC:90-93: the NDT maps go with their clouds (tied to them by identity either way)
   h->nd.have_lin = false;
+  std::swap(h->vc.pc[kSrc], h->vc.pc[kTgt]);  // VC:97-107: the prepared clouds go with their clouds; the map is then another target's and is rebuilt
+  h->vc.have_lin = false;
   return 0;
 }
 
@@ -1860,6 +2103,7 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
     if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
     if (h->nd.on) return nd_linearize(h, T, H, b, cost, nullptr);
     if (h->vg.on) return vg_linearize(h, T, H, b, cost, nullptr);
+    if (h->vc.on) return vc_linearize(h, T, H, b, cost, nullptr);
     APD_TRY(ensure_pair(h));
     APD_TRY(h->eng.probe_linearize(T, H, b, cost, nullptr));
     h->have_corr = true;
@@ -1873,6 +2117,7 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
     if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
     if (h->nd.on) return nd_error(h, T, cost);
     if (h->vg.on) return vg_error(h, T, cost);
+    if (h->vc.on) return vc_error(h, T, cost);
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
     return h->eng.probe_error(T, cost);
   });
@@ -1884,6 +2129,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
     if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps its own correspondences: apdgicp_icp_get_correspondences");
     if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
+    if (h->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA has no point correspondences: apdgicp_vgicp_cuda_get_correspondences");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -1906,6 +2152,7 @@ int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
     if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps no per-point Mahalanobis matrices");
     if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT keeps no per-point Mahalanobis matrices");
     if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP keeps no per-point Mahalanobis matrices");
+    if (h->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA keeps no per-point Mahalanobis matrices");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -1933,6 +2180,7 @@ int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out)
     if (h->ic.on) return ic_align(h, guess, out);
     if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
+    if (h->vc.on) return vc_align(h, guess, out);
     float g[16];
     if (guess) memcpy(g, guess, sizeof(g));
     else identity16(g);
@@ -1969,6 +2217,7 @@ int apdgicp_align_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_re
     if (h->ic.on) return ic_align(h, guess, out);
     if (h->nd.on) return nd_align(h, guess, out);
     if (h->vg.on) return vg_align(h, guess, out);
+    if (h->vc.on) return vc_align(h, guess, out);
     APD_TRY(ensure_pair(h));
     Engine& e = h->eng;
     return host_loop(
@@ -2000,6 +2249,7 @@ int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
   v.on = true;
   h->nd.on = false;  // N9: the two modes are exclusive
   h->ic.on = false;  // IC9: likewise
+  h->vc.on = false;  // VC10: likewise
   return 0;
 }
 
@@ -2049,6 +2299,146 @@ int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------ FAST_VGICP_CUDA
+void apdgicp_vgicp_cuda_default_params(apdgicp_vgicp_cuda_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->resolution = 1.0;                                 // VCI:24
+  p->neighbor_search = APDGICP_VGICP_DIRECT1;          // VC:28
+  p->search_radius = 1.5;                              // (pygicp's default for DIRECT_RADIUS)
+  p->regularization = APDGICP_REG_PLANE;               // VCI:26
+  p->nn_method = APDGICP_NN_CPU_PARALLEL_KDTREE;       // VCI:27
+}
+
+int apdgicp_set_vgicp_cuda(apdgicp_handle* h, const apdgicp_vgicp_cuda_params* p) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  VcState& v = h->vc;
+  if (!p) {  // back to what apdgicp_params says: the APD kernels' correspondences are those of their own last linearize, if any was left
+    if (v.on) h->have_corr = false;
+    v.on = false;
+    return 0;
+  }
+  APD_TRY(check_vgicp_cuda_params(p));
+  const bool same_offsets = p->neighbor_search == v.prm.neighbor_search && (p->neighbor_search != APDGICP_VGICP_CUDA_DIRECT_RADIUS || p->search_radius == v.prm.search_radius);
+  if (!v.on || p->resolution != v.prm.resolution || p->regularization != v.prm.regularization || !same_offsets) v.have_lin = false;
+  if (!same_offsets) v.offs.clear();
+  if (!v.on) {
+    h->have_corr = false;
+    v.reset_final_H();
+  }
+  v.prm = *p;
+  v.on = true;
+  h->vg.on = false, h->nd.on = false, h->ic.on = false;  // VC10: the four modes are exclusive
+  return 0;
+}
+
+int apdgicp_get_vgicp_cuda(const apdgicp_handle* h, apdgicp_vgicp_cuda_params* p, int* enabled) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (p) *p = h->vc.prm;
+  if (enabled) *enabled = h->vc.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_vgicp_cuda_offsets(const apdgicp_vgicp_cuda_params* p, int32_t* out_n3, int64_t* n) {
+  return guarded([&]() -> int {
+    if (!p || !n) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(check_vgicp_cuda_params(p));
+    std::vector<int32_t> offs;
+    vc_offsets(*p, offs);
+    *n = (int64_t)(offs.size() / 3);
+    if (out_n3) memcpy(out_n3, offs.data(), offs.size() * sizeof(int32_t));
+    return 0;
+  });
+}
+
+static const char* const kVcOff = "FAST_VGICP_CUDA is off (apdgicp_set_vgicp_cuda)";
+
+int apdgicp_vgicp_cuda_kept(apdgicp_handle* h, int which, int64_t* n_kept, int32_t* kept_index, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h || !n_kept || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    APD_TRY(vc_prepare_cloud(h, which));
+    const VcState::Prepared& pc = h->vc.pc[which];
+    *n_kept = pc.n_kept;
+    if (!kept_index || pc.n_kept == 0) return 0;
+    if (capacity < pc.n_kept) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+    APD_HIP(hipMemcpyAsync(kept_index, pc.kept.p, (size_t)pc.n_kept * 4, hipMemcpyDeviceToHost, h->eng.stream));
+    APD_HIP(hipStreamSynchronize(h->eng.stream));
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_cuda_get_covariances(apdgicp_handle* h, int which, double* raw_n6, double* reg_n9, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!h || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    APD_TRY(vc_prepare_cloud(h, which));
+    const VcState::Prepared& pc = h->vc.pc[which];
+    const int64_t nk = pc.n_kept;
+    if (capacity < nk) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+    if (nk == 0) return 0;
+    hipStream_t st = h->eng.stream;
+    std::vector<double> all(raw_n6 ? (size_t)pc.n * 6 : 0), k6(reg_n9 ? (size_t)nk * 6 : 0);
+    std::vector<int> kept(raw_n6 ? (size_t)nk : 0);
+    if (raw_n6) {
+      APD_HIP(hipMemcpyAsync(all.data(), pc.raw.p, all.size() * 8, hipMemcpyDeviceToHost, st));
+      APD_HIP(hipMemcpyAsync(kept.data(), pc.kept.p, kept.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (reg_n9) APD_HIP(hipMemcpyAsync(k6.data(), pc.kcov.p, k6.size() * 8, hipMemcpyDeviceToHost, st));
+    APD_HIP(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < nk && raw_n6; j++) {
+      if (kept[j] < 0 || kept[j] >= pc.n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept index");
+      memcpy(raw_n6 + 6 * j, &all[6 * (size_t)kept[j]], 6 * sizeof(double));
+    }
+    for (int64_t j = 0; j < nk && reg_n9; j++) {  // kcov: [6][n_kept]
+      const double xx = k6[j], xy = k6[nk + j], xz = k6[2 * nk + j], yy = k6[3 * nk + j], yz = k6[4 * nk + j], zz = k6[5 * nk + j];
+      double* o = reg_n9 + 9 * j;
+      o[0] = xx, o[1] = xy, o[2] = xz, o[3] = xy, o[4] = yy, o[5] = yz, o[6] = xz, o[7] = yz, o[8] = zz;
+    }
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_cuda_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!h || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    APD_TRY(vc_build_map(h));
+    *n_voxels = h->vc.n_vox;
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_cuda_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    APD_TRY(vc_build_map(h));
+    if (h->vc.n_vox == 0) return 0;
+    return read_voxels(h->eng.stream, h->vc.buf, h->vc.n_vox, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
+  });
+}
+
+int apdgicp_vgicp_cuda_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_kept_source) {
+  return guarded([&]() -> int {
+    if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    VcState& v = h->vc;
+    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
+    if (n_kept_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_kept_source does not match the kept source size");
+    if (v.n_src_lin == 0) return 0;
+    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_kept_source * v.noff_lin * 4, hipMemcpyDeviceToHost, h->eng.stream));
+    APD_HIP(hipStreamSynchronize(h->eng.stream));
+    return 0;
+  });
+}
+
+int apdgicp_vgicp_cuda_build_count(apdgicp_handle* h, int64_t* n_builds) {
+  if (!h || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *n_builds = h->vc.builds;
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------ NDT
 void apdgicp_ndt_default_params(apdgicp_ndt_params* p) {
   if (!p) return;
@@ -2075,6 +2465,7 @@ int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
   v.on = true;
   h->vg.on = false;  // N9: the two modes are exclusive
   h->ic.on = false;  // IC9: likewise
+  h->vc.on = false;  // VC10: likewise
   return 0;
 }
 
@@ -2104,6 +2495,7 @@ int apdgicp_set_icp(apdgicp_handle* h, const apdgicp_icp_params* p) {
   v.on = true, v.have = false;
   v.state = APDGICP_ICP_NOT_CONVERGED;
   h->vg.on = false, h->nd.on = false;  // IC9: the three modes are exclusive
+  h->vc.on = false;                    // VC10: likewise
   return 0;
 }
 
@@ -2443,6 +2835,10 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
     if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
     if (h->nd.on) {  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
       memcpy(H, h->nd.final_H, 36 * sizeof(double));
+      return 0;
+    }
+    if (h->vc.on) {  // FAST_VGICP_CUDA: likewise
+      memcpy(H, h->vc.final_H, 36 * sizeof(double));
       return 0;
     }
     if (!h->pair_ready) {  // L:23: identity until the first accepted step

@@ -111,6 +111,9 @@ SYMBOLS = [
     "apdgicp_scan_context_detect", "apdgicp_scan_context_detect_batch", "apdgicp_scan_context_descriptors",
     "apdgicp_vgicp_default_params", "apdgicp_set_vgicp", "apdgicp_get_vgicp", "apdgicp_vgicp_voxel_count", "apdgicp_vgicp_get_voxels",
     "apdgicp_vgicp_get_correspondences", "apdgicp_vgicp_build_count",
+    "apdgicp_vgicp_cuda_default_params", "apdgicp_set_vgicp_cuda", "apdgicp_get_vgicp_cuda", "apdgicp_vgicp_cuda_offsets", "apdgicp_vgicp_cuda_kept",
+    "apdgicp_vgicp_cuda_get_covariances", "apdgicp_vgicp_cuda_voxel_count", "apdgicp_vgicp_cuda_get_voxels", "apdgicp_vgicp_cuda_get_correspondences",
+    "apdgicp_vgicp_cuda_build_count",
     "apdgicp_batch_set_vgicp", "apdgicp_batch_get_vgicp", "apdgicp_batch_vgicp_voxel_count", "apdgicp_batch_vgicp_get_voxels", "apdgicp_batch_vgicp_build_count",
     "apdgicp_ndt_default_params", "apdgicp_set_ndt", "apdgicp_get_ndt", "apdgicp_ndt_voxel_count", "apdgicp_ndt_get_voxels",
     "apdgicp_ndt_get_correspondences", "apdgicp_ndt_build_count",
@@ -298,6 +301,17 @@ def load_library(path: str | None = None):
     L.apdgicp_vgicp_get_voxels.argtypes = [vp, i64, vp, vp, vp, vp]
     L.apdgicp_vgicp_get_correspondences.argtypes = [vp, vp, i64]
     L.apdgicp_vgicp_build_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_vgicp_cuda_default_params.argtypes = [vp]
+    L.apdgicp_vgicp_cuda_default_params.restype = None
+    L.apdgicp_set_vgicp_cuda.argtypes = [vp, vp]
+    L.apdgicp_get_vgicp_cuda.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_vgicp_cuda_offsets.argtypes = [vp, vp, C.POINTER(i64)]
+    L.apdgicp_vgicp_cuda_kept.argtypes = [vp, i32, C.POINTER(i64), vp, i64]
+    L.apdgicp_vgicp_cuda_get_covariances.argtypes = [vp, i32, vp, vp, i64]
+    L.apdgicp_vgicp_cuda_voxel_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_vgicp_cuda_get_voxels.argtypes = [vp, i64, vp, vp, vp, vp]
+    L.apdgicp_vgicp_cuda_get_correspondences.argtypes = [vp, vp, i64]
+    L.apdgicp_vgicp_cuda_build_count.argtypes = [vp, C.POINTER(i64)]
     L.apdgicp_batch_set_vgicp.argtypes = [vp, vp]
     L.apdgicp_batch_get_vgicp.argtypes = [vp, vp, C.POINTER(i32)]
     L.apdgicp_batch_vgicp_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
