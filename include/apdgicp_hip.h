@@ -50,7 +50,8 @@ extern "C" {
                                       still 6 (additive): + the apdgicp_scan_ingest_* object (power gate and packing of a radar message, IMU deskew, frame transform);
                                       still 6 (additive): + apdgicp_set_icp / _get_icp and the apdgicp_icp_* calls (point-to-point ICP as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_icp / _get_icp and the apdgicp_batch_icp_* calls (point-to-point ICP as a mode of the batch handle);
-                                      still 6 (additive): + apdgicp_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the registration handle) */
+                                      still 6 (additive): + apdgicp_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the registration handle);
+                                      still 6 (additive): + apdgicp_batch_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_batch_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the batch handle) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -415,6 +416,37 @@ int apdgicp_vgicp_build_count(apdgicp_handle* h, int64_t* n_builds);
  *        host-driven loop over them as in the FAST_VGICP mode (trace, final Hessian, apdgicp_result).  fitness_score, nearest_neighbours*,
  *        transform_source and get_points are unchanged, over the whole cloud; apdgicp_get_correspondences / _get_mahalanobis return
  *        APDGICP_ERR_UNSUPPORTED.
+ *
+ * Batch handles have the same mode (apdgicp_batch_set_vgicp_cuda, declared with the batch calls below; kernels:
+ * riv-slam_amd/csrc/apd_vgicp_cuda_batch.hpp), with the optimiser loop on the device:
+ *   VC11. Prepared clouds per slot.  Every slot named by a pair of the batch, as source or as target, gets the prepared cloud of VC1 .. VC4:
+ *        kept list, raw and regularised covariances and kept points are bit-equal to what the single handle prepares from the same points
+ *        (the same device functions under kernels that carry the slot in the grid).  It is cached per slot by the identity of the slot's
+ *        points and the regularisation: rebuilt when the slot is set again, the regularisation changes, or apdgicp_batch_clear ran.  The
+ *        covariances of apdgicp_batch_compute_covariances / _set_covariances are neither read nor written and an align does not ask for
+ *        them, so a cloud of 20 .. k_correspondences - 1 points aligns.  Preparing all uncached slots of a batch costs ONE host wait: the
+ *        launches of all slots are enqueued with no wait in between, every slot's kept count comes back in one copy and the k-NN error
+ *        flag in another, and the buffers behind the compaction are sized for n kept points.  (A slot whose buffers exist and are too
+ *        small for its new cloud costs one more wait, before they are replaced.)  A slot of fewer than 20 points named by a pair fails the
+ *        align with APDGICP_ERR_TOO_FEW_POINTS, the message naming the slot; no pair has run and the handle stays usable.
+ *   VC12. Maps per target slot.  VC5 over the kept points of every slot named as target_cloud, by the builder of V8: at most one more wait
+ *        per batch, none when every map is current.  A map is cached by its preparation's identity and the resolution and is bit-equal to
+ *        the single handle's.  A target slot without a kept point gets an empty map without a sort.  A kept target point that V2 refuses
+ *        fails the align with APDGICP_ERR_INVALID_ARG, the message naming the slot and the point by its index in the caller's cloud; no
+ *        pair has run and the handle stays usable.
+ *   VC13. The per-point arithmetic is that of VC6 .. VC8 through the same device functions: one kept source point per lane in the caller's
+ *        order in blocks of 256, every search (DIRECT1 / 7 / 27 too) through the offset table, the block rows added in block order starting
+ *        from 0.0.  Hence H, b, cost and n_matched of a pair's FIRST linearize equal apdgicp_linearize of a single handle in this mode at the
+ *        same guess, bit for bit.
+ *   VC14. Optimiser: V10 as it stands, the frozen indices n_kept x n_offsets per pair (pairs x max n_kept x n_offsets int32 in one buffer,
+ *        its size computed in size_t; an allocation that fails comes back as APDGICP_ERR_HIP), and V7 / VC9: a pair with no kept point on
+ *        either side ends at its first linearize with n_matched = 0, n_linearize = 1, T = the guess.
+ *   VC15. A pair's record is a pure function of the pair, as V11.
+ *   VC16. Ticks and mode rules.  One tick is two launches, ticks go out in chunks of 4, one pinned word is looked at between chunks (V12).
+ *        apdgicp_batch_set_vgicp_cuda is exclusive with apdgicp_batch_set_vgicp, _set_ndt and _set_icp in both directions: switching one
+ *        on switches the others off.  With the mode on apdgicp_batch_align_enqueue / _collect / _pump return APDGICP_ERR_UNSUPPORTED and
+ *        apdgicp_batch_is_pooled returns 0; apdgicp_batch_fitness and the cloud calls are unchanged, over the whole clouds.  With the mode
+ *        off a batch handle does exactly what one that never had it on does.  The sharded path and the pair pool do not run this mode.
  * Deviations from the reference, all of them: (a) fp64 in a written order where the reference is fp32 with float atomics (GV:107-113) and
  * thrust::transform_reduce (CD:161-176) in no defined order; (b) q by V4 in fp64 (FC:55-60 casts to fp32); (c) the exact voxel set -- the
  * reference's hash table may drop up to 1 % of the points (GV:276); (d) voxels in key order, indices stored point-major (the reference:
@@ -806,6 +838,32 @@ int apdgicp_batch_icp_get_working_cloud(apdgicp_batch* b, int64_t pair, float* x
 int apdgicp_batch_icp_get_trace(apdgicp_batch* b, int64_t pair, int64_t capacity, float* T_k16, int64_t* n_corr, double* mse, int32_t* similar, int64_t* n_iterations);
 /* Debug: launches, host waits and ticks of the last align in this mode (tests/measure/bench_icp_batch.py); any output may be NULL */
 int apdgicp_batch_icp_debug_counts(apdgicp_batch* b, int64_t* launches, int64_t* waits, int64_t* ticks);
+/* FAST_VGICP_CUDA as a mode of the batch handle: VC11 .. VC16 above.  p != NULL: the mode on with these parameters (batch voxelized GICP, NDT
+ * and ICP off); NULL: mode off.  The parameters are checked before the handle, with the single handle's error codes.  Prepared clouds and maps
+ * built so far are kept across off / on. */
+int apdgicp_batch_set_vgicp_cuda(apdgicp_batch* b, const apdgicp_vgicp_cuda_params* p);
+int apdgicp_batch_get_vgicp_cuda(const apdgicp_batch* b, apdgicp_vgicp_cuda_params* p, int* enabled);   /* either output may be NULL */
+/* The four getters below need the mode on and slot `cloud` only; they prepare the slot (and build its map) when it is not current.
+ * VC4: the kept list of the slot, as apdgicp_vgicp_cuda_kept */
+int apdgicp_batch_vgicp_cuda_kept(apdgicp_batch* b, int32_t cloud, int64_t* n_kept, int32_t* kept_index, int64_t capacity);
+/* VC2 / VC3 per kept point of the slot, as apdgicp_vgicp_cuda_get_covariances */
+int apdgicp_batch_vgicp_cuda_get_covariances(apdgicp_batch* b, int32_t cloud, double* raw_n6, double* reg_n9, int64_t capacity);
+/* the map over the slot's kept points, as apdgicp_vgicp_cuda_voxel_count / _get_voxels */
+int apdgicp_batch_vgicp_cuda_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels);
+int apdgicp_batch_vgicp_cuda_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9);
+/* the frozen indices of pair `pair`'s last linearize in the last align in this mode: n_kept(source) x n_offsets, point-major, -1 = miss.
+ * APDGICP_ERR_NO_INPUT before any such align, or once a cloud slot or the mode has been set since.  voxel_index = NULL: nothing is copied and
+ * the return value is the pair's n_kept(source). */
+int apdgicp_batch_vgicp_cuda_get_correspondences(apdgicp_batch* b, int64_t pair, int32_t* voxel_index, int64_t n_kept_source);
+/* Debug: how many clouds this handle has prepared and how many maps it has built in this mode, all slots together; either may be NULL */
+int apdgicp_batch_vgicp_cuda_build_count(apdgicp_batch* b, int64_t* n_prepared, int64_t* n_maps);
+/* Debug: host waits this handle has spent preparing clouds and building maps since it was created, and the ticks of the last align; any
+ * output may be NULL (the tests of VC11 / VC12 and tests/measure/bench_vgicp_cuda_batch.py read them) */
+int apdgicp_batch_vgicp_cuda_debug_counts(apdgicp_batch* b, int64_t* prepare_waits, int64_t* map_waits, int64_t* ticks);
+/* Measurement: preparation, map builds and ticks of the last align in this mode, in ms by the host clock.  Meaningful with
+ * apdgicp_batch_set_profiling on, which puts one more wait in front of the preparation (the cloud sorts end there); the other boundaries are
+ * behind waits the align makes anyway. */
+int apdgicp_batch_vgicp_cuda_last_phases(apdgicp_batch* b, double ms[3]);
 int apdgicp_batch_debug_stats(apdgicp_batch* b, unsigned long long out[16]);
 /* APDGICP_STATS=2 and a library built with -DAPD_BLOCK_TIMELINE (a diagnostics variant: tools/build_variant.py) only: {start, end} (100 MHz wall-clock ticks) and the index of every block of the LAST one-pair dense search launch
  * (k_nn_pruned), three words per block, up to 8192 blocks; reading resets.  For tools/c5_blocks.py: where the time of a 100k x 500k

@@ -59,6 +59,10 @@ class LoopVerifierHip {
   /// record byte-equal to IterativeClosestPointHip's for the same candidate; switches voxelized GICP and NDT off, as they switch this off;
   /// nullptr or enable = 0: back to APD-GICP / plain GICP as the parameters say
   int setICP(const apdgicp_icp_params* p) { return batch_ ? apdgicp_batch_set_icp(batch_, p) : APDGICP_ERR_HIP; }
+  /// registration_method = FAST_VGICP_CUDA: the candidates are registered with fast_gicp::FastVGICPCuda's algorithm (apdgicp_batch_set_vgicp_cuda,
+  /// VC11 .. VC16 of the C header): k = 20, PLANE removes line-like points from both clouds, DIRECT1 / 7 / 27 / DIRECT_RADIUS; switches voxelized
+  /// GICP, NDT and ICP off, as they switch this off; nullptr: back to APD-GICP / plain GICP as the parameters say
+  int setVGICPCuda(const apdgicp_vgicp_cuda_params* p) { return batch_ ? apdgicp_batch_set_vgicp_cuda(batch_, p) : APDGICP_ERR_HIP; }
 
   /// guesses: n_candidates x 16 floats, column-major ((new_keyframe_estimate^-1 * candidate_estimate) with guess(2,3) = 0,
   /// loop_detector.cpp:405-411), or nullptr for the identity (:225).  Returns 0 or a negative apdgicp_status.

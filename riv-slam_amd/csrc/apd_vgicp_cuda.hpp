@@ -40,9 +40,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(APD_KNN_WPE,
   knn_cov_coop_wave<L, KNN_EPI_RAWSUM>(c, bx, (int)threadIdx.x, knn_smem, k, 0, err_flag, stats, 0, nullptr, raw_out);
 }
 
-// VC3: raw[6 i ..] -> flag[i], reg[6 i ..] (both in the caller's order), bsum[block] = kept points of the block
-__global__ __launch_bounds__(VC_BLK) void k_vc_regularize(const double* raw, int n, int method, unsigned char* flag, double* reg, int* bsum) {
-  __shared__ int wsum[VC_BLK / 64];
+// VC3: raw[6 i ..] -> flag[i], reg[6 i ..] (both in the caller's order), bsum[block] = kept points of the block.  The body of one block, shared
+// with the slot-indexed form of apd_vgicp_cuda_batch.hpp.
+__device__ __forceinline__ void vc_regularize_block(const double* raw, int n, int method, unsigned char* flag, double* reg, int* bsum, int* wsum) {
   const int i = blockIdx.x * VC_BLK + threadIdx.x;
   bool keep = false;
   if (i < n) {
@@ -64,12 +64,15 @@ __global__ __launch_bounds__(VC_BLK) void k_vc_regularize(const double* raw, int
   }
   ego_block_counts(keep, wsum, bsum);
 }
+__global__ __launch_bounds__(VC_BLK) void k_vc_regularize(const double* raw, int n, int method, unsigned char* flag, double* reg, int* bsum) {
+  __shared__ int wsum[VC_BLK / 64];
+  vc_regularize_block(raw, n, method, flag, reg, bsum, wsum);
+}
 
 // VC4: bsum scanned by k_scan_bsum, *total = n_kept.  kcov: [6][n_kept] like the engine's covariances, so that k_vg_voxels and the
 // linearize read it as they read those; ident[j] = j stands where those kernels expect the original-index -> curve-position table.
-__global__ __launch_bounds__(VC_BLK) void k_vc_scatter(const float4* opts, const double* reg, const unsigned char* flag, int n, const int* bsum, const int* total,
-                                                       float4* kpts, double* kcov, int* kept_index, int* ident) {
-  __shared__ int wsum[VC_BLK / 64];
+__device__ __forceinline__ void vc_scatter_block(const float4* opts, const double* reg, const unsigned char* flag, int n, const int* bsum, const int* total, float4* kpts,
+                                                 double* kcov, int* kept_index, int* ident, int* wsum) {
   const int i = blockIdx.x * VC_BLK + threadIdx.x;
   const bool ok = i < n && flag[i];
   const int slot = ego_block_slot(ok, wsum, bsum[blockIdx.x]);
@@ -81,6 +84,11 @@ __global__ __launch_bounds__(VC_BLK) void k_vc_scatter(const float4* opts, const
   for (int q = 0; q < 6; q++) kcov[(size_t)q * nk + slot] = r[q];
   kept_index[slot] = i;
   ident[slot] = slot;
+}
+__global__ __launch_bounds__(VC_BLK) void k_vc_scatter(const float4* opts, const double* reg, const unsigned char* flag, int n, const int* bsum, const int* total,
+                                                       float4* kpts, double* kcov, int* kept_index, int* ident) {
+  __shared__ int wsum[VC_BLK / 64];
+  vc_scatter_block(opts, reg, flag, n, bsum, total, kpts, kcov, kept_index, ident, wsum);
 }
 
 // VC6 / VC7: as k_vg_linearize, the offsets from a table of noff x 3 ints

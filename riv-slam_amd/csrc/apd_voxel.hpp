@@ -165,9 +165,9 @@ __global__ __launch_bounds__(SCAN_BLK) void k_vox_heads(const unsigned long long
   }
   if (tid == 0) bsum[blockIdx.x] = total;
 }
-// exclusive scan of up to SCAN_BLK * 16 block sums in one block; out_total = number of voxels
-__global__ __launch_bounds__(SCAN_BLK) void k_scan_bsum(int* bsum, int nb, int* out_total) {
-  __shared__ int lds[SCAN_BLK / 64];
+// exclusive scan of up to SCAN_BLK * 16 block sums in one block; out_total = number of voxels.  (The body: also behind the slot-indexed scan of
+// apd_vgicp_cuda_batch.hpp.)
+__device__ __forceinline__ void scan_bsum_block(int* bsum, int nb, int* out_total, int* lds) {
   const int tid = threadIdx.x;
   int carry = 0;
   for (int b0 = 0; b0 < nb; b0 += SCAN_BLK) {
@@ -179,6 +179,10 @@ __global__ __launch_bounds__(SCAN_BLK) void k_scan_bsum(int* bsum, int nb, int* 
     carry += total;
   }
   if (tid == 0) *out_total = carry;
+}
+__global__ __launch_bounds__(SCAN_BLK) void k_scan_bsum(int* bsum, int nb, int* out_total) {
+  __shared__ int lds[SCAN_BLK / 64];
+  scan_bsum_block(bsum, nb, out_total, lds);
 }
 
 // CentroidPoint<PointXYZI>: float sums of x, y, z, intensity over the voxel, then / n

@@ -1,6 +1,7 @@
 // libapdgicp_hip.so -- the C ABI declared in include/apdgicp_hip.h, on top of apd::Engine.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -shared -fPIC (see build.py)
 #include <cstddef>
+#include <functional>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -16,6 +17,7 @@
 #include "apd_vgicp.hpp"
 #include "apd_vgicp_batch.hpp"
 #include "apd_vgicp_cuda.hpp"
+#include "apd_vgicp_cuda_batch.hpp"
 #include "apd_ndt.hpp"
 #include "apd_ndt_batch.hpp"
 #include "apd_icp.hpp"
@@ -321,6 +323,52 @@ struct IcbState {
   }
 };
 
+// apdgicp_batch_set_vgicp_cuda (include/apdgicp_hip.h, VC11 .. VC16): per cloud slot the prepared cloud of VC1 .. VC4 and, for targets, the voxel
+// map of its kept points, both cached by identity like VcState's; per align the pair table, the frozen indices and the block rows.  Scratch and
+// device-loop state: the handle's, as for VgbState.
+struct VcbState {
+  struct Slot {
+    bool ready = false;        // the prepared cloud: points pts_gen, regularisation reg
+    uint64_t pts_gen = 0;
+    int reg = 0;
+    int64_t id = 0;            // which preparation this is (VcbState::preps when it was made): names it for the map
+    int n = 0, n_kept = 0;
+    DevBuf raw, reg6, flag, bsum, kpts, kcov, kept, ident;  // raw / reg6 / flag: per point of the cloud; the rest sized for n kept points
+    bool map_built = false;    // the map: preparation map_prep_id at map_res
+    int64_t map_prep_id = 0;
+    double map_res = 0.0;
+    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
+    VoxMapBufs buf;            // sized for nv <= n
+  };
+  bool on = false;
+  apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
+  std::vector<Slot> slots;
+  int64_t preps = 0, builds = 0;
+  int64_t prep_waits = 0, map_waits = 0;  // host waits spent preparing clouds / building maps since the handle was created
+  double phase_ms[3] = {0, 0, 0};         // of the last align: preparation, map builds, ticks by the host clock (meaningful with profiling on)
+  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
+  int scal_slots = 0;
+  DevBuf nk;                   // per slot: the kept count of its preparation
+  int nk_slots = 0;
+  std::vector<int32_t> offs;   // VC6: the table behind d_offs (3 ints per offset), and what it was made from
+  int offs_search = -1;
+  double offs_radius = 0.0;
+  // what apdgicp_batch_vgicp_cuda_get_correspondences may read: the last align in this mode, while no cloud slot has been written since
+  bool have = false;
+  uint64_t have_epoch = 0;
+  std::vector<int> have_nk;    // per pair of that align: kept source points
+  size_t have_stride = 0;
+  int have_noff = 0;
+  DevBuf corr, part;
+  CachedTable pairs, prep_tab, prep_ids, d_offs;
+  void release() {  // apdgicp_batch_clear: the prepared clouds and the maps go with the clouds
+    slots.clear();
+    have = false;
+    scal.release(), nk.release(), corr.release(), part.release(), pairs.dev.release(), prep_tab.dev.release(), prep_ids.dev.release();
+    scal_slots = nk_slots = 0;
+  }
+};
+
 // The device optimiser loop of a batch handle (V12 / N15 / IC15), whichever mode runs it: the done counter the step kernels count into, the
 // pinned words the host reads, the events of the last two chunks.
 struct DeviceLoop {
@@ -347,6 +395,7 @@ struct apdgicp_batch {
   VgbState vg;  // (freed by its members' destructors, behind the wait of ~apdgicp_batch)
   NdbState nd;  // (likewise)
   IcbState ic;  // (likewise)
+  VcbState vc;  // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two never run together
   DeviceLoop loop;      // (likewise; its events by its own destructor)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
@@ -354,6 +403,7 @@ struct apdgicp_batch {
     vg.release();
     nd.release();
     ic.release();
+    vc.release();
     sort = VoxSortScratch{};
     loop.release();
   }
@@ -1391,7 +1441,7 @@ int device_loop_ensure_words(apdgicp_batch* b, size_t ints) {
 // built(t, nv); prefix: "voxelized GICP: " / "NDT: ".  errflag (voxelized GICP): the covariance kernels' flag, read with the same wait.
 template <class Current, class Grows, class Launch, class Built>
 int batch_build_maps(apdgicp_batch* b, const std::vector<int>& slots, const char* prefix, double resolution, const DevBuf& scal, Current&& current, Grows&& grows,
-                     Launch&& launch, Built&& built, int* errflag = nullptr) {
+                     Launch&& launch, Built&& built, int* errflag = nullptr, const std::function<int(int, int)>* caller_index = nullptr) {
   Engine& e = b->eng;
   std::vector<int> todo;
   int nmax = 0;
@@ -1416,7 +1466,8 @@ int batch_build_maps(apdgicp_batch* b, const std::vector<int>& slots, const char
   for (int t : todo) {
     const int* w = hw + 4 * (size_t)(t - lo);
     if (w[0] != kVgBadNone) {
-      if (rc == 0) rc = voxel_key_range_error(std::string(prefix) + "point " + std::to_string(w[0]) + " of cloud slot " + std::to_string(t), resolution);
+      // (caller_index: the mode built the map over a compacted cloud and names the point by its index in the caller's)
+      if (rc == 0) rc = voxel_key_range_error(std::string(prefix) + "point " + std::to_string(caller_index ? (*caller_index)(t, w[0]) : w[0]) + " of cloud slot " + std::to_string(t), resolution);
     } else if (w[1] < 1 || w[1] > e.clouds[t].n) {
       if (rc == 0) rc = fail(APDGICP_ERR_INTERNAL, std::string(prefix) + "inconsistent voxel count");
     } else {
@@ -1731,6 +1782,239 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   });
 }
 
+// ---- FAST_VGICP_CUDA on a batch handle (include/apdgicp_hip.h VC11 .. VC16; kernels: apd_vgicp_cuda_batch.hpp)
+// room for every slot's state and device words; the words of what is built survive a growth
+int vcb_ensure_slots(apdgicp_batch* b) {
+  Engine& e = b->eng;
+  VcbState& v = b->vc;
+  if (v.slots.size() < e.clouds.size()) v.slots.resize(e.clouds.size());
+  APD_TRY(batch_ensure_slot_words(e, v.scal, v.scal_slots));
+  const int want = (int)e.clouds.size();
+  if (want <= v.nk_slots) return 0;
+  const int cap = std::max(64, 2 * want);
+  DevBuf grown;
+  APD_TRY(grown.ensure((size_t)cap * 4));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  if (v.nk_slots) APD_HIP(hipMemcpy(grown.p, v.nk.p, (size_t)v.nk_slots * 4, hipMemcpyDeviceToDevice));
+  v.nk = std::move(grown);
+  v.nk_slots = cap;
+  return 0;
+}
+
+bool vcb_prepared(const apdgicp_batch* b, int slot) {
+  const VcbState::Slot& sl = b->vc.slots[slot];
+  return sl.ready && sl.pts_gen == b->eng.clouds[slot].pts_gen && sl.reg == b->vc.prm.regularization;
+}
+
+bool vcb_map_current(const apdgicp_batch* b, int slot) {
+  const VcbState::Slot& sl = b->vc.slots[slot];
+  return vcb_prepared(b, slot) && sl.map_built && sl.map_prep_id == sl.id && sl.map_res == b->vc.prm.resolution;
+}
+
+// VC11: the prepared clouds of the listed slots (sorted) that are not current.  The launches of all of them go out with no wait in between;
+// ONE copy brings every slot's kept count back, one the k-NN error flag, and one wait covers both.
+int vcb_prepare_slots(apdgicp_batch* b, const std::vector<int>& slots) {
+  Engine& e = b->eng;
+  VcbState& v = b->vc;
+  APD_TRY(vcb_ensure_slots(b));
+  std::vector<int> todo;
+  for (int t : slots) {
+    if (e.clouds[t].n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "FAST_VGICP_CUDA: cloud slot " + std::to_string(t) + " has fewer than " + std::to_string(VC_K) + " points");
+    if (!vcb_prepared(b, t) && std::find(todo.begin(), todo.end(), t) == todo.end()) todo.push_back(t);
+  }
+  if (todo.empty()) return 0;
+  std::sort(todo.begin(), todo.end());
+  const int lo = todo.front(), hi = todo.back(), count = (int)todo.size();
+  APD_TRY(device_loop_ensure_words(b, 4 + (size_t)(hi - lo + 1)));
+  bool replaces = false;  // a buffer that exists and is too small may still be read by what is enqueued: wait before it goes
+  int nmax = 0;
+  long long total = 0;
+  for (int t : todo) {
+    const VcbState::Slot& sl = v.slots[t];
+    const size_t n = (size_t)e.clouds[t].n, nb = (n + VC_BLK - 1) / VC_BLK;
+    auto small = [](const DevBuf& d, size_t bytes) { return d.cap != 0 && bytes > d.cap; };
+    replaces |= small(sl.raw, n * 48) || small(sl.reg6, n * 48) || small(sl.flag, n) || small(sl.bsum, nb * 4) || small(sl.kpts, n * 16) || small(sl.kcov, n * 48) ||
+                small(sl.kept, n * 4) || small(sl.ident, n * 4);
+    nmax = std::max(nmax, e.clouds[t].n), total += e.clouds[t].n;
+  }
+  if (replaces) {
+    APD_HIP(hipStreamSynchronize(e.stream));
+    v.prep_waits++;
+  }
+  std::vector<VcbSlot> tab((size_t)count);
+  for (int q = 0; q < count; q++) {
+    const int t = todo[q];
+    VcbState::Slot& sl = v.slots[t];
+    const size_t n = (size_t)e.clouds[t].n, nb = (n + VC_BLK - 1) / VC_BLK;
+    sl.ready = sl.map_built = false;
+    APD_TRY(sl.raw.ensure(n * 48));
+    APD_TRY(sl.reg6.ensure(n * 48));
+    APD_TRY(sl.flag.ensure(n));
+    APD_TRY(sl.bsum.ensure(nb * 4));
+    APD_TRY(sl.kpts.ensure(n * 16));  // (VC11: the buffers behind the compaction are sized for n kept points -- the count is not known yet)
+    APD_TRY(sl.kcov.ensure(n * 48));
+    APD_TRY(sl.kept.ensure(n * 4));
+    APD_TRY(sl.ident.ensure(n * 4));
+    tab[q] = VcbSlot{e.clouds[t].opts.as<float4>(), sl.raw.as<double>(), sl.reg6.as<double>(), sl.flag.as<unsigned char>(), sl.bsum.as<int>(), v.nk.as<int>() + t,
+                     sl.kpts.as<float4>(), sl.kcov.as<double>(), sl.kept.as<int>(), sl.ident.as<int>(), (int)n, 0};
+  }
+  APD_TRY(v.prep_tab.upload(tab.data(), tab.size() * sizeof(VcbSlot), e.stream));
+  APD_TRY(v.prep_ids.upload(todo.data(), todo.size() * sizeof(int), e.stream));
+  const CloudDesc* desc = e.d_desc.as<CloudDesc>();
+  const int* ids = v.prep_ids.as<int>();
+  const VcbSlot* dt = v.prep_tab.as<VcbSlot>();
+  int* eflag = e.d_errflag.as<int>();
+  unsigned long long* stats = e.d_stats.as<unsigned long long>();
+  const int qpw = total >= 100000 ? 16 : total >= 40000 ? 8 : 4;  // (as Engine::launch_knn for a batch: by the points of all clouds)
+  const dim3 kgrid((unsigned)((nmax + qpw - 1) / qpw), (unsigned)count), bgrid((unsigned)((nmax + VC_BLK - 1) / VC_BLK), (unsigned)count);
+  if (qpw == 16) hipLaunchKernelGGL(k_vcb_knn_raw<4>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
+  else if (qpw == 8) hipLaunchKernelGGL(k_vcb_knn_raw<8>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
+  else hipLaunchKernelGGL(k_vcb_knn_raw<16>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
+  hipLaunchKernelGGL(k_vcb_regularize, bgrid, dim3(VC_BLK), 0, e.stream, dt, (int)v.prm.regularization);
+  hipLaunchKernelGGL(k_vcb_scan, dim3((unsigned)count), dim3(SCAN_BLK), 0, e.stream, dt);
+  hipLaunchKernelGGL(k_vcb_scatter, bgrid, dim3(VC_BLK), 0, e.stream, dt);
+  APD_HIP(hipGetLastError());
+  int* hw = b->loop.h_words.as<int>();
+  APD_HIP(hipMemcpyAsync(hw + 4, v.nk.as<int>() + lo, (size_t)(hi - lo + 1) * 4, hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(hw + 2, eflag, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  v.prep_waits++;
+  if (hw[2]) {
+    const int flag = hw[2];
+    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+    return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA k-NN: " + Engine::errflag_text(flag));
+  }
+  for (int t : todo) {
+    const int nk = hw[4 + (t - lo)];
+    if (nk < 0 || nk > e.clouds[t].n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept count");
+  }
+  for (int t : todo) {
+    VcbState::Slot& sl = v.slots[t];
+    sl.n = e.clouds[t].n, sl.n_kept = hw[4 + (t - lo)];
+    sl.pts_gen = e.clouds[t].pts_gen, sl.reg = v.prm.regularization, sl.id = ++v.preps;
+    sl.ready = true;
+  }
+  return 0;
+}
+
+// VC12: the maps of the listed slots (prepared) that are not current, over their kept points
+int vcb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
+  Engine& e = b->eng;
+  VcbState& v = b->vc;
+  std::vector<int> full;
+  for (int t : targets) {
+    VcbState::Slot& sl = v.slots[t];
+    if (vcb_map_current(b, t)) continue;
+    if (sl.n_kept > 0) {
+      full.push_back(t);
+      continue;
+    }
+    // no kept point: an empty map, no sort (the shared builder calls a voxel count of 0 inconsistent) -- the device word the tick reads is 0
+    APD_HIP(hipMemsetAsync(v.scal.as<int>() + 4 * (size_t)t, 0, 16, e.stream));
+    sl.nv = 0;
+    sl.map_built = true, sl.map_prep_id = sl.id, sl.map_res = v.prm.resolution;
+    v.builds++;
+  }
+  if (full.empty()) return 0;
+  v.map_waits++;
+  const std::function<int(int, int)> caller_index = [&](int t, int j) -> int {  // kept point j of slot t in the caller's cloud (an error path: its own wait)
+    int orig = -1;
+    if (j >= 0 && j < v.slots[t].n_kept && hipMemcpy(&orig, v.slots[t].kept.as<int>() + j, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) orig = -1;
+    return orig;
+  };
+  return batch_build_maps(
+      b, full, "FAST_VGICP_CUDA: ", v.prm.resolution, v.scal, [&](int) { return false; }, [&](int t) { return (size_t)v.slots[t].n_kept * 48 > v.slots[t].buf.vcov.cap; },
+      [&](int t) -> int {
+        VcbState::Slot& sl = v.slots[t];
+        const int n = sl.n_kept;
+        sl.map_built = false;
+        APD_TRY(sl.buf.ensure((size_t)n, false));
+        VoxSorted s;
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, sl.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), sl.kpts.as<float4>(), sl.kcov.as<double>(), sl.ident.as<int>(),
+                           sl.buf.vkeys.as<unsigned long long>(), sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vcov.as<double>(), n);
+        APD_HIP(hipGetLastError());
+        return 0;
+      },
+      [&](int t, int nv) {
+        VcbState::Slot& sl = v.slots[t];
+        sl.nv = nv;
+        sl.map_built = true, sl.map_prep_id = sl.id, sl.map_res = v.prm.resolution;
+        v.builds++;
+      },
+      nullptr, &caller_index);
+}
+
+static const char* const kVcbOff = "FAST_VGICP_CUDA is off (apdgicp_batch_set_vgicp_cuda)";
+
+// one slot for the getters: sorted, prepared, and with want_map its map built
+int vcb_slot(apdgicp_batch* b, int32_t cloud, bool want_map) {
+  Engine& e = b->eng;
+  if (!b->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcbOff);
+  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.pool_leave());
+  APD_TRY(e.finish_align());
+  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+  APD_TRY(vcb_prepare_slots(b, {cloud}));
+  return want_map ? vcb_build_maps(b, {cloud}) : 0;
+}
+
+// VC14 / VC16: the optimiser loop of every pair on the device; returns with the device records complete
+int vcb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
+  Engine& e = b->eng;
+  VcbState& v = b->vc;
+  v.have = false;
+  APD_TRY(e.finish_align());  // (an uncollected deferred align from before the mode was switched on)
+  APD_TRY(e.setup_pairs(pairs, n_pairs, true, /*pipeline_cov=*/false, /*need_cov=*/false));  // VC11: clouds sorted, d_state / d_results / d_guess; no covariances
+  e.results_on_host = false;
+  const int np = e.npairs;
+  std::vector<int> named, targets;
+  for (int i = 0; i < np; i++) named.push_back(e.h_pairs[i].src), named.push_back(e.h_pairs[i].tgt), targets.push_back(e.h_pairs[i].tgt);
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  // apdgicp_batch_set_profiling: the phases of this align by the host clock.  One more wait in front (the sorts of the clouds set since the
+  // last align are not this mode's preparation); every other boundary is behind a wait the align makes anyway.
+  if (e.profile_nn) APD_HIP(hipStreamSynchronize(e.stream));
+  clock::time_point t0 = clock::now();
+  APD_TRY(vcb_prepare_slots(b, named));
+  v.phase_ms[0] = ms_since(t0), t0 = clock::now();
+  APD_TRY(vcb_build_maps(b, targets));
+  v.phase_ms[1] = ms_since(t0), t0 = clock::now();
+  if (v.offs.empty() || v.offs_search != v.prm.neighbor_search || v.offs_radius != v.prm.search_radius) {
+    vc_offsets(v.prm, v.offs);
+    v.offs_search = v.prm.neighbor_search, v.offs_radius = v.prm.search_radius;
+  }
+  APD_TRY(v.d_offs.upload(v.offs.data(), v.offs.size() * sizeof(int32_t), e.stream));
+  const int noff = (int)(v.offs.size() / 3);
+  std::vector<VgbPair> tab(np);
+  std::vector<int> nks(np);
+  int nk_max = 0;
+  for (int i = 0; i < np; i++) {
+    const VcbState::Slot &s = v.slots[e.h_pairs[i].src], &t = v.slots[e.h_pairs[i].tgt];
+    tab[i] = VgbPair{s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), s.n_kept, 0, t.buf.map(v.scal.as<int>() + 4 * (size_t)e.h_pairs[i].tgt + 1)};
+    nks[i] = s.n_kept;
+    nk_max = std::max(nk_max, s.n_kept);
+  }
+  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
+  const int nblk_max = std::max(1, (nk_max + VG_BLK - 1) / VG_BLK);  // (no kept source point anywhere: one block per pair, which returns)
+  const size_t corr_stride = (size_t)nk_max * (size_t)noff;         // frozen indices: pairs x max n_kept x n_offsets ints, computed in size_t
+  APD_TRY(ensure_corr_part(e, v.corr, v.part, std::max<size_t>(16, (size_t)np * corr_stride * 4), (size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(device_loop_prepare(b));
+  const Consts cst = e.consts();
+  PairState* st = e.d_state.as<PairState>();
+  ResultRec* recs = e.d_results.as<ResultRec>();
+  int* done = b->loop.done.as<int>();
+  APD_TRY(device_loop_run(b, [&]() {
+    hipLaunchKernelGGL(k_vcb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution, v.d_offs.as<int>(), noff,
+                       v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
+    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, done);
+  }));
+  v.phase_ms[2] = ms_since(t0);
+  v.have = true, v.have_epoch = e.pts_epoch, v.have_nk = nks, v.have_stride = corr_stride, v.have_noff = noff;
+  return 0;
+}
+
 // ---- point-to-point ICP on a batch handle (include/apdgicp_hip.h IC11 .. IC16; kernels: apd_icp_batch.hpp)
 constexpr int kIcbTraceCap = 1024;  // a pair's trace keeps its first this many iterations (the count goes on)
 
@@ -1852,7 +2136,8 @@ int icb_check_have(apdgicp_batch* b, int64_t pair) {
 
 const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 const char* const kNdbNoPipeline = "NDT on a batch handle (apdgicp_batch_set_ndt) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
-const char* const kIcbNoPipeline = "point-to-point ICP on a batch handle (apdgicp_batch_set_icp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+const char* const kVcbNoPipeline = "FAST_VGICP_CUDA on a batch handle (apdgicp_batch_set_vgicp_cuda) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
+const char* const kIcbNoPipeline ="point-to-point ICP on a batch handle (apdgicp_batch_set_icp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 
 // what the single and the batch setters refuse (null: nothing to check -- the mode is being switched off)
 int check_vgicp_params(const apdgicp_vgicp_params* p) {
@@ -2647,10 +2932,11 @@ int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on && !b->nd.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
+    if (!v.on && !b->nd.on && !b->ic.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.prm = *p;
     v.on = true;
     b->nd.on = false;  // N15: the two modes are exclusive
+    b->vc.on = false;  // VC16
     if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
     return 0;
   });
@@ -2697,10 +2983,11 @@ int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on && !b->vg.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
+    if (!v.on && !b->vg.on && !b->ic.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.prm = *p;
     v.on = true;
     b->vg.on = false;  // N15: the two modes are exclusive
+    b->vc.on = false;  // VC16
     if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
     return 0;
   });
@@ -2735,6 +3022,134 @@ int apdgicp_batch_ndt_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capaci
 int apdgicp_batch_ndt_build_count(apdgicp_batch* b, int64_t* n_builds) {
   if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
   *n_builds = b->nd.builds;
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------ FAST_VGICP_CUDA on batch handles
+int apdgicp_batch_set_vgicp_cuda(apdgicp_batch* b, const apdgicp_vgicp_cuda_params* p) {
+  return guarded([&]() -> int {
+    // (the parameters first: what is wrong with them does not depend on the handle)
+    APD_TRY(check_vgicp_cuda_params(p));
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    VcbState& v = b->vc;
+    if (!p) {
+      v.on = false;
+      return 0;
+    }
+    if (!v.on && !b->vg.on && !b->nd.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
+    v.have = false;
+    v.prm = *p;
+    v.on = true;
+    b->vg.on = false, b->nd.on = false;  // VC16: the four modes are exclusive
+    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
+    return 0;
+  });
+}
+
+int apdgicp_batch_get_vgicp_cuda(const apdgicp_batch* b, apdgicp_vgicp_cuda_params* p, int* enabled) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (p) *p = b->vc.prm;
+  if (enabled) *enabled = b->vc.on ? 1 : 0;
+  return 0;
+}
+
+int apdgicp_batch_vgicp_cuda_kept(apdgicp_batch* b, int32_t cloud, int64_t* n_kept, int32_t* kept_index, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!b || !n_kept) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(vcb_slot(b, cloud, false));
+    const VcbState::Slot& sl = b->vc.slots[cloud];
+    *n_kept = sl.n_kept;
+    if (!kept_index || sl.n_kept == 0) return 0;
+    if (capacity < sl.n_kept) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+    APD_HIP(hipMemcpyAsync(kept_index, sl.kept.p, (size_t)sl.n_kept * 4, hipMemcpyDeviceToHost, b->eng.stream));
+    APD_HIP(hipStreamSynchronize(b->eng.stream));
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_cuda_get_covariances(apdgicp_batch* b, int32_t cloud, double* raw_n6, double* reg_n9, int64_t capacity) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    APD_TRY(vcb_slot(b, cloud, false));
+    const VcbState::Slot& sl = b->vc.slots[cloud];
+    const int64_t nk = sl.n_kept;
+    if (capacity < nk) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+    if (nk == 0) return 0;
+    hipStream_t st = b->eng.stream;
+    std::vector<double> all(raw_n6 ? (size_t)sl.n * 6 : 0), k6(reg_n9 ? (size_t)nk * 6 : 0);
+    std::vector<int> kept(raw_n6 ? (size_t)nk : 0);
+    if (raw_n6) {
+      APD_HIP(hipMemcpyAsync(all.data(), sl.raw.p, all.size() * 8, hipMemcpyDeviceToHost, st));
+      APD_HIP(hipMemcpyAsync(kept.data(), sl.kept.p, kept.size() * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (reg_n9) APD_HIP(hipMemcpyAsync(k6.data(), sl.kcov.p, k6.size() * 8, hipMemcpyDeviceToHost, st));
+    APD_HIP(hipStreamSynchronize(st));
+    for (int64_t j = 0; j < nk && raw_n6; j++) {
+      if (kept[j] < 0 || kept[j] >= sl.n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept index");
+      memcpy(raw_n6 + 6 * j, &all[6 * (size_t)kept[j]], 6 * sizeof(double));
+    }
+    for (int64_t j = 0; j < nk && reg_n9; j++) {  // kcov: [6][n_kept]
+      const double xx = k6[j], xy = k6[nk + j], xz = k6[2 * nk + j], yy = k6[3 * nk + j], yz = k6[4 * nk + j], zz = k6[5 * nk + j];
+      double* o = reg_n9 + 9 * j;
+      o[0] = xx, o[1] = xy, o[2] = xz, o[3] = xy, o[4] = yy, o[5] = yz, o[6] = xz, o[7] = yz, o[8] = zz;
+    }
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_cuda_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_voxels) {
+  return guarded([&]() -> int {
+    if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(vcb_slot(b, cloud, true));
+    *n_voxels = b->vc.slots[cloud].nv;
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_cuda_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    APD_TRY(vcb_slot(b, cloud, true));
+    const VcbState::Slot& sl = b->vc.slots[cloud];
+    if (sl.nv == 0) return 0;
+    return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
+  });
+}
+
+int apdgicp_batch_vgicp_cuda_get_correspondences(apdgicp_batch* b, int64_t pair, int32_t* voxel_index, int64_t n_kept_source) {
+  return guarded([&]() -> int {
+    if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+    const VcbState& v = b->vc;
+    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, kVcbOff);
+    if (!v.have || v.have_epoch != b->eng.pts_epoch) return fail(APDGICP_ERR_NO_INPUT, "no align in this mode since the cloud slots and the mode were last set");
+    if (pair < 0 || pair >= (int64_t)v.have_nk.size()) return fail(APDGICP_ERR_INVALID_ARG, "pair is not one of the last align");
+    if (!voxel_index) return v.have_nk[pair];  // (the size query)
+    if (n_kept_source != v.have_nk[pair]) return fail(APDGICP_ERR_INVALID_ARG, "n_kept_source does not match the pair's kept source size");
+    if (n_kept_source == 0) return 0;
+    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.as<int>() + (size_t)pair * v.have_stride, (size_t)n_kept_source * v.have_noff * 4, hipMemcpyDeviceToHost, b->eng.stream));
+    APD_HIP(hipStreamSynchronize(b->eng.stream));
+    return 0;
+  });
+}
+
+int apdgicp_batch_vgicp_cuda_build_count(apdgicp_batch* b, int64_t* n_prepared, int64_t* n_maps) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (n_prepared) *n_prepared = b->vc.preps;
+  if (n_maps) *n_maps = b->vc.builds;
+  return 0;
+}
+
+int apdgicp_batch_vgicp_cuda_last_phases(apdgicp_batch* b, double ms[3]) {
+  if (!b || !ms) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  memcpy(ms, b->vc.phase_ms, sizeof(b->vc.phase_ms));
+  return 0;
+}
+
+int apdgicp_batch_vgicp_cuda_debug_counts(apdgicp_batch* b, int64_t* prepare_waits, int64_t* map_waits, int64_t* ticks) {
+  if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
+  if (prepare_waits) *prepare_waits = b->vc.prep_waits;
+  if (map_waits) *map_waits = b->vc.map_waits;
+  if (ticks) *ticks = b->loop.last_ticks;
   return 0;
 }
 
@@ -3123,6 +3538,11 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
       if (d_results) *d_results = b->eng.d_results.p;
       return 0;
     }
+    if (b->vc.on) {  // FAST_VGICP_CUDA: likewise (VC16)
+      APD_TRY(vcb_align(b, pairs, n_pairs));
+      if (d_results) *d_results = b->eng.d_results.p;
+      return 0;
+    }
     if (b->eng.pool_eligible()) {  // Levenberg-Marquardt: through the pair pool (complete on return, like every LM run)
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
@@ -3141,6 +3561,7 @@ int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
+    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_eligible()) return e.pool_enqueue(pairs, n_pairs, ticket);
     APD_TRY(e.ensure_alt_slot());
@@ -3160,13 +3581,14 @@ int apdgicp_batch_pump(apdgicp_batch* b) {
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
+    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
     return b->eng.pool.on ? b->eng.pool_pump(false) : 0;
   });
 }
 
 int apdgicp_batch_is_pooled(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-  if (b->vg.on || b->nd.on || b->ic.on) return 0;
+  if (b->vg.on || b->nd.on || b->ic.on || b->vc.on) return 0;
   return b->eng.pool_eligible() ? Engine::pool_lanes_cfg() : 0;
 }
 
@@ -3176,6 +3598,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
     if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
     if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
     if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
+    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
     Engine& e = b->eng;
     if (e.pool_find(ticket)) return e.pool_collect(ticket, d_results, host_results);
     const bool previous = ticket + 1 == e.align_seq;
@@ -3202,7 +3625,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
 int apdgicp_batch_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, apdgicp_result* results) {
   return guarded([&]() -> int {
     if (!results) return fail(APDGICP_ERR_INVALID_ARG, "results is null");
-    if (b && pairs && !b->vg.on && !b->nd.on && !b->ic.on && b->eng.pool_eligible()) {
+    if (b && pairs && !b->vg.on && !b->nd.on && !b->ic.on && !b->vc.on && b->eng.pool_eligible()) {
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
       return b->eng.pool_collect(ticket, nullptr, results);
@@ -3336,9 +3759,10 @@ int apdgicp_batch_set_icp(apdgicp_batch* b, const apdgicp_icp_params* p) {
       v.on = false;
       return 0;
     }
-    if (!v.on && !b->vg.on && !b->nd.on) APD_TRY(batch_enter_device_loop_mode(b));
+    if (!v.on && !b->vg.on && !b->nd.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
     v.on = true, v.have = false;
     b->vg.on = false, b->nd.on = false;  // IC16: the three modes are exclusive
+    b->vc.on = false;                    // VC16
     return 0;
   });
 }

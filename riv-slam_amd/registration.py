@@ -122,6 +122,9 @@ SYMBOLS = [
     "apdgicp_icp_get_working_cloud", "apdgicp_icp_get_trace", "apdgicp_icp_convergence_state", "apdgicp_icp_debug_counts",
     "apdgicp_batch_set_icp", "apdgicp_batch_get_icp", "apdgicp_batch_icp_states", "apdgicp_batch_icp_get_correspondences", "apdgicp_batch_icp_get_working_cloud",
     "apdgicp_batch_icp_get_trace", "apdgicp_batch_icp_debug_counts",
+    "apdgicp_batch_set_vgicp_cuda", "apdgicp_batch_get_vgicp_cuda", "apdgicp_batch_vgicp_cuda_kept", "apdgicp_batch_vgicp_cuda_get_covariances",
+    "apdgicp_batch_vgicp_cuda_voxel_count", "apdgicp_batch_vgicp_cuda_get_voxels", "apdgicp_batch_vgicp_cuda_get_correspondences",
+    "apdgicp_batch_vgicp_cuda_build_count", "apdgicp_batch_vgicp_cuda_debug_counts", "apdgicp_batch_vgicp_cuda_last_phases",
     "apdgicp_dbscan_default_params", "apdgicp_dbscan_create", "apdgicp_dbscan_destroy", "apdgicp_dbscan_set_params", "apdgicp_dbscan_run", "apdgicp_dbscan_labels",
     "apdgicp_dbscan_copy_labels", "apdgicp_dbscan_clusters", "apdgicp_dbscan_members", "apdgicp_dbscan_debug", "apdgicp_dbscan_set_profiling", "apdgicp_dbscan_stats",
     "apdgicp_scan_ingest_default_params", "apdgicp_scan_ingest_create", "apdgicp_scan_ingest_destroy", "apdgicp_scan_ingest_set_params", "apdgicp_scan_ingest_run",
@@ -347,6 +350,16 @@ def load_library(path: str | None = None):
     L.apdgicp_batch_ndt_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
     L.apdgicp_batch_ndt_get_voxels.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp, vp]
     L.apdgicp_batch_ndt_build_count.argtypes = [vp, C.POINTER(i64)]
+    L.apdgicp_batch_set_vgicp_cuda.argtypes = [vp, vp]
+    L.apdgicp_batch_get_vgicp_cuda.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_batch_vgicp_cuda_kept.argtypes = [vp, C.c_int32, C.POINTER(i64), vp, i64]
+    L.apdgicp_batch_vgicp_cuda_get_covariances.argtypes = [vp, C.c_int32, vp, vp, i64]
+    L.apdgicp_batch_vgicp_cuda_voxel_count.argtypes = [vp, C.c_int32, C.POINTER(i64)]
+    L.apdgicp_batch_vgicp_cuda_get_voxels.argtypes = [vp, C.c_int32, i64, vp, vp, vp, vp]
+    L.apdgicp_batch_vgicp_cuda_get_correspondences.argtypes = [vp, i64, vp, i64]
+    L.apdgicp_batch_vgicp_cuda_build_count.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_batch_vgicp_cuda_debug_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_batch_vgicp_cuda_last_phases.argtypes = [vp, vp]
     L.apdgicp_dbscan_default_params.argtypes = [vp]
     L.apdgicp_dbscan_default_params.restype = None
     L.apdgicp_dbscan_create.argtypes = [vp, i32, vp, C.POINTER(vp)]

@@ -2,6 +2,8 @@
 `registration.FastAPDGICP` with apdgicp_set_vgicp_cuda switched on and the reference's setters
 (fast_apdgicp/include/fast_gicp/gicp/fast_vgicp_cuda.hpp).  Semantics: the list VC1 .. VC10 in include/apdgicp_hip.h -- k fixed at 20, a
 PLANE regularisation that removes line-like points from both clouds, DIRECT1 / 7 / 27 / DIRECT_RADIUS over the voxel map of what is left.
+`BatchVGICPCuda` is `registration.BatchAPDGICP` with apdgicp_batch_set_vgicp_cuda switched on: per-slot prepared clouds and voxel maps and the
+optimiser loop on the device (VC11 .. VC16).
 
 There is NO CPU fallback: without the HIP library or a GPU every call that needs the device raises.
 """
@@ -151,3 +153,122 @@ class FastVGICPCuda(reg.FastAPDGICP):
         n = C.c_int64()
         _check(self.L.apdgicp_vgicp_cuda_build_count(self.h, C.byref(n)))
         return n.value
+
+
+class BatchVGICPCuda(reg.BatchAPDGICP):
+    """Many independent FAST_VGICP_CUDA registrations on one GPU: a batch handle with apdgicp_batch_set_vgicp_cuda on (VC11 .. VC16): per-slot
+    prepared clouds and voxel maps, the optimiser loop on the device.  Clouds, align, align_async / synchronize and fitness are the base
+    class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is; align_enqueue / align_collect raise (one batch at a time).
+    `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.vparams = default_vgicp_cuda_params()
+        self._push_mode()
+
+    def _push_mode(self):
+        _check(self.L.apdgicp_batch_set_vgicp_cuda(self.b, C.byref(self.vparams)))
+
+    def _set(self, **fields):
+        old = {k: getattr(self.vparams, k) for k in fields}
+        for k, val in fields.items():
+            setattr(self.vparams, k, val)
+        try:
+            self._push_mode()
+        except reg.ApdgicpError:
+            for k, val in old.items():
+                setattr(self.vparams, k, val)
+            raise
+
+    def setCorrespondenceRandomness(self, k):   # VCI:38: a no-op, k is 20
+        pass
+
+    def setResolution(self, resolution: float):
+        self._set(resolution=float(resolution))
+
+    def setRegularizationMethod(self, method: int):
+        self._set(regularization=int(method))
+
+    def setNeighborSearchMethod(self, method: int, radius: float = -1.0):
+        """DIRECT1 / DIRECT7 / DIRECT27, or DIRECT_RADIUS with its radius in voxels (a radius the mode does not read is not stored)."""
+        if int(method) == DIRECT_RADIUS:
+            self._set(neighbor_search=DIRECT_RADIUS, search_radius=float(radius))
+        else:
+            self._set(neighbor_search=int(method))
+
+    def setNearestNeighborSearchMethod(self, method: int):
+        self._set(nn_method=int(method))
+
+    def disable(self):
+        _check(self.L.apdgicp_batch_set_vgicp_cuda(self.b, None))
+
+    def enable(self):
+        self._push_mode()
+
+    def get_mode(self):
+        """(VgicpCudaParams, enabled) as the library holds them."""
+        p, on = VgicpCudaParams(), C.c_int()
+        _check(self.L.apdgicp_batch_get_vgicp_cuda(self.b, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
+
+    def enabled(self) -> bool:
+        return self.get_mode()[1]
+
+    def offsets(self) -> np.ndarray:
+        return neighbor_offsets(self.vparams)
+
+    def kept(self, cloud: int) -> np.ndarray:
+        """VC4 / VC11: the original indices of the kept points of cloud slot `cloud` (prepared if it is not current), ascending."""
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_cuda_kept(self.b, int(cloud), C.byref(n), None, 0))
+        out = np.empty(n.value, dtype=np.int32)
+        _check(self.L.apdgicp_batch_vgicp_cuda_kept(self.b, int(cloud), C.byref(n), _ptr(out), n.value))
+        return out
+
+    def covariances(self, cloud: int):
+        """(raw [n_kept, 3, 3], regularised [n_kept, 3, 3]) per kept point of cloud slot `cloud` (VC2 / VC3)."""
+        n = len(self.kept(cloud))
+        raw6, reg9 = np.empty((n, 6)), np.empty((n, 9))
+        _check(self.L.apdgicp_batch_vgicp_cuda_get_covariances(self.b, int(cloud), _ptr(raw6), _ptr(reg9), n))
+        raw = raw6[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(n, 3, 3)
+        return raw, reg9.reshape(n, 3, 3)
+
+    def voxel_count(self, cloud: int) -> int:
+        n = C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_cuda_voxel_count(self.b, int(cloud), C.byref(n)))
+        return n.value
+
+    def voxels(self, cloud: int):
+        """The voxel map over the kept points of cloud slot `cloud` (built if it is not current), as FastVGICPCuda.voxels()."""
+        n = self.voxel_count(cloud)
+        coords = np.empty((n, 3), dtype=np.int32)
+        counts = np.empty(n, dtype=np.int32)
+        means = np.empty((n, 3))
+        covs = np.empty((n, 9))
+        _check(self.L.apdgicp_batch_vgicp_cuda_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
+        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+
+    def voxel_correspondences(self, pair: int) -> np.ndarray:
+        """[n_kept(source), n_offsets] frozen voxel indices of pair `pair`'s last linearize in the last align, in offset order; -1 = miss."""
+        n = _check(self.L.apdgicp_batch_vgicp_cuda_get_correspondences(self.b, int(pair), None, 0))
+        out = np.empty((n, len(self.offsets())), dtype=np.int32)
+        _check(self.L.apdgicp_batch_vgicp_cuda_get_correspondences(self.b, int(pair), _ptr(out), n))
+        return out
+
+    def build_count(self):
+        """(clouds prepared, maps built) by this handle in this mode, all slots together (the cache rules' test hook)."""
+        p, m = C.c_int64(), C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_cuda_build_count(self.b, C.byref(p), C.byref(m)))
+        return p.value, m.value
+
+    def debug_counts(self):
+        """(host waits spent preparing clouds, host waits spent building maps, both since the handle was created; ticks of the last align)."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(self.L.apdgicp_batch_vgicp_cuda_debug_counts(self.b, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def last_phases(self):
+        """(preparation, map builds, ticks) of the last align in ms by the host clock; meaningful after set_profiling(True)."""
+        ms = (C.c_double * 3)()
+        _check(self.L.apdgicp_batch_vgicp_cuda_last_phases(self.b, ms))
+        return tuple(ms)
