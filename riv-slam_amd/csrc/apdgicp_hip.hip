@@ -120,7 +120,6 @@ static int n_offsets(int neighbor_search) { return neighbor_search == APDGICP_VG
 // apdgicp_set_vgicp: the voxel map of the target and the frozen state of the last linearize (include/apdgicp_hip.h, V1 .. V7).  The scratch of
 // a map build is the handle's (apdgicp_handle::sort).
 struct VgState {
-  bool on = false;
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
   // What the cached pieces were made FROM, by identity: apdgicp_handle::cloud_gen names the points of a slot (and their order on the curve),
   // Engine::Cloud::cov_gen one writing of a cloud's covariances.  A piece is used only while those still name what the handle holds, so no call
@@ -142,37 +141,74 @@ struct VgState {
   VgMap map() const { return buf.map((int)n_vox); }
 };
 
+// VC1 .. VC4 of one cloud, on either handle kind: a pure function of (points, regularisation), cached by identity
+struct VcPrepared {
+  bool ready = false;
+  uint64_t pts_gen = 0;          // which setting of the cloud's points it was made from (apdgicp_handle::cloud_gen / Engine::Cloud::pts_gen)
+  int reg = 0;
+  int64_t id = 0;                // which preparation this is (the owner's preps when it was made): names it for the map and the frozen state
+  int n = 0, n_kept = 0;
+  DevBuf raw, reg6, flag, bsum, kpts, kcov, kept, ident;  // raw / reg6 / flag: per point of the cloud; the rest sized for n kept points
+};
+
+// VC6: the offsets of p (checked by the caller), 3 ints each
+static void vc_offsets(const apdgicp_vgicp_cuda_params& p, std::vector<int32_t>& out) {
+  out.clear();
+  auto push = [&](int i, int j, int k) { out.push_back(i), out.push_back(j), out.push_back(k); };
+  if (p.neighbor_search == APDGICP_VGICP_DIRECT1) {
+    push(0, 0, 0);
+  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT7) {  // VC:55-64
+    push(0, 0, 0), push(1, 0, 0), push(-1, 0, 0), push(0, 1, 0), push(0, -1, 0), push(0, 0, 1), push(0, 0, -1);
+  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT27) {  // VC:66-75
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++)
+        for (int k = 0; k < 3; k++) push(i - 1, j - 1, k - 1);
+  } else {  // VC:77-90
+    const int range = (int)std::ceil(p.search_radius);
+    for (int i = -range; i <= range; i++)
+      for (int j = -range; j <= range; j++)
+        for (int k = -range; k <= range; k++)
+          if (std::sqrt((double)(i * i + j * j + k * k)) <= p.search_radius + 1e-3) push(i, j, k);
+  }
+}
+
+// VC6: the offset table (3 ints per offset), what it was made from, and its device copy
+struct VcOffsets {
+  std::vector<int32_t> host;
+  int search = -1;
+  double radius = 0.0;
+  CachedTable dev;
+  int count() const { return (int)(host.size() / 3); }
+  void clear() { host.clear(); }
+  int ensure(const apdgicp_vgicp_cuda_params& prm, hipStream_t stream) {
+    if (host.empty() || search != prm.neighbor_search || radius != prm.search_radius) {
+      vc_offsets(prm, host);
+      search = prm.neighbor_search, radius = prm.search_radius;
+    }
+    return dev.upload(host.data(), host.size() * sizeof(int32_t), stream);
+  }
+};
+
 // apdgicp_set_vgicp_cuda: per cloud the prepared cloud (kept points, their covariances, their original indices), the voxel map of the
 // prepared target and the frozen state of the last linearize (include/apdgicp_hip.h, VC1 .. VC10).  The scratch of a map build is the
 // handle's (apdgicp_handle::sort).
 struct VcState {
-  struct Prepared {              // VC1 .. VC4 of one cloud: a pure function of (points, regularisation), cached by identity
-    bool ready = false;
-    uint64_t pts_gen = 0;        // apdgicp_handle::cloud_gen of the points it was made from
-    int reg = 0;
-    int64_t id = 0;              // which preparation this is (VcState::preps when it was made): names it for the map and the frozen state
-    int n = 0, n_kept = 0;
-    DevBuf raw, reg6, flag, bsum, kpts, kcov, kept, ident;  // raw / reg6 / flag: per point of the cloud; the rest per kept point
-  };
-  bool on = false;
   apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
-  Prepared pc[2];                // [source, target]; swapped with the clouds
+  VcPrepared pc[2];              // [source, target]; swapped with the clouds
   int64_t preps = 0;
   bool map_built = false;        // the map: prepared target map_prep_id at map_res
   int64_t map_prep_id = 0;
   double map_res = 0.0;
   int64_t n_vox = 0, builds = 0;
-  std::vector<int32_t> offs;     // VC6: the table behind d_offs (3 ints per offset), and what it was made from
-  int offs_search = -1;
-  double offs_radius = 0.0;
+  VcOffsets offs;
   bool have_lin = false;         // corr / T_lin: a linearize of prepared source lin_src_id against map number lin_build
   int64_t lin_src_id = 0, lin_build = 0;
   int n_src_lin = 0, noff_lin = 0;
   double T_lin[12];
   double final_H[36];            // of the last align in this mode (identity until then), on the host like NdState's
   VoxMapBufs buf;
-  CachedTable d_offs;
-  DevBuf scal, corr, part, T, out;
+  CachedTable prep_tab[2], prep_ids[2];  // per cloud, the VcbSlot table and the cloud id of its preparation: uploaded again only when a pointer or n changes
+  DevBuf scal, corr, part, T, out;  // scal, ints: [0, 4) a map build, [4 + which] n_kept of cloud `which`'s preparation
   VgMap map() const { return buf.map((int)n_vox); }
   VcState() { reset_final_H(); }
   void reset_final_H() {
@@ -192,7 +228,6 @@ struct NdState {
     VoxMapBufs buf;
     VgMap map() const { return buf.map(nv); }
   };
-  bool on = false;
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
   Map maps[2];                 // [source, target]; swapped with the clouds
   int64_t builds = 0;
@@ -212,7 +247,6 @@ struct NdState {
 // apdgicp_set_icp: the working cloud W (in the source's curve order), its boxes, the matches and the record of the last iteration
 // (include/apdgicp_hip.h, IC1 .. IC10).  The forward search runs through the engine's own buffers (Work::nnpt / sqd).
 struct IcState {
-  bool on = false;
   apdgicp_icp_params prm{1, 0, 3, 0, -std::numeric_limits<double>::max(), 0.0, 1e-12};
   bool brute = false;          // APDGICP_ICP_RECIP_MODE=brute (read when the handle is created): the reciprocal search without its boxes
   bool have = false;           // W / match / dsq describe source points have_src_gen (n_have of them) against target points have_tgt_gen
@@ -228,13 +262,18 @@ struct IcState {
   PinnedBuf h_rec;             // mirror of rec: one IcpRecord
 };
 
+// Which pipeline a handle runs: its own APD-GICP / plain GICP kernels, or one of the modes switched on through apdgicp_[batch_]set_*.
+// One value per handle, written by set_mode() alone ("Mode transitions").
+enum class Mode { APD, VGICP, VGICP_CUDA, NDT, ICP };
+
 struct apdgicp_handle {
   Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
   VgState vg;   // (freed by its members' destructors, behind the wait of ~apdgicp_handle)
   VcState vc;   // (likewise)
   NdState nd;   // (likewise)
   IcState ic;   // (likewise)
-  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two are exclusive
+  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of whichever voxel mode is on
+  Mode mode = Mode::APD;
   ~apdgicp_handle() {
     if (eng.stream) (void)hipStreamSynchronize(eng.stream);  // the voxel kernels run there; the members are freed once this body has run
   }
@@ -261,7 +300,6 @@ struct VgbState {
     DevBuf inv;
     VoxMapBufs buf;            // sized for nv <= n
   };
-  bool on = false;
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
   std::vector<Slot> slots;
   int64_t builds = 0;
@@ -286,7 +324,6 @@ struct NdbState {
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
     VoxMapBufs buf;            // sized for nv <= n
   };
-  bool on = false;
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
   std::vector<Slot> slots;
   int64_t builds = 0;
@@ -304,7 +341,6 @@ struct NdbState {
 // apdgicp_batch_set_icp (include/apdgicp_hip.h, IC11 .. IC16): per align the working clouds of all pairs (one buffer, a slice per pair), their
 // boxes, matches, block rows and records.  Nothing is kept per cloud slot.  The state of the device loop is the handle's (apdgicp_batch::loop).
 struct IcbState {
-  bool on = false;
   apdgicp_icp_params prm{1, 0, 3, 0, -std::numeric_limits<double>::max(), 0.0, 1e-12};
   bool brute = false;          // APDGICP_ICP_RECIP_MODE=brute (read when the handle is created), as on the single handle
   // what the getters may read: the last align in this mode, while no cloud slot has been written since (epoch: Engine::pts_epoch at the align)
@@ -328,19 +364,13 @@ struct IcbState {
 // device-loop state: the handle's, as for VgbState.
 struct VcbState {
   struct Slot {
-    bool ready = false;        // the prepared cloud: points pts_gen, regularisation reg
-    uint64_t pts_gen = 0;
-    int reg = 0;
-    int64_t id = 0;            // which preparation this is (VcbState::preps when it was made): names it for the map
-    int n = 0, n_kept = 0;
-    DevBuf raw, reg6, flag, bsum, kpts, kcov, kept, ident;  // raw / reg6 / flag: per point of the cloud; the rest sized for n kept points
+    VcPrepared pc;
     bool map_built = false;    // the map: preparation map_prep_id at map_res
     int64_t map_prep_id = 0;
     double map_res = 0.0;
     int nv = 0;                // host copy of the voxel count (the kernels read the device word)
     VoxMapBufs buf;            // sized for nv <= n
   };
-  bool on = false;
   apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
   std::vector<Slot> slots;
   int64_t preps = 0, builds = 0;
@@ -350,9 +380,7 @@ struct VcbState {
   int scal_slots = 0;
   DevBuf nk;                   // per slot: the kept count of its preparation
   int nk_slots = 0;
-  std::vector<int32_t> offs;   // VC6: the table behind d_offs (3 ints per offset), and what it was made from
-  int offs_search = -1;
-  double offs_radius = 0.0;
+  VcOffsets offs;
   // what apdgicp_batch_vgicp_cuda_get_correspondences may read: the last align in this mode, while no cloud slot has been written since
   bool have = false;
   uint64_t have_epoch = 0;
@@ -360,7 +388,7 @@ struct VcbState {
   size_t have_stride = 0;
   int have_noff = 0;
   DevBuf corr, part;
-  CachedTable pairs, prep_tab, prep_ids, d_offs;
+  CachedTable pairs, prep_tab, prep_ids;
   void release() {  // apdgicp_batch_clear: the prepared clouds and the maps go with the clouds
     slots.clear();
     have = false;
@@ -396,7 +424,8 @@ struct apdgicp_batch {
   NdbState nd;  // (likewise)
   IcbState ic;  // (likewise)
   VcbState vc;  // (likewise)
-  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of either mode: the two never run together
+  VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of whichever voxel mode is on
+  Mode mode = Mode::APD;
   DeviceLoop loop;      // (likewise; its events by its own destructor)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
   void release_voxel_modes() {  // apdgicp_batch_clear
@@ -587,6 +616,22 @@ namespace {
 constexpr int kSrc = 0, kTgt = 1;
 const char* cloud_name(int which) { return which == kSrc ? "source" : "target"; }
 
+// What the error texts call a mode and the setter that switches it on, indexed by Mode.
+struct ModeText {
+  const char *name, *setter;
+};
+constexpr ModeText kModeText[] = {{"APD-GICP", ""}, {"voxelized GICP", "set_vgicp"}, {"FAST_VGICP_CUDA", "set_vgicp_cuda"}, {"NDT", "set_ndt"}, {"point-to-point ICP", "set_icp"}};
+// a getter of mode m on a handle that is in another one: "NDT is off (apdgicp_batch_set_ndt)"
+int mode_is_off(Mode m, bool batch) {
+  const ModeText& t = kModeText[(int)m];
+  return fail(APDGICP_ERR_NO_INPUT, std::string(t.name) + " is off (apdgicp_" + (batch ? "batch_" : "") + t.setter + ")");
+}
+// align_enqueue / align_collect / pump on a batch handle in mode m (not APD)
+int no_pipeline(Mode m) {
+  const ModeText& t = kModeText[(int)m];
+  return fail(APDGICP_ERR_UNSUPPORTED, std::string(t.name) + " on a batch handle (apdgicp_batch_" + t.setter + ") runs one batch at a time: align_enqueue / align_collect / pump are not offered");
+}
+
 void identity16(float* g) {
   memset(g, 0, 16 * sizeof(float));
   g[0] = g[5] = g[10] = g[15] = 1.f;
@@ -598,7 +643,7 @@ int ensure_pair(apdgicp_handle* h, const float* guess16 = nullptr) {
   Engine& e = h->eng;
   if (e.clouds.size() < 2 || e.clouds[kSrc].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "source cloud is not set");
   if (e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
-  const bool need_cov = !h->ic.on;  // IC9: the ICP mode searches only, clouds of any size
+  const bool need_cov = h->mode != Mode::ICP;  // IC9: the ICP mode searches only, clouds of any size
   if (h->pair_ready && (!need_cov || (e.clouds[kSrc].cov_valid && e.clouds[kTgt].cov_valid))) return 0;
   apdgicp_pair p;
   p.source_cloud = kSrc;
@@ -669,23 +714,31 @@ int voxel_key_range_error(const std::string& what, double resolution) {
   return fail(APDGICP_ERR_INVALID_ARG, what + " is not finite or lies outside the voxel key range (|c| < 2^20 at resolution " + std::to_string(resolution) + ")");
 }
 
-// A single handle's build up to the voxel kernel: waits before the scratch may be replaced, sorts cloud `which`, waits again to read the voxel
-// count *nv.  prefix: "voxelized GICP: " / "NDT: ".
-int handle_sort_voxels(apdgicp_handle* h, int which, double resolution, DevBuf& scal, const char* prefix, VoxSorted* sorted, int* nv) {
+// A single handle's build up to the voxel kernel: waits before the scratch may be replaced, sorts pts[0 .. n), waits again to read the voxel
+// count *nv.  prefix: "voxelized GICP: " / "NDT: " / "FAST_VGICP_CUDA: "; point_name(j) words point j for the caller ("target point 7"),
+// called on the error path only.
+template <class PointName>
+int handle_sort_voxels(apdgicp_handle* h, const float4* pts, int n, double resolution, DevBuf& scal, const char* prefix, PointName&& point_name, VoxSorted* sorted,
+                       int* nv) {
   Engine& e = h->eng;
-  const Engine::Cloud& c = e.clouds[which];
   APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below, and the caller's after this, may be replaced)
-  APD_TRY(h->sort.ensure(c.n));
+  APD_TRY(h->sort.ensure(n));
   APD_TRY(scal.ensure(16));
-  APD_TRY(enqueue_voxel_sort(e.stream, h->sort, c.opts.as<float4>(), c.n, resolution, scal.as<int>(), sorted));
+  APD_TRY(enqueue_voxel_sort(e.stream, h->sort, pts, n, resolution, scal.as<int>(), sorted));
   APD_HIP(hipGetLastError());
   int hs[4];
   APD_HIP(hipMemcpyAsync(hs, scal.p, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
-  if (hs[0] != kVgBadNone) return voxel_key_range_error(std::string(prefix) + cloud_name(which) + " point " + std::to_string(hs[0]), resolution);
-  if (hs[1] < 1 || hs[1] > c.n) return fail(APDGICP_ERR_INTERNAL, std::string(prefix) + "inconsistent voxel count");
+  if (hs[0] != kVgBadNone) return voxel_key_range_error(std::string(prefix) + point_name(hs[0]), resolution);
+  if (hs[1] < 1 || hs[1] > n) return fail(APDGICP_ERR_INTERNAL, std::string(prefix) + "inconsistent voxel count");
   *nv = hs[1];
   return 0;
+}
+// (a whole cloud slot: the point's index is the caller's)
+int handle_sort_voxels(apdgicp_handle* h, int which, double resolution, DevBuf& scal, const char* prefix, VoxSorted* sorted, int* nv) {
+  const Engine::Cloud& c = h->eng.clouds[which];
+  return handle_sort_voxels(
+      h, c.opts.as<float4>(), c.n, resolution, scal, prefix, [&](int j) { return std::string(cloud_name(which)) + " point " + std::to_string(j); }, sorted, nv);
 }
 
 // the getters' read-back of a map of nv voxels: keys unpacked into coordinates, covariances expanded from 6 to 9 (every output may be null)
@@ -961,25 +1014,107 @@ int check_vgicp_cuda_params(const apdgicp_vgicp_cuda_params* p) {
   return 0;
 }
 
-// VC6: the offsets of p (checked by the caller), 3 ints each
-void vc_offsets(const apdgicp_vgicp_cuda_params& p, std::vector<int32_t>& out) {
-  out.clear();
-  auto push = [&](int i, int j, int k) { out.push_back(i), out.push_back(j), out.push_back(k); };
-  if (p.neighbor_search == APDGICP_VGICP_DIRECT1) {
-    push(0, 0, 0);
-  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT7) {  // VC:55-64
-    push(0, 0, 0), push(1, 0, 0), push(-1, 0, 0), push(0, 1, 0), push(0, -1, 0), push(0, 0, 1), push(0, 0, -1);
-  } else if (p.neighbor_search == APDGICP_VGICP_DIRECT27) {  // VC:66-75
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++)
-        for (int k = 0; k < 3; k++) push(i - 1, j - 1, k - 1);
-  } else {  // VC:77-90
-    const int range = (int)std::ceil(p.search_radius);
-    for (int i = -range; i <= range; i++)
-      for (int j = -range; j <= range; j++)
-        for (int k = -range; k <= range; k++)
-          if (std::sqrt((double)(i * i + j * j + k * k)) <= p.search_radius + 1e-3) push(i, j, k);
+// One cloud of a preparation: its index in the engine's cloud list, where the prepared cloud goes, the device word that takes its kept count.
+struct VcJob {
+  int cloud;
+  VcPrepared* pc;
+  int* total;
+};
+
+// VC1 .. VC4 of every listed cloud (sorted, its descriptor uploaded, VC_K points or more), enqueued on the engine's stream with no wait in
+// between: the slot in the grid, the queries per wave by the points of all of them (as Engine::launch_knn).  A buffer that exists and is too
+// small may still be read by what is enqueued, so the stream is waited for once before one goes (*waited).  Reading the kept counts and the
+// k-NN error flag back, and marking the clouds ready, is the caller's: each handle kind has its own pinned words and its own count of waits.
+int vc_enqueue_prepare(Engine& e, const std::vector<VcJob>& jobs, int regularization, CachedTable& d_tab, CachedTable& d_ids, bool* waited) {
+  const int count = (int)jobs.size();
+  bool replaces = false;
+  int nmax = 0;
+  long long total = 0;
+  for (const VcJob& j : jobs) {
+    const VcPrepared& pc = *j.pc;
+    const size_t n = (size_t)e.clouds[j.cloud].n, nb = (n + VC_BLK - 1) / VC_BLK;
+    auto small = [](const DevBuf& d, size_t bytes) { return d.cap != 0 && bytes > d.cap; };
+    replaces |= small(pc.raw, n * 48) || small(pc.reg6, n * 48) || small(pc.flag, n) || small(pc.bsum, nb * 4) || small(pc.kpts, n * 16) || small(pc.kcov, n * 48) ||
+                small(pc.kept, n * 4) || small(pc.ident, n * 4);
+    nmax = std::max(nmax, e.clouds[j.cloud].n), total += e.clouds[j.cloud].n;
   }
+  *waited = replaces;
+  if (replaces) APD_HIP(hipStreamSynchronize(e.stream));
+  std::vector<VcbSlot> tab((size_t)count);
+  std::vector<int> ids((size_t)count);
+  for (int q = 0; q < count; q++) {
+    VcPrepared& pc = *jobs[q].pc;
+    const size_t n = (size_t)e.clouds[jobs[q].cloud].n, nb = (n + VC_BLK - 1) / VC_BLK;
+    pc.ready = false;
+    APD_TRY(pc.raw.ensure(n * 48));
+    APD_TRY(pc.reg6.ensure(n * 48));
+    APD_TRY(pc.flag.ensure(n));
+    APD_TRY(pc.bsum.ensure(nb * 4));
+    APD_TRY(pc.kpts.ensure(n * 16));  // (the buffers behind the compaction are sized for n kept points -- the count is not known yet)
+    APD_TRY(pc.kcov.ensure(n * 48));
+    APD_TRY(pc.kept.ensure(n * 4));
+    APD_TRY(pc.ident.ensure(n * 4));
+    tab[q] = VcbSlot{e.clouds[jobs[q].cloud].opts.as<float4>(), pc.raw.as<double>(), pc.reg6.as<double>(), pc.flag.as<unsigned char>(), pc.bsum.as<int>(), jobs[q].total,
+                     pc.kpts.as<float4>(), pc.kcov.as<double>(), pc.kept.as<int>(), pc.ident.as<int>(), (int)n, 0};
+    ids[q] = jobs[q].cloud;
+  }
+  APD_TRY(d_tab.upload(tab.data(), tab.size() * sizeof(VcbSlot), e.stream));
+  APD_TRY(d_ids.upload(ids.data(), ids.size() * sizeof(int), e.stream));
+  const CloudDesc* desc = e.d_desc.as<CloudDesc>();
+  const VcbSlot* dt = d_tab.as<VcbSlot>();
+  int* eflag = e.d_errflag.as<int>();
+  unsigned long long* stats = e.d_stats.as<unsigned long long>();
+  const int qpw = total >= 100000 ? 16 : total >= 40000 ? 8 : 4;
+  const dim3 kgrid((unsigned)((nmax + qpw - 1) / qpw), (unsigned)count), bgrid((unsigned)((nmax + VC_BLK - 1) / VC_BLK), (unsigned)count);
+  if (qpw == 16) hipLaunchKernelGGL(k_vcb_knn_raw<4>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, d_ids.as<int>(), dt, VC_K, eflag, stats);
+  else if (qpw == 8) hipLaunchKernelGGL(k_vcb_knn_raw<8>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, d_ids.as<int>(), dt, VC_K, eflag, stats);
+  else hipLaunchKernelGGL(k_vcb_knn_raw<16>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, d_ids.as<int>(), dt, VC_K, eflag, stats);
+  hipLaunchKernelGGL(k_vcb_regularize, bgrid, dim3(VC_BLK), 0, e.stream, dt, regularization);
+  hipLaunchKernelGGL(k_vcb_scan, dim3((unsigned)count), dim3(SCAN_BLK), 0, e.stream, dt);
+  hipLaunchKernelGGL(k_vcb_scatter, bgrid, dim3(VC_BLK), 0, e.stream, dt);
+  APD_HIP(hipGetLastError());
+  return 0;
+}
+
+// the k-NN error flag a preparation's read-back brought home
+int vc_knn_flag_error(Engine& e, int flag) {
+  APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
+  return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA k-NN: " + Engine::errflag_text(flag));
+}
+
+// VC4 for the getters: the kept count of a prepared cloud and, with kept_index given, the original indices
+int read_kept(hipStream_t stream, const VcPrepared& pc, int64_t* n_kept, int32_t* kept_index, int64_t capacity) {
+  *n_kept = pc.n_kept;
+  if (!kept_index || pc.n_kept == 0) return 0;
+  if (capacity < pc.n_kept) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+  APD_HIP(hipMemcpyAsync(kept_index, pc.kept.p, (size_t)pc.n_kept * 4, hipMemcpyDeviceToHost, stream));
+  APD_HIP(hipStreamSynchronize(stream));
+  return 0;
+}
+
+// VC2 / VC3 for the getters: per kept point the raw covariance (6 doubles) and the regularised one (9), either may be null
+int read_prepared_covariances(hipStream_t stream, const VcPrepared& pc, double* raw_n6, double* reg_n9, int64_t capacity) {
+  const int64_t nk = pc.n_kept;
+  if (capacity < nk) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
+  if (nk == 0) return 0;
+  std::vector<double> all(raw_n6 ? (size_t)pc.n * 6 : 0), k6(reg_n9 ? (size_t)nk * 6 : 0);
+  std::vector<int> kept(raw_n6 ? (size_t)nk : 0);
+  if (raw_n6) {
+    APD_HIP(hipMemcpyAsync(all.data(), pc.raw.p, all.size() * 8, hipMemcpyDeviceToHost, stream));
+    APD_HIP(hipMemcpyAsync(kept.data(), pc.kept.p, kept.size() * 4, hipMemcpyDeviceToHost, stream));
+  }
+  if (reg_n9) APD_HIP(hipMemcpyAsync(k6.data(), pc.kcov.p, k6.size() * 8, hipMemcpyDeviceToHost, stream));
+  APD_HIP(hipStreamSynchronize(stream));
+  for (int64_t j = 0; j < nk && raw_n6; j++) {
+    if (kept[j] < 0 || kept[j] >= pc.n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept index");
+    memcpy(raw_n6 + 6 * j, &all[6 * (size_t)kept[j]], 6 * sizeof(double));
+  }
+  for (int64_t j = 0; j < nk && reg_n9; j++) {  // kcov: [6][n_kept]
+    const double xx = k6[j], xy = k6[nk + j], xz = k6[2 * nk + j], yy = k6[3 * nk + j], yz = k6[4 * nk + j], zz = k6[5 * nk + j];
+    double* o = reg_n9 + 9 * j;
+    o[0] = xx, o[1] = xy, o[2] = xz, o[3] = xy, o[4] = yy, o[5] = yz, o[6] = xz, o[7] = yz, o[8] = zz;
+  }
+  return 0;
 }
 
 // VC1 .. VC4: the prepared cloud `which`.  One wait: the kept count and the error flag come back together.
@@ -987,54 +1122,22 @@ int vc_prepare_cloud(apdgicp_handle* h, int which) {
   Engine& e = h->eng;
   VcState& v = h->vc;
   if (e.clouds.size() < 2 || e.clouds[which].n <= 0) return fail(APDGICP_ERR_NO_INPUT, std::string(cloud_name(which)) + " cloud is not set");
-  VcState::Prepared& pc = v.pc[which];
+  VcPrepared& pc = v.pc[which];
   if (pc.ready && pc.pts_gen == h->cloud_gen[which] && pc.reg == v.prm.regularization) return 0;
-  if (e.clouds[which].n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "cloud has fewer points than k_correspondences");
+  const int n = e.clouds[which].n;
+  if (n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "cloud has fewer points than k_correspondences");
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.upload_desc());  // (sorts what is not sorted yet)
-  const Engine::Cloud& c = e.clouds[which];
-  const int n = c.n, nb = (n + VC_BLK - 1) / VC_BLK;
-  pc.ready = false;
   v.have_lin = false;
-  const size_t b48 = (size_t)n * 48, b16 = (size_t)n * 16, b4 = (size_t)n * 4;
-  if (b48 > pc.raw.cap || b48 > pc.reg6.cap || (size_t)n > pc.flag.cap || (size_t)nb * 4 > pc.bsum.cap || b16 > pc.kpts.cap || b48 > pc.kcov.cap || b4 > pc.kept.cap ||
-      b4 > pc.ident.cap || 32 > v.scal.cap)
-    APD_HIP(hipStreamSynchronize(e.stream));  // (a buffer about to be replaced may still be read)
-  APD_TRY(pc.raw.ensure(b48));
-  APD_TRY(pc.reg6.ensure(b48));
-  APD_TRY(pc.flag.ensure((size_t)n));
-  APD_TRY(pc.bsum.ensure((size_t)nb * 4));
-  APD_TRY(pc.kpts.ensure(b16));
-  APD_TRY(pc.kcov.ensure(b48));
-  APD_TRY(pc.kept.ensure(b4));
-  APD_TRY(pc.ident.ensure(b4));
-  APD_TRY(v.scal.ensure(32));  // ints: [0, 4) a map build, [4] n_kept of a preparation
-  APD_TRY(e.d_ids.upload(&which, sizeof(int), e.cstream));
-  const CloudDesc* desc = e.d_desc.as<CloudDesc>();
-  const int* ids = e.d_ids.as<int>();
-  int* eflag = e.d_errflag.as<int>();
-  unsigned long long* stats = e.d_stats.as<unsigned long long>();
-  double* raw = pc.raw.as<double>();
-  const int qpw = n >= 100000 ? 16 : n >= 40000 ? 8 : 4;  // (as Engine::launch_knn)
-  const dim3 grid((unsigned)((n + qpw - 1) / qpw), 1u);
-  if (qpw == 16) hipLaunchKernelGGL(k_vc_knn_raw<4>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
-  else if (qpw == 8) hipLaunchKernelGGL(k_vc_knn_raw<8>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
-  else hipLaunchKernelGGL(k_vc_knn_raw<16>, grid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, VC_K, eflag, stats, raw);
-  int* d_total = v.scal.as<int>() + 4;
-  hipLaunchKernelGGL(k_vc_regularize, dim3(nb), dim3(VC_BLK), 0, e.stream, raw, n, (int)v.prm.regularization, pc.flag.as<unsigned char>(), pc.reg6.as<double>(), pc.bsum.as<int>());
-  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, pc.bsum.as<int>(), nb, d_total);
-  hipLaunchKernelGGL(k_vc_scatter, dim3(nb), dim3(VC_BLK), 0, e.stream, c.opts.as<float4>(), pc.reg6.as<double>(), pc.flag.as<unsigned char>(), n, pc.bsum.as<int>(), d_total,
-                     pc.kpts.as<float4>(), pc.kcov.as<double>(), pc.kept.as<int>(), pc.ident.as<int>());
-  APD_HIP(hipGetLastError());
+  APD_TRY(v.scal.ensure(32));
+  int* d_total = v.scal.as<int>() + 4 + which;
+  bool waited = false;
+  APD_TRY(vc_enqueue_prepare(e, {VcJob{which, &pc, d_total}}, v.prm.regularization, v.prep_tab[which], v.prep_ids[which], &waited));
   int* hw = e.h_probe.as<int>();
   APD_HIP(hipMemcpyAsync(hw, d_total, sizeof(int), hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipMemcpyAsync(hw + 1, eflag, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(hw + 1, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
-  if (hw[1]) {
-    const int flag = hw[1];
-    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
-    return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA k-NN: " + Engine::errflag_text(flag));
-  }
+  if (hw[1]) return vc_knn_flag_error(e, hw[1]);
   if (hw[0] < 0 || hw[0] > n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept count");
   pc.n = n, pc.n_kept = hw[0];
   pc.pts_gen = h->cloud_gen[which], pc.reg = v.prm.regularization, pc.id = ++v.preps;
@@ -1047,27 +1150,19 @@ int vc_build_map(apdgicp_handle* h) {
   Engine& e = h->eng;
   VcState& v = h->vc;
   APD_TRY(vc_prepare_cloud(h, kTgt));
-  const VcState::Prepared& t = v.pc[kTgt];
+  const VcPrepared& t = v.pc[kTgt];
   if (v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution) return 0;
   v.map_built = v.have_lin = false;
   int nv = 0;
-  if (t.n_kept > 0) {
+  if (t.n_kept > 0) {  // (no kept point: an empty map, no sort)
     const int n = t.n_kept;
-    APD_HIP(hipStreamSynchronize(e.stream));  // (buffers below may be replaced)
-    APD_TRY(h->sort.ensure(n));
     VoxSorted s;
-    APD_TRY(enqueue_voxel_sort(e.stream, h->sort, t.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>(), &s));
-    APD_HIP(hipGetLastError());
-    int hs[4];
-    APD_HIP(hipMemcpyAsync(hs, v.scal.p, sizeof(hs), hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    if (hs[0] != kVgBadNone) {  // VC4: the message names the point by its index in the caller's cloud
+    auto point_name = [&](int j) {  // VC4: the message names the point by its index in the caller's cloud (an error path: its own wait)
       int orig = -1;
-      if (hs[0] >= 0 && hs[0] < n) APD_HIP(hipMemcpy(&orig, t.kept.as<int>() + hs[0], sizeof(int), hipMemcpyDeviceToHost));
-      return voxel_key_range_error("FAST_VGICP_CUDA: target point " + std::to_string(orig), v.prm.resolution);
-    }
-    if (hs[1] < 1 || hs[1] > n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent voxel count");
-    nv = hs[1];
+      if (j >= 0 && j < n && hipMemcpy(&orig, t.kept.as<int>() + j, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) orig = -1;
+      return "target point " + std::to_string(orig);
+    };
+    APD_TRY(handle_sort_voxels(h, t.kpts.as<float4>(), n, v.prm.resolution, v.scal, "FAST_VGICP_CUDA: ", point_name, &s, &nv));
     APD_TRY(v.buf.ensure((size_t)nv, false));
     hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, h->sort.bsum.as<int>(), t.kpts.as<float4>(), t.kcov.as<double>(), t.ident.as<int>(),
                        v.buf.vkeys.as<unsigned long long>(), v.buf.vcount.as<int>(), v.buf.vmean.as<double>(), v.buf.vcov.as<double>(), nv);
@@ -1081,22 +1176,17 @@ int vc_build_map(apdgicp_handle* h) {
 
 // both prepared clouds, the map and the offset table: everything k_vc_linearize reads
 int vc_prepare(apdgicp_handle* h) {
-  VcState& v = h->vc;
   APD_TRY(vc_prepare_cloud(h, kSrc));
   APD_TRY(vc_build_map(h));
-  if (v.offs.empty() || v.offs_search != v.prm.neighbor_search || v.offs_radius != v.prm.search_radius) {
-    vc_offsets(v.prm, v.offs);
-    v.offs_search = v.prm.neighbor_search, v.offs_radius = v.prm.search_radius;
-  }
-  return v.d_offs.upload(v.offs.data(), v.offs.size() * sizeof(int32_t), h->eng.stream);
+  return h->vc.offs.ensure(h->vc.prm, h->eng.stream);
 }
 
 int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
   APD_TRY(vc_prepare(h));
   Engine& e = h->eng;
   VcState& v = h->vc;
-  const VcState::Prepared& s = v.pc[kSrc];
-  const int n = s.n_kept, noff = (int)(v.offs.size() / 3), nblk = (n + VG_BLK - 1) / VG_BLK;
+  const VcPrepared& s = v.pc[kSrc];
+  const int n = s.n_kept, noff = v.offs.count(), nblk = (n + VG_BLK - 1) / VG_BLK;
   APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)n * noff * 4, (size_t)nblk * VG_RED * 8));
   APD_TRY(v.T.ensure(24 * sizeof(double)));
   APD_TRY(v.out.ensure(64 * sizeof(double)));
@@ -1105,7 +1195,7 @@ int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   const int want = H && b ? 1 : 0;
   if (nblk > 0)
     hipLaunchKernelGGL(k_vc_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), v.T.as<double>(),
-                       v.prm.resolution, v.d_offs.as<int>(), noff, want, v.corr.as<int>(), v.part.as<double>());
+                       v.prm.resolution, v.offs.dev.as<int>(), noff, want, v.corr.as<int>(), v.part.as<double>());
   APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));  // (no kept source point: no block rows, every sum 0)
   v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
   v.lin_src_id = s.id, v.lin_build = v.builds;
@@ -1115,7 +1205,7 @@ int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
 // VC8: the frozen state must still describe what the handle holds
 bool vc_frozen_ok(const apdgicp_handle* h) {
   const VcState& v = h->vc;
-  const VcState::Prepared &s = v.pc[kSrc], &t = v.pc[kTgt];
+  const VcPrepared &s = v.pc[kSrc], &t = v.pc[kTgt];
   return v.have_lin && s.ready && s.pts_gen == h->cloud_gen[kSrc] && s.reg == v.prm.regularization && s.id == v.lin_src_id && s.n_kept == v.n_src_lin && t.ready &&
          t.pts_gen == h->cloud_gen[kTgt] && t.reg == v.prm.regularization && v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution && v.lin_build == v.builds;
 }
@@ -1124,7 +1214,7 @@ int vc_error(apdgicp_handle* h, const double* T16, double* cost) {
   Engine& e = h->eng;
   VcState& v = h->vc;
   if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds, regularisation and voxel map the handle holds now");
-  const VcState::Prepared& s = v.pc[kSrc];
+  const VcPrepared& s = v.pc[kSrc];
   const int n = s.n_kept, noff = v.noff_lin, nblk = (n + VG_BLK - 1) / VG_BLK;
   APD_HIP(hipSetDevice(e.device));
   double t24[24];
@@ -1412,6 +1502,18 @@ int ic_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return 0;
 }
 
+// the align of the mode that is on (APD has two loops of its own: apdgicp_align, apdgicp_align_host_loop)
+int mode_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  switch (h->mode) {
+    case Mode::ICP: return ic_align(h, guess, out);
+    case Mode::NDT: return nd_align(h, guess, out);
+    case Mode::VGICP: return vg_align(h, guess, out);
+    case Mode::VGICP_CUDA: return vc_align(h, guess, out);
+    case Mode::APD: break;
+  }
+  return fail(APDGICP_ERR_INTERNAL, "no mode is on");
+}
+
 int check_icp_params(const apdgicp_icp_params* p) {
   if (!p) return 0;
   if (p->min_correspondences < 1) return fail(APDGICP_ERR_INVALID_ARG, "ICP: min_correspondences must be at least 1");
@@ -1642,7 +1744,7 @@ int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
 // one slot's map for the getters: sorted, covariances computed, built
 int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
   Engine& e = b->eng;
-  if (!b->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_batch_set_vgicp)");
+  if (b->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, true);
   if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.pool_leave());
@@ -1729,7 +1831,7 @@ int ndb_build_maps(apdgicp_batch* b, const std::vector<int>& slots) {
 // one slot's map for the getters: sorted, built
 int ndb_slot_map(apdgicp_batch* b, int32_t cloud) {
   Engine& e = b->eng;
-  if (!b->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_batch_set_ndt)");
+  if (b->mode != Mode::NDT) return mode_is_off(Mode::NDT, true);
   if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.pool_leave());
@@ -1802,13 +1904,13 @@ int vcb_ensure_slots(apdgicp_batch* b) {
 }
 
 bool vcb_prepared(const apdgicp_batch* b, int slot) {
-  const VcbState::Slot& sl = b->vc.slots[slot];
-  return sl.ready && sl.pts_gen == b->eng.clouds[slot].pts_gen && sl.reg == b->vc.prm.regularization;
+  const VcPrepared& pc = b->vc.slots[slot].pc;
+  return pc.ready && pc.pts_gen == b->eng.clouds[slot].pts_gen && pc.reg == b->vc.prm.regularization;
 }
 
 bool vcb_map_current(const apdgicp_batch* b, int slot) {
   const VcbState::Slot& sl = b->vc.slots[slot];
-  return vcb_prepared(b, slot) && sl.map_built && sl.map_prep_id == sl.id && sl.map_res == b->vc.prm.resolution;
+  return vcb_prepared(b, slot) && sl.map_built && sl.map_prep_id == sl.pc.id && sl.map_res == b->vc.prm.resolution;
 }
 
 // VC11: the prepared clouds of the listed slots (sorted) that are not current.  The launches of all of them go out with no wait in between;
@@ -1824,75 +1926,32 @@ int vcb_prepare_slots(apdgicp_batch* b, const std::vector<int>& slots) {
   }
   if (todo.empty()) return 0;
   std::sort(todo.begin(), todo.end());
-  const int lo = todo.front(), hi = todo.back(), count = (int)todo.size();
+  const int lo = todo.front(), hi = todo.back();
   APD_TRY(device_loop_ensure_words(b, 4 + (size_t)(hi - lo + 1)));
-  bool replaces = false;  // a buffer that exists and is too small may still be read by what is enqueued: wait before it goes
-  int nmax = 0;
-  long long total = 0;
+  std::vector<VcJob> jobs;
   for (int t : todo) {
-    const VcbState::Slot& sl = v.slots[t];
-    const size_t n = (size_t)e.clouds[t].n, nb = (n + VC_BLK - 1) / VC_BLK;
-    auto small = [](const DevBuf& d, size_t bytes) { return d.cap != 0 && bytes > d.cap; };
-    replaces |= small(sl.raw, n * 48) || small(sl.reg6, n * 48) || small(sl.flag, n) || small(sl.bsum, nb * 4) || small(sl.kpts, n * 16) || small(sl.kcov, n * 48) ||
-                small(sl.kept, n * 4) || small(sl.ident, n * 4);
-    nmax = std::max(nmax, e.clouds[t].n), total += e.clouds[t].n;
+    v.slots[t].map_built = false;
+    jobs.push_back(VcJob{t, &v.slots[t].pc, v.nk.as<int>() + t});
   }
-  if (replaces) {
-    APD_HIP(hipStreamSynchronize(e.stream));
-    v.prep_waits++;
-  }
-  std::vector<VcbSlot> tab((size_t)count);
-  for (int q = 0; q < count; q++) {
-    const int t = todo[q];
-    VcbState::Slot& sl = v.slots[t];
-    const size_t n = (size_t)e.clouds[t].n, nb = (n + VC_BLK - 1) / VC_BLK;
-    sl.ready = sl.map_built = false;
-    APD_TRY(sl.raw.ensure(n * 48));
-    APD_TRY(sl.reg6.ensure(n * 48));
-    APD_TRY(sl.flag.ensure(n));
-    APD_TRY(sl.bsum.ensure(nb * 4));
-    APD_TRY(sl.kpts.ensure(n * 16));  // (VC11: the buffers behind the compaction are sized for n kept points -- the count is not known yet)
-    APD_TRY(sl.kcov.ensure(n * 48));
-    APD_TRY(sl.kept.ensure(n * 4));
-    APD_TRY(sl.ident.ensure(n * 4));
-    tab[q] = VcbSlot{e.clouds[t].opts.as<float4>(), sl.raw.as<double>(), sl.reg6.as<double>(), sl.flag.as<unsigned char>(), sl.bsum.as<int>(), v.nk.as<int>() + t,
-                     sl.kpts.as<float4>(), sl.kcov.as<double>(), sl.kept.as<int>(), sl.ident.as<int>(), (int)n, 0};
-  }
-  APD_TRY(v.prep_tab.upload(tab.data(), tab.size() * sizeof(VcbSlot), e.stream));
-  APD_TRY(v.prep_ids.upload(todo.data(), todo.size() * sizeof(int), e.stream));
-  const CloudDesc* desc = e.d_desc.as<CloudDesc>();
-  const int* ids = v.prep_ids.as<int>();
-  const VcbSlot* dt = v.prep_tab.as<VcbSlot>();
-  int* eflag = e.d_errflag.as<int>();
-  unsigned long long* stats = e.d_stats.as<unsigned long long>();
-  const int qpw = total >= 100000 ? 16 : total >= 40000 ? 8 : 4;  // (as Engine::launch_knn for a batch: by the points of all clouds)
-  const dim3 kgrid((unsigned)((nmax + qpw - 1) / qpw), (unsigned)count), bgrid((unsigned)((nmax + VC_BLK - 1) / VC_BLK), (unsigned)count);
-  if (qpw == 16) hipLaunchKernelGGL(k_vcb_knn_raw<4>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
-  else if (qpw == 8) hipLaunchKernelGGL(k_vcb_knn_raw<8>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
-  else hipLaunchKernelGGL(k_vcb_knn_raw<16>, kgrid, dim3(64), knn_coop_lds_bytes(qpw), e.stream, desc, ids, dt, VC_K, eflag, stats);
-  hipLaunchKernelGGL(k_vcb_regularize, bgrid, dim3(VC_BLK), 0, e.stream, dt, (int)v.prm.regularization);
-  hipLaunchKernelGGL(k_vcb_scan, dim3((unsigned)count), dim3(SCAN_BLK), 0, e.stream, dt);
-  hipLaunchKernelGGL(k_vcb_scatter, bgrid, dim3(VC_BLK), 0, e.stream, dt);
-  APD_HIP(hipGetLastError());
+  bool waited = false;
+  const int rc = vc_enqueue_prepare(e, jobs, v.prm.regularization, v.prep_tab, v.prep_ids, &waited);
+  if (waited) v.prep_waits++;
+  APD_TRY(rc);
   int* hw = b->loop.h_words.as<int>();
   APD_HIP(hipMemcpyAsync(hw + 4, v.nk.as<int>() + lo, (size_t)(hi - lo + 1) * 4, hipMemcpyDeviceToHost, e.stream));
-  APD_HIP(hipMemcpyAsync(hw + 2, eflag, sizeof(int), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(hw + 2, e.d_errflag.p, sizeof(int), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   v.prep_waits++;
-  if (hw[2]) {
-    const int flag = hw[2];
-    APD_HIP(hipMemsetAsync(e.d_errflag.p, 0, sizeof(int), e.stream));
-    return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA k-NN: " + Engine::errflag_text(flag));
-  }
+  if (hw[2]) return vc_knn_flag_error(e, hw[2]);
   for (int t : todo) {
     const int nk = hw[4 + (t - lo)];
     if (nk < 0 || nk > e.clouds[t].n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept count");
   }
   for (int t : todo) {
-    VcbState::Slot& sl = v.slots[t];
-    sl.n = e.clouds[t].n, sl.n_kept = hw[4 + (t - lo)];
-    sl.pts_gen = e.clouds[t].pts_gen, sl.reg = v.prm.regularization, sl.id = ++v.preps;
-    sl.ready = true;
+    VcPrepared& pc = v.slots[t].pc;
+    pc.n = e.clouds[t].n, pc.n_kept = hw[4 + (t - lo)];
+    pc.pts_gen = e.clouds[t].pts_gen, pc.reg = v.prm.regularization, pc.id = ++v.preps;
+    pc.ready = true;
   }
   return 0;
 }
@@ -1905,33 +1964,34 @@ int vcb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
   for (int t : targets) {
     VcbState::Slot& sl = v.slots[t];
     if (vcb_map_current(b, t)) continue;
-    if (sl.n_kept > 0) {
+    if (sl.pc.n_kept > 0) {
       full.push_back(t);
       continue;
     }
     // no kept point: an empty map, no sort (the shared builder calls a voxel count of 0 inconsistent) -- the device word the tick reads is 0
     APD_HIP(hipMemsetAsync(v.scal.as<int>() + 4 * (size_t)t, 0, 16, e.stream));
     sl.nv = 0;
-    sl.map_built = true, sl.map_prep_id = sl.id, sl.map_res = v.prm.resolution;
+    sl.map_built = true, sl.map_prep_id = sl.pc.id, sl.map_res = v.prm.resolution;
     v.builds++;
   }
   if (full.empty()) return 0;
   v.map_waits++;
   const std::function<int(int, int)> caller_index = [&](int t, int j) -> int {  // kept point j of slot t in the caller's cloud (an error path: its own wait)
     int orig = -1;
-    if (j >= 0 && j < v.slots[t].n_kept && hipMemcpy(&orig, v.slots[t].kept.as<int>() + j, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) orig = -1;
+    if (j >= 0 && j < v.slots[t].pc.n_kept && hipMemcpy(&orig, v.slots[t].pc.kept.as<int>() + j, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) orig = -1;
     return orig;
   };
   return batch_build_maps(
-      b, full, "FAST_VGICP_CUDA: ", v.prm.resolution, v.scal, [&](int) { return false; }, [&](int t) { return (size_t)v.slots[t].n_kept * 48 > v.slots[t].buf.vcov.cap; },
+      b, full, "FAST_VGICP_CUDA: ", v.prm.resolution, v.scal, [&](int) { return false; }, [&](int t) { return (size_t)v.slots[t].pc.n_kept * 48 > v.slots[t].buf.vcov.cap; },
       [&](int t) -> int {
         VcbState::Slot& sl = v.slots[t];
-        const int n = sl.n_kept;
+        const VcPrepared& pc = sl.pc;
+        const int n = pc.n_kept;
         sl.map_built = false;
         APD_TRY(sl.buf.ensure((size_t)n, false));
         VoxSorted s;
-        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, sl.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
-        hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), sl.kpts.as<float4>(), sl.kcov.as<double>(), sl.ident.as<int>(),
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, pc.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), pc.kpts.as<float4>(), pc.kcov.as<double>(), pc.ident.as<int>(),
                            sl.buf.vkeys.as<unsigned long long>(), sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vcov.as<double>(), n);
         APD_HIP(hipGetLastError());
         return 0;
@@ -1939,18 +1999,16 @@ int vcb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
       [&](int t, int nv) {
         VcbState::Slot& sl = v.slots[t];
         sl.nv = nv;
-        sl.map_built = true, sl.map_prep_id = sl.id, sl.map_res = v.prm.resolution;
+        sl.map_built = true, sl.map_prep_id = sl.pc.id, sl.map_res = v.prm.resolution;
         v.builds++;
       },
       nullptr, &caller_index);
 }
 
-static const char* const kVcbOff = "FAST_VGICP_CUDA is off (apdgicp_batch_set_vgicp_cuda)";
-
 // one slot for the getters: sorted, prepared, and with want_map its map built
 int vcb_slot(apdgicp_batch* b, int32_t cloud, bool want_map) {
   Engine& e = b->eng;
-  if (!b->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcbOff);
+  if (b->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, true);
   if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.pool_leave());
@@ -1981,17 +2039,14 @@ int vcb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   v.phase_ms[0] = ms_since(t0), t0 = clock::now();
   APD_TRY(vcb_build_maps(b, targets));
   v.phase_ms[1] = ms_since(t0), t0 = clock::now();
-  if (v.offs.empty() || v.offs_search != v.prm.neighbor_search || v.offs_radius != v.prm.search_radius) {
-    vc_offsets(v.prm, v.offs);
-    v.offs_search = v.prm.neighbor_search, v.offs_radius = v.prm.search_radius;
-  }
-  APD_TRY(v.d_offs.upload(v.offs.data(), v.offs.size() * sizeof(int32_t), e.stream));
-  const int noff = (int)(v.offs.size() / 3);
+  APD_TRY(v.offs.ensure(v.prm, e.stream));
+  const int noff = v.offs.count();
   std::vector<VgbPair> tab(np);
   std::vector<int> nks(np);
   int nk_max = 0;
   for (int i = 0; i < np; i++) {
-    const VcbState::Slot &s = v.slots[e.h_pairs[i].src], &t = v.slots[e.h_pairs[i].tgt];
+    const VcPrepared& s = v.slots[e.h_pairs[i].src].pc;
+    const VcbState::Slot& t = v.slots[e.h_pairs[i].tgt];
     tab[i] = VgbPair{s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), s.n_kept, 0, t.buf.map(v.scal.as<int>() + 4 * (size_t)e.h_pairs[i].tgt + 1)};
     nks[i] = s.n_kept;
     nk_max = std::max(nk_max, s.n_kept);
@@ -2006,7 +2061,7 @@ int vcb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   ResultRec* recs = e.d_results.as<ResultRec>();
   int* done = b->loop.done.as<int>();
   APD_TRY(device_loop_run(b, [&]() {
-    hipLaunchKernelGGL(k_vcb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution, v.d_offs.as<int>(), noff,
+    hipLaunchKernelGGL(k_vcb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution, v.offs.dev.as<int>(), noff,
                        v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
     hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, done);
   }));
@@ -2128,16 +2183,11 @@ int icb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
 // the last align in this mode must still describe the slots as they are
 int icb_check_have(apdgicp_batch* b, int64_t pair) {
   const IcbState& v = b->ic;
-  if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_batch_set_icp)");
+  if (b->mode != Mode::ICP) return mode_is_off(Mode::ICP, true);
   if (!v.have || v.have_epoch != b->eng.pts_epoch) return fail(APDGICP_ERR_NO_INPUT, "no align in this mode of the clouds the handle holds now");
   if (pair < 0 || pair >= (int64_t)v.src.size()) return fail(APDGICP_ERR_INVALID_ARG, "pair is not one of the last align");
   return 0;
 }
-
-const char* const kVgbNoPipeline = "voxelized GICP on a batch handle (apdgicp_batch_set_vgicp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
-const char* const kNdbNoPipeline = "NDT on a batch handle (apdgicp_batch_set_ndt) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
-const char* const kVcbNoPipeline = "FAST_VGICP_CUDA on a batch handle (apdgicp_batch_set_vgicp_cuda) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
-const char* const kIcbNoPipeline ="point-to-point ICP on a batch handle (apdgicp_batch_set_icp) runs one batch at a time: align_enqueue / align_collect / pump are not offered";
 
 // what the single and the batch setters refuse (null: nothing to check -- the mode is being switched off)
 int check_vgicp_params(const apdgicp_vgicp_params* p) {
@@ -2165,6 +2215,33 @@ int batch_enter_device_loop_mode(apdgicp_batch* b) {
     APD_TRY(b->eng.finish_align());
   }
   if (!b->loop.chunk) b->loop.chunk = std::max(1, std::min(1024, env_int("APDGICP_VGB_CHUNK", kVgbChunk)));
+  return 0;
+}
+
+// The one writer of apdgicp_handle::mode, with every effect of leaving one mode and entering another ("Mode transitions").  A setter
+// that changes the parameters of the mode that is already on does not come through here.
+void set_mode(apdgicp_handle* h, Mode to) {
+  const Mode from = h->mode;
+  if (from == to) return;
+  h->have_corr = false;  // (the APD kernels' correspondences are those of their own last linearize, and none is left)
+  if (from == Mode::ICP || to == Mode::ICP) h->pair_ready = false;  // (the pair of the other side was set up with / without covariances)
+  switch (to) {
+    case Mode::APD: break;
+    case Mode::VGICP: h->vg.have_lin = false; break;
+    case Mode::VGICP_CUDA: h->vc.have_lin = false, h->vc.reset_final_H(); break;
+    case Mode::NDT: h->nd.have_lin = false, h->nd.reset_final_H(); break;
+    case Mode::ICP: break;  // (apdgicp_set_icp forgets the last estimate with every enabling call, entering or not)
+  }
+  h->mode = to;
+}
+
+// ... and of apdgicp_batch::mode.  Fails, with the mode unchanged, when the APD path's aligns in flight cannot be finished.
+int set_mode(apdgicp_batch* b, Mode to) {
+  const Mode from = b->mode;
+  if (from == to) return 0;
+  if (from == Mode::APD) APD_TRY(batch_enter_device_loop_mode(b));
+  if (from == Mode::ICP) b->eng.poses_of_align = false;  // IC16: the engine's pair state holds that mode's identity poses, not an align's
+  b->mode = to;  // (what the ICP and FAST_VGICP_CUDA getters may read goes with every enabling call of their setters, entering or not)
   return 0;
 }
 
@@ -2385,10 +2462,13 @@ int apdgicp_set_covariances(apdgicp_handle* h, int which, const double* in, int6
 int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], double b[6], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
-    if (h->nd.on) return nd_linearize(h, T, H, b, cost, nullptr);
-    if (h->vg.on) return vg_linearize(h, T, H, b, cost, nullptr);
-    if (h->vc.on) return vc_linearize(h, T, H, b, cost, nullptr);
+    switch (h->mode) {
+      case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
+      case Mode::NDT: return nd_linearize(h, T, H, b, cost, nullptr);
+      case Mode::VGICP: return vg_linearize(h, T, H, b, cost, nullptr);
+      case Mode::VGICP_CUDA: return vc_linearize(h, T, H, b, cost, nullptr);
+      case Mode::APD: break;
+    }
     APD_TRY(ensure_pair(h));
     APD_TRY(h->eng.probe_linearize(T, H, b, cost, nullptr));
     h->have_corr = true;
@@ -2399,10 +2479,13 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
 int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
   return guarded([&]() -> int {
     if (!h || !T || !cost) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
-    if (h->nd.on) return nd_error(h, T, cost);
-    if (h->vg.on) return vg_error(h, T, cost);
-    if (h->vc.on) return vc_error(h, T, cost);
+    switch (h->mode) {
+      case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
+      case Mode::NDT: return nd_error(h, T, cost);
+      case Mode::VGICP: return vg_error(h, T, cost);
+      case Mode::VGICP_CUDA: return vc_error(h, T, cost);
+      case Mode::APD: break;
+    }
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
     return h->eng.probe_error(T, cost);
   });
@@ -2411,10 +2494,13 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
 int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int64_t n) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
-    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps its own correspondences: apdgicp_icp_get_correspondences");
-    if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
-    if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
-    if (h->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA has no point correspondences: apdgicp_vgicp_cuda_get_correspondences");
+    switch (h->mode) {
+      case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps its own correspondences: apdgicp_icp_get_correspondences");
+      case Mode::NDT: return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
+      case Mode::VGICP: return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
+      case Mode::VGICP_CUDA: return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA has no point correspondences: apdgicp_vgicp_cuda_get_correspondences");
+      case Mode::APD: break;
+    }
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -2434,10 +2520,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
 int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps no per-point Mahalanobis matrices");
-    if (h->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, "NDT keeps no per-point Mahalanobis matrices");
-    if (h->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP keeps no per-point Mahalanobis matrices");
-    if (h->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA keeps no per-point Mahalanobis matrices");
+    if (h->mode != Mode::APD) return fail(APDGICP_ERR_UNSUPPORTED, std::string(kModeText[(int)h->mode].name) + " keeps no per-point Mahalanobis matrices");
     Engine& e = h->eng;
     if (!h->pair_ready || !h->have_corr) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n != e.clouds[kSrc].n) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -2462,10 +2545,7 @@ int apdgicp_get_mahalanobis(apdgicp_handle* h, double* out, int64_t n) {
 int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (h->ic.on) return ic_align(h, guess, out);
-    if (h->nd.on) return nd_align(h, guess, out);
-    if (h->vg.on) return vg_align(h, guess, out);
-    if (h->vc.on) return vc_align(h, guess, out);
+    if (h->mode != Mode::APD) return mode_align(h, guess, out);
     float g[16];
     if (guess) memcpy(g, guess, sizeof(g));
     else identity16(g);
@@ -2499,10 +2579,7 @@ int apdgicp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out)
 int apdgicp_align_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return guarded([&]() -> int {
     if (!h || !out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (h->ic.on) return ic_align(h, guess, out);
-    if (h->nd.on) return nd_align(h, guess, out);
-    if (h->vg.on) return vg_align(h, guess, out);
-    if (h->vc.on) return vc_align(h, guess, out);
+    if (h->mode != Mode::APD) return mode_align(h, guess, out);
     APD_TRY(ensure_pair(h));
     Engine& e = h->eng;
     return host_loop(
@@ -2522,33 +2599,28 @@ void apdgicp_vgicp_default_params(apdgicp_vgicp_params* p) {
 int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   VgState& v = h->vg;
-  if (!p) {  // back to the APD-GICP / plain GICP kernels: their correspondences are those of their own last linearize, if any was left
-    if (v.on) h->have_corr = false;
-    v.on = false;
+  if (!p) {  // back to the APD-GICP / plain GICP kernels (a no-op while another mode is on)
+    if (h->mode == Mode::VGICP) set_mode(h, Mode::APD);
     return 0;
   }
   APD_TRY(check_vgicp_params(p));
-  if (!v.on || p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
-  if (!v.on) h->have_corr = false;
+  if (p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
   v.prm = *p;
-  v.on = true;
-  h->nd.on = false;  // N9: the two modes are exclusive
-  h->ic.on = false;  // IC9: likewise
-  h->vc.on = false;  // VC10: likewise
+  set_mode(h, Mode::VGICP);
   return 0;
 }
 
 int apdgicp_get_vgicp(const apdgicp_handle* h, apdgicp_vgicp_params* p, int* enabled) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   if (p) *p = h->vg.prm;
-  if (enabled) *enabled = h->vg.on ? 1 : 0;
+  if (enabled) *enabled = h->mode == Mode::VGICP ? 1 : 0;
   return 0;
 }
 
 int apdgicp_vgicp_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
   return guarded([&]() -> int {
     if (!h || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (!h->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    if (h->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, false);
     APD_TRY(vg_build_map(h));
     *n_voxels = h->vg.n_vox;
     return 0;
@@ -2558,7 +2630,7 @@ int apdgicp_vgicp_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
 int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
-    if (!h->vg.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    if (h->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, false);
     APD_TRY(vg_build_map(h));
     return read_voxels(h->eng.stream, h->vg.buf, h->vg.n_vox, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
   });
@@ -2569,7 +2641,7 @@ int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, i
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     VgState& v = h->vg;
     Engine& e = h->eng;
-    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "voxelized GICP is off (apdgicp_set_vgicp)");
+    if (h->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, false);
     if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_source does not match the source size");
     APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_source * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
@@ -2598,29 +2670,23 @@ void apdgicp_vgicp_cuda_default_params(apdgicp_vgicp_cuda_params* p) {
 int apdgicp_set_vgicp_cuda(apdgicp_handle* h, const apdgicp_vgicp_cuda_params* p) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   VcState& v = h->vc;
-  if (!p) {  // back to what apdgicp_params says: the APD kernels' correspondences are those of their own last linearize, if any was left
-    if (v.on) h->have_corr = false;
-    v.on = false;
+  if (!p) {  // back to what apdgicp_params says (a no-op while another mode is on)
+    if (h->mode == Mode::VGICP_CUDA) set_mode(h, Mode::APD);
     return 0;
   }
   APD_TRY(check_vgicp_cuda_params(p));
   const bool same_offsets = p->neighbor_search == v.prm.neighbor_search && (p->neighbor_search != APDGICP_VGICP_CUDA_DIRECT_RADIUS || p->search_radius == v.prm.search_radius);
-  if (!v.on || p->resolution != v.prm.resolution || p->regularization != v.prm.regularization || !same_offsets) v.have_lin = false;
+  if (p->resolution != v.prm.resolution || p->regularization != v.prm.regularization || !same_offsets) v.have_lin = false;
   if (!same_offsets) v.offs.clear();
-  if (!v.on) {
-    h->have_corr = false;
-    v.reset_final_H();
-  }
   v.prm = *p;
-  v.on = true;
-  h->vg.on = false, h->nd.on = false, h->ic.on = false;  // VC10: the four modes are exclusive
+  set_mode(h, Mode::VGICP_CUDA);
   return 0;
 }
 
 int apdgicp_get_vgicp_cuda(const apdgicp_handle* h, apdgicp_vgicp_cuda_params* p, int* enabled) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   if (p) *p = h->vc.prm;
-  if (enabled) *enabled = h->vc.on ? 1 : 0;
+  if (enabled) *enabled = h->mode == Mode::VGICP_CUDA ? 1 : 0;
   return 0;
 }
 
@@ -2636,58 +2702,28 @@ int apdgicp_vgicp_cuda_offsets(const apdgicp_vgicp_cuda_params* p, int32_t* out_
   });
 }
 
-static const char* const kVcOff = "FAST_VGICP_CUDA is off (apdgicp_set_vgicp_cuda)";
-
 int apdgicp_vgicp_cuda_kept(apdgicp_handle* h, int which, int64_t* n_kept, int32_t* kept_index, int64_t capacity) {
   return guarded([&]() -> int {
     if (!h || !n_kept || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
-    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     APD_TRY(vc_prepare_cloud(h, which));
-    const VcState::Prepared& pc = h->vc.pc[which];
-    *n_kept = pc.n_kept;
-    if (!kept_index || pc.n_kept == 0) return 0;
-    if (capacity < pc.n_kept) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
-    APD_HIP(hipMemcpyAsync(kept_index, pc.kept.p, (size_t)pc.n_kept * 4, hipMemcpyDeviceToHost, h->eng.stream));
-    APD_HIP(hipStreamSynchronize(h->eng.stream));
-    return 0;
+    return read_kept(h->eng.stream, h->vc.pc[which], n_kept, kept_index, capacity);
   });
 }
 
 int apdgicp_vgicp_cuda_get_covariances(apdgicp_handle* h, int which, double* raw_n6, double* reg_n9, int64_t capacity) {
   return guarded([&]() -> int {
     if (!h || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
-    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     APD_TRY(vc_prepare_cloud(h, which));
-    const VcState::Prepared& pc = h->vc.pc[which];
-    const int64_t nk = pc.n_kept;
-    if (capacity < nk) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
-    if (nk == 0) return 0;
-    hipStream_t st = h->eng.stream;
-    std::vector<double> all(raw_n6 ? (size_t)pc.n * 6 : 0), k6(reg_n9 ? (size_t)nk * 6 : 0);
-    std::vector<int> kept(raw_n6 ? (size_t)nk : 0);
-    if (raw_n6) {
-      APD_HIP(hipMemcpyAsync(all.data(), pc.raw.p, all.size() * 8, hipMemcpyDeviceToHost, st));
-      APD_HIP(hipMemcpyAsync(kept.data(), pc.kept.p, kept.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (reg_n9) APD_HIP(hipMemcpyAsync(k6.data(), pc.kcov.p, k6.size() * 8, hipMemcpyDeviceToHost, st));
-    APD_HIP(hipStreamSynchronize(st));
-    for (int64_t j = 0; j < nk && raw_n6; j++) {
-      if (kept[j] < 0 || kept[j] >= pc.n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept index");
-      memcpy(raw_n6 + 6 * j, &all[6 * (size_t)kept[j]], 6 * sizeof(double));
-    }
-    for (int64_t j = 0; j < nk && reg_n9; j++) {  // kcov: [6][n_kept]
-      const double xx = k6[j], xy = k6[nk + j], xz = k6[2 * nk + j], yy = k6[3 * nk + j], yz = k6[4 * nk + j], zz = k6[5 * nk + j];
-      double* o = reg_n9 + 9 * j;
-      o[0] = xx, o[1] = xy, o[2] = xz, o[3] = xy, o[4] = yy, o[5] = yz, o[6] = xz, o[7] = yz, o[8] = zz;
-    }
-    return 0;
+    return read_prepared_covariances(h->eng.stream, h->vc.pc[which], raw_n6, reg_n9, capacity);
   });
 }
 
 int apdgicp_vgicp_cuda_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
   return guarded([&]() -> int {
     if (!h || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     APD_TRY(vc_build_map(h));
     *n_voxels = h->vc.n_vox;
     return 0;
@@ -2697,7 +2733,7 @@ int apdgicp_vgicp_cuda_voxel_count(apdgicp_handle* h, int64_t* n_voxels) {
 int apdgicp_vgicp_cuda_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* covs_n9) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
-    if (!h->vc.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     APD_TRY(vc_build_map(h));
     if (h->vc.n_vox == 0) return 0;
     return read_voxels(h->eng.stream, h->vc.buf, h->vc.n_vox, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
@@ -2708,7 +2744,7 @@ int apdgicp_vgicp_cuda_get_correspondences(apdgicp_handle* h, int32_t* voxel_ind
   return guarded([&]() -> int {
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     VcState& v = h->vc;
-    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, kVcOff);
+    if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n_kept_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_kept_source does not match the kept source size");
     if (v.n_src_lin == 0) return 0;
@@ -2735,22 +2771,14 @@ void apdgicp_ndt_default_params(apdgicp_ndt_params* p) {
 int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   NdState& v = h->nd;
-  if (!p) {  // back to what apdgicp_params says: the APD kernels' correspondences are those of their own last linearize, if any was left
-    if (v.on) h->have_corr = false;
-    v.on = false;
+  if (!p) {  // back to what apdgicp_params says (a no-op while another mode is on)
+    if (h->mode == Mode::NDT) set_mode(h, Mode::APD);
     return 0;
   }
   APD_TRY(check_ndt_params(p));
-  if (!v.on || p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
-  if (!v.on) {
-    h->have_corr = false;
-    v.reset_final_H();
-  }
+  if (p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
   v.prm = *p;
-  v.on = true;
-  h->vg.on = false;  // N9: the two modes are exclusive
-  h->ic.on = false;  // IC9: likewise
-  h->vc.on = false;  // VC10: likewise
+  set_mode(h, Mode::NDT);
   return 0;
 }
 
@@ -2771,16 +2799,12 @@ int apdgicp_set_icp(apdgicp_handle* h, const apdgicp_icp_params* p) {
   IcState& v = h->ic;
   APD_TRY(check_icp_params(p));
   if (p) v.prm = *p;
-  const bool on = p && p->enable != 0;
-  if (on != v.on) h->have_corr = false, h->pair_ready = false;  // (the pair of the other side was set up with / without covariances)
-  if (!on) {
-    v.on = false;
+  if (!p || !p->enable) {  // (a no-op while another mode is on)
+    if (h->mode == Mode::ICP) set_mode(h, Mode::APD);
     return 0;
   }
-  v.on = true, v.have = false;
-  v.state = APDGICP_ICP_NOT_CONVERGED;
-  h->vg.on = false, h->nd.on = false;  // IC9: the three modes are exclusive
-  h->vc.on = false;                    // VC10: likewise
+  set_mode(h, Mode::ICP);
+  v.have = false, v.state = APDGICP_ICP_NOT_CONVERGED;  // (of every enabling call: what the last estimate or align left is not this setting's)
   return 0;
 }
 
@@ -2788,16 +2812,16 @@ int apdgicp_get_icp(const apdgicp_handle* h, apdgicp_icp_params* p, int* enabled
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   if (p) {
     *p = h->ic.prm;
-    p->enable = h->ic.on ? 1 : 0;
+    p->enable = h->mode == Mode::ICP ? 1 : 0;
   }
-  if (enabled) *enabled = h->ic.on ? 1 : 0;
+  if (enabled) *enabled = h->mode == Mode::ICP ? 1 : 0;
   return 0;
 }
 
 int apdgicp_icp_estimate(apdgicp_handle* h, const float T[16], float T_out[16], int64_t* n_corr, double* mse, double sums[16]) {
   return guarded([&]() -> int {
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (!h->ic.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_set_icp)");
+    if (h->mode != Mode::ICP) return mode_is_off(Mode::ICP, false);
     return ic_estimate(h, T, T_out, n_corr, mse, sums);
   });
 }
@@ -2805,7 +2829,7 @@ int apdgicp_icp_estimate(apdgicp_handle* h, const float T[16], float T_out[16], 
 // the last estimate / align must still describe the clouds the handle holds
 static int ic_check_have(apdgicp_handle* h, int64_t n) {
   const IcState& v = h->ic;
-  if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "point-to-point ICP is off (apdgicp_set_icp)");
+  if (h->mode != Mode::ICP) return mode_is_off(Mode::ICP, false);
   if (!v.have || v.have_src_gen != h->cloud_gen[kSrc] || v.have_tgt_gen != h->cloud_gen[kTgt] || h->eng.clouds[kSrc].n != v.n_have)
     return fail(APDGICP_ERR_NO_INPUT, "no estimate or align of the clouds the handle holds now");
   if (n != v.n_have) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
@@ -2878,14 +2902,14 @@ int apdgicp_icp_debug_counts(apdgicp_handle* h, int64_t* launches, int64_t* wait
 int apdgicp_get_ndt(const apdgicp_handle* h, apdgicp_ndt_params* p, int* enabled) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   if (p) *p = h->nd.prm;
-  if (enabled) *enabled = h->nd.on ? 1 : 0;
+  if (enabled) *enabled = h->mode == Mode::NDT ? 1 : 0;
   return 0;
 }
 
 int apdgicp_ndt_voxel_count(apdgicp_handle* h, int which, int64_t* n_voxels) {
   return guarded([&]() -> int {
     if (!h || !n_voxels || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
-    if (!h->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    if (h->mode != Mode::NDT) return mode_is_off(Mode::NDT, false);
     APD_TRY(nd_build_map(h, which));
     *n_voxels = h->nd.maps[which].nv;
     return 0;
@@ -2895,7 +2919,7 @@ int apdgicp_ndt_voxel_count(apdgicp_handle* h, int which, int64_t* n_voxels) {
 int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32_t* coords_n3, int32_t* counts, double* means_n3, double* raw_covs_n6, double* covs_n9) {
   return guarded([&]() -> int {
     if (!h || (which != kSrc && which != kTgt)) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
-    if (!h->nd.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    if (h->mode != Mode::NDT) return mode_is_off(Mode::NDT, false);
     APD_TRY(nd_build_map(h, which));
     const NdState::Map& m = h->nd.maps[which];
     return read_voxels(h->eng.stream, m.buf, m.nv, capacity, coords_n3, counts, means_n3, raw_covs_n6, covs_n9);
@@ -2907,7 +2931,7 @@ int apdgicp_ndt_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     NdState& v = h->nd;
     Engine& e = h->eng;
-    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, "NDT is off (apdgicp_set_ndt)");
+    if (h->mode != Mode::NDT) return mode_is_off(Mode::NDT, false);
     if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
     if (n_rows != v.n_rows_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_rows does not match the rows of the last linearize");
     APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_rows * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
@@ -2927,17 +2951,9 @@ int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
     // (the parameters first: what is wrong with them does not depend on the handle)
     APD_TRY(check_vgicp_params(p));
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-    VgbState& v = b->vg;
-    if (!p) {
-      v.on = false;
-      return 0;
-    }
-    if (!v.on && !b->nd.on && !b->ic.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
-    v.prm = *p;
-    v.on = true;
-    b->nd.on = false;  // N15: the two modes are exclusive
-    b->vc.on = false;  // VC16
-    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
+    if (!p) return b->mode == Mode::VGICP ? set_mode(b, Mode::APD) : 0;  // (a no-op while another mode is on)
+    APD_TRY(set_mode(b, Mode::VGICP));
+    b->vg.prm = *p;
     return 0;
   });
 }
@@ -2945,7 +2961,7 @@ int apdgicp_batch_set_vgicp(apdgicp_batch* b, const apdgicp_vgicp_params* p) {
 int apdgicp_batch_get_vgicp(const apdgicp_batch* b, apdgicp_vgicp_params* p, int* enabled) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (p) *p = b->vg.prm;
-  if (enabled) *enabled = b->vg.on ? 1 : 0;
+  if (enabled) *enabled = b->mode == Mode::VGICP ? 1 : 0;
   return 0;
 }
 
@@ -2978,17 +2994,9 @@ int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
     // (the parameters first: what is wrong with them does not depend on the handle)
     APD_TRY(check_ndt_params(p));
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-    NdbState& v = b->nd;
-    if (!p) {
-      v.on = false;
-      return 0;
-    }
-    if (!v.on && !b->vg.on && !b->ic.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
-    v.prm = *p;
-    v.on = true;
-    b->vg.on = false;  // N15: the two modes are exclusive
-    b->vc.on = false;  // VC16
-    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
+    if (!p) return b->mode == Mode::NDT ? set_mode(b, Mode::APD) : 0;  // (a no-op while another mode is on)
+    APD_TRY(set_mode(b, Mode::NDT));
+    b->nd.prm = *p;
     return 0;
   });
 }
@@ -2996,7 +3004,7 @@ int apdgicp_batch_set_ndt(apdgicp_batch* b, const apdgicp_ndt_params* p) {
 int apdgicp_batch_get_ndt(const apdgicp_batch* b, apdgicp_ndt_params* p, int* enabled) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (p) *p = b->nd.prm;
-  if (enabled) *enabled = b->nd.on ? 1 : 0;
+  if (enabled) *enabled = b->mode == Mode::NDT ? 1 : 0;
   return 0;
 }
 
@@ -3031,17 +3039,10 @@ int apdgicp_batch_set_vgicp_cuda(apdgicp_batch* b, const apdgicp_vgicp_cuda_para
     // (the parameters first: what is wrong with them does not depend on the handle)
     APD_TRY(check_vgicp_cuda_params(p));
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-    VcbState& v = b->vc;
-    if (!p) {
-      v.on = false;
-      return 0;
-    }
-    if (!v.on && !b->vg.on && !b->nd.on && !b->ic.on) APD_TRY(batch_enter_device_loop_mode(b));
-    v.have = false;
-    v.prm = *p;
-    v.on = true;
-    b->vg.on = false, b->nd.on = false;  // VC16: the four modes are exclusive
-    if (b->ic.on) b->ic.on = false, b->eng.poses_of_align = false;  // IC16
+    if (!p) return b->mode == Mode::VGICP_CUDA ? set_mode(b, Mode::APD) : 0;  // (a no-op while another mode is on)
+    APD_TRY(set_mode(b, Mode::VGICP_CUDA));
+    b->vc.have = false;
+    b->vc.prm = *p;
     return 0;
   });
 }
@@ -3049,7 +3050,7 @@ int apdgicp_batch_set_vgicp_cuda(apdgicp_batch* b, const apdgicp_vgicp_cuda_para
 int apdgicp_batch_get_vgicp_cuda(const apdgicp_batch* b, apdgicp_vgicp_cuda_params* p, int* enabled) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (p) *p = b->vc.prm;
-  if (enabled) *enabled = b->vc.on ? 1 : 0;
+  if (enabled) *enabled = b->mode == Mode::VGICP_CUDA ? 1 : 0;
   return 0;
 }
 
@@ -3057,13 +3058,7 @@ int apdgicp_batch_vgicp_cuda_kept(apdgicp_batch* b, int32_t cloud, int64_t* n_ke
   return guarded([&]() -> int {
     if (!b || !n_kept) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_TRY(vcb_slot(b, cloud, false));
-    const VcbState::Slot& sl = b->vc.slots[cloud];
-    *n_kept = sl.n_kept;
-    if (!kept_index || sl.n_kept == 0) return 0;
-    if (capacity < sl.n_kept) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
-    APD_HIP(hipMemcpyAsync(kept_index, sl.kept.p, (size_t)sl.n_kept * 4, hipMemcpyDeviceToHost, b->eng.stream));
-    APD_HIP(hipStreamSynchronize(b->eng.stream));
-    return 0;
+    return read_kept(b->eng.stream, b->vc.slots[cloud].pc, n_kept, kept_index, capacity);
   });
 }
 
@@ -3071,29 +3066,7 @@ int apdgicp_batch_vgicp_cuda_get_covariances(apdgicp_batch* b, int32_t cloud, do
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(vcb_slot(b, cloud, false));
-    const VcbState::Slot& sl = b->vc.slots[cloud];
-    const int64_t nk = sl.n_kept;
-    if (capacity < nk) return fail(APDGICP_ERR_INVALID_ARG, "capacity is below the kept count");
-    if (nk == 0) return 0;
-    hipStream_t st = b->eng.stream;
-    std::vector<double> all(raw_n6 ? (size_t)sl.n * 6 : 0), k6(reg_n9 ? (size_t)nk * 6 : 0);
-    std::vector<int> kept(raw_n6 ? (size_t)nk : 0);
-    if (raw_n6) {
-      APD_HIP(hipMemcpyAsync(all.data(), sl.raw.p, all.size() * 8, hipMemcpyDeviceToHost, st));
-      APD_HIP(hipMemcpyAsync(kept.data(), sl.kept.p, kept.size() * 4, hipMemcpyDeviceToHost, st));
-    }
-    if (reg_n9) APD_HIP(hipMemcpyAsync(k6.data(), sl.kcov.p, k6.size() * 8, hipMemcpyDeviceToHost, st));
-    APD_HIP(hipStreamSynchronize(st));
-    for (int64_t j = 0; j < nk && raw_n6; j++) {
-      if (kept[j] < 0 || kept[j] >= sl.n) return fail(APDGICP_ERR_INTERNAL, "FAST_VGICP_CUDA: inconsistent kept index");
-      memcpy(raw_n6 + 6 * j, &all[6 * (size_t)kept[j]], 6 * sizeof(double));
-    }
-    for (int64_t j = 0; j < nk && reg_n9; j++) {  // kcov: [6][n_kept]
-      const double xx = k6[j], xy = k6[nk + j], xz = k6[2 * nk + j], yy = k6[3 * nk + j], yz = k6[4 * nk + j], zz = k6[5 * nk + j];
-      double* o = reg_n9 + 9 * j;
-      o[0] = xx, o[1] = xy, o[2] = xz, o[3] = xy, o[4] = yy, o[5] = yz, o[6] = xz, o[7] = yz, o[8] = zz;
-    }
-    return 0;
+    return read_prepared_covariances(b->eng.stream, b->vc.slots[cloud].pc, raw_n6, reg_n9, capacity);
   });
 }
 
@@ -3120,7 +3093,7 @@ int apdgicp_batch_vgicp_cuda_get_correspondences(apdgicp_batch* b, int64_t pair,
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     const VcbState& v = b->vc;
-    if (!v.on) return fail(APDGICP_ERR_NO_INPUT, kVcbOff);
+    if (b->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, true);
     if (!v.have || v.have_epoch != b->eng.pts_epoch) return fail(APDGICP_ERR_NO_INPUT, "no align in this mode since the cloud slots and the mode were last set");
     if (pair < 0 || pair >= (int64_t)v.have_nk.size()) return fail(APDGICP_ERR_INVALID_ARG, "pair is not one of the last align");
     if (!voxel_index) return v.have_nk[pair];  // (the size query)
@@ -3247,14 +3220,16 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
   return guarded([&]() -> int {
     if (!h || !H) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     Engine& e = h->eng;
-    if (h->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
-    if (h->nd.on) {  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
-      memcpy(H, h->nd.final_H, 36 * sizeof(double));
-      return 0;
-    }
-    if (h->vc.on) {  // FAST_VGICP_CUDA: likewise
-      memcpy(H, h->vc.final_H, 36 * sizeof(double));
-      return 0;
+    switch (h->mode) {
+      case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
+      case Mode::NDT:  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
+        memcpy(H, h->nd.final_H, 36 * sizeof(double));
+        return 0;
+      case Mode::VGICP_CUDA:  // FAST_VGICP_CUDA: likewise
+        memcpy(H, h->vc.final_H, 36 * sizeof(double));
+        return 0;
+      case Mode::VGICP:
+      case Mode::APD: break;  // (on the device, in the pair state)
     }
     if (!h->pair_ready) {  // L:23: identity until the first accepted step
       for (int q = 0; q < 36; q++) H[q] = (q % 7 == 0) ? 1.0 : 0.0;
@@ -3523,23 +3498,14 @@ int apdgicp_batch_compute_covariances(apdgicp_batch* b) {
 int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, void** d_results) {
   return guarded([&]() -> int {
     if (!b || !pairs) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (b->vg.on) {  // voxelized GICP: complete on return (V12)
-      APD_TRY(vgb_align(b, pairs, n_pairs));
-      if (d_results) *d_results = b->eng.d_results.p;
-      return 0;
-    }
-    if (b->nd.on) {  // NDT: likewise (N15)
-      APD_TRY(ndb_align(b, pairs, n_pairs));
-      if (d_results) *d_results = b->eng.d_results.p;
-      return 0;
-    }
-    if (b->ic.on) {  // point-to-point ICP: likewise (IC15)
-      APD_TRY(icb_align(b, pairs, n_pairs));
-      if (d_results) *d_results = b->eng.d_results.p;
-      return 0;
-    }
-    if (b->vc.on) {  // FAST_VGICP_CUDA: likewise (VC16)
-      APD_TRY(vcb_align(b, pairs, n_pairs));
+    if (b->mode != Mode::APD) {  // the device-loop modes: complete on return (V12 / N15 / IC15 / VC16)
+      switch (b->mode) {
+        case Mode::VGICP: APD_TRY(vgb_align(b, pairs, n_pairs)); break;
+        case Mode::NDT: APD_TRY(ndb_align(b, pairs, n_pairs)); break;
+        case Mode::ICP: APD_TRY(icb_align(b, pairs, n_pairs)); break;
+        case Mode::VGICP_CUDA: APD_TRY(vcb_align(b, pairs, n_pairs)); break;
+        case Mode::APD: break;
+      }
       if (d_results) *d_results = b->eng.d_results.p;
       return 0;
     }
@@ -3558,10 +3524,7 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
 int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, uint64_t* ticket) {
   return guarded([&]() -> int {
     if (!b || !pairs || !ticket) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
-    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
-    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
-    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
+    if (b->mode != Mode::APD) return no_pipeline(b->mode);
     Engine& e = b->eng;
     if (e.pool_eligible()) return e.pool_enqueue(pairs, n_pairs, ticket);
     APD_TRY(e.ensure_alt_slot());
@@ -3578,27 +3541,21 @@ int apdgicp_batch_align_enqueue(apdgicp_batch* b, const apdgicp_pair* pairs, int
 int apdgicp_batch_pump(apdgicp_batch* b) {
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
-    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
-    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
-    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
+    if (b->mode != Mode::APD) return no_pipeline(b->mode);
     return b->eng.pool.on ? b->eng.pool_pump(false) : 0;
   });
 }
 
 int apdgicp_batch_is_pooled(apdgicp_batch* b) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-  if (b->vg.on || b->nd.on || b->ic.on || b->vc.on) return 0;
+  if (b->mode != Mode::APD) return 0;
   return b->eng.pool_eligible() ? Engine::pool_lanes_cfg() : 0;
 }
 
 int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_results, apdgicp_result* host_results) {
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
-    if (b->vg.on) return fail(APDGICP_ERR_UNSUPPORTED, kVgbNoPipeline);
-    if (b->nd.on) return fail(APDGICP_ERR_UNSUPPORTED, kNdbNoPipeline);
-    if (b->ic.on) return fail(APDGICP_ERR_UNSUPPORTED, kIcbNoPipeline);
-    if (b->vc.on) return fail(APDGICP_ERR_UNSUPPORTED, kVcbNoPipeline);
+    if (b->mode != Mode::APD) return no_pipeline(b->mode);
     Engine& e = b->eng;
     if (e.pool_find(ticket)) return e.pool_collect(ticket, d_results, host_results);
     const bool previous = ticket + 1 == e.align_seq;
@@ -3625,7 +3582,7 @@ int apdgicp_batch_align_collect(apdgicp_batch* b, uint64_t ticket, void** d_resu
 int apdgicp_batch_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs, apdgicp_result* results) {
   return guarded([&]() -> int {
     if (!results) return fail(APDGICP_ERR_INVALID_ARG, "results is null");
-    if (b && pairs && !b->vg.on && !b->nd.on && !b->ic.on && !b->vc.on && b->eng.pool_eligible()) {
+    if (b && pairs && b->mode == Mode::APD && b->eng.pool_eligible()) {
       uint64_t ticket = 0;
       APD_TRY(b->eng.pool_enqueue(pairs, n_pairs, &ticket));
       return b->eng.pool_collect(ticket, nullptr, results);
@@ -3664,7 +3621,7 @@ int apdgicp_batch_fitness(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n
         same_pairs = false;
       }
     }
-    if (!T && b->ic.on && same_pairs && e.poses_of_align) {  // IC16: the poses of an ICP align are its records' (the pair state holds the identity)
+    if (!T && b->mode == Mode::ICP && same_pairs && e.poses_of_align) {  // IC16: the poses of an ICP align are its records' (the pair state holds the identity)
       std::vector<ResultRec> recs((size_t)n_pairs);
       APD_HIP(hipMemcpyAsync(recs.data(), e.d_results.p, recs.size() * sizeof(ResultRec), hipMemcpyDeviceToHost, e.stream));
       APD_HIP(hipStreamSynchronize(e.stream));
@@ -3754,15 +3711,9 @@ int apdgicp_batch_set_icp(apdgicp_batch* b, const apdgicp_icp_params* p) {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     IcbState& v = b->ic;
     if (p) v.prm = *p;
-    if (!p || !p->enable) {
-      if (v.on) b->eng.poses_of_align = false;  // (the engine's pair state holds this mode's identity poses, not an align's)
-      v.on = false;
-      return 0;
-    }
-    if (!v.on && !b->vg.on && !b->nd.on && !b->vc.on) APD_TRY(batch_enter_device_loop_mode(b));
-    v.on = true, v.have = false;
-    b->vg.on = false, b->nd.on = false;  // IC16: the three modes are exclusive
-    b->vc.on = false;                    // VC16
+    if (!p || !p->enable) return b->mode == Mode::ICP ? set_mode(b, Mode::APD) : 0;  // (a no-op while another mode is on)
+    APD_TRY(set_mode(b, Mode::ICP));
+    v.have = false;
     return 0;
   });
 }
@@ -3771,9 +3722,9 @@ int apdgicp_batch_get_icp(const apdgicp_batch* b, apdgicp_icp_params* p, int* en
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (p) {
     *p = b->ic.prm;
-    p->enable = b->ic.on ? 1 : 0;
+    p->enable = b->mode == Mode::ICP ? 1 : 0;
   }
-  if (enabled) *enabled = b->ic.on ? 1 : 0;
+  if (enabled) *enabled = b->mode == Mode::ICP ? 1 : 0;
   return 0;
 }
 
