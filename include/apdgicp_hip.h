@@ -51,7 +51,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_set_icp / _get_icp and the apdgicp_icp_* calls (point-to-point ICP as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_icp / _get_icp and the apdgicp_batch_icp_* calls (point-to-point ICP as a mode of the batch handle);
                                       still 6 (additive): + apdgicp_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the registration handle);
-                                      still 6 (additive): + apdgicp_batch_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_batch_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the batch handle) */
+                                      still 6 (additive): + apdgicp_batch_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_batch_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the batch handle);
+                                      still 6 (additive): + apdgicp_knn_of, apdgicp_radius_search_of / _rows, apdgicp_search_group_stats (exact k-nearest and radius queries of the target) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -255,6 +256,46 @@ int apdgicp_nearest_neighbours_of(apdgicp_handle* h, const float* queries_xyz, i
 /* the points of the source / target cloud as set, n x {x, y, z} floats in the caller's order, into host memory (the fall-back of
  * that search object for a query that is not one of the transformed source points needs the target of a device-resident submap) */
 int apdgicp_get_points(apdgicp_handle* h, int which, float* out_xyz, int64_t n);
+
+/* ------------------------------------------------------------------ exact k-nearest and radius queries of the target
+ * What else a pcl::search::KdTree over the target is asked for (nearestKSearch with k > 1, radiusSearch: DBSCAN_kdtree.h, the non-dense
+ * branch of RadiusOutlierRemoval, FastGICPMultiPoints::update_correspondences), for ARBITRARY query points, in one device pass per call.
+ * The kernels (riv-slam_amd/csrc/apd_search.hpp) and the restatement the tests compare with (tests/search_np.py) follow this list:
+ *   Q1. Order.  The distance is d2 = sqdist1(t, q): fp32 differences, dx*dx, + dy*dy, + dz*dz, each operation rounded, no contraction.
+ *       The key of a target point is (bits of d2) << 32 | its index in the target as set; keys are unique, and ascending key is FLANN's
+ *       L2_Simple order with ties by ascending index, the order of every other search here.  The target is the whole target cloud as
+ *       set (host or device-resident), in every mode of the handle; mode kernels, maps and prepared clouds are neither read nor written.
+ *   Q2. apdgicp_knn_of: for every query the n_found = min(k, M) smallest keys, ascending (M: the target's size).  Output is row-major
+ *       n x k: int32 index into the target as set and float distance; the unused tail of a row is -1 / +Inf.  1 <= k <= 64; k < 1 is
+ *       APDGICP_ERR_INVALID_ARG, k > 64 is APDGICP_ERR_UNSUPPORTED.
+ *   Q3. Queries.  Host memory, n x {x, y, z, ...} floats, stride_bytes >= 12 and a multiple of 4, as in apdgicp_nearest_neighbours_of.
+ *       A non-finite coordinate refuses the call with APDGICP_ERR_INVALID_ARG, the message naming the first such query; this is checked
+ *       on the host before anything is enqueued.  n <= 0 or a null pointer: APDGICP_ERR_INVALID_ARG; no target: APDGICP_ERR_NO_INPUT.
+ *   Q4. Radius.  r2 = (float)((double)radius * (double)radius).  A target point is a hit iff d2 < r2, strictly (FLANN's
+ *       RadiusResultSet::addPoint behind pcl::KdTreeFLANN::radiusSearch, which passes that float).  radius is finite and >= 0 (otherwise
+ *       APDGICP_ERR_INVALID_ARG); radius = 0 yields no hit, not even a coincident point.
+ *   Q5. Rows.  A row holds its hits in ascending key.  With max_nn = 0 or max_nn >= M it holds all of them, otherwise the max_nn
+ *       smallest (PCL's max_nn).  max_nn < 0: APDGICP_ERR_INVALID_ARG.
+ *   Q6. Rows come back in two calls.  apdgicp_radius_search_of searches, writes row_start[0 .. n] (row i is [row_start[i],
+ *       row_start[i + 1])) and *total = row_start[n], and leaves the rows in buffers of the handle; apdgicp_radius_search_rows copies
+ *       `total` entries.  The second call without a first is APDGICP_ERR_NO_INPUT, and so is one after the target was set, cleared or
+ *       swapped since, or after a search that failed.  More than 2^31 - 1 hits in all: APDGICP_ERR_UNSUPPORTED.  An allocation that
+ *       fails is APDGICP_ERR_HIP, and the handle stays usable.
+ *   Q7. Handle state is as after apdgicp_nearest_neighbours_of: the handle's own pair is set up again by whoever needs it next, and
+ *       the next align returns the bytes it returned before.  Source, target, covariances and cached maps are untouched.
+ *   Q8. A row is a pure function of (target, query, k or radius, max_nn): it does not depend on the other queries of the call, on
+ *       their order or on their number.
+ *   Q9. k = 1 returns the bytes of apdgicp_nearest_neighbours_of.  A radius search with 0 < max_nn <= 64 returns the first max_nn
+ *       entries of apdgicp_knn_of(k = max_nn) that pass Q4. */
+int apdgicp_knn_of(apdgicp_handle* h, const float* queries_xyz, int64_t n, int64_t stride_bytes, int32_t k, int32_t* index, float* sq_dist, int32_t* n_found);
+int apdgicp_radius_search_of(apdgicp_handle* h, const float* queries_xyz, int64_t n, int64_t stride_bytes, double radius, int32_t max_nn, int64_t* row_start /* n + 1 */,
+                             int64_t* total);
+int apdgicp_radius_search_rows(apdgicp_handle* h, int32_t* index, float* sq_dist);
+/* of the last apdgicp_knn_of / apdgicp_radius_search_of: target groups (128 points) whose points a wave of the searching launch
+ * (the counting one, where a second fills the rows) looked at, summed over its waves, and waves x groups, the same sum with no
+ * pruning (the measurement of tests/measure/bench_search_queries.py) */
+int apdgicp_search_group_stats(apdgicp_handle* h, int64_t* groups_visited, int64_t* groups_total);
+
 int apdgicp_synchronize(apdgicp_handle* h);
 /* Ordering against the stream that PRODUCED device-resident inputs.  The handle's streams are non-blocking: without this
  * call nothing orders a kernel that still writes the cloud (on the caller's stream) against the handle's pack kernel.

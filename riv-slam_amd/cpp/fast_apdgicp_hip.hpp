@@ -385,7 +385,68 @@ class FastAPDGICPHip : public pcl::Registration<PointSource, PointTarget, float>
       }
       report("nearest neighbours of a batch of queries");
     }
+    if (k > 1 && k <= 64 && handle_ && target_on_device_) {  // apdgicp_knn_of: the k smallest (distance, index) of every query, ONE device pass
+      std::vector<float> q(3 * n), d(n * (std::size_t)k);
+      std::vector<int32_t> j(n * (std::size_t)k);
+      int32_t found = 0;
+      for (std::size_t i = 0; i < n; i++) {
+        const auto& pt = cloud.points[indices.empty() ? i : (std::size_t)indices[i]];
+        q[3 * i] = pt.x, q[3 * i + 1] = pt.y, q[3 * i + 2] = pt.z;
+      }
+      if (apdgicp_knn_of(handle_, q.data(), (int64_t)n, 12, k, j.data(), d.data(), &found) == 0) {
+        nn_stats_.device_queries += (long)n;
+        nn_cache_epoch_ = 0;  // (as behind apdgicp_nearest_neighbours_of in device_nn: the next cached pass re-arms the handle's pair)
+        for (std::size_t i = 0; i < n; i++) {  // rows as host_nn leaves them: min(k, target size) entries
+          k_indices[i].assign(j.begin() + i * k, j.begin() + i * k + found);
+          k_sqr_distances[i].assign(d.begin() + i * k, d.begin() + i * k + found);
+        }
+        return;
+      }
+      report("k nearest neighbours of a batch of queries");
+    }
     for (std::size_t i = 0; i < n; i++) host_nn(cloud.points[indices.empty() ? i : (std::size_t)indices[i]], k, k_indices[i], k_sqr_distances[i]);
+  }
+
+  /// pcl::search::Search::radiusSearch(cloud, indices, radius, ...) against the target, on the device (apdgicp_radius_search_of / _rows):
+  /// per listed point of `cloud` (all of them when `indices` is empty) the target points with fp32 squared distance strictly below
+  /// (float)(radius * radius), ascending by (distance, index), at most max_nn of them (0: all) -- pcl::KdTreeFLANN::radiusSearch with
+  /// sorted results.  A plain member, not an override of the search object: callers that hold this class call it directly.  Returns
+  /// false, with every row empty, when the device call fails (the error is reported like every other).
+  template <typename Cloud, typename IdxIn, typename IdxOut>
+  bool deviceRadiusSearch(const Cloud& cloud, const IdxIn& indices, double radius, std::vector<IdxOut>& k_indices, std::vector<std::vector<float>>& k_sqr_distances,
+                          unsigned int max_nn = 0) {
+    const std::size_t n = indices.empty() ? cloud.size() : indices.size();
+    k_indices.assign(n, IdxOut()), k_sqr_distances.assign(n, std::vector<float>());
+    if (!n) return true;
+    if (!handle_ || !target_on_device_) {
+      report("deviceRadiusSearch (no GPU handle or no target)");
+      return false;
+    }
+    std::vector<float> q(3 * n);
+    for (std::size_t i = 0; i < n; i++) {
+      const auto& pt = cloud.points[indices.empty() ? i : (std::size_t)indices[i]];
+      q[3 * i] = pt.x, q[3 * i + 1] = pt.y, q[3 * i + 2] = pt.z;
+    }
+    std::vector<int64_t> row_start(n + 1);
+    int64_t total = 0;
+    const int32_t cap = max_nn > 0x7fffffffu ? 0x7fffffff : (int32_t)max_nn;
+    if (apdgicp_radius_search_of(handle_, q.data(), (int64_t)n, 12, radius, cap, row_start.data(), &total) != 0) {
+      report("radius search of a batch of queries");
+      return false;
+    }
+    nn_cache_epoch_ = 0;  // (the handle's pair is set up again by the next cached pass)
+    std::vector<int32_t> j((std::size_t)total);
+    std::vector<float> d((std::size_t)total);
+    if (apdgicp_radius_search_rows(handle_, j.data(), d.data()) != 0) {
+      report("rows of a radius search");
+      return false;
+    }
+    nn_stats_.device_queries += (long)n;
+    for (std::size_t i = 0; i < n; i++) {
+      k_indices[i].assign(j.begin() + row_start[i], j.begin() + row_start[i + 1]);
+      k_sqr_distances[i].assign(d.begin() + row_start[i], d.begin() + row_start[i + 1]);
+    }
+    return true;
   }
 
  protected:

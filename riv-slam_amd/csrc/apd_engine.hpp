@@ -169,6 +169,17 @@ class Engine {
   std::vector<float> h_guesses;
   DevBuf d_state, d_results, d_errflag, d_probe, d_stage, d_T;
   DevBuf d_keys, d_box6, d_stats;
+  // apdgicp_knn_of / apdgicp_radius_search_of (apd_search.hpp; Q1 .. Q9 of the header): the keys of the last search -- the [n][k] table of
+  // k_knn_queries or the rows of k_radius_fill -- and, on the host, where each row of the last radius search lies in them
+  struct SearchState {
+    DevBuf keys, cnt, pos, bsum, visit;
+    std::vector<int64_t> src_start;  // row i: keys[src_start[i] .. + len[i])
+    std::vector<int> len;
+    int64_t total = 0, span = 0;     // entries of all rows; keys the rows are spread over
+    bool rows_valid = false;
+    uint64_t tgt_gen = 0;            // apdgicp_handle::cloud_gen of the target the rows were found in
+    int64_t groups_visited = 0, groups_total = 0;
+  } sq;
   CachedTable d_desc, d_pairs, d_guess, d_ids, d_packjobs, d_sortjobs, d_sortjobs_reg[3], d_tilejobs[3], d_active;
   DevBuf d_tkeys;          // sorted tiles of the clouds being sorted by the tiled path
   int n_stage_pending = 0;   // clouds whose pinned copy a sort has been enqueued for, no align behind it yet

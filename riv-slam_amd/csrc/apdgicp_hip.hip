@@ -25,6 +25,7 @@
 #include "apd_dbscan.hpp"
 #include "apd_ingest.hpp"
 #include "apd_approx_voxel.hpp"
+#include "apd_search.hpp"
 
 using namespace apd;
 
@@ -3359,6 +3360,185 @@ int apdgicp_nearest_neighbours_of(apdgicp_handle* h, const float* queries_xyz, i
     APD_HIP(hipStreamSynchronize(e.stream));
     return 0;
   });
+}
+
+// ---- exact k-nearest and radius queries of the target (apd_search.hpp; Q1 .. Q9 of the header)
+// Q3: everything that can be said about the queries without a handle, in the order the header lists it
+static int search_check_queries(const float* queries_xyz, int64_t n, int64_t stride_bytes) {
+  if (!queries_xyz || n <= 0) return fail(APDGICP_ERR_INVALID_ARG, "null argument or no queries");
+  if (n > (1 << 30)) return fail(APDGICP_ERR_INVALID_ARG, "too many queries");
+  if (stride_bytes < 12 || (stride_bytes & 3)) return fail(APDGICP_ERR_INVALID_ARG, "stride_bytes must be a multiple of 4 and >= 12");
+  for (int64_t i = 0; i < n; i++) {
+    const float* p = (const float*)((const char*)queries_xyz + i * stride_bytes);
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2]))
+      return fail(APDGICP_ERR_INVALID_ARG, "query " + std::to_string(i) + " has a non-finite coordinate");
+  }
+  return 0;
+}
+
+// the queries into the scratch slot, sorted; Q7: the handle's own pair is set up again by whoever needs it next
+static int search_set_queries(apdgicp_handle* h, const float* queries_xyz, int64_t n, int64_t stride_bytes, SearchTarget* T, int* nblk) {
+  constexpr int kQry = 2;  // the scratch cloud slot of apdgicp_nearest_neighbours_of
+  Engine& e = h->eng;
+  e.sq.rows_valid = false;
+  e.sq.groups_visited = e.sq.groups_total = 0;
+  APD_TRY(e.set_cloud(kQry, queries_xyz, n, stride_bytes, 0, 0));
+  h->pair_ready = false, h->have_corr = false;
+  APD_TRY(e.pool_leave());   // (everything below runs on e.stream)
+  APD_TRY(e.upload_desc());  // sorts what is not sorted yet: the queries, and a target nobody has searched so far
+  const Engine::Cloud& t = e.clouds[kTgt];
+  *T = SearchTarget{t.pts.as<float4>(), t.perm.as<int>(), t.cbox.as<Box>(), t.gbox.as<Box>(), t.n, 0};
+  *nblk = (int)((n + SQ_BLK - 1) / SQ_BLK);
+  APD_TRY(e.sq.visit.ensure((size_t)*nblk * sizeof(int)));
+  return 0;
+}
+
+// groups the waves of the call's first searching launch looked at (apdgicp_search_group_stats): read behind the wait of the call
+static int search_add_group_stats(Engine& e, int nblk, int target_n) {
+  std::vector<int> v((size_t)nblk);
+  APD_HIP(hipMemcpy(v.data(), e.sq.visit.p, v.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int x : v) e.sq.groups_visited += x;
+  e.sq.groups_total += (int64_t)v.size() * ((target_n + kGroupPts - 1) / kGroupPts);
+  return 0;
+}
+
+// k_knn_queries into sq.keys ([n][k]) and sq.cnt ([n]), enqueued
+static int search_launch_knn(Engine& e, const SearchTarget& T, int64_t n, int nblk, int k, bool bounded, float r2) {
+  constexpr int kQry = 2;
+  APD_TRY(e.sq.keys.ensure((size_t)n * k * sizeof(unsigned long long)));
+  APD_TRY(e.sq.cnt.ensure((size_t)n * sizeof(int)));
+  const Engine::Cloud& q = e.clouds[kQry];
+  hipLaunchKernelGGL(k_knn_queries, dim3((unsigned)nblk), dim3(SQ_BLK), 0, e.stream, T, q.pts.as<float4>(), q.perm.as<int>(), (int)n, k, bounded ? 1 : 0, r2,
+                     e.sq.keys.as<unsigned long long>(), e.sq.cnt.as<int>(), e.sq.visit.as<int>());
+  APD_HIP(hipGetLastError());
+  return 0;
+}
+
+int apdgicp_knn_of(apdgicp_handle* h, const float* queries_xyz, int64_t n, int64_t stride_bytes, int32_t k, int32_t* index, float* sq_dist, int32_t* n_found) {
+  return guarded([&]() -> int {
+    if (k < 1) return fail(APDGICP_ERR_INVALID_ARG, "k must be at least 1");
+    if (k > SQ_KMAX) return fail(APDGICP_ERR_UNSUPPORTED, "k above 64 is not offered");
+    APD_TRY(search_check_queries(queries_xyz, n, stride_bytes));
+    if (!h || !index || !sq_dist) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    Engine& e = h->eng;
+    if (e.clouds.size() < 2 || e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
+    roctx_range rr("apdgicp:knn_of");
+    SearchTarget T;
+    int nblk = 0;
+    APD_TRY(search_set_queries(h, queries_xyz, n, stride_bytes, &T, &nblk));
+    APD_TRY(search_launch_knn(e, T, n, nblk, k, false, 0.f));
+    std::vector<unsigned long long> keys((size_t)n * k);
+    APD_HIP(hipMemcpyAsync(keys.data(), e.sq.keys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    APD_TRY(search_add_group_stats(e, nblk, T.n));
+    for (size_t i = 0; i < keys.size(); i++) {
+      const unsigned long long key = keys[i];
+      const uint32_t bits = key == ~0ull ? 0x7f800000u : (uint32_t)(key >> 32);
+      index[i] = key == ~0ull ? -1 : (int32_t)(uint32_t)key;
+      memcpy(&sq_dist[i], &bits, 4);
+    }
+    if (n_found) *n_found = std::min<int32_t>(k, T.n);
+    return 0;
+  });
+}
+
+int apdgicp_radius_search_of(apdgicp_handle* h, const float* queries_xyz, int64_t n, int64_t stride_bytes, double radius, int32_t max_nn, int64_t* row_start,
+                             int64_t* total) {
+  return guarded([&]() -> int {
+    if (!std::isfinite(radius) || radius < 0.0) return fail(APDGICP_ERR_INVALID_ARG, "radius must be finite and not negative");
+    if (max_nn < 0) return fail(APDGICP_ERR_INVALID_ARG, "max_nn must not be negative");
+    APD_TRY(search_check_queries(queries_xyz, n, stride_bytes));
+    if (!h || !row_start || !total) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    Engine& e = h->eng;
+    if (e.clouds.size() < 2 || e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
+    roctx_range rr("apdgicp:radius_search_of");
+    const float r2 = (float)(radius * radius);  // Q4
+    SearchTarget T;
+    int nblk = 0;
+    APD_TRY(search_set_queries(h, queries_xyz, n, stride_bytes, &T, &nblk));
+    Engine::SearchState& s = e.sq;
+    s.src_start.assign((size_t)n + 1, 0);
+    s.len.assign((size_t)n, 0);
+    const Engine::Cloud& q = e.clouds[2];
+    if (max_nn > 0 && max_nn <= SQ_KMAX && max_nn < T.n) {
+      // Q9: the k-nearest kernel with r2 as its bound; row i is the head of the table's row i
+      APD_TRY(search_launch_knn(e, T, n, nblk, max_nn, true, r2));
+      APD_HIP(hipMemcpyAsync(s.len.data(), s.cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+      APD_HIP(hipStreamSynchronize(e.stream));
+      APD_TRY(search_add_group_stats(e, nblk, T.n));
+      for (int64_t i = 0; i < n; i++) s.src_start[i] = i * max_nn;
+      s.span = n * max_nn;
+    } else {
+      // every hit: count, scan, (one wait: the total sizes the rows), fill, sort each row
+      const int nsb = (int)((n + SCAN_BLK - 1) / SCAN_BLK);
+      APD_TRY(s.cnt.ensure((size_t)n * sizeof(int)));
+      APD_TRY(s.pos.ensure((size_t)n * sizeof(int)));
+      APD_TRY(s.bsum.ensure(((size_t)nsb + 1) * sizeof(int)));
+      hipLaunchKernelGGL(k_radius_count, dim3((unsigned)nblk), dim3(SQ_BLK), 0, e.stream, T, q.pts.as<float4>(), q.perm.as<int>(), (int)n, r2, s.cnt.as<int>(),
+                         s.visit.as<int>());
+      hipLaunchKernelGGL(k_radius_scan, dim3((unsigned)nsb), dim3(SCAN_BLK), 0, e.stream, s.cnt.as<int>(), (int)n, s.pos.as<int>(), s.bsum.as<int>());
+      hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, s.bsum.as<int>(), nsb, s.bsum.as<int>() + nsb);
+      APD_HIP(hipGetLastError());
+      APD_HIP(hipMemcpyAsync(s.len.data(), s.cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+      APD_HIP(hipStreamSynchronize(e.stream));
+      // (the device's scan is in int32: the host's own sum decides whether it can be trusted)
+      int64_t all = 0;
+      for (int64_t i = 0; i < n; i++) s.src_start[i] = all, all += s.len[i];
+      if (all > 0x7fffffffll) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^31 - 1 hits in all (" + std::to_string(all) + ")");
+      s.span = all;
+      if (all > 0) {
+        APD_TRY(s.keys.ensure((size_t)all * sizeof(unsigned long long)));
+        hipLaunchKernelGGL(k_radius_fill, dim3((unsigned)nblk), dim3(SQ_BLK), 0, e.stream, T, q.pts.as<float4>(), q.perm.as<int>(), (int)n, r2, s.cnt.as<int>(),
+                           s.pos.as<int>(), s.bsum.as<int>(), s.keys.as<unsigned long long>());
+        hipLaunchKernelGGL(k_radius_sort_rows, dim3((unsigned)n), dim3(SQ_SORT_BLK), 0, e.stream, s.cnt.as<int>(), s.pos.as<int>(), s.bsum.as<int>(),
+                           s.keys.as<unsigned long long>());
+        APD_HIP(hipGetLastError());
+        APD_HIP(hipStreamSynchronize(e.stream));
+      }
+      APD_TRY(search_add_group_stats(e, nblk, T.n));
+      if (max_nn > 0 && max_nn < T.n)  // Q5: the max_nn smallest of a longer row
+        for (int64_t i = 0; i < n; i++) s.len[i] = std::min<int>(s.len[i], max_nn);
+    }
+    int64_t sum = 0;
+    for (int64_t i = 0; i < n; i++) row_start[i] = sum, sum += s.len[i];
+    row_start[n] = sum;
+    if (sum > 0x7fffffffll) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^31 - 1 hits in all (" + std::to_string(sum) + ")");
+    *total = s.total = sum;
+    s.tgt_gen = h->cloud_gen[kTgt];
+    s.rows_valid = true;
+    return 0;
+  });
+}
+
+int apdgicp_radius_search_rows(apdgicp_handle* h, int32_t* index, float* sq_dist) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    Engine& e = h->eng;
+    Engine::SearchState& s = e.sq;
+    if (!s.rows_valid) return fail(APDGICP_ERR_NO_INPUT, "no radius search whose rows are kept (apdgicp_radius_search_of)");
+    if (s.tgt_gen != h->cloud_gen[kTgt]) return fail(APDGICP_ERR_NO_INPUT, "the target has been set since the radius search");
+    if (s.total == 0) return 0;
+    if (!index || !sq_dist) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_HIP(hipSetDevice(e.device));
+    std::vector<unsigned long long> keys((size_t)s.span);
+    APD_HIP(hipMemcpyAsync(keys.data(), s.keys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    int64_t o = 0;
+    for (size_t i = 0; i < s.len.size(); i++)
+      for (int r = 0; r < s.len[i]; r++, o++) {
+        const unsigned long long key = keys[(size_t)s.src_start[i] + r];
+        const uint32_t bits = (uint32_t)(key >> 32);
+        index[o] = (int32_t)(uint32_t)key;
+        memcpy(&sq_dist[o], &bits, 4);
+      }
+    return 0;
+  });
+}
+
+int apdgicp_search_group_stats(apdgicp_handle* h, int64_t* groups_visited, int64_t* groups_total) {
+  if (!h || !groups_visited || !groups_total) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  *groups_visited = h->eng.sq.groups_visited, *groups_total = h->eng.sq.groups_total;
+  return 0;
 }
 
 int apdgicp_get_points(apdgicp_handle* h, int which, float* out_xyz, int64_t n) {

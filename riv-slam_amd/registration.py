@@ -84,6 +84,7 @@ assert RESULT_DTYPE.itemsize == C.sizeof(Result) == 96
 SYMBOLS = [
     "apdgicp_abi_version", "apdgicp_source_stamp", "apdgicp_build_flags", "apdgicp_last_error", "apdgicp_device_count", "apdgicp_default_params",
     "apdgicp_set_trace", "apdgicp_get_trace", "apdgicp_get_trace_step_norms", "apdgicp_debug_atan2f", "apdgicp_debug_live_buffers", "apdgicp_nearest_neighbours", "apdgicp_nearest_neighbours_of", "apdgicp_get_points",
+    "apdgicp_knn_of", "apdgicp_radius_search_of", "apdgicp_radius_search_rows", "apdgicp_search_group_stats",
     "apdgicp_create", "apdgicp_destroy", "apdgicp_set_params", "apdgicp_get_params",
     "apdgicp_set_source", "apdgicp_set_target", "apdgicp_clear_source", "apdgicp_clear_target",
     "apdgicp_swap_source_and_target", "apdgicp_compute_covariances", "apdgicp_get_covariances",
@@ -208,6 +209,10 @@ def load_library(path: str | None = None):
     L.apdgicp_nearest_neighbours.argtypes = [vp, vp, vp, vp, i64]
     L.apdgicp_nearest_neighbours_of.argtypes = [vp, vp, i64, i64, vp, vp]
     L.apdgicp_get_points.argtypes = [vp, i32, vp, i64]
+    L.apdgicp_knn_of.argtypes = [vp, vp, i64, i64, i32, vp, vp, C.POINTER(i32)]
+    L.apdgicp_radius_search_of.argtypes = [vp, vp, i64, i64, dbl, i32, vp, C.POINTER(i64)]
+    L.apdgicp_radius_search_rows.argtypes = [vp, vp, vp]
+    L.apdgicp_search_group_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     L.apdgicp_transform_source.argtypes = [vp, vp, vp, i64, i64]
     L.apdgicp_fitness_score.argtypes = [vp, vp, dbl, C.POINTER(dbl), C.POINTER(i64)]
     L.apdgicp_inlier_fraction.argtypes = [vp, vp, dbl, C.POINTER(dbl), C.POINTER(i64)]
@@ -730,6 +735,39 @@ class FastAPDGICP:
         sqd = np.empty(len(q), dtype=np.float32)
         _check(self.L.apdgicp_nearest_neighbours_of(self.h, _ptr(q), len(q), q.strides[0], _ptr(idx), _ptr(sqd)))
         return idx, sqd
+
+    def nearestKSearchOf(self, queries, k: int):
+        """(index [n, k] int32, sq_dist [n, k] float32) of the k nearest target points of arbitrary host query points [n, >= 3]
+        float32, ascending by (distance, index): one device pass (apdgicp_knn_of, Q1 .. Q3 of include/apdgicp_hip.h).  A target of
+        fewer than k points leaves the tail of every row at -1 / +Inf; self.last_n_found says how many entries of a row hold."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        kk = max(int(k), 0)
+        idx = np.empty((len(q), kk), dtype=np.int32)
+        sqd = np.empty((len(q), kk), dtype=np.float32)
+        found = C.c_int32()
+        _check(self.L.apdgicp_knn_of(self.h, _ptr(q), len(q), q.strides[0] if q.ndim == 2 else 0, int(k), _ptr(idx), _ptr(sqd), C.byref(found)))
+        self.last_n_found = found.value
+        return idx, sqd
+
+    def radiusSearchOf(self, queries, radius: float, max_nn: int = 0):
+        """(row_start [n + 1] int64, index [total] int32, sq_dist [total] float32): the target points strictly inside `radius` of every
+        query, row i = [row_start[i], row_start[i + 1]), ascending by (distance, index), at most max_nn of them when 0 < max_nn < M
+        (apdgicp_radius_search_of / _rows, Q4 .. Q6)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        row_start = np.zeros(len(q) + 1, dtype=np.int64)
+        total = C.c_int64()
+        _check(self.L.apdgicp_radius_search_of(self.h, _ptr(q), len(q), q.strides[0] if q.ndim == 2 else 0, float(radius), int(max_nn), _ptr(row_start),
+                                               C.byref(total)))
+        idx = np.empty(total.value, dtype=np.int32)
+        sqd = np.empty(total.value, dtype=np.float32)
+        _check(self.L.apdgicp_radius_search_rows(self.h, _ptr(idx), _ptr(sqd)))
+        return row_start, idx, sqd
+
+    def searchGroupStats(self):
+        """(groups visited, groups without pruning) of the last nearestKSearchOf / radiusSearchOf"""
+        a, b = C.c_int64(), C.c_int64()
+        _check(self.L.apdgicp_search_group_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def getPoints(self, which) -> np.ndarray:
         n = self._n(which)
