@@ -118,8 +118,19 @@ struct VoxMapBufs {
 
 static int n_offsets(int neighbor_search) { return neighbor_search == APDGICP_VGICP_DIRECT27 ? 27 : neighbor_search == APDGICP_VGICP_DIRECT7 ? 7 : 1; }
 
-// apdgicp_set_vgicp: the voxel map of the target and the frozen state of the last linearize (include/apdgicp_hip.h, V1 .. V7).  The scratch of
-// a map build is the handle's (apdgicp_handle::sort).
+// The frozen state of the last linearize of whichever voxel mode is on (V6 / VC8 / N7): the voxel indices it found (rows x noff ints), the
+// block rows of the reduction, the pose pair on the device and the 44 doubles read back.  ONE per handle (apdgicp_handle::lin): set_mode()
+// clears `have` on every transition, so nothing in here ever has to outlive a mode switch.  What a linearize was made FROM stays with the
+// mode, as identity stamps (lin_src_gen, lin_build, ...), and so does the test that those still name what the handle holds.
+struct FrozenLin {
+  bool have = false;
+  int rows = 0, noff = 0;
+  double T_lin[12];
+  DevBuf corr, part, T, out;
+};
+
+// apdgicp_set_vgicp: the voxel map of the target and what the last linearize was made from (include/apdgicp_hip.h, V1 .. V7).  The scratch of
+// a map build and the frozen state are the handle's (apdgicp_handle::sort, apdgicp_handle::lin).
 struct VgState {
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
   // What the cached pieces were made FROM, by identity: apdgicp_handle::cloud_gen names the points of a slot (and their order on the curve),
@@ -131,14 +142,11 @@ struct VgState {
   int map_mode = 0;
   uint64_t inv_src_gen = 0;    // inv_s: the inverse of the permutation of source points inv_src_gen, inv_n entries
   int inv_n = 0;
-  bool have_lin = false;       // corr / T_lin: a linearize of source lin_src_gen with covariances lin_src_cov_gen against map number lin_build
-  uint64_t lin_src_gen = 0, lin_src_cov_gen = 0;
+  uint64_t lin_src_gen = 0, lin_src_cov_gen = 0;  // apdgicp_handle::lin: a linearize of source lin_src_gen with covariances lin_src_cov_gen against map number lin_build
   int64_t lin_build = 0;
   int64_t n_vox = 0, builds = 0;
-  int n_src_lin = 0, noff_lin = 0;
-  double T_lin[12];
   VoxMapBufs buf;
-  DevBuf scal, inv_t, inv_s, corr, part, T, out;
+  DevBuf scal, inv_t, inv_s;
   VgMap map() const { return buf.map((int)n_vox); }
 };
 
@@ -191,8 +199,8 @@ struct VcOffsets {
 };
 
 // apdgicp_set_vgicp_cuda: per cloud the prepared cloud (kept points, their covariances, their original indices), the voxel map of the
-// prepared target and the frozen state of the last linearize (include/apdgicp_hip.h, VC1 .. VC10).  The scratch of a map build is the
-// handle's (apdgicp_handle::sort).
+// prepared target and what the last linearize was made from (include/apdgicp_hip.h, VC1 .. VC10).  The scratch of a map build, the frozen
+// state and the Hessian of the last align are the handle's (apdgicp_handle::sort, ::lin, ::final_H).
 struct VcState {
   apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
   VcPrepared pc[2];              // [source, target]; swapped with the clouds
@@ -202,23 +210,15 @@ struct VcState {
   double map_res = 0.0;
   int64_t n_vox = 0, builds = 0;
   VcOffsets offs;
-  bool have_lin = false;         // corr / T_lin: a linearize of prepared source lin_src_id against map number lin_build
-  int64_t lin_src_id = 0, lin_build = 0;
-  int n_src_lin = 0, noff_lin = 0;
-  double T_lin[12];
-  double final_H[36];            // of the last align in this mode (identity until then), on the host like NdState's
+  int64_t lin_src_id = 0, lin_build = 0;  // apdgicp_handle::lin: a linearize of prepared source lin_src_id against map number lin_build
   VoxMapBufs buf;
   CachedTable prep_tab[2], prep_ids[2];  // per cloud, the VcbSlot table and the cloud id of its preparation: uploaded again only when a pointer or n changes
-  DevBuf scal, corr, part, T, out;  // scal, ints: [0, 4) a map build, [4 + which] n_kept of cloud `which`'s preparation
+  DevBuf scal;                   // ints: [0, 4) a map build, [4 + which] n_kept of cloud `which`'s preparation
   VgMap map() const { return buf.map((int)n_vox); }
-  VcState() { reset_final_H(); }
-  void reset_final_H() {
-    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
-  }
 };
 
-// apdgicp_set_ndt: the voxel maps of target and source and the frozen state of the last linearize (include/apdgicp_hip.h, N1 .. N9).  The
-// scratch of a map build is the handle's (apdgicp_handle::sort).
+// apdgicp_set_ndt: the voxel maps of target and source and what the last linearize was made from (include/apdgicp_hip.h, N1 .. N9).  The
+// scratch of a map build, the frozen state and the Hessian of the last align are the handle's (apdgicp_handle::sort, ::lin, ::final_H).
 struct NdState {
   struct Map {                 // one cloud's map: a pure function of (points, resolution), cached by identity like VgState's
     bool built = false;
@@ -232,17 +232,10 @@ struct NdState {
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
   Map maps[2];                 // [source, target]; swapped with the clouds
   int64_t builds = 0;
-  bool have_lin = false;       // corr / T_lin: a linearize of source lin_src_gen against map lin_tgt_id (and, D2D, over the rows of map lin_src_id)
-  uint64_t lin_src_gen = 0;
+  uint64_t lin_src_gen = 0;    // apdgicp_handle::lin: a linearize of source lin_src_gen against map lin_tgt_id (and, D2D, over the rows of map lin_src_id)
   int64_t lin_tgt_id = 0, lin_src_id = 0;
-  int lin_mode = 0, n_rows_lin = 0, noff_lin = 0;
-  double T_lin[12];
-  double final_H[36];          // of the last align in this mode (identity until then)
-  DevBuf scal, corr, part, T, out;
-  NdState() { reset_final_H(); }
-  void reset_final_H() {
-    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
-  }
+  int lin_mode = 0;
+  DevBuf scal;
 };
 
 // apdgicp_set_icp: the working cloud W (in the source's curve order), its boxes, the matches and the record of the last iteration
@@ -274,7 +267,13 @@ struct apdgicp_handle {
   NdState nd;   // (likewise)
   IcState ic;   // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of whichever voxel mode is on
+  FrozenLin lin;        // (likewise) the frozen state of the last linearize of whichever voxel mode is on
+  double final_H[36];   // FAST_VGICP_CUDA and NDT: the Hessian of the last align in the mode, on the host (identity until then, and again when either is entered)
   Mode mode = Mode::APD;
+  apdgicp_handle() { reset_final_H(); }
+  void reset_final_H() {
+    for (int q = 0; q < 36; q++) final_H[q] = (q % 7 == 0) ? 1.0 : 0.0;
+  }
   ~apdgicp_handle() {
     if (eng.stream) (void)hipStreamSynchronize(eng.stream);  // the voxel kernels run there; the members are freed once this body has run
   }
@@ -287,56 +286,57 @@ struct apdgicp_handle {
   std::vector<double> tr_lambda, tr_rho, tr_y0, tr_yi, tr_dnorm, tr_poses;  // poses: 16 doubles each, column-major
 };
 
-// apdgicp_batch_set_vgicp (include/apdgicp_hip.h, V8 .. V12): per cloud slot the voxel map and the inverse permutation, cached by identity like
-// VgState's pieces; per align the pair table, the frozen indices and the block rows.  The scratch of a map build and the state of the device
-// loop are the handle's (apdgicp_batch::sort, apdgicp_batch::loop).
-struct VgbState {
+// What every voxel mode of a batch handle owns per cloud slot and per handle: the slots' voxel maps and their device words, the count of
+// builds.  Each mode has its OWN table (VgbState::vox, NdbState::vox, VcbState::vox), so that a mode's cached maps survive a switch to another
+// mode and back; what a slot's map was made from stays with the mode, slot by slot, in a list of the same length (its `slots`).
+struct VoxSlots {
   struct Slot {
+    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
+    VoxMapBufs buf;            // sized for nv <= n
+  };
+  std::vector<Slot> slots;
+  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
+  int scal_slots = 0;
+  int64_t builds = 0;
+  int* words(int slot) const { return scal.as<int>() + 4 * (size_t)slot; }
+  VgbMap map(int slot) const { return slots[slot].buf.map(words(slot) + 1); }
+  void release() {  // apdgicp_batch_clear: the maps go with the clouds
+    slots.clear();
+    scal.release();
+    scal_slots = 0;
+  }
+};
+
+// apdgicp_batch_set_vgicp (include/apdgicp_hip.h, V8 .. V12): per cloud slot the voxel map and the inverse permutation, cached by identity like
+// VgState's pieces.  The scratch of a map build, the state of the device loop and what an align leaves (pair table, frozen indices, block rows)
+// are the handle's (apdgicp_batch::sort, ::loop, ::run).
+struct VgbState {
+  struct Slot {                // (its map: vox.slots, same index)
     bool map_built = false;    // the map: points map_pts_gen, covariances map_cov_gen, map_res, map_mode
     uint64_t map_pts_gen = 0, map_cov_gen = 0;
     double map_res = 0.0;
     int map_mode = 0;
     uint64_t inv_pts_gen = 0;  // inv: the inverse of the permutation of points inv_pts_gen (0: none)
-    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
     DevBuf inv;
-    VoxMapBufs buf;            // sized for nv <= n
   };
   apdgicp_vgicp_params prm{1.0, APDGICP_VGICP_DIRECT1, APDGICP_VGICP_ADDITIVE};
   std::vector<Slot> slots;
-  int64_t builds = 0;
-  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
-  int scal_slots = 0;
-  DevBuf corr, part;
-  CachedTable pairs;
-  void release() {  // apdgicp_batch_clear: the maps go with the clouds
-    slots.clear();
-    scal.release(), corr.release(), part.release(), pairs.dev.release();
-    scal_slots = 0;
-  }
+  VoxSlots vox;
+  void release() { slots.clear(), vox.release(); }  // apdgicp_batch_clear
 };
 
-// apdgicp_batch_set_ndt (include/apdgicp_hip.h, N10 .. N15): per cloud slot the NDT voxel map, cached by identity like NdState's; per align the
-// pair table, the frozen indices and the block rows.  Scratch and device-loop state: the handle's, as for VgbState.
+// apdgicp_batch_set_ndt (include/apdgicp_hip.h, N10 .. N15): per cloud slot the NDT voxel map, cached by identity like NdState's.  Scratch,
+// device-loop state and what an align leaves: the handle's, as for VgbState.
 struct NdbState {
-  struct Slot {
+  struct Slot {                // (its map: vox.slots, same index)
     bool built = false;        // the map: points pts_gen, resolution res
     uint64_t pts_gen = 0;
     double res = 0.0;
-    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
-    VoxMapBufs buf;            // sized for nv <= n
   };
   apdgicp_ndt_params prm{1.0, APDGICP_NDT_D2D, APDGICP_VGICP_DIRECT7};
   std::vector<Slot> slots;
-  int64_t builds = 0;
-  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
-  int scal_slots = 0;
-  DevBuf corr, part;
-  CachedTable pairs;
-  void release() {  // apdgicp_batch_clear: the maps go with the clouds
-    slots.clear();
-    scal.release(), corr.release(), part.release(), pairs.dev.release();
-    scal_slots = 0;
-  }
+  VoxSlots vox;
+  void release() { slots.clear(), vox.release(); }  // apdgicp_batch_clear
 };
 
 // apdgicp_batch_set_icp (include/apdgicp_hip.h, IC11 .. IC16): per align the working clouds of all pairs (one buffer, a slice per pair), their
@@ -361,41 +361,46 @@ struct IcbState {
 };
 
 // apdgicp_batch_set_vgicp_cuda (include/apdgicp_hip.h, VC11 .. VC16): per cloud slot the prepared cloud of VC1 .. VC4 and, for targets, the voxel
-// map of its kept points, both cached by identity like VcState's; per align the pair table, the frozen indices and the block rows.  Scratch and
-// device-loop state: the handle's, as for VgbState.
+// map of its kept points, both cached by identity like VcState's.  Scratch, device-loop state and what an align leaves: the handle's, as for
+// VgbState.
 struct VcbState {
-  struct Slot {
+  struct Slot {                // (its map: vox.slots, same index)
     VcPrepared pc;
     bool map_built = false;    // the map: preparation map_prep_id at map_res
     int64_t map_prep_id = 0;
     double map_res = 0.0;
-    int nv = 0;                // host copy of the voxel count (the kernels read the device word)
-    VoxMapBufs buf;            // sized for nv <= n
   };
   apdgicp_vgicp_cuda_params prm{1.0, APDGICP_VGICP_DIRECT1, 1.5, APDGICP_REG_PLANE, APDGICP_NN_CPU_PARALLEL_KDTREE};
   std::vector<Slot> slots;
-  int64_t preps = 0, builds = 0;
+  VoxSlots vox;
+  int64_t preps = 0;
   int64_t prep_waits = 0, map_waits = 0;  // host waits spent preparing clouds / building maps since the handle was created
   double phase_ms[3] = {0, 0, 0};         // of the last align: preparation, map builds, ticks by the host clock (meaningful with profiling on)
-  DevBuf scal;                 // per slot {first bad point, voxel count, radix scratch word, -}: 4 ints
-  int scal_slots = 0;
   DevBuf nk;                   // per slot: the kept count of its preparation
   int nk_slots = 0;
   VcOffsets offs;
-  // what apdgicp_batch_vgicp_cuda_get_correspondences may read: the last align in this mode, while no cloud slot has been written since
+  // what apdgicp_batch_vgicp_cuda_get_correspondences may read of apdgicp_batch::run: the last align in this mode, while no cloud slot has
+  // been written since (cleared by every enabling call of the setter, so never another mode's indices)
   bool have = false;
   uint64_t have_epoch = 0;
   std::vector<int> have_nk;    // per pair of that align: kept source points
-  size_t have_stride = 0;
-  int have_noff = 0;
-  DevBuf corr, part;
-  CachedTable pairs, prep_tab, prep_ids;
+  CachedTable prep_tab, prep_ids;
   void release() {  // apdgicp_batch_clear: the prepared clouds and the maps go with the clouds
-    slots.clear();
+    slots.clear(), vox.release();
     have = false;
-    scal.release(), nk.release(), corr.release(), part.release(), pairs.dev.release(), prep_tab.dev.release(), prep_ids.dev.release();
-    scal_slots = nk_slots = 0;
+    nk.release(), prep_tab.dev.release(), prep_ids.dev.release();
+    nk_slots = 0;
   }
+};
+
+// What an align of a voxel mode of a batch handle leaves, whichever mode ran it (only one align runs at a time): the pair table, per pair the
+// frozen voxel indices of its last linearize and the block rows of the reduction.
+struct VoxRun {
+  DevBuf corr, part;
+  CachedTable pairs;
+  size_t corr_stride = 0;      // of the last align: ints between two pairs' indices, offsets per row
+  int noff = 0;
+  void release() { corr.release(), part.release(), pairs.dev.release(); }  // apdgicp_batch_clear
 };
 
 // The device optimiser loop of a batch handle (V12 / N15 / IC15), whichever mode runs it: the done counter the step kernels count into, the
@@ -426,6 +431,7 @@ struct apdgicp_batch {
   IcbState ic;  // (likewise)
   VcbState vc;  // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of whichever voxel mode is on
+  VoxRun run;           // (likewise) the pair table, frozen indices and block rows of the last align of whichever voxel mode ran it
   Mode mode = Mode::APD;
   DeviceLoop loop;      // (likewise; its events by its own destructor)
   int64_t slot_pairs[2] = {0, 0};  // pairs of the last two enqueued batches (by ticket parity)
@@ -434,6 +440,7 @@ struct apdgicp_batch {
     nd.release();
     ic.release();
     vc.release();
+    run.release();
     sort = VoxSortScratch{};
     loop.release();
   }
@@ -773,11 +780,50 @@ int ensure_corr_part(Engine& e, DevBuf& corr, DevBuf& part, size_t corr_bytes, s
   return part.ensure(part_bytes);
 }
 
+void colmajor_to_rows12(const double* T16, double* r12) {
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) r12[4 * i + j] = T16[i + 4 * j];
+}
+
+// The head of a single handle's linearize at T (column-major 4x4) over `rows` rows of `noff` offsets: the frozen state is void until the
+// mode says otherwise, its buffers sized (behind a wait when the indices or the block rows are replaced), the pose on the device.
+int lin_begin(Engine& e, FrozenLin& f, int rows, int noff, const double* T16) {
+  const int nblk = (rows + VG_BLK - 1) / VG_BLK;
+  f.have = false;
+  APD_TRY(ensure_corr_part(e, f.corr, f.part, (size_t)rows * noff * 4, (size_t)nblk * VG_RED * 8));
+  APD_TRY(f.T.ensure(24 * sizeof(double)));
+  APD_TRY(f.out.ensure(64 * sizeof(double)));
+  f.rows = rows, f.noff = noff;
+  colmajor_to_rows12(T16, f.T_lin);
+  APD_HIP(hipMemcpyAsync(f.T.p, f.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  return 0;
+}
+
+// The head of a single handle's compute_error at T (the caller has found the frozen state current): the new pose, then the pose of the linearize
+int err_begin(Engine& e, const FrozenLin& f, const double* T16) {
+  APD_HIP(hipSetDevice(e.device));
+  double t24[24];
+  colmajor_to_rows12(T16, t24);
+  memcpy(t24 + 12, f.T_lin, 12 * sizeof(double));
+  APD_HIP(hipMemcpyAsync(f.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  return 0;
+}
+
+// The body of the three apdgicp_*_get_correspondences (the caller has checked its mode and that the frozen state is its own and current):
+// rows x noff voxel indices.  rows_msg: what the mode calls a wrong n_rows.  (No row: FAST_VGICP_CUDA without a kept source point.)
+int read_frozen_corr(Engine& e, const FrozenLin& f, int32_t* voxel_index, int64_t n_rows, const char* rows_msg) {
+  if (n_rows != f.rows) return fail(APDGICP_ERR_INVALID_ARG, rows_msg);
+  if (f.rows == 0) return 0;
+  APD_HIP(hipMemcpyAsync(voxel_index, f.corr.p, (size_t)n_rows * f.noff * 4, hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  return 0;
+}
+
 // The tail of a single handle's linearize (offset 0) and compute_error (offset 27): the block rows reduced, the 44 doubles read with a wait.
-int reduce_and_read(Engine& e, const DevBuf& part, DevBuf& out, int nblk, int offset, double* H, double* b, double* cost, int* matched) {
-  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, part.as<double>(), nblk, offset, out.as<double>());
+int reduce_and_read(Engine& e, const FrozenLin& f, int offset, double* H, double* b, double* cost, int* matched) {
+  hipLaunchKernelGGL(k_vg_reduce, dim3(1), dim3(64), 0, e.stream, f.part.as<double>(), (f.rows + VG_BLK - 1) / VG_BLK, offset, f.out.as<double>());
   APD_HIP(hipGetLastError());
-  APD_HIP(hipMemcpyAsync(e.h_probe.p, out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipMemcpyAsync(e.h_probe.p, f.out.p, 44 * sizeof(double), hipMemcpyDeviceToHost, e.stream));
   APD_HIP(hipStreamSynchronize(e.stream));
   if (H && b) {
     memcpy(H, e.h_probe.p, 36 * sizeof(double));
@@ -800,7 +846,7 @@ int vg_build_map(apdgicp_handle* h) {
   if (v.map_built && v.map_tgt_gen == h->cloud_gen[kTgt] && v.map_cov_gen == c.cov_gen && v.map_res == v.prm.resolution && v.map_mode == v.prm.voxel_mode) return 0;
   const int n = c.n;
   APD_HIP(hipSetDevice(e.device));
-  v.map_built = v.have_lin = false;
+  v.map_built = h->lin.have = false;
   VoxSorted s;
   int nv = 0;
   APD_TRY(handle_sort_voxels(h, kTgt, v.prm.resolution, v.scal, "voxelized GICP: ", &s, &nv));
@@ -834,28 +880,20 @@ int vg_prepare(apdgicp_handle* h) {
   return 0;
 }
 
-void colmajor_to_rows12(const double* T16, double* r12) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 4; j++) r12[4 * i + j] = T16[i + 4 * j];
-}
-
 // linearize (V:119-180) at T (column-major 4x4)
 int vg_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
   APD_TRY(vg_prepare(h));
   Engine& e = h->eng;
   VgState& v = h->vg;
+  FrozenLin& f = h->lin;
   const Engine::Cloud& s = e.clouds[kSrc];
   const int n = s.n, noff = n_offsets(v.prm.neighbor_search), nblk = (n + VG_BLK - 1) / VG_BLK;
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)n * noff * 4, (size_t)nblk * VG_RED * 8));
-  APD_TRY(v.T.ensure(24 * sizeof(double)));
-  APD_TRY(v.out.ensure(64 * sizeof(double)));
-  colmajor_to_rows12(T16, v.T_lin);
-  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  APD_TRY(lin_begin(e, f, n, noff, T16));
   const int want = H && b ? 1 : 0;
-  hipLaunchKernelGGL(k_vg_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(),
-                     v.prm.resolution, (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
-  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));
-  v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
+  hipLaunchKernelGGL(k_vg_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), f.T.as<double>(),
+                     v.prm.resolution, (int)v.prm.neighbor_search, noff, want, f.corr.as<int>(), f.part.as<double>());
+  APD_TRY(reduce_and_read(e, f, 0, H, b, cost, matched));
+  f.have = true;
   v.lin_src_gen = h->cloud_gen[kSrc], v.lin_src_cov_gen = s.cov_gen, v.lin_build = v.builds;
   return 0;
 }
@@ -864,22 +902,19 @@ int vg_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
 int vg_error(apdgicp_handle* h, const double* T16, double* cost) {
   Engine& e = h->eng;
   VgState& v = h->vg;
+  const FrozenLin& f = h->lin;
   if (e.clouds.size() < 2) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
   const Engine::Cloud &s = e.clouds[kSrc], &t = e.clouds[kTgt];
   // the frozen state must still describe what the handle holds: the same source points and covariances, the same map of the same target
-  const bool frozen_ok = v.have_lin && s.n > 0 && s.n == v.n_src_lin && s.cov_valid && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_src_cov_gen == s.cov_gen &&
+  const bool frozen_ok = f.have && s.n > 0 && s.n == f.rows && s.cov_valid && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_src_cov_gen == s.cov_gen &&
                          v.inv_src_gen == h->cloud_gen[kSrc] && v.inv_n == s.n && v.map_built && v.lin_build == v.builds && t.cov_valid &&
                          v.map_tgt_gen == h->cloud_gen[kTgt] && v.map_cov_gen == t.cov_gen && v.map_res == v.prm.resolution && v.map_mode == v.prm.voxel_mode;
   if (!frozen_ok) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds, covariances and voxel map the handle holds now");
-  const int n = s.n, noff = v.noff_lin, nblk = (n + VG_BLK - 1) / VG_BLK;
-  APD_HIP(hipSetDevice(e.device));
-  double t24[24];
-  colmajor_to_rows12(T16, t24);
-  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
-  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
-  hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), v.T.as<double>(), noff,
-                     v.corr.as<int>(), v.part.as<double>());
-  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
+  const int n = s.n, nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_TRY(err_begin(e, f, T16));
+  hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), s.cov.as<double>(), v.inv_s.as<int>(), n, v.map(), f.T.as<double>(), f.noff,
+                     f.corr.as<int>(), f.part.as<double>());
+  return reduce_and_read(e, f, 27, nullptr, nullptr, cost, nullptr);
 }
 
 // The reference's own control flow (L:55-173) on the host over two callables: lin(T16, H, b, &y0, &matched) and err(T16, &yi), the two
@@ -990,11 +1025,19 @@ int host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, Lin
   return 0;
 }
 
+// The host loop of a voxel mode over its linearize and its compute_error: a linearize without a correspondence ends it (V7 / VC9 / N8).
+// final_H_out: see host_loop.
+using LinFn = int (*)(apdgicp_handle*, const double*, double*, double*, double*, int*);
+using ErrFn = int (*)(apdgicp_handle*, const double*, double*);
+int voxel_host_loop(apdgicp_handle* h, const float guess[16], apdgicp_result* out, LinFn lin, ErrFn err, double* final_H_out) {
+  return host_loop(
+      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return lin(h, T, H, b, y0, m); },
+      [&](const double* T, double* yi) { return err(h, T, yi); }, true, final_H_out);
+}
+
 int vg_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   APD_TRY(vg_prepare(h));
-  return host_loop(
-      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vg_linearize(h, T, H, b, y0, m); },
-      [&](const double* T, double* yi) { return vg_error(h, T, yi); }, true);
+  return voxel_host_loop(h, guess, out, vg_linearize, vg_error, nullptr);
 }
 
 // ---- FAST_VGICP_CUDA (include/apdgicp_hip.h VC1 .. VC10; kernels: apd_vgicp_cuda.hpp)
@@ -1129,7 +1172,7 @@ int vc_prepare_cloud(apdgicp_handle* h, int which) {
   if (n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "cloud has fewer points than k_correspondences");
   APD_HIP(hipSetDevice(e.device));
   APD_TRY(e.upload_desc());  // (sorts what is not sorted yet)
-  v.have_lin = false;
+  h->lin.have = false;
   APD_TRY(v.scal.ensure(32));
   int* d_total = v.scal.as<int>() + 4 + which;
   bool waited = false;
@@ -1153,7 +1196,7 @@ int vc_build_map(apdgicp_handle* h) {
   APD_TRY(vc_prepare_cloud(h, kTgt));
   const VcPrepared& t = v.pc[kTgt];
   if (v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution) return 0;
-  v.map_built = v.have_lin = false;
+  v.map_built = h->lin.have = false;
   int nv = 0;
   if (t.n_kept > 0) {  // (no kept point: an empty map, no sort)
     const int n = t.n_kept;
@@ -1186,19 +1229,16 @@ int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   APD_TRY(vc_prepare(h));
   Engine& e = h->eng;
   VcState& v = h->vc;
+  FrozenLin& f = h->lin;
   const VcPrepared& s = v.pc[kSrc];
   const int n = s.n_kept, noff = v.offs.count(), nblk = (n + VG_BLK - 1) / VG_BLK;
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)n * noff * 4, (size_t)nblk * VG_RED * 8));
-  APD_TRY(v.T.ensure(24 * sizeof(double)));
-  APD_TRY(v.out.ensure(64 * sizeof(double)));
-  colmajor_to_rows12(T16, v.T_lin);
-  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  APD_TRY(lin_begin(e, f, n, noff, T16));
   const int want = H && b ? 1 : 0;
   if (nblk > 0)
-    hipLaunchKernelGGL(k_vc_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), v.T.as<double>(),
-                       v.prm.resolution, v.offs.dev.as<int>(), noff, want, v.corr.as<int>(), v.part.as<double>());
-  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));  // (no kept source point: no block rows, every sum 0)
-  v.have_lin = true, v.n_src_lin = n, v.noff_lin = noff;
+    hipLaunchKernelGGL(k_vc_linearize, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), f.T.as<double>(),
+                       v.prm.resolution, v.offs.dev.as<int>(), noff, want, f.corr.as<int>(), f.part.as<double>());
+  APD_TRY(reduce_and_read(e, f, 0, H, b, cost, matched));  // (no kept source point: no block rows, every sum 0)
+  f.have = true;
   v.lin_src_id = s.id, v.lin_build = v.builds;
   return 0;
 }
@@ -1207,32 +1247,27 @@ int vc_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
 bool vc_frozen_ok(const apdgicp_handle* h) {
   const VcState& v = h->vc;
   const VcPrepared &s = v.pc[kSrc], &t = v.pc[kTgt];
-  return v.have_lin && s.ready && s.pts_gen == h->cloud_gen[kSrc] && s.reg == v.prm.regularization && s.id == v.lin_src_id && s.n_kept == v.n_src_lin && t.ready &&
+  return h->lin.have && s.ready && s.pts_gen == h->cloud_gen[kSrc] && s.reg == v.prm.regularization && s.id == v.lin_src_id && s.n_kept == h->lin.rows && t.ready &&
          t.pts_gen == h->cloud_gen[kTgt] && t.reg == v.prm.regularization && v.map_built && v.map_prep_id == t.id && v.map_res == v.prm.resolution && v.lin_build == v.builds;
 }
 
 int vc_error(apdgicp_handle* h, const double* T16, double* cost) {
   Engine& e = h->eng;
   VcState& v = h->vc;
+  const FrozenLin& f = h->lin;
   if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds, regularisation and voxel map the handle holds now");
   const VcPrepared& s = v.pc[kSrc];
-  const int n = s.n_kept, noff = v.noff_lin, nblk = (n + VG_BLK - 1) / VG_BLK;
-  APD_HIP(hipSetDevice(e.device));
-  double t24[24];
-  colmajor_to_rows12(T16, t24);
-  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
-  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  const int n = s.n_kept, nblk = (n + VG_BLK - 1) / VG_BLK;
+  APD_TRY(err_begin(e, f, T16));
   if (nblk > 0)
-    hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), v.T.as<double>(), noff,
-                       v.corr.as<int>(), v.part.as<double>());
-  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
+    hipLaunchKernelGGL(k_vg_error, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), n, v.map(), f.T.as<double>(), f.noff,
+                       f.corr.as<int>(), f.part.as<double>());
+  return reduce_and_read(e, f, 27, nullptr, nullptr, cost, nullptr);
 }
 
 int vc_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   APD_TRY(vc_prepare(h));
-  return host_loop(
-      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return vc_linearize(h, T, H, b, y0, m); },
-      [&](const double* T, double* yi) { return vc_error(h, T, yi); }, true, h->vc.final_H);
+  return voxel_host_loop(h, guess, out, vc_linearize, vc_error, h->final_H);
 }
 
 // ---- NDT (include/apdgicp_hip.h N1 .. N9; kernels: apd_ndt.hpp)
@@ -1247,7 +1282,7 @@ int nd_build_map(apdgicp_handle* h, int which) {
   APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
   Engine::Cloud& c = e.clouds[which];
   m.built = false;
-  v.have_lin = false;
+  h->lin.have = false;
   VoxSorted s;
   int nv = 0;
   APD_TRY(handle_sort_voxels(h, which, v.prm.resolution, v.scal, "NDT: ", &s, &nv));
@@ -1278,25 +1313,22 @@ int nd_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
   APD_TRY(nd_prepare(h));
   Engine& e = h->eng;
   NdState& v = h->nd;
+  FrozenLin& f = h->lin;
   const Engine::Cloud& s = e.clouds[kSrc];
   const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
   const NdState::Map &mt = v.maps[kTgt], &ms = v.maps[kSrc];
   const int nrows = d2d ? ms.nv : s.n, noff = n_offsets(v.prm.neighbor_search), nblk = (nrows + VG_BLK - 1) / VG_BLK;
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)nrows * noff * 4, (size_t)nblk * VG_RED * 8));
-  APD_TRY(v.T.ensure(24 * sizeof(double)));
-  APD_TRY(v.out.ensure(64 * sizeof(double)));
-  colmajor_to_rows12(T16, v.T_lin);
-  APD_HIP(hipMemcpyAsync(v.T.p, v.T_lin, 12 * sizeof(double), hipMemcpyHostToDevice, e.stream));
+  APD_TRY(lin_begin(e, f, nrows, noff, T16));
   const int want = H && b ? 1 : 0;
   const VgMap smap = d2d ? ms.map() : VgMap{nullptr, nullptr, nullptr, nullptr, 0};
   if (d2d)
-    hipLaunchKernelGGL(k_ndt_linearize<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution,
-                       (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
+    hipLaunchKernelGGL(k_ndt_linearize<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), f.T.as<double>(), v.prm.resolution,
+                       (int)v.prm.neighbor_search, noff, want, f.corr.as<int>(), f.part.as<double>());
   else
-    hipLaunchKernelGGL(k_ndt_linearize<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution,
-                       (int)v.prm.neighbor_search, noff, want, v.corr.as<int>(), v.part.as<double>());
-  APD_TRY(reduce_and_read(e, v.part, v.out, nblk, 0, H, b, cost, matched));
-  v.have_lin = true, v.n_rows_lin = nrows, v.noff_lin = noff, v.lin_mode = v.prm.distance_mode;
+    hipLaunchKernelGGL(k_ndt_linearize<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), f.T.as<double>(), v.prm.resolution,
+                       (int)v.prm.neighbor_search, noff, want, f.corr.as<int>(), f.part.as<double>());
+  APD_TRY(reduce_and_read(e, f, 0, H, b, cost, matched));
+  f.have = true, v.lin_mode = v.prm.distance_mode;
   v.lin_src_gen = h->cloud_gen[kSrc], v.lin_tgt_id = mt.id, v.lin_src_id = d2d ? ms.id : 0;
   return 0;
 }
@@ -1305,38 +1337,33 @@ int nd_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, dou
 int nd_error(apdgicp_handle* h, const double* T16, double* cost) {
   Engine& e = h->eng;
   NdState& v = h->nd;
+  const FrozenLin& f = h->lin;
   if (e.clouds.size() < 2) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize");
   const Engine::Cloud& s = e.clouds[kSrc];
   const bool d2d = v.prm.distance_mode == APDGICP_NDT_D2D;
   const NdState::Map &mt = v.maps[kTgt], &ms = v.maps[kSrc];
   // the frozen state must still describe what the handle holds: the same source points, the same maps, the same mode and resolution
-  const bool frozen_ok = v.have_lin && s.n > 0 && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_mode == v.prm.distance_mode && mt.built && mt.id == v.lin_tgt_id &&
+  const bool frozen_ok = f.have && s.n > 0 && v.lin_src_gen == h->cloud_gen[kSrc] && v.lin_mode == v.prm.distance_mode && mt.built && mt.id == v.lin_tgt_id &&
                          mt.pts_gen == h->cloud_gen[kTgt] && mt.res == v.prm.resolution && e.clouds[kTgt].n > 0 &&
-                         (d2d ? (ms.built && ms.id == v.lin_src_id && ms.pts_gen == h->cloud_gen[kSrc] && ms.res == v.prm.resolution && ms.nv == v.n_rows_lin)
-                              : s.n == v.n_rows_lin);
+                         (d2d ? (ms.built && ms.id == v.lin_src_id && ms.pts_gen == h->cloud_gen[kSrc] && ms.res == v.prm.resolution && ms.nv == f.rows)
+                              : s.n == f.rows);
   if (!frozen_ok) return fail(APDGICP_ERR_NO_INPUT, "compute_error needs a previous linearize of the clouds and voxel maps the handle holds now");
-  const int nrows = v.n_rows_lin, noff = v.noff_lin, nblk = (nrows + VG_BLK - 1) / VG_BLK;
-  APD_HIP(hipSetDevice(e.device));
-  double t24[24];
-  colmajor_to_rows12(T16, t24);
-  memcpy(t24 + 12, v.T_lin, 12 * sizeof(double));
-  APD_HIP(hipMemcpyAsync(v.T.p, t24, sizeof(t24), hipMemcpyHostToDevice, e.stream));
+  const int nrows = f.rows, nblk = (nrows + VG_BLK - 1) / VG_BLK;
+  APD_TRY(err_begin(e, f, T16));
   const VgMap smap = d2d ? ms.map() : VgMap{nullptr, nullptr, nullptr, nullptr, 0};
   if (d2d)
-    hipLaunchKernelGGL(k_ndt_error<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution, noff,
-                       v.corr.as<int>(), v.part.as<double>());
+    hipLaunchKernelGGL(k_ndt_error<true>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), f.T.as<double>(), v.prm.resolution, f.noff,
+                       f.corr.as<int>(), f.part.as<double>());
   else
-    hipLaunchKernelGGL(k_ndt_error<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), v.T.as<double>(), v.prm.resolution, noff,
-                       v.corr.as<int>(), v.part.as<double>());
-  return reduce_and_read(e, v.part, v.out, nblk, 27, nullptr, nullptr, cost, nullptr);
+    hipLaunchKernelGGL(k_ndt_error<false>, dim3(nblk), dim3(VG_BLK), 0, e.stream, s.opts.as<float4>(), smap, nrows, mt.map(), f.T.as<double>(), v.prm.resolution, f.noff,
+                       f.corr.as<int>(), f.part.as<double>());
+  return reduce_and_read(e, f, 27, nullptr, nullptr, cost, nullptr);
 }
 
 int nd_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   APD_TRY(nd_prepare(h));
-  h->nd.reset_final_H();
-  const int rc = host_loop(
-      h, guess, out, [&](const double* T, double* H, double* b, double* y0, int* m) { return nd_linearize(h, T, H, b, y0, m); },
-      [&](const double* T, double* yi) { return nd_error(h, T, yi); }, true, h->nd.final_H);
+  h->reset_final_H();
+  const int rc = voxel_host_loop(h, guess, out, nd_linearize, nd_error, h->final_H);
   h->have_corr = false;  // (the APD kernels' correspondences are not what this mode wrote)
   return rc;
 }
@@ -1580,18 +1607,38 @@ int batch_build_maps(apdgicp_batch* b, const std::vector<int>& slots, const char
   return rc;
 }
 
-// room for the scal words of every slot of the engine; the words of built maps survive a growth
-int batch_ensure_slot_words(Engine& e, DevBuf& scal, int& scal_slots) {
+// room for `bytes` device bytes per slot of the engine; the words of what is built survive a growth
+int batch_ensure_slot_words(Engine& e, DevBuf& words, int& slots, size_t bytes) {
   const int want = (int)e.clouds.size();
-  if (want <= scal_slots) return 0;
+  if (want <= slots) return 0;
   const int cap = std::max(64, 2 * want);
   DevBuf grown;
-  APD_TRY(grown.ensure((size_t)cap * 16));
+  APD_TRY(grown.ensure((size_t)cap * bytes));
   APD_HIP(hipStreamSynchronize(e.stream));
-  if (scal_slots) APD_HIP(hipMemcpy(grown.p, scal.p, (size_t)scal_slots * 16, hipMemcpyDeviceToDevice));
-  scal = std::move(grown);
-  scal_slots = cap;
+  if (slots) APD_HIP(hipMemcpy(grown.p, words.p, (size_t)slots * bytes, hipMemcpyDeviceToDevice));
+  words = std::move(grown);
+  slots = cap;
   return 0;
+}
+
+// room for every slot of the engine in a mode's table and in the list of what its maps were made from (ids: the mode's `slots`)
+template <class Id>
+int ensure_slots(Engine& e, VoxSlots& s, std::vector<Id>& ids) {
+  if (ids.size() < e.clouds.size()) ids.resize(e.clouds.size());
+  if (s.slots.size() < e.clouds.size()) s.slots.resize(e.clouds.size());
+  return batch_ensure_slot_words(e, s.scal, s.scal_slots, 16);
+}
+
+void mark_built(VoxSlots& s, int t, int nv) { s.slots[t].nv = nv, s.builds++; }  // slot t's build has come home (what it was made from: stamped by the mode)
+
+// the head of a getter of one slot in mode m; the caller goes on to upload_desc (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+int batch_slot_enter(apdgicp_batch* b, Mode m, int32_t cloud) {
+  Engine& e = b->eng;
+  if (b->mode != m) return mode_is_off(m, true);
+  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
+  APD_HIP(hipSetDevice(e.device));
+  APD_TRY(e.pool_leave());
+  return e.finish_align();
 }
 
 // V12 / N15: what the tick loop needs besides the pairs -- the done counter, the pinned words, the two events
@@ -1675,13 +1722,36 @@ int device_loop_run(apdgicp_batch* b, Tick&& launch_tick) {
       launch_tick);
 }
 
-// ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
-int vgb_ensure_slots(apdgicp_batch* b) {
-  VgbState& v = b->vg;
-  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
-  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
+struct VoxTick {  // what the two launches of a voxel mode's tick read besides the mode's own: sizes, strides and pointers of this align
+  int np, nblk_max;
+  size_t corr_stride;
+  Consts cst;
+  PairState* st;
+  ResultRec* recs;
+  int *corr, *done;
+  double* part;
+};
+
+// V10 / V12 / N13 / N15 / VC14 / VC16: the tail of a voxel mode's align, its pair table uploaded (apdgicp_batch::run) -- the frozen indices
+// (pairs x rows_max x noff ints, min_corr_bytes at least) and the block rows sized, then the loop of every pair on the device, a tick being
+// launch_points(t) then launch_step(t).  (rows_max is 0 only where FAST_VGICP_CUDA kept no source point anywhere: one block per pair, which
+// returns.)
+template <class Points, class Step>
+int voxel_batch_run(apdgicp_batch* b, int rows_max, int noff, size_t min_corr_bytes, Points&& launch_points, Step&& launch_step) {
+  Engine& e = b->eng;
+  VoxRun& r = b->run;
+  const int np = e.npairs, nblk_max = std::max(1, (rows_max + VG_BLK - 1) / VG_BLK);
+  r.noff = noff, r.corr_stride = (size_t)rows_max * (size_t)noff;  // (computed in size_t)
+  APD_TRY(ensure_corr_part(e, r.corr, r.part, std::max(min_corr_bytes, (size_t)np * r.corr_stride * 4), (size_t)np * nblk_max * VG_RED * 8));
+  APD_TRY(device_loop_prepare(b));
+  const VoxTick t{np, nblk_max, r.corr_stride, e.consts(), e.d_state.as<PairState>(), e.d_results.as<ResultRec>(), r.corr.as<int>(), b->loop.done.as<int>(), r.part.as<double>()};
+  return device_loop_run(b, [&]() {
+    launch_points(t);
+    launch_step(t);
+  });
 }
 
+// ---- voxelized GICP on a batch handle (include/apdgicp_hip.h V8 .. V12; kernels: apd_vgicp_batch.hpp)
 bool vgb_map_current(const apdgicp_batch* b, int slot) {
   const VgbState& v = b->vg;
   const Engine::Cloud& c = b->eng.clouds[slot];
@@ -1708,31 +1778,31 @@ int vgb_ensure_inv(apdgicp_batch* b, int slot) {
 int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
   Engine& e = b->eng;
   VgbState& v = b->vg;
-  APD_TRY(vgb_ensure_slots(b));
+  APD_TRY(ensure_slots(e, v.vox, v.slots));
   int flag = 0;
   int rc = batch_build_maps(
-      b, targets, "voxelized GICP: ", v.prm.resolution, v.scal, [&](int t) { return vgb_map_current(b, t); },
-      [&](int t) { return (size_t)e.clouds[t].n * 48 > v.slots[t].buf.vcov.cap || (size_t)e.clouds[t].n * 4 > v.slots[t].inv.cap; },
+      b, targets, "voxelized GICP: ", v.prm.resolution, v.vox.scal, [&](int t) { return vgb_map_current(b, t); },
+      [&](int t) { return (size_t)e.clouds[t].n * 48 > v.vox.slots[t].buf.vcov.cap || (size_t)e.clouds[t].n * 4 > v.slots[t].inv.cap; },
       [&](int t) -> int {
         Engine::Cloud& c = e.clouds[t];
         VgbState::Slot& sl = v.slots[t];
+        VoxMapBufs& buf = v.vox.slots[t].buf;
         const int n = c.n;
         sl.map_built = false;
-        APD_TRY(sl.buf.ensure((size_t)n, false));
+        APD_TRY(buf.ensure((size_t)n, false));
         APD_TRY(vgb_ensure_inv(b, t));
         VoxSorted s;
-        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.vox.words(t), &s));
         hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), c.opts.as<float4>(), c.cov.as<double>(), sl.inv.as<int>(),
-                           sl.buf.vkeys.as<unsigned long long>(), sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vcov.as<double>(), n);
+                           buf.vkeys.as<unsigned long long>(), buf.vcount.as<int>(), buf.vmean.as<double>(), buf.vcov.as<double>(), n);
         APD_HIP(hipGetLastError());
         return 0;
       },
       [&](int t, int nv) {
         VgbState::Slot& sl = v.slots[t];
         const Engine::Cloud& c = e.clouds[t];
-        sl.nv = nv;
+        mark_built(v.vox, t, nv);
         sl.map_built = true, sl.map_pts_gen = c.pts_gen, sl.map_cov_gen = c.cov_gen, sl.map_res = v.prm.resolution, sl.map_mode = v.prm.voxel_mode;
-        v.builds++;
       },
       &flag);
   if (flag) {  // a point that is not finite trips the covariance kernels too: the message about the point is the useful one
@@ -1745,11 +1815,7 @@ int vgb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
 // one slot's map for the getters: sorted, covariances computed, built
 int vgb_slot_map(apdgicp_batch* b, int32_t cloud) {
   Engine& e = b->eng;
-  if (b->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, true);
-  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
-  APD_HIP(hipSetDevice(e.device));
-  APD_TRY(e.pool_leave());
-  APD_TRY(e.finish_align());
+  APD_TRY(batch_slot_enter(b, Mode::VGICP, cloud));
   APD_TRY(e.compute_covariances({cloud}));
   APD_TRY(e.upload_desc());
   return vgb_build_maps(b, {cloud});
@@ -1770,32 +1836,21 @@ int vgb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   std::vector<VgbPair> tab(np);
   for (int i = 0; i < np; i++) {
     const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
-    tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0,
-                     v.slots[t].buf.map(v.scal.as<int>() + 4 * (size_t)t + 1)};
+    tab[i] = VgbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].cov.as<double>(), v.slots[s].inv.as<int>(), e.clouds[s].n, 0, v.vox.map(t)};
   }
-  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
-  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
-  const size_t corr_stride = (size_t)e.nmax_src * noff;
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)np * corr_stride * 4, (size_t)np * nblk_max * VG_RED * 8));
-  APD_TRY(device_loop_prepare(b));
-  const Consts cst = e.consts();
-  PairState* st = e.d_state.as<PairState>();
-  ResultRec* recs = e.d_results.as<ResultRec>();
-  int* done = b->loop.done.as<int>();
-  return device_loop_run(b, [&]() {
-    hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution,
-                       (int)v.prm.neighbor_search, noff, v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, done);
-  });
+  APD_TRY(b->run.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
+  return voxel_batch_run(
+      b, e.nmax_src, noff, 0,
+      [&](const VoxTick& t) {
+        hipLaunchKernelGGL(k_vgb_points, dim3((unsigned)t.nblk_max, (unsigned)t.np), dim3(VG_BLK), 0, e.stream, b->run.pairs.as<VgbPair>(), t.st, v.prm.resolution,
+                           (int)v.prm.neighbor_search, noff, t.corr, t.corr_stride, t.part, t.nblk_max);
+      },
+      [&](const VoxTick& t) {
+        hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)t.np), dim3(64), 0, e.stream, b->run.pairs.as<VgbPair>(), t.st, t.cst, t.part, t.nblk_max, t.recs, t.done);
+      });
 }
 
 // ---- NDT on a batch handle (include/apdgicp_hip.h N10 .. N15; kernels: apd_ndt_batch.hpp)
-int ndb_ensure_slots(apdgicp_batch* b) {
-  NdbState& v = b->nd;
-  if (v.slots.size() < b->eng.clouds.size()) v.slots.resize(b->eng.clouds.size());
-  return batch_ensure_slot_words(b->eng, v.scal, v.scal_slots);
-}
-
 bool ndb_map_current(const apdgicp_batch* b, int slot) {
   const NdbState::Slot& sl = b->nd.slots[slot];
   return sl.built && sl.pts_gen == b->eng.clouds[slot].pts_gen && sl.res == b->nd.prm.resolution;
@@ -1805,39 +1860,34 @@ bool ndb_map_current(const apdgicp_batch* b, int slot) {
 int ndb_build_maps(apdgicp_batch* b, const std::vector<int>& slots) {
   Engine& e = b->eng;
   NdbState& v = b->nd;
-  APD_TRY(ndb_ensure_slots(b));
+  APD_TRY(ensure_slots(e, v.vox, v.slots));
   return batch_build_maps(
-      b, slots, "NDT: ", v.prm.resolution, v.scal, [&](int t) { return ndb_map_current(b, t); }, [&](int t) { return (size_t)e.clouds[t].n * 48 > v.slots[t].buf.vcov.cap; },
+      b, slots, "NDT: ", v.prm.resolution, v.vox.scal, [&](int t) { return ndb_map_current(b, t); },
+      [&](int t) { return (size_t)e.clouds[t].n * 48 > v.vox.slots[t].buf.vcov.cap; },
       [&](int t) -> int {
         Engine::Cloud& c = e.clouds[t];
-        NdbState::Slot& sl = v.slots[t];
+        VoxMapBufs& buf = v.vox.slots[t].buf;
         const int n = c.n;
-        sl.built = false;
-        APD_TRY(sl.buf.ensure((size_t)n, true));
+        v.slots[t].built = false;
+        APD_TRY(buf.ensure((size_t)n, true));
         VoxSorted s;
-        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
-        hipLaunchKernelGGL(k_ndt_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), c.opts.as<float4>(), sl.buf.vkeys.as<unsigned long long>(),
-                           sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vraw.as<double>(), sl.buf.vcov.as<double>(), n);
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, c.opts.as<float4>(), n, v.prm.resolution, v.vox.words(t), &s));
+        hipLaunchKernelGGL(k_ndt_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), c.opts.as<float4>(), buf.vkeys.as<unsigned long long>(),
+                           buf.vcount.as<int>(), buf.vmean.as<double>(), buf.vraw.as<double>(), buf.vcov.as<double>(), n);
         APD_HIP(hipGetLastError());
         return 0;
       },
       [&](int t, int nv) {
         NdbState::Slot& sl = v.slots[t];
-        sl.nv = nv;
+        mark_built(v.vox, t, nv);
         sl.built = true, sl.pts_gen = e.clouds[t].pts_gen, sl.res = v.prm.resolution;
-        v.builds++;
       });
 }
 
 // one slot's map for the getters: sorted, built
 int ndb_slot_map(apdgicp_batch* b, int32_t cloud) {
-  Engine& e = b->eng;
-  if (b->mode != Mode::NDT) return mode_is_off(Mode::NDT, true);
-  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
-  APD_HIP(hipSetDevice(e.device));
-  APD_TRY(e.pool_leave());
-  APD_TRY(e.finish_align());
-  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+  APD_TRY(batch_slot_enter(b, Mode::NDT, cloud));
+  APD_TRY(b->eng.upload_desc());
   return ndb_build_maps(b, {cloud});
 }
 
@@ -1856,54 +1906,30 @@ int ndb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
     if (d2d) slots.push_back(e.h_pairs[i].src);
   }
   APD_TRY(ndb_build_maps(b, slots));
-  auto map_of = [&](int slot) { return v.slots[slot].buf.map(v.scal.as<int>() + 4 * (size_t)slot + 1); };
   std::vector<NdbPair> tab(np);
   for (int i = 0; i < np; i++) {
     const int s = e.h_pairs[i].src, t = e.h_pairs[i].tgt;
-    tab[i] = NdbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].n, 0, d2d ? map_of(s) : VgbMap{nullptr, nullptr, nullptr, nullptr, nullptr}, map_of(t)};
+    tab[i] = NdbPair{e.clouds[s].opts.as<float4>(), e.clouds[s].n, 0, d2d ? v.vox.map(s) : VgbMap{nullptr, nullptr, nullptr, nullptr, nullptr}, v.vox.map(t)};
   }
-  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(NdbPair), e.stream));
+  APD_TRY(b->run.pairs.upload(tab.data(), tab.size() * sizeof(NdbPair), e.stream));
   // (a pair's rows are at most its source's points: the grid and the strides are sized by the points, the blocks beyond a pair's rows return)
-  const int nblk_max = (e.nmax_src + VG_BLK - 1) / VG_BLK;
-  const size_t corr_stride = (size_t)e.nmax_src * noff;
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, (size_t)np * corr_stride * 4, (size_t)np * nblk_max * VG_RED * 8));
-  APD_TRY(device_loop_prepare(b));
-  const Consts cst = e.consts();
-  PairState* st = e.d_state.as<PairState>();
-  ResultRec* recs = e.d_results.as<ResultRec>();
-  int* done = b->loop.done.as<int>();
-  const dim3 grid((unsigned)nblk_max, (unsigned)np);
-  return device_loop_run(b, [&]() {
-    if (d2d)
-      hipLaunchKernelGGL(k_ndb_points<true>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
-                         v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-    else
-      hipLaunchKernelGGL(k_ndb_points<false>, grid, dim3(VG_BLK), 0, e.stream, v.pairs.as<NdbPair>(), st, v.prm.resolution, (int)v.prm.neighbor_search, noff,
-                         v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-    hipLaunchKernelGGL(k_ndb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<NdbPair>(), st, cst, v.part.as<double>(), nblk_max, d2d ? 1 : 0, recs,
-                       done);
-  });
+  return voxel_batch_run(
+      b, e.nmax_src, noff, 0,
+      [&](const VoxTick& t) {
+        const dim3 grid((unsigned)t.nblk_max, (unsigned)t.np);
+        if (d2d)
+          hipLaunchKernelGGL(k_ndb_points<true>, grid, dim3(VG_BLK), 0, e.stream, b->run.pairs.as<NdbPair>(), t.st, v.prm.resolution, (int)v.prm.neighbor_search, noff, t.corr,
+                             t.corr_stride, t.part, t.nblk_max);
+        else
+          hipLaunchKernelGGL(k_ndb_points<false>, grid, dim3(VG_BLK), 0, e.stream, b->run.pairs.as<NdbPair>(), t.st, v.prm.resolution, (int)v.prm.neighbor_search, noff, t.corr,
+                             t.corr_stride, t.part, t.nblk_max);
+      },
+      [&](const VoxTick& t) {
+        hipLaunchKernelGGL(k_ndb_step, dim3((unsigned)t.np), dim3(64), 0, e.stream, b->run.pairs.as<NdbPair>(), t.st, t.cst, t.part, t.nblk_max, d2d ? 1 : 0, t.recs, t.done);
+      });
 }
 
 // ---- FAST_VGICP_CUDA on a batch handle (include/apdgicp_hip.h VC11 .. VC16; kernels: apd_vgicp_cuda_batch.hpp)
-// room for every slot's state and device words; the words of what is built survive a growth
-int vcb_ensure_slots(apdgicp_batch* b) {
-  Engine& e = b->eng;
-  VcbState& v = b->vc;
-  if (v.slots.size() < e.clouds.size()) v.slots.resize(e.clouds.size());
-  APD_TRY(batch_ensure_slot_words(e, v.scal, v.scal_slots));
-  const int want = (int)e.clouds.size();
-  if (want <= v.nk_slots) return 0;
-  const int cap = std::max(64, 2 * want);
-  DevBuf grown;
-  APD_TRY(grown.ensure((size_t)cap * 4));
-  APD_HIP(hipStreamSynchronize(e.stream));
-  if (v.nk_slots) APD_HIP(hipMemcpy(grown.p, v.nk.p, (size_t)v.nk_slots * 4, hipMemcpyDeviceToDevice));
-  v.nk = std::move(grown);
-  v.nk_slots = cap;
-  return 0;
-}
-
 bool vcb_prepared(const apdgicp_batch* b, int slot) {
   const VcPrepared& pc = b->vc.slots[slot].pc;
   return pc.ready && pc.pts_gen == b->eng.clouds[slot].pts_gen && pc.reg == b->vc.prm.regularization;
@@ -1919,7 +1945,8 @@ bool vcb_map_current(const apdgicp_batch* b, int slot) {
 int vcb_prepare_slots(apdgicp_batch* b, const std::vector<int>& slots) {
   Engine& e = b->eng;
   VcbState& v = b->vc;
-  APD_TRY(vcb_ensure_slots(b));
+  APD_TRY(ensure_slots(e, v.vox, v.slots));
+  APD_TRY(batch_ensure_slot_words(e, v.nk, v.nk_slots, 4));  // (the kept counts, one int per slot)
   std::vector<int> todo;
   for (int t : slots) {
     if (e.clouds[t].n < VC_K) return fail(APDGICP_ERR_TOO_FEW_POINTS, "FAST_VGICP_CUDA: cloud slot " + std::to_string(t) + " has fewer than " + std::to_string(VC_K) + " points");
@@ -1970,10 +1997,9 @@ int vcb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
       continue;
     }
     // no kept point: an empty map, no sort (the shared builder calls a voxel count of 0 inconsistent) -- the device word the tick reads is 0
-    APD_HIP(hipMemsetAsync(v.scal.as<int>() + 4 * (size_t)t, 0, 16, e.stream));
-    sl.nv = 0;
+    APD_HIP(hipMemsetAsync(v.vox.words(t), 0, 16, e.stream));
+    mark_built(v.vox, t, 0);
     sl.map_built = true, sl.map_prep_id = sl.pc.id, sl.map_res = v.prm.resolution;
-    v.builds++;
   }
   if (full.empty()) return 0;
   v.map_waits++;
@@ -1983,38 +2009,34 @@ int vcb_build_maps(apdgicp_batch* b, const std::vector<int>& targets) {
     return orig;
   };
   return batch_build_maps(
-      b, full, "FAST_VGICP_CUDA: ", v.prm.resolution, v.scal, [&](int) { return false; }, [&](int t) { return (size_t)v.slots[t].pc.n_kept * 48 > v.slots[t].buf.vcov.cap; },
+      b, full, "FAST_VGICP_CUDA: ", v.prm.resolution, v.vox.scal, [&](int) { return false; },
+      [&](int t) { return (size_t)v.slots[t].pc.n_kept * 48 > v.vox.slots[t].buf.vcov.cap; },
       [&](int t) -> int {
         VcbState::Slot& sl = v.slots[t];
+        VoxMapBufs& buf = v.vox.slots[t].buf;
         const VcPrepared& pc = sl.pc;
         const int n = pc.n_kept;
         sl.map_built = false;
-        APD_TRY(sl.buf.ensure((size_t)n, false));
+        APD_TRY(buf.ensure((size_t)n, false));
         VoxSorted s;
-        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, pc.kpts.as<float4>(), n, v.prm.resolution, v.scal.as<int>() + 4 * (size_t)t, &s));
+        APD_TRY(enqueue_voxel_sort(e.stream, b->sort, pc.kpts.as<float4>(), n, v.prm.resolution, v.vox.words(t), &s));
         hipLaunchKernelGGL(k_vg_voxels, dim3(s.nhb), dim3(MAP_BLK), 0, e.stream, s.keys, s.idx, n, b->sort.bsum.as<int>(), pc.kpts.as<float4>(), pc.kcov.as<double>(), pc.ident.as<int>(),
-                           sl.buf.vkeys.as<unsigned long long>(), sl.buf.vcount.as<int>(), sl.buf.vmean.as<double>(), sl.buf.vcov.as<double>(), n);
+                           buf.vkeys.as<unsigned long long>(), buf.vcount.as<int>(), buf.vmean.as<double>(), buf.vcov.as<double>(), n);
         APD_HIP(hipGetLastError());
         return 0;
       },
       [&](int t, int nv) {
         VcbState::Slot& sl = v.slots[t];
-        sl.nv = nv;
+        mark_built(v.vox, t, nv);
         sl.map_built = true, sl.map_prep_id = sl.pc.id, sl.map_res = v.prm.resolution;
-        v.builds++;
       },
       nullptr, &caller_index);
 }
 
 // one slot for the getters: sorted, prepared, and with want_map its map built
 int vcb_slot(apdgicp_batch* b, int32_t cloud, bool want_map) {
-  Engine& e = b->eng;
-  if (b->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, true);
-  if (cloud < 0 || cloud >= (int)e.clouds.size() || e.clouds[cloud].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "cloud not set");
-  APD_HIP(hipSetDevice(e.device));
-  APD_TRY(e.pool_leave());
-  APD_TRY(e.finish_align());
-  APD_TRY(e.upload_desc());  // (sorts what is not sorted yet: a staged cloud's opts are written by its sort)
+  APD_TRY(batch_slot_enter(b, Mode::VGICP_CUDA, cloud));
+  APD_TRY(b->eng.upload_desc());
   APD_TRY(vcb_prepare_slots(b, {cloud}));
   return want_map ? vcb_build_maps(b, {cloud}) : 0;
 }
@@ -2047,27 +2069,22 @@ int vcb_align(apdgicp_batch* b, const apdgicp_pair* pairs, int64_t n_pairs) {
   int nk_max = 0;
   for (int i = 0; i < np; i++) {
     const VcPrepared& s = v.slots[e.h_pairs[i].src].pc;
-    const VcbState::Slot& t = v.slots[e.h_pairs[i].tgt];
-    tab[i] = VgbPair{s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), s.n_kept, 0, t.buf.map(v.scal.as<int>() + 4 * (size_t)e.h_pairs[i].tgt + 1)};
+    tab[i] = VgbPair{s.kpts.as<float4>(), s.kcov.as<double>(), s.ident.as<int>(), s.n_kept, 0, v.vox.map(e.h_pairs[i].tgt)};
     nks[i] = s.n_kept;
     nk_max = std::max(nk_max, s.n_kept);
   }
-  APD_TRY(v.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
-  const int nblk_max = std::max(1, (nk_max + VG_BLK - 1) / VG_BLK);  // (no kept source point anywhere: one block per pair, which returns)
-  const size_t corr_stride = (size_t)nk_max * (size_t)noff;         // frozen indices: pairs x max n_kept x n_offsets ints, computed in size_t
-  APD_TRY(ensure_corr_part(e, v.corr, v.part, std::max<size_t>(16, (size_t)np * corr_stride * 4), (size_t)np * nblk_max * VG_RED * 8));
-  APD_TRY(device_loop_prepare(b));
-  const Consts cst = e.consts();
-  PairState* st = e.d_state.as<PairState>();
-  ResultRec* recs = e.d_results.as<ResultRec>();
-  int* done = b->loop.done.as<int>();
-  APD_TRY(device_loop_run(b, [&]() {
-    hipLaunchKernelGGL(k_vcb_points, dim3((unsigned)nblk_max, (unsigned)np), dim3(VG_BLK), 0, e.stream, v.pairs.as<VgbPair>(), st, v.prm.resolution, v.offs.dev.as<int>(), noff,
-                       v.corr.as<int>(), corr_stride, v.part.as<double>(), nblk_max);
-    hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)np), dim3(64), 0, e.stream, v.pairs.as<VgbPair>(), st, cst, v.part.as<double>(), nblk_max, recs, done);
-  }));
+  APD_TRY(b->run.pairs.upload(tab.data(), tab.size() * sizeof(VgbPair), e.stream));
+  APD_TRY(voxel_batch_run(
+      b, nk_max, noff, 16,
+      [&](const VoxTick& t) {
+        hipLaunchKernelGGL(k_vcb_points, dim3((unsigned)t.nblk_max, (unsigned)t.np), dim3(VG_BLK), 0, e.stream, b->run.pairs.as<VgbPair>(), t.st, v.prm.resolution,
+                           v.offs.dev.as<int>(), noff, t.corr, t.corr_stride, t.part, t.nblk_max);
+      },
+      [&](const VoxTick& t) {
+        hipLaunchKernelGGL(k_vgb_step, dim3((unsigned)t.np), dim3(64), 0, e.stream, b->run.pairs.as<VgbPair>(), t.st, t.cst, t.part, t.nblk_max, t.recs, t.done);
+      }));
   v.phase_ms[2] = ms_since(t0);
-  v.have = true, v.have_epoch = e.pts_epoch, v.have_nk = nks, v.have_stride = corr_stride, v.have_noff = noff;
+  v.have = true, v.have_epoch = e.pts_epoch, v.have_nk = nks;
   return 0;
 }
 
@@ -2226,14 +2243,9 @@ void set_mode(apdgicp_handle* h, Mode to) {
   if (from == to) return;
   h->have_corr = false;  // (the APD kernels' correspondences are those of their own last linearize, and none is left)
   if (from == Mode::ICP || to == Mode::ICP) h->pair_ready = false;  // (the pair of the other side was set up with / without covariances)
-  switch (to) {
-    case Mode::APD: break;
-    case Mode::VGICP: h->vg.have_lin = false; break;
-    case Mode::VGICP_CUDA: h->vc.have_lin = false, h->vc.reset_final_H(); break;
-    case Mode::NDT: h->nd.have_lin = false, h->nd.reset_final_H(); break;
-    case Mode::ICP: break;  // (apdgicp_set_icp forgets the last estimate with every enabling call, entering or not)
-  }
-  h->mode = to;
+  h->lin.have = false;  // (the one frozen state is the mode's that made it)
+  if (to == Mode::VGICP_CUDA || to == Mode::NDT) h->reset_final_H();
+  h->mode = to;  // (apdgicp_set_icp forgets the last estimate with every enabling call, entering or not)
 }
 
 // ... and of apdgicp_batch::mode.  Fails, with the mode unchanged, when the APD path's aligns in flight cannot be finished.
@@ -2410,9 +2422,8 @@ int apdgicp_swap_source_and_target(apdgicp_handle* h) {
   h->pair_ready = h->have_corr = false;
   std::swap(h->cloud_gen[kSrc], h->cloud_gen[kTgt]);
   std::swap(h->nd.maps[kSrc], h->nd.maps[kTgt]);  // NC:90-93: the NDT maps go with their clouds (tied to them by identity either way)
-  h->nd.have_lin = false;
   std::swap(h->vc.pc[kSrc], h->vc.pc[kTgt]);  // VC:97-107: the prepared clouds go with their clouds; the map is then another target's and is rebuilt
-  h->vc.have_lin = false;
+  if (h->mode != Mode::VGICP) h->lin.have = false;  // (voxelized GICP tracks its frozen state by identity alone: a second swap makes it current again, V6)
   return 0;
 }
 
@@ -2605,7 +2616,7 @@ int apdgicp_set_vgicp(apdgicp_handle* h, const apdgicp_vgicp_params* p) {
     return 0;
   }
   APD_TRY(check_vgicp_params(p));
-  if (p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
+  if (p->resolution != v.prm.resolution || p->voxel_mode != v.prm.voxel_mode || p->neighbor_search != v.prm.neighbor_search) h->lin.have = false;
   v.prm = *p;
   set_mode(h, Mode::VGICP);
   return 0;
@@ -2640,14 +2651,9 @@ int apdgicp_vgicp_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* coord
 int apdgicp_vgicp_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_source) {
   return guarded([&]() -> int {
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    VgState& v = h->vg;
-    Engine& e = h->eng;
     if (h->mode != Mode::VGICP) return mode_is_off(Mode::VGICP, false);
-    if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
-    if (n_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_source does not match the source size");
-    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_source * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    return 0;
+    if (!h->lin.have || h->vg.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
+    return read_frozen_corr(h->eng, h->lin, voxel_index, n_source, "n_source does not match the source size");
   });
 }
 
@@ -2677,7 +2683,7 @@ int apdgicp_set_vgicp_cuda(apdgicp_handle* h, const apdgicp_vgicp_cuda_params* p
   }
   APD_TRY(check_vgicp_cuda_params(p));
   const bool same_offsets = p->neighbor_search == v.prm.neighbor_search && (p->neighbor_search != APDGICP_VGICP_CUDA_DIRECT_RADIUS || p->search_radius == v.prm.search_radius);
-  if (p->resolution != v.prm.resolution || p->regularization != v.prm.regularization || !same_offsets) v.have_lin = false;
+  if (p->resolution != v.prm.resolution || p->regularization != v.prm.regularization || !same_offsets) h->lin.have = false;
   if (!same_offsets) v.offs.clear();
   v.prm = *p;
   set_mode(h, Mode::VGICP_CUDA);
@@ -2744,14 +2750,9 @@ int apdgicp_vgicp_cuda_get_voxels(apdgicp_handle* h, int64_t capacity, int32_t* 
 int apdgicp_vgicp_cuda_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_kept_source) {
   return guarded([&]() -> int {
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    VcState& v = h->vc;
     if (h->mode != Mode::VGICP_CUDA) return mode_is_off(Mode::VGICP_CUDA, false);
     if (!vc_frozen_ok(h)) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
-    if (n_kept_source != v.n_src_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_kept_source does not match the kept source size");
-    if (v.n_src_lin == 0) return 0;
-    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_kept_source * v.noff_lin * 4, hipMemcpyDeviceToHost, h->eng.stream));
-    APD_HIP(hipStreamSynchronize(h->eng.stream));
-    return 0;
+    return read_frozen_corr(h->eng, h->lin, voxel_index, n_kept_source, "n_kept_source does not match the kept source size");
   });
 }
 
@@ -2777,7 +2778,7 @@ int apdgicp_set_ndt(apdgicp_handle* h, const apdgicp_ndt_params* p) {
     return 0;
   }
   APD_TRY(check_ndt_params(p));
-  if (p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) v.have_lin = false;
+  if (p->resolution != v.prm.resolution || p->distance_mode != v.prm.distance_mode || p->neighbor_search != v.prm.neighbor_search) h->lin.have = false;
   v.prm = *p;
   set_mode(h, Mode::NDT);
   return 0;
@@ -2930,14 +2931,9 @@ int apdgicp_ndt_get_voxels(apdgicp_handle* h, int which, int64_t capacity, int32
 int apdgicp_ndt_get_correspondences(apdgicp_handle* h, int32_t* voxel_index, int64_t n_rows) {
   return guarded([&]() -> int {
     if (!h || !voxel_index) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-    NdState& v = h->nd;
-    Engine& e = h->eng;
     if (h->mode != Mode::NDT) return mode_is_off(Mode::NDT, false);
-    if (!v.have_lin || v.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
-    if (n_rows != v.n_rows_lin) return fail(APDGICP_ERR_INVALID_ARG, "n_rows does not match the rows of the last linearize");
-    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.p, (size_t)n_rows * v.noff_lin * 4, hipMemcpyDeviceToHost, e.stream));
-    APD_HIP(hipStreamSynchronize(e.stream));
-    return 0;
+    if (!h->lin.have || h->nd.lin_src_gen != h->cloud_gen[kSrc]) return fail(APDGICP_ERR_NO_INPUT, "no correspondences yet");
+    return read_frozen_corr(h->eng, h->lin, voxel_index, n_rows, "n_rows does not match the rows of the last linearize");
   });
 }
 
@@ -2970,7 +2966,7 @@ int apdgicp_batch_vgicp_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_
   return guarded([&]() -> int {
     if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_TRY(vgb_slot_map(b, cloud));
-    *n_voxels = b->vg.slots[cloud].nv;
+    *n_voxels = b->vg.vox.slots[cloud].nv;
     return 0;
   });
 }
@@ -2979,14 +2975,14 @@ int apdgicp_batch_vgicp_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capa
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(vgb_slot_map(b, cloud));
-    const VgbState::Slot& sl = b->vg.slots[cloud];
+    const VoxSlots::Slot& sl = b->vg.vox.slots[cloud];
     return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
   });
 }
 
 int apdgicp_batch_vgicp_build_count(apdgicp_batch* b, int64_t* n_builds) {
   if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-  *n_builds = b->vg.builds;
+  *n_builds = b->vg.vox.builds;
   return 0;
 }
 
@@ -3013,7 +3009,7 @@ int apdgicp_batch_ndt_voxel_count(apdgicp_batch* b, int32_t cloud, int64_t* n_vo
   return guarded([&]() -> int {
     if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_TRY(ndb_slot_map(b, cloud));
-    *n_voxels = b->nd.slots[cloud].nv;
+    *n_voxels = b->nd.vox.slots[cloud].nv;
     return 0;
   });
 }
@@ -3023,14 +3019,14 @@ int apdgicp_batch_ndt_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t capaci
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(ndb_slot_map(b, cloud));
-    const NdbState::Slot& sl = b->nd.slots[cloud];
+    const VoxSlots::Slot& sl = b->nd.vox.slots[cloud];
     return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, raw_covs_n6, covs_n9);
   });
 }
 
 int apdgicp_batch_ndt_build_count(apdgicp_batch* b, int64_t* n_builds) {
   if (!b || !n_builds) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
-  *n_builds = b->nd.builds;
+  *n_builds = b->nd.vox.builds;
   return 0;
 }
 
@@ -3075,7 +3071,7 @@ int apdgicp_batch_vgicp_cuda_voxel_count(apdgicp_batch* b, int32_t cloud, int64_
   return guarded([&]() -> int {
     if (!b || !n_voxels) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_TRY(vcb_slot(b, cloud, true));
-    *n_voxels = b->vc.slots[cloud].nv;
+    *n_voxels = b->vc.vox.slots[cloud].nv;
     return 0;
   });
 }
@@ -3084,7 +3080,7 @@ int apdgicp_batch_vgicp_cuda_get_voxels(apdgicp_batch* b, int32_t cloud, int64_t
   return guarded([&]() -> int {
     if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
     APD_TRY(vcb_slot(b, cloud, true));
-    const VcbState::Slot& sl = b->vc.slots[cloud];
+    const VoxSlots::Slot& sl = b->vc.vox.slots[cloud];
     if (sl.nv == 0) return 0;
     return read_voxels(b->eng.stream, sl.buf, sl.nv, capacity, coords_n3, counts, means_n3, nullptr, covs_n9);
   });
@@ -3100,7 +3096,7 @@ int apdgicp_batch_vgicp_cuda_get_correspondences(apdgicp_batch* b, int64_t pair,
     if (!voxel_index) return v.have_nk[pair];  // (the size query)
     if (n_kept_source != v.have_nk[pair]) return fail(APDGICP_ERR_INVALID_ARG, "n_kept_source does not match the pair's kept source size");
     if (n_kept_source == 0) return 0;
-    APD_HIP(hipMemcpyAsync(voxel_index, v.corr.as<int>() + (size_t)pair * v.have_stride, (size_t)n_kept_source * v.have_noff * 4, hipMemcpyDeviceToHost, b->eng.stream));
+    APD_HIP(hipMemcpyAsync(voxel_index, b->run.corr.as<int>() + (size_t)pair * b->run.corr_stride, (size_t)n_kept_source * b->run.noff * 4, hipMemcpyDeviceToHost, b->eng.stream));
     APD_HIP(hipStreamSynchronize(b->eng.stream));
     return 0;
   });
@@ -3109,7 +3105,7 @@ int apdgicp_batch_vgicp_cuda_get_correspondences(apdgicp_batch* b, int64_t pair,
 int apdgicp_batch_vgicp_cuda_build_count(apdgicp_batch* b, int64_t* n_prepared, int64_t* n_maps) {
   if (!b) return fail(APDGICP_ERR_INVALID_ARG, "batch is null");
   if (n_prepared) *n_prepared = b->vc.preps;
-  if (n_maps) *n_maps = b->vc.builds;
+  if (n_maps) *n_maps = b->vc.vox.builds;
   return 0;
 }
 
@@ -3223,11 +3219,9 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
     Engine& e = h->eng;
     switch (h->mode) {
       case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
-      case Mode::NDT:  // the NDT mode keeps the Hessian of its last align on the host (identity until then)
-        memcpy(H, h->nd.final_H, 36 * sizeof(double));
-        return 0;
-      case Mode::VGICP_CUDA:  // FAST_VGICP_CUDA: likewise
-        memcpy(H, h->vc.final_H, 36 * sizeof(double));
+      case Mode::NDT:  // NDT and FAST_VGICP_CUDA keep the Hessian of their last align on the host (identity until then)
+      case Mode::VGICP_CUDA:
+        memcpy(H, h->final_H, 36 * sizeof(double));
         return 0;
       case Mode::VGICP:
       case Mode::APD: break;  // (on the device, in the pair state)

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import registration as reg
-from .registration import SOURCE, TARGET, _check, _ptr
+from .registration import SOURCE, TARGET, _check, _ptr, _read_voxels, _set_fields
 from .vgicp import DIRECT1, DIRECT7, DIRECT27, N_OFFSETS  # noqa: F401  NeighborSearchMethod, as the voxelized GICP mode numbers it
 
 P2D, D2D = 0, 1          # NDTDistanceMode (ndt_settings.hpp)
@@ -30,27 +30,11 @@ def default_ndt_params() -> NdtParams:
     return p
 
 
-class NDT(reg.FastAPDGICP):
-    """One registration object (== one fast_gicp::NDTCuda) on one GPU.  setInputSource / setInputTarget / swapSourceAndTarget /
-    clearSource / clearTarget / align / linearize / compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are
-    the base class's; align always runs the host-driven loop.  `disable()` hands the handle back to APD-GICP."""
-
-    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
-        super().__init__(params, device, stream)
-        self.nparams = default_ndt_params()
-        self._push_ndt()
-
-    def _push_ndt(self):
-        _check(self.L.apdgicp_set_ndt(self.h, C.byref(self.nparams)))
+class _NdtSetters:
+    """The reference's setters, enable() and enabled() over `nparams` and the `_push_mode()` / `get_ndt()` of the single or the batch class."""
 
     def _set(self, field: str, value):
-        old = getattr(self.nparams, field)
-        setattr(self.nparams, field, value)
-        try:
-            self._push_ndt()
-        except reg.ApdgicpError:
-            setattr(self.nparams, field, old)
-            raise
+        _set_fields(self.nparams, self._push_mode, **{field: value})
 
     def setDistanceMode(self, mode: int):
         self._set("distance_mode", int(mode))
@@ -62,6 +46,26 @@ class NDT(reg.FastAPDGICP):
         """`radius` belongs to DIRECT_RADIUS, which is not offered."""
         self._set("neighbor_search", int(method))
 
+    def enable(self):
+        self._push_mode()
+
+    def enabled(self) -> bool:
+        return self.get_ndt()[1]
+
+
+class NDT(_NdtSetters, reg.FastAPDGICP):
+    """One registration object (== one fast_gicp::NDTCuda) on one GPU.  setInputSource / setInputTarget / swapSourceAndTarget /
+    clearSource / clearTarget / align / linearize / compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are
+    the base class's; align always runs the host-driven loop.  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.nparams = default_ndt_params()
+        self._push_mode()
+
+    def _push_mode(self):
+        _check(self.L.apdgicp_set_ndt(self.h, C.byref(self.nparams)))
+
     def get_ndt(self):
         """(NdtParams, enabled) as the library holds them."""
         p, on = NdtParams(), C.c_int()
@@ -72,12 +76,6 @@ class NDT(reg.FastAPDGICP):
         """apdgicp_set_ndt(h, NULL): the handle is an APD-GICP / plain GICP object again."""
         _check(self.L.apdgicp_set_ndt(self.h, None))
 
-    def enable(self):
-        self._push_ndt()
-
-    def enabled(self) -> bool:
-        return self.get_ndt()[1]
-
     def voxel_count(self, which: int = TARGET) -> int:
         n = C.c_int64()
         _check(self.L.apdgicp_ndt_voxel_count(self.h, int(which), C.byref(n)))
@@ -86,14 +84,7 @@ class NDT(reg.FastAPDGICP):
     def voxels(self, which: int = TARGET):
         """The voxel map of SOURCE or TARGET in voxel order (ascending key): dict(coords [n,3] int32, counts [n] int32, means [n,3],
         raw [n,6] (N2: xx, yx, zx, yy, zy, zz), covs [n,3,3] (N3))."""
-        n = self.voxel_count(which)
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        raw = np.empty((n, 6))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_ndt_get_voxels(self.h, int(which), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(raw), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "raw": raw, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_ndt_get_voxels(self.h, int(which), *a), self.voxel_count(which), raw=True)
 
     def n_rows(self) -> int:
         """Rows of a linearize: source voxels (D2D) or source points (P2D)."""
@@ -113,7 +104,7 @@ class NDT(reg.FastAPDGICP):
         return n.value
 
 
-class BatchNDT(reg.BatchAPDGICP):
+class BatchNDT(_NdtSetters, reg.BatchAPDGICP):
     """Many independent NDT registrations on one GPU: a batch handle with apdgicp_batch_set_ndt on (N10 .. N15).  Clouds, align,
     align_async / synchronize and fitness are the base class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is;
     align_enqueue / align_collect raise (one batch at a time).  `disable()` hands the handle back to APD-GICP."""
@@ -121,29 +112,10 @@ class BatchNDT(reg.BatchAPDGICP):
     def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
         super().__init__(params, device, stream)
         self.nparams = default_ndt_params()
-        self._push_ndt()
+        self._push_mode()
 
-    def _push_ndt(self):
+    def _push_mode(self):
         _check(self.L.apdgicp_batch_set_ndt(self.b, C.byref(self.nparams)))
-
-    def _set(self, field: str, value):
-        old = getattr(self.nparams, field)
-        setattr(self.nparams, field, value)
-        try:
-            self._push_ndt()
-        except reg.ApdgicpError:
-            setattr(self.nparams, field, old)
-            raise
-
-    def setDistanceMode(self, mode: int):
-        self._set("distance_mode", int(mode))
-
-    def setResolution(self, resolution: float):
-        self._set("resolution", float(resolution))
-
-    def setNeighborSearchMethod(self, method: int, radius: float = -1.0):
-        """`radius` belongs to DIRECT_RADIUS, which is not offered."""
-        self._set("neighbor_search", int(method))
 
     def get_ndt(self):
         """(NdtParams, enabled) as the library holds them."""
@@ -154,12 +126,6 @@ class BatchNDT(reg.BatchAPDGICP):
     def disable(self):
         _check(self.L.apdgicp_batch_set_ndt(self.b, None))
 
-    def enable(self):
-        self._push_ndt()
-
-    def enabled(self) -> bool:
-        return self.get_ndt()[1]
-
     def voxel_count(self, cloud: int) -> int:
         n = C.c_int64()
         _check(self.L.apdgicp_batch_ndt_voxel_count(self.b, int(cloud), C.byref(n)))
@@ -167,14 +133,7 @@ class BatchNDT(reg.BatchAPDGICP):
 
     def voxels(self, cloud: int):
         """The voxel map of cloud slot `cloud` (built if it is not current), as NDT.voxels()."""
-        n = self.voxel_count(cloud)
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        raw = np.empty((n, 6))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_batch_ndt_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(raw), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "raw": raw, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_batch_ndt_get_voxels(self.b, int(cloud), *a), self.voxel_count(cloud), raw=True)
 
     def build_count(self) -> int:
         """How many NDT voxel maps this handle has built, all slots together (the cache rules' test hook)."""

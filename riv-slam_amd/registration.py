@@ -437,6 +437,31 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _set_fields(params, push, **fields):
+    """A mode's setter: write `fields` into its parameter struct and push() it to the library; what the library refuses is rolled back."""
+    old = {k: getattr(params, k) for k in fields}
+    for k, val in fields.items():
+        setattr(params, k, val)
+    try:
+        push()
+    except ApdgicpError:
+        for k, val in old.items():
+            setattr(params, k, val)
+        raise
+
+
+def _read_voxels(call, n: int, raw: bool = False):
+    """A voxel mode's voxels(): the map of n voxels in voxel order (ascending key) through call(capacity, coords, counts, means, [raw,] covs) --
+    dict(coords [n,3] int32, counts [n] int32, means [n,3], with `raw` raw [n,6], covs [n,3,3])."""
+    out = {"coords": np.empty((n, 3), dtype=np.int32), "counts": np.empty(n, dtype=np.int32), "means": np.empty((n, 3))}
+    if raw:
+        out["raw"] = np.empty((n, 6))
+    out["covs"] = np.empty((n, 9))
+    _check(call(n, *(_ptr(a) for a in out.values())))
+    out["covs"] = out["covs"].reshape(n, 3, 3)
+    return out
+
+
 class DevicePoints:
     """n points in device memory, `stride_bytes` apart, xyz first (e.g. the cloud a SubmapAssembler holds);
     accepted wherever a cloud is: the pointer is passed straight through.  `owner` keeps the memory alive."""

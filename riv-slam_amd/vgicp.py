@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import registration as reg
-from .registration import _check, _ptr
+from .registration import _check, _ptr, _read_voxels, _set_fields
 
 DIRECT1, DIRECT7, DIRECT27 = 0, 1, 2                    # NeighborSearchMethod (gicp_settings.hpp)
 ADDITIVE, ADDITIVE_WEIGHTED, MULTIPLICATIVE = 0, 1, 2   # VoxelAccumulationMode
@@ -30,7 +30,26 @@ def default_vgicp_params() -> VgicpParams:
     return p
 
 
-class FastVGICP(reg.FastAPDGICP):
+class _VgicpSetters:
+    """The reference's three setters and enable() over `vparams` and the `_push_mode()` of the single or the batch class."""
+
+    def _set(self, field: str, value):
+        _set_fields(self.vparams, self._push_mode, **{field: value})
+
+    def setResolution(self, resolution: float):
+        self._set("resolution", float(resolution))
+
+    def setNeighborSearchMethod(self, method: int):
+        self._set("neighbor_search", int(method))
+
+    def setVoxelAccumulationMode(self, mode: int):
+        self._set("voxel_mode", int(mode))
+
+    def enable(self):
+        self._push_mode()
+
+
+class FastVGICP(_VgicpSetters, reg.FastAPDGICP):
     """One registration object (== one fast_gicp::FastVGICP) on one GPU.  setInputSource / setInputTarget / align / linearize /
     compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are the base class's; align always runs the
     host-driven loop.  `disable()` hands the handle back to APD-GICP."""
@@ -38,44 +57,14 @@ class FastVGICP(reg.FastAPDGICP):
     def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
         super().__init__(params, device, stream)
         self.vparams = default_vgicp_params()
-        self._push_vgicp()
+        self._push_mode()
 
-    def _push_vgicp(self):
+    def _push_mode(self):
         _check(self.L.apdgicp_set_vgicp(self.h, C.byref(self.vparams)))
-
-    def setResolution(self, resolution: float):
-        old = self.vparams.resolution
-        self.vparams.resolution = float(resolution)
-        try:
-            self._push_vgicp()
-        except reg.ApdgicpError:
-            self.vparams.resolution = old
-            raise
-
-    def setNeighborSearchMethod(self, method: int):
-        old = self.vparams.neighbor_search
-        self.vparams.neighbor_search = int(method)
-        try:
-            self._push_vgicp()
-        except reg.ApdgicpError:
-            self.vparams.neighbor_search = old
-            raise
-
-    def setVoxelAccumulationMode(self, mode: int):
-        old = self.vparams.voxel_mode
-        self.vparams.voxel_mode = int(mode)
-        try:
-            self._push_vgicp()
-        except reg.ApdgicpError:
-            self.vparams.voxel_mode = old
-            raise
 
     def disable(self):
         """apdgicp_set_vgicp(h, NULL): the handle is an APD-GICP / plain GICP object again."""
         _check(self.L.apdgicp_set_vgicp(self.h, None))
-
-    def enable(self):
-        self._push_vgicp()
 
     def enabled(self) -> bool:
         on = C.c_int()
@@ -89,13 +78,7 @@ class FastVGICP(reg.FastAPDGICP):
 
     def voxels(self):
         """The target's voxel map in voxel order (ascending key): dict(coords [n,3] int32, counts [n] int32, means [n,3], covs [n,3,3])."""
-        n = self.voxel_count()
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_vgicp_get_voxels(self.h, n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_vgicp_get_voxels(self.h, *a), self.voxel_count())
 
     def voxel_correspondences(self) -> np.ndarray:
         """[n_source, n_offsets] voxel indices of the last linearize, in offset order; -1 = miss."""
@@ -110,7 +93,7 @@ class FastVGICP(reg.FastAPDGICP):
         return n.value
 
 
-class BatchVGICP(reg.BatchAPDGICP):
+class BatchVGICP(_VgicpSetters, reg.BatchAPDGICP):
     """Many independent voxelized-GICP registrations on one GPU: a batch handle with apdgicp_batch_set_vgicp on (V8 .. V12).  Clouds, align,
     align_async / synchronize and fitness are the base class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is;
     align_enqueue / align_collect raise (one batch at a time).  `disable()` hands the handle back to APD-GICP."""
@@ -118,28 +101,10 @@ class BatchVGICP(reg.BatchAPDGICP):
     def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
         super().__init__(params, device, stream)
         self.vparams = default_vgicp_params()
-        self._push_vgicp()
+        self._push_mode()
 
-    def _push_vgicp(self):
+    def _push_mode(self):
         _check(self.L.apdgicp_batch_set_vgicp(self.b, C.byref(self.vparams)))
-
-    def _set(self, field: str, value):
-        old = getattr(self.vparams, field)
-        setattr(self.vparams, field, value)
-        try:
-            self._push_vgicp()
-        except reg.ApdgicpError:
-            setattr(self.vparams, field, old)
-            raise
-
-    def setResolution(self, resolution: float):
-        self._set("resolution", float(resolution))
-
-    def setNeighborSearchMethod(self, method: int):
-        self._set("neighbor_search", int(method))
-
-    def setVoxelAccumulationMode(self, mode: int):
-        self._set("voxel_mode", int(mode))
 
     def get_vgicp(self):
         """(VgicpParams, enabled) as the library holds them."""
@@ -149,9 +114,6 @@ class BatchVGICP(reg.BatchAPDGICP):
 
     def disable(self):
         _check(self.L.apdgicp_batch_set_vgicp(self.b, None))
-
-    def enable(self):
-        self._push_vgicp()
 
     def enabled(self) -> bool:
         return self.get_vgicp()[1]
@@ -163,13 +125,7 @@ class BatchVGICP(reg.BatchAPDGICP):
 
     def voxels(self, cloud: int):
         """The voxel map of cloud slot `cloud` (built if it is not current), as FastVGICP.voxels()."""
-        n = self.voxel_count(cloud)
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_batch_vgicp_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_batch_vgicp_get_voxels(self.b, int(cloud), *a), self.voxel_count(cloud))
 
     def build_count(self) -> int:
         """How many voxel maps this handle has built, all slots together (the cache rules' test hook)."""

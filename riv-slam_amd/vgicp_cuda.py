@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import registration as reg
-from .registration import _check, _ptr
+from .registration import _check, _ptr, _read_voxels, _set_fields
 
 DIRECT1, DIRECT7, DIRECT27, DIRECT_RADIUS = 0, 1, 2, 3                      # apdgicp_vgicp_cuda_params.neighbor_search
 NONE, MIN_EIG, NORMALIZED_MIN_EIG, PLANE, FROBENIUS = 0, 1, 2, 3, 4         # RegularizationMethod (gicp_settings.hpp)
@@ -43,40 +43,17 @@ def neighbor_offsets(params: VgicpCudaParams) -> np.ndarray:
     return out[:n.value].copy()
 
 
-class FastVGICPCuda(reg.FastAPDGICP):
-    """One registration object (== one fast_gicp::FastVGICPCuda) on one GPU.  setInputSource / setInputTarget / swapSourceAndTarget /
-    clearSource / clearTarget / align / linearize / compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are the
-    base class's; align always runs the host-driven loop.  `disable()` hands the handle back to APD-GICP."""
-
-    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
-        super().__init__(params, device, stream)
-        self.vparams = default_vgicp_cuda_params()
-        self.kernel_width, self.kernel_max_dist = 0.5, 3.0   # VCI:31 (stored; only GPU_RBF_KERNEL would read them)
-        self._push_mode()
-
-    def _push_mode(self):
-        _check(self.L.apdgicp_set_vgicp_cuda(self.h, C.byref(self.vparams)))
+class _VgicpCudaSetters:
+    """The reference's setters, enable(), enabled() and offsets() over `vparams` and the `_push_mode()` / `get_mode()` of the single or the batch class."""
 
     def _set(self, **fields):
-        old = {k: getattr(self.vparams, k) for k in fields}
-        for k, val in fields.items():
-            setattr(self.vparams, k, val)
-        try:
-            self._push_mode()
-        except reg.ApdgicpError:
-            for k, val in old.items():
-                setattr(self.vparams, k, val)
-            raise
+        _set_fields(self.vparams, self._push_mode, **fields)
 
     def setCorrespondenceRandomness(self, k):   # VCI:38: a no-op, k is 20
         pass
 
     def setResolution(self, resolution: float):
         self._set(resolution=float(resolution))
-
-    def setKernelWidth(self, kernel_width: float, max_dist: float = -1.0):   # VCI:45-51
-        self.kernel_width = float(kernel_width)
-        self.kernel_max_dist = float(max_dist) if max_dist > 0.0 else 5.0 * float(kernel_width)
 
     def setRegularizationMethod(self, method: int):
         self._set(regularization=int(method))
@@ -91,24 +68,43 @@ class FastVGICPCuda(reg.FastAPDGICP):
     def setNearestNeighborSearchMethod(self, method: int):
         self._set(nn_method=int(method))
 
-    def disable(self):
-        """apdgicp_set_vgicp_cuda(h, NULL): the handle is an APD-GICP / plain GICP object again."""
-        _check(self.L.apdgicp_set_vgicp_cuda(self.h, None))
-
     def enable(self):
         self._push_mode()
-
-    def get_mode(self):
-        """(VgicpCudaParams, enabled) as the library holds them."""
-        p, on = VgicpCudaParams(), C.c_int()
-        _check(self.L.apdgicp_get_vgicp_cuda(self.h, C.byref(p), C.byref(on)))
-        return p, bool(on.value)
 
     def enabled(self) -> bool:
         return self.get_mode()[1]
 
     def offsets(self) -> np.ndarray:
         return neighbor_offsets(self.vparams)
+
+
+class FastVGICPCuda(_VgicpCudaSetters, reg.FastAPDGICP):
+    """One registration object (== one fast_gicp::FastVGICPCuda) on one GPU.  setInputSource / setInputTarget / swapSourceAndTarget /
+    clearSource / clearTarget / align / linearize / compute_error / hasConverged / getFinalTransformation / getFitnessScore / trace are the
+    base class's; align always runs the host-driven loop.  `disable()` hands the handle back to APD-GICP."""
+
+    def __init__(self, params: reg.Params | None = None, device: int = 0, stream=None):
+        super().__init__(params, device, stream)
+        self.vparams = default_vgicp_cuda_params()
+        self.kernel_width, self.kernel_max_dist = 0.5, 3.0   # VCI:31 (stored; only GPU_RBF_KERNEL would read them)
+        self._push_mode()
+
+    def _push_mode(self):
+        _check(self.L.apdgicp_set_vgicp_cuda(self.h, C.byref(self.vparams)))
+
+    def setKernelWidth(self, kernel_width: float, max_dist: float = -1.0):   # VCI:45-51
+        self.kernel_width = float(kernel_width)
+        self.kernel_max_dist = float(max_dist) if max_dist > 0.0 else 5.0 * float(kernel_width)
+
+    def disable(self):
+        """apdgicp_set_vgicp_cuda(h, NULL): the handle is an APD-GICP / plain GICP object again."""
+        _check(self.L.apdgicp_set_vgicp_cuda(self.h, None))
+
+    def get_mode(self):
+        """(VgicpCudaParams, enabled) as the library holds them."""
+        p, on = VgicpCudaParams(), C.c_int()
+        _check(self.L.apdgicp_get_vgicp_cuda(self.h, C.byref(p), C.byref(on)))
+        return p, bool(on.value)
 
     def kept(self, which: int) -> np.ndarray:
         """VC4: the original indices of the kept points of cloud `which`, ascending."""
@@ -133,13 +129,7 @@ class FastVGICPCuda(reg.FastAPDGICP):
 
     def voxels(self):
         """The prepared target's voxel map in voxel order: dict(coords [n,3] int32, counts [n] int32, means [n,3], covs [n,3,3])."""
-        n = self.voxel_count()
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_vgicp_cuda_get_voxels(self.h, n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_vgicp_cuda_get_voxels(self.h, *a), self.voxel_count())
 
     def voxel_correspondences(self) -> np.ndarray:
         """[n_kept(source), n_offsets] voxel indices of the last linearize, in offset order; -1 = miss."""
@@ -155,7 +145,7 @@ class FastVGICPCuda(reg.FastAPDGICP):
         return n.value
 
 
-class BatchVGICPCuda(reg.BatchAPDGICP):
+class BatchVGICPCuda(_VgicpCudaSetters, reg.BatchAPDGICP):
     """Many independent FAST_VGICP_CUDA registrations on one GPU: a batch handle with apdgicp_batch_set_vgicp_cuda on (VC11 .. VC16): per-slot
     prepared clouds and voxel maps, the optimiser loop on the device.  Clouds, align, align_async / synchronize and fitness are the base
     class's, so `loop_verifier.verify_candidates(batch, ...)` takes one as it is; align_enqueue / align_collect raise (one batch at a time).
@@ -169,53 +159,14 @@ class BatchVGICPCuda(reg.BatchAPDGICP):
     def _push_mode(self):
         _check(self.L.apdgicp_batch_set_vgicp_cuda(self.b, C.byref(self.vparams)))
 
-    def _set(self, **fields):
-        old = {k: getattr(self.vparams, k) for k in fields}
-        for k, val in fields.items():
-            setattr(self.vparams, k, val)
-        try:
-            self._push_mode()
-        except reg.ApdgicpError:
-            for k, val in old.items():
-                setattr(self.vparams, k, val)
-            raise
-
-    def setCorrespondenceRandomness(self, k):   # VCI:38: a no-op, k is 20
-        pass
-
-    def setResolution(self, resolution: float):
-        self._set(resolution=float(resolution))
-
-    def setRegularizationMethod(self, method: int):
-        self._set(regularization=int(method))
-
-    def setNeighborSearchMethod(self, method: int, radius: float = -1.0):
-        """DIRECT1 / DIRECT7 / DIRECT27, or DIRECT_RADIUS with its radius in voxels (a radius the mode does not read is not stored)."""
-        if int(method) == DIRECT_RADIUS:
-            self._set(neighbor_search=DIRECT_RADIUS, search_radius=float(radius))
-        else:
-            self._set(neighbor_search=int(method))
-
-    def setNearestNeighborSearchMethod(self, method: int):
-        self._set(nn_method=int(method))
-
     def disable(self):
         _check(self.L.apdgicp_batch_set_vgicp_cuda(self.b, None))
-
-    def enable(self):
-        self._push_mode()
 
     def get_mode(self):
         """(VgicpCudaParams, enabled) as the library holds them."""
         p, on = VgicpCudaParams(), C.c_int()
         _check(self.L.apdgicp_batch_get_vgicp_cuda(self.b, C.byref(p), C.byref(on)))
         return p, bool(on.value)
-
-    def enabled(self) -> bool:
-        return self.get_mode()[1]
-
-    def offsets(self) -> np.ndarray:
-        return neighbor_offsets(self.vparams)
 
     def kept(self, cloud: int) -> np.ndarray:
         """VC4 / VC11: the original indices of the kept points of cloud slot `cloud` (prepared if it is not current), ascending."""
@@ -240,13 +191,7 @@ class BatchVGICPCuda(reg.BatchAPDGICP):
 
     def voxels(self, cloud: int):
         """The voxel map over the kept points of cloud slot `cloud` (built if it is not current), as FastVGICPCuda.voxels()."""
-        n = self.voxel_count(cloud)
-        coords = np.empty((n, 3), dtype=np.int32)
-        counts = np.empty(n, dtype=np.int32)
-        means = np.empty((n, 3))
-        covs = np.empty((n, 9))
-        _check(self.L.apdgicp_batch_vgicp_cuda_get_voxels(self.b, int(cloud), n, _ptr(coords), _ptr(counts), _ptr(means), _ptr(covs)))
-        return {"coords": coords, "counts": counts, "means": means, "covs": covs.reshape(n, 3, 3)}
+        return _read_voxels(lambda *a: self.L.apdgicp_batch_vgicp_cuda_get_voxels(self.b, int(cloud), *a), self.voxel_count(cloud))
 
     def voxel_correspondences(self, pair: int) -> np.ndarray:
         """[n_kept(source), n_offsets] frozen voxel indices of pair `pair`'s last linearize in the last align, in offset order; -1 = miss."""

@@ -4,7 +4,10 @@
 setter (to APD: A's setter with NULL), and must then be indistinguishable from a handle that was only ever in B -- exactly B's enabled
 flag, the align's record and pose byte for byte, and on the single handle the final Hessian too, while A's own getter answers
 APDGICP_ERR_NO_INPUT.  Nothing is compared against a restatement here: both sides run the same kernels on the same clouds, so the bar is
-equality.
+equality.  What the voxel modes share (one frozen-linearize state per single handle; per batch handle one set of frozen indices, block rows
+and pair table, and a slot table of its own per mode) has tests of its own below the switches: a round trip A -> B -> A builds nothing again
+and reproduces A's first align; a walk over 27, 1, 7 and 27 offsets on one handle equals fresh handles, with every getter refusing indices
+that are not its own mode's; voxelized GICP's frozen state survives a swap and the swap back.
 
 Clouds: pair["source"][:257] and pair["target"][:700] of tests/golden/vgicp_cuda_pair.npz (257: two blocks of the per-point kernels and a
 tail); the batch handle's second pair is the first 129 source points against the same target.  max_iterations = 3.
@@ -194,6 +197,173 @@ def test_flags_follow_every_switch_without_clouds(reg, mode_params):
                 _switch(L, h, b, "apd", mode_params, batch=is_batch)
             assert _flags(L, h, batch=is_batch) == _want_flags("apd")
     single.close(), batch.close()
+
+
+# ---------------------------------------------------------------------- what the voxel modes share
+VOXEL_MODES = ("vgicp", "vgicp_cuda", "ndt")
+# By how much a round trip A -> B -> A (an align in each) grows A's build counts, per (handle kind, A): what the parent of the change that gave
+# the voxel modes one frozen state and one run tail per handle does, measured there with this test.  The identity keys (cloud_gen, cov_gen,
+# pts_gen, preparation id, resolution) do not change on the way, so nothing is built again -- whichever B.
+ROUND_TRIP_BUILDS = {("single", "vgicp"): (0,), ("single", "vgicp_cuda"): (0,), ("single", "ndt"): (0,),
+                     ("batch", "vgicp"): (0,), ("batch", "vgicp_cuda"): (0, 0), ("batch", "ndt"): (0,)}
+
+
+def _build_counts(L, h, mode, batch):
+    """the mode's build count(s): maps built; on a batch handle FAST_VGICP_CUDA counts (clouds prepared, maps built)"""
+    fn = getattr(L, ("apdgicp_batch_" if batch else "apdgicp_") + mode + "_build_count")
+    n = [C.c_int64(-1) for _ in range(2 if batch and mode == "vgicp_cuda" else 1)]
+    assert fn(h, *[C.byref(x) for x in n]) == 0
+    return tuple(x.value for x in n)
+
+
+@gpu
+@pytest.mark.parametrize("a", VOXEL_MODES)
+def test_single_handle_caches_survive_a_round_trip(reg, pair, mode_params, a):
+    g = _single(reg, pair)
+    L = g.L
+    _switch(L, g.h, "apd", a, mode_params)
+    first = _single_align(g, pair)
+    assert first[0] == 0, L.apdgicp_last_error().decode()
+    for b in (m for m in MODES if m != a):
+        before = _build_counts(L, g.h, a, False)
+        _switch(L, g.h, a, b, mode_params)
+        assert _single_align(g, pair)[0] == 0, (b, L.apdgicp_last_error().decode())
+        _switch(L, g.h, b, a, mode_params)
+        again = _single_align(g, pair)
+        grown = tuple(y - x for x, y in zip(before, _build_counts(L, g.h, a, False)))
+        assert again == first, b
+        assert grown == ROUND_TRIP_BUILDS["single", a], b
+    g.close()
+
+
+@gpu
+@pytest.mark.parametrize("a", VOXEL_MODES)
+def test_batch_handle_caches_survive_a_round_trip(reg, pair, mode_params, a):
+    g = _batch(reg, pair)
+    L = g.L
+    _switch(L, g.b, "apd", a, mode_params, batch=True)
+    first = _batch_align(g, pair).tobytes()
+    for b in (m for m in MODES if m != a):
+        before = _build_counts(L, g.b, a, True)
+        _switch(L, g.b, a, b, mode_params, batch=True)
+        _batch_align(g, pair)
+        _switch(L, g.b, b, a, mode_params, batch=True)
+        again = _batch_align(g, pair).tobytes()
+        grown = tuple(y - x for x, y in zip(before, _build_counts(L, g.b, a, True)))
+        assert again == first, b
+        assert grown == ROUND_TRIP_BUILDS["batch", a], b
+    g.close()
+
+
+def _stride_walk(mode_params):
+    """(mode, parameters) in turn: the widest stride of the frozen indices (27 offsets), the narrowest (1), 7, and the widest again"""
+    def with_search(mode, search):
+        p = type(mode_params[mode])()
+        C.memmove(C.byref(p), C.byref(mode_params[mode]), C.sizeof(p))
+        p.neighbor_search = search
+        return p
+    DIRECT1, DIRECT7, DIRECT27 = 0, 1, 2
+    nd27 = with_search("ndt", DIRECT27)
+    return [("ndt", nd27), ("vgicp", with_search("vgicp", DIRECT1)), ("vgicp_cuda", with_search("vgicp_cuda", DIRECT7)), ("ndt", nd27)]
+
+
+def _n_offsets(p):
+    return {0: 1, 1: 7, 2: 27}[p.neighbor_search]
+
+
+@gpu
+def test_batch_handle_shares_buffers_across_strides(reg, pair, mode_params):
+    walk = _stride_walk(mode_params)
+    fresh = []
+    for mode, p in walk[:3]:
+        g = _batch(reg, pair)
+        assert _setter(g.L, mode, True)(g.b, C.byref(p)) == 0, g.L.apdgicp_last_error().decode()
+        fresh.append(_batch_align(g, pair).tobytes())
+        g.close()
+    fresh.append(fresh[0])
+    g = _batch(reg, pair)
+    vc_corr = lambda: g.L.apdgicp_batch_vgicp_cuda_get_correspondences(g.b, 0, None, 0)  # (the size query of pair 0)
+    for k, (mode, p) in enumerate(walk):
+        assert _setter(g.L, mode, True)(g.b, C.byref(p)) == 0, g.L.apdgicp_last_error().decode()
+        assert vc_corr() == NO_INPUT, (k, mode)  # off, or on with no align of its own yet: the shared buffers hold another mode's indices
+        assert _batch_align(g, pair).tobytes() == fresh[k], (k, mode)
+        assert (vc_corr() >= 0) == (mode == "vgicp_cuda"), (k, mode)
+    # back in FAST_VGICP_CUDA with NDT's indices in the shared buffers: its own align of before is forgotten with them
+    assert _setter(g.L, "vgicp_cuda", True)(g.b, C.byref(walk[2][1])) == 0
+    assert vc_corr() == NO_INPUT
+    g.close()
+
+
+def _corr_rows(g, mode):
+    """rows of the mode's frozen indices: source points, kept source points, source voxels (NDT, D2D)"""
+    n = C.c_int64(-1)
+    if mode == "vgicp":
+        return g.n_src
+    rc = g.L.apdgicp_vgicp_cuda_kept(g.h, SRC, C.byref(n), None, 0) if mode == "vgicp_cuda" else g.L.apdgicp_ndt_voxel_count(g.h, SRC, C.byref(n))
+    assert rc == 0, g.L.apdgicp_last_error().decode()
+    return n.value
+
+
+def _corr_getter(L, mode):
+    return getattr(L, "apdgicp_" + mode + "_get_correspondences")
+
+
+def _probe(g, mode, p):
+    """linearize and compute_error at the identity, then the mode's frozen indices: everything as bytes"""
+    cost, H, b = g.linearize(np.eye(4))
+    err = g.compute_error(np.eye(4))
+    rows = _corr_rows(g, mode)
+    corr = np.full((rows, _n_offsets(p)), -9, dtype=np.int32)
+    assert _corr_getter(g.L, mode)(g.h, corr.ctypes.data_as(C.c_void_p), rows) == 0, g.L.apdgicp_last_error().decode()
+    return H.tobytes(), b.tobytes(), np.float64(cost).tobytes(), np.float64(err).tobytes(), corr.tobytes()
+
+
+@gpu
+def test_single_handle_shares_the_frozen_state_across_strides(reg, pair, mode_params):
+    walk = _stride_walk(mode_params)
+    fresh = []
+    for mode, p in walk[:3]:
+        g = _single(reg, pair)
+        assert _setter(g.L, mode, False)(g.h, C.byref(p)) == 0, g.L.apdgicp_last_error().decode()
+        fresh.append(_probe(g, mode, p))
+        g.close()
+    fresh.append(fresh[0])
+    g = _single(reg, pair)
+    scratch = np.zeros(700 * 27, dtype=np.int32)
+    for k, (mode, p) in enumerate(walk):
+        assert _setter(g.L, mode, False)(g.h, C.byref(p)) == 0, g.L.apdgicp_last_error().decode()
+        if k:  # the mode that was left no longer answers for its indices
+            assert _corr_getter(g.L, walk[k - 1][0])(g.h, scratch.ctypes.data_as(C.c_void_p), 1) == NO_INPUT
+        # ... and the mode that was entered has none yet: the one frozen state still holds the other mode's indices, and is void
+        assert _corr_getter(g.L, mode)(g.h, scratch.ctypes.data_as(C.c_void_p), 1) == NO_INPUT, (k, mode)
+        assert g.L.apdgicp_compute_error(g.h, np.eye(4).ctypes.data_as(C.c_void_p), C.byref(C.c_double())) == NO_INPUT, (k, mode)
+        assert _probe(g, mode, p) == fresh[k], (k, mode)
+    g.close()
+
+
+@gpu
+def test_vgicp_frozen_state_is_current_again_after_two_swaps(reg, pair, mode_params):
+    """V6: voxelized GICP ties its frozen state to the clouds by identity, not by call -- a swap makes it stale, the swap back current again
+    (no prepare ran in between); the other two voxel modes forget theirs with the first swap."""
+    for mode in VOXEL_MODES:
+        g = _single(reg, pair)
+        p = mode_params[mode]
+        _switch(g.L, g.h, "apd", mode, mode_params)
+        first = _probe(g, mode, p)
+        rows = _corr_rows(g, mode)
+        corr = np.full((rows, _n_offsets(p)), -9, dtype=np.int32)
+        T, cost = np.eye(4), C.c_double(-1.0)
+        error = lambda: g.L.apdgicp_compute_error(g.h, T.ctypes.data_as(C.c_void_p), C.byref(cost))
+        getter = lambda: _corr_getter(g.L, mode)(g.h, corr.ctypes.data_as(C.c_void_p), rows)
+        assert g.L.apdgicp_swap_source_and_target(g.h) == 0
+        assert error() == NO_INPUT and getter() == NO_INPUT, mode
+        assert g.L.apdgicp_swap_source_and_target(g.h) == 0
+        if mode == "vgicp":
+            assert error() == 0 and getter() == 0, g.L.apdgicp_last_error().decode()
+            assert (np.float64(cost.value).tobytes(), corr.tobytes()) == (first[3], first[4])
+        else:
+            assert error() == NO_INPUT and getter() == NO_INPUT, mode
+        g.close()
 
 
 # ---------------------------------------------------------------------- without a device
