@@ -52,7 +52,8 @@ extern "C" {
                                       still 6 (additive): + apdgicp_batch_set_icp / _get_icp and the apdgicp_batch_icp_* calls (point-to-point ICP as a mode of the batch handle);
                                       still 6 (additive): + apdgicp_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the registration handle);
                                       still 6 (additive): + apdgicp_batch_set_vgicp_cuda / _get_vgicp_cuda and the apdgicp_batch_vgicp_cuda_* calls (FAST_VGICP_CUDA as a mode of the batch handle);
-                                      still 6 (additive): + apdgicp_knn_of, apdgicp_radius_search_of / _rows, apdgicp_search_group_stats (exact k-nearest and radius queries of the target) */
+                                      still 6 (additive): + apdgicp_knn_of, apdgicp_radius_search_of / _rows, apdgicp_search_group_stats (exact k-nearest and radius queries of the target);
+                                      still 6 (additive): + apdgicp_scan_ingest_run_polar and apdgicp_scan_ingest_histogram_* (the polar message of cloud_callback_scan, the distance histogram) */
 
 typedef enum {
   APDGICP_OK = 0,
@@ -1447,7 +1448,7 @@ int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, d
  * What PreprocessingNodelet::cloud_callback ("P:" = radar_graph_slam/apps/preprocessing_nodelet.cpp) does to the message before the
  * ego-velocity estimate (P:667-697; the hugin callback P:497-506) and to src_cloud between that estimate and distance_filter
  * (deskewing P:914-975, the base-link transform P:796-810).  With this object every per-point step of the callback is on the device:
- *   _run -> apdgicp_ego_velocity_run on the rows -> its inliers (or the rows) -> _deskew -> apdgicp_scan_filter_run -> apdgicp_set_source.
+ *   _run (or _run_polar) -> apdgicp_ego_velocity_run on the rows -> its inliers (or the rows) -> _deskew -> apdgicp_scan_filter_run -> apdgicp_set_source.
  *   I1. Lanes (P:667-683, P:497-506).  A point's x, y, z are three consecutive floats at xyz + i * xyz_stride_bytes; intensity (the
  *       message's "Power") and doppler are one float each at their own base and stride.  geometry_msgs::Point32[] plus channels[2] /
  *       channels[0]: strides 12 / 4 / 4.  A sensor_msgs::PointCloud2 or any array of structures: all strides = point_step, the bases
@@ -1484,8 +1485,52 @@ int apdgicp_dbscan_stats(apdgicp_dbscan* h, int64_t* launches, int64_t* waits, d
  *       apdgicp_set_source accept; valid until the next _deskew.  No host wait: n is the caller's.  A consumer on another stream orders
  *       itself behind the launch with _synchronize (or shares the object's stream).  The call is legal on the rows the same object's
  *       _run produced and on any other device or host cloud.
- * Not part of this object: the polar message (cloud_callback_scan), the ranges / predicted_ranges topics (P:660-700), the colour
- * cloud (P:921-937), the distance histogram (P:818-828), underfloor_filter (its result is unused, P:816). */
+ * The polar message: _run_polar is the head of cloud_callback_scan (P:324-464), the callback of every dataset that is neither hugin
+ * nor eagle -- a msgs_radar/RadarScanExtended with range, azimuth, elevation, velocity and snr per target.  Behind it the chain is the one
+ * above, with the ego-velocity inlier cloud always as the source (P:416-420).
+ *   PI1. Lanes (P:331-337).  Five byte-strided float lanes as in I1: range, azimuth, elevation, snr, velocity, each one float per target
+ *       at its own base and stride; strides are multiples of 4 and >= 4.  A RadarTargetExtended[] is one array of 76-byte structures
+ *       (19 floats): all strides 76, the bases at the field offsets 0 / 4 / 8 / 16 / 12.  The lanes are all on the host or all on the
+ *       device.  on_device = 0: staged by copies on the object's stream without a wait; one copy when all five lie inside one array of
+ *       structures (same stride, bases within one stride of each other), as I1.
+ *   PI2. No gate.  P:331-340 pushes every target: n_out = n, power_threshold and gate are not read, non-finite values pass through.  No
+ *       count, no scan and NO HOST WAIT: *n_out is written from n.
+ *   PI3. Coordinates (P:333-335).  `using namespace std;` (P:47) makes the unqualified cos / sin of a float member the float overloads, so
+ *       the reference is x = (range * cosf(el)) * cosf(az), y = (range * cosf(el)) * sinf(az), z = (-range) * sinf(el), all fp32, left to
+ *       right, each product rounded on its own, no FMA.  The C library's cosf / sinf are not correctly rounded and their algorithm is not
+ *       restated here (apd_atan2f.h covers atan2f only).  The device defines each of the four factors as THE FP64 VALUE ROUNDED ONCE TO
+ *       FP32: for |angle| <= pi, (float)cos((double)angle) and (float)sin((double)angle) through sincos_pi (csrc/apd_math.hpp, at most
+ *       0.77 ulp in fp64); for any other argument, NaN and +-inf included, through the device library's fp64 sincos.  The three products
+ *       follow in fp32 exactly as written above, without contraction.
+ *       Deviation from the reference: a factor can differ from the C library's by one fp32 ulp.  Measured against glibc 2.35
+ *       (tests/test_polar_ingest_cpu.py): over every 64th float of [2^-20, 1.6] cosf differs from the rounded fp64 value in 0.13 % and
+ *       sinf in 0.47 % of the arguments, never by more than one ulp; over 2 000 000 targets (range 2 .. 100 m, azimuth +-0.986 rad,
+ *       elevation +-0.262 rad) 0.54 % / 1.85 % / 1.90 % of x / y / z differ at all, by 3 / 2 / 2 ulps at most (the derived bound is 6:
+ *       two factors off by one ulp each and two product roundings).
+ *   PI4. Output.  n rows of 32 bytes {x, y, z, snr, velocity, 0, 0, 0} and index[i] = i, in input order, from one launch; _points,
+ *       _copy and _stats serve them as they serve _run's.  n = 0: status 0, no launch.  n > 2^24: APDGICP_ERR_UNSUPPORTED.  A stride that
+ *       is not a multiple of 4 or is below 4, a NULL lane with n > 0, n < 0: APDGICP_ERR_INVALID_ARG.  After an error the object stays
+ *       usable and the rows of the last good run stay readable.
+ *   PI5. Interplay.  A _run_polar after a _run, or the other way round, replaces the rows; a smaller second run leaves nothing of the
+ *       first visible (n of _points is the new one).  _deskew on the object's own polar rows is legal (I7).
+ * The distance histogram that ends all three callbacks (P:451-461, P:618-628, P:818-828; num_frame is never incremented, so it runs on
+ * every frame) and the point_distribution command that reads it (P:1009-1021):
+ *   H1. Per point d = sqrtf((x * x + y * y) + z * z) in fp32, each product rounded on its own, no FMA: the writing of
+ *       getVector3fMap().norm() that the scan filter's range gate uses.  b = (int)floorf(d); the point is counted in bin b iff d is finite
+ *       and b < 100.  A non-finite d is NOT counted: the reference converts it to int, which is undefined, and on x86 the result
+ *       (INT_MIN) passes `dist < 100` and indexes out of bounds.
+ *   H2. _histogram_add costs two launches (zero the frame's counts, then count) and NO HOST WAIT.  It leaves the frame's 100 int32 counts
+ *       on the device, adds them to a running int64[100] sum on the device and increments a frame counter there.  Per-block LDS
+ *       histograms with 32-bit integer atomics, then at most 100 integer atomic adds per block to global memory; integer addition
+ *       commutes, so the bytes are the same on every run.  n = 0 is a frame of zeros, as the reference pushes one.
+ *   H3. _histogram_last returns the counts of the last _add (zeros before the first), _histogram_read the running sum and the number of
+ *       frames; either of its two destinations may be NULL.  The point_distribution command is the sum divided by frames, element-wise, as
+ *       integer division.  The reference adds into an Eigen::VectorXi data(100) that was never zeroed; this sum starts from zero.
+ *       _histogram_reset zeroes the counts, the sum and the frame counter (no wait).
+ *   H4. Errors as PI4.  stride_bytes >= 12 and a multiple of 4.  The input can be the cloud of apdgicp_scan_filter_points (16-byte rows),
+ *       the ingest rows (32 bytes) or any host cloud; a producer on another stream is the caller's to order, as for _deskew.
+ * Not part of this object: the ranges / predicted_ranges topics (P:660-700), the colour cloud (P:921-937), the Doppler statistics of the
+ * outlier cloud (P:395-405: nothing reads them), underfloor_filter (its result is unused, P:449, P:816). */
 typedef struct {
   float power_threshold;   /* "power_threshold", P:107 ; default 0 */
   int32_t gate;            /* 1 (default): I2 ; 0: every point is kept (P:497-506) */
@@ -1501,6 +1546,10 @@ int apdgicp_scan_ingest_set_params(apdgicp_scan_ingest* h, const apdgicp_scan_in
 /* I1 .. I4 of one message; the three lanes all in device memory (on_device = 1) or all on the host; pre_transform: float[16] column-major or NULL */
 int apdgicp_scan_ingest_run(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t xyz_stride_bytes, const float* intensity, int64_t intensity_stride_bytes,
                             const float* doppler, int64_t doppler_stride_bytes, int on_device, const float* pre_transform, int64_t* n_out);
+/* PI1 .. PI5 of one polar message; the five lanes all in device memory (on_device = 1) or all on the host.  Does not wait. */
+int apdgicp_scan_ingest_run_polar(apdgicp_scan_ingest* h, const float* range, int64_t range_stride_bytes, const float* azimuth, int64_t azimuth_stride_bytes,
+                                  const float* elevation, int64_t elevation_stride_bytes, const float* snr, int64_t snr_stride_bytes, const float* velocity,
+                                  int64_t velocity_stride_bytes, int64_t n, int on_device, int64_t* n_out);
 /* the rows of the last run and their message indices in device memory, valid until the next run; any pointer but h may be NULL */
 int apdgicp_scan_ingest_points(apdgicp_scan_ingest* h, const float** device_rows, const int32_t** device_index, int64_t* n);
 /* the same to HOST memory: rows [8 * capacity] floats, index [capacity]; either may be NULL */
@@ -1513,7 +1562,12 @@ int apdgicp_scan_ingest_deskew(apdgicp_scan_ingest* h, const float* xyz, int64_t
 int apdgicp_scan_ingest_deskewed(apdgicp_scan_ingest* h, const float** device_xyzi, int64_t* n);
 int apdgicp_scan_ingest_deskewed_copy(apdgicp_scan_ingest* h, float* xyzi, int64_t capacity);   /* the same to HOST memory, [4 * capacity] floats; waits */
 int apdgicp_scan_ingest_synchronize(apdgicp_scan_ingest* h);                                      /* waits for the object's stream (I7) */
-/* kernel launches and host waits of the last _run or _deskew as counted by the host code that enqueued them (for the measurement scripts) */
+/* H1 .. H4: one frame of the distance histogram from a device or host cloud (xyz first); does not wait */
+int apdgicp_scan_ingest_histogram_add(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t stride_bytes, int on_device);
+int apdgicp_scan_ingest_histogram_last(apdgicp_scan_ingest* h, int32_t counts[100]);                 /* waits */
+int apdgicp_scan_ingest_histogram_read(apdgicp_scan_ingest* h, int64_t sum[100], int64_t* frames);   /* waits */
+int apdgicp_scan_ingest_histogram_reset(apdgicp_scan_ingest* h);
+/* kernel launches and host waits of the last _run, _run_polar, _deskew or _histogram_add as counted by the host code that enqueued them (for the measurement scripts) */
 int apdgicp_scan_ingest_stats(apdgicp_scan_ingest* h, int64_t* launches, int64_t* waits);
 
 #ifdef __cplusplus

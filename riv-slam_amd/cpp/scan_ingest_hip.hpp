@@ -1,10 +1,12 @@
 // radar_graph_slam::ScanIngestHip -- the two ends of PreprocessingNodelet::cloud_callback
 // (radar_graph_slam/apps/preprocessing_nodelet.cpp) on an MI355X through the C ABI of libapdgicp_hip.so (include/apdgicp_hip.h,
-// apdgicp_scan_ingest_*, I1 .. I7 there):
+// apdgicp_scan_ingest_*, I1 .. I7, PI1 .. PI5 and H1 .. H4 there):
 //   ingest()  the power gate and the packing of the message's arrays into {x, y, z, intensity, doppler} rows (:667-697; setGate(false):
 //             the hugin callback, :497-506), with an optional fixed transform (:477-480);
 //   deskew()  deskewing (:914-975) with the IMU message the reference picks from its queue (:939-949), then the transform into the
 //             base-link frame (:796-810).
+//   runPolar()  the head of cloud_callback_scan (:331-340, PI1 .. PI5): range / azimuth / elevation targets into the same rows;
+//   histogramAdd() / histogramLast() / pointDistribution()  the distance histogram that ends all three callbacks (:451-461, H1 .. H4).
 // The rows and the deskewed cloud stay on the device: deviceRows() is what apdgicp_ego_velocity_run(handle, rows, n, 32, 12, 16, 1, ...)
 // accepts (RadarEgoVelocityEstimatorHip::handle()), deviceDeskewed() what apdgicp_scan_filter_run(handle, xyzi, n, 16, 12, 1, ...)
 // accepts (ScanFilterHip::handle()) after synchronize() -- those objects run on streams of their own.
@@ -79,6 +81,46 @@ class ScanIngestHip {
     rows.resize((std::size_t)n * 8), index.resize((std::size_t)n);
     return n == 0 || !check(apdgicp_scan_ingest_copy(h_, rows.data(), index.data(), n), "copy");
   }
+
+  // PI1 .. PI5 of one msgs_radar::RadarScanExtended (cloud_callback_scan, :331-340): every target becomes a row, no gate, no wait.  TargetT is
+  // msgs_radar::RadarTargetExtended or any structure with float members range, azimuth, elevation, snr, velocity: the lanes are the member
+  // addresses of targets[0], the stride is sizeof(TargetT).  Returns the number of rows (= n), -1 on failure.
+  template <class TargetT>
+  int64_t runPolar(const TargetT* targets, std::size_t n, bool on_device = false) {
+    int64_t n_out = 0;
+    if (!ready()) return -1;
+    const TargetT* t = targets;  // (the lanes: the member addresses of targets[0]; no target, no lanes)
+    const int64_t s = (int64_t)sizeof(TargetT);
+    if (check(apdgicp_scan_ingest_run_polar(h_, t ? &t->range : nullptr, s, t ? &t->azimuth : nullptr, s, t ? &t->elevation : nullptr, s, t ? &t->snr : nullptr, s,
+                                            t ? &t->velocity : nullptr, s, (int64_t)n, on_device ? 1 : 0, &n_out), "run_polar"))
+      return -1;
+    return n_out;
+  }
+
+  // H1 .. H4: the distance histogram of the filtered cloud (:451-461, :618-628, :818-828) as one more frame; does not wait
+  bool histogramAdd(const float* xyz, int64_t n, int64_t stride_bytes, bool on_device) {
+    return ready() && !check(apdgicp_scan_ingest_histogram_add(h_, xyz, n, stride_bytes, on_device ? 1 : 0), "histogram_add");
+  }
+  bool histogramAdd(const Cloud& cloud) {
+    static_assert(sizeof(PointT) == 32, "pcl::PointXYZI layout");
+    return histogramAdd(cloud.empty() ? nullptr : &cloud.points[0].x, (int64_t)cloud.size(), sizeof(PointT), false);
+  }
+  // the 100 counts of the last frame (num_at_dist, :454); empty on failure
+  std::vector<int32_t> histogramLast() {
+    std::vector<int32_t> counts(100, 0);
+    if (!ready() || check(apdgicp_scan_ingest_histogram_last(h_, counts.data()), "histogram_last")) counts.clear();
+    return counts;
+  }
+  // the point_distribution command (:1009-1021): the sum of the frames divided by their number, element-wise, as integer division
+  // (zeros without a frame); empty on failure
+  std::vector<int64_t> pointDistribution() {
+    std::vector<int64_t> sum(100, 0);
+    int64_t frames = 0;
+    if (!ready() || check(apdgicp_scan_ingest_histogram_read(h_, sum.data(), &frames), "histogram_read")) return {};
+    for (int64_t& v : sum) v = frames ? v / frames : 0;
+    return sum;
+  }
+  bool histogramReset() { return ready() && !check(apdgicp_scan_ingest_histogram_reset(h_), "histogram_reset"); }
 
   // I5 .. I7 of a device or host cloud with the IMU message selectImu picks for `scan_stamp` (the queue loses what the reference erases);
   // an empty queue: the cloud passes through.  T: float[16] column-major into the base-link frame, or nullptr.  Does not wait.

@@ -13,7 +13,9 @@
 //   - T * p per row: xf_row (apd_kernels.hpp).
 // Every operation is rounded on its own: the library is built with -ffp-contract=off (build.py), so no FMA forms; the *_rn spellings
 // below only say so where the order matters.  Divisions are IEEE divisions (hipcc's default for fp32 as well).  The compaction is the
-// one of the ego-velocity stage (ego_block_counts / ego_block_slot around k_scan_bsum): input order is kept.  No atomics at all.
+// one of the ego-velocity stage (ego_block_counts / ego_block_slot around k_scan_bsum): input order is kept.  No atomics in any of these.
+// Behind them, at the end of the file: the polar message of cloud_callback_scan (:331-340, PI1 .. PI5) and the distance histogram that ends
+// all three callbacks (:451-461, H1 .. H4; 32-bit integer atomics, so its bytes do not depend on the order of the blocks either).
 // Every pointer of this file is a kernel argument.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -113,6 +115,74 @@ __global__ __launch_bounds__(ING_DESKEW_BLK) void k_ing_deskew(const char* pts, 
     vx = tx, vy = ty, vz = tz;
   }
   out[i] = make_float4(vx, vy, vz, intensity);
+}
+
+// ------------------------------------------------------------------ the polar message: cloud_callback_scan, :331-340 (PI1 .. PI5)
+struct PolarLanes {  // PI1: five byte-strided lanes of one RadarScanExtended
+  const char *range, *azimuth, *elevation, *snr, *velocity;
+  long long range_stride, azimuth_stride, elevation_stride, snr_stride, velocity_stride;  // bytes, multiples of 4
+};
+
+// PI3: sine and cosine of an fp32 angle, each the fp64 value rounded once to fp32: sincos_pi for |a| <= pi, the device library's
+// fp64 sincos for everything else (a NaN fails the comparison and goes there too)
+__device__ __forceinline__ void ing_sincosf(float a, float* s, float* c) {
+  const double x = (double)a;
+  double sd, cd;
+  if (fabs(x) <= 3.14159265358979323846) sincos_pi(x, &sd, &cd);
+  else sincos(x, &sd, &cd);
+  *s = (float)sd, *c = (float)cd;
+}
+
+// one target per lane: {(r ce) ca, (r ce) sa, (-r) se, snr, velocity, 0, 0, 0} and index = i; no gate (PI2)
+__global__ __launch_bounds__(ING_BLK) void k_ing_polar(PolarLanes L, int n, float4* rows, int* index) {
+  const int i = blockIdx.x * ING_BLK + threadIdx.x;
+  if (i >= n) return;
+  const float r = *(const float*)(L.range + (size_t)i * L.range_stride);
+  const float az = *(const float*)(L.azimuth + (size_t)i * L.azimuth_stride);
+  const float el = *(const float*)(L.elevation + (size_t)i * L.elevation_stride);
+  const float snr = *(const float*)(L.snr + (size_t)i * L.snr_stride);
+  const float vel = *(const float*)(L.velocity + (size_t)i * L.velocity_stride);
+  float se, ce, sa, ca;
+  ing_sincosf(el, &se, &ce);
+  ing_sincosf(az, &sa, &ca);
+  const float rc = __fmul_rn(r, ce);
+  rows[2 * (size_t)i] = make_float4(__fmul_rn(rc, ca), __fmul_rn(rc, sa), __fmul_rn(-r, se), snr);
+  rows[2 * (size_t)i + 1] = make_float4(vel, 0.f, 0.f, 0.f);
+  index[i] = i;
+}
+
+// ------------------------------------------------------------------ the distance histogram: :451-461, :618-628, :818-828 (H1 .. H4)
+constexpr int ING_HIST_BINS = 100;
+constexpr int ING_HIST_WORDS = ING_HIST_BINS + 1;  // counts: 100 bins and the ticket of k_ing_hist; sum: 100 bins and the frame counter
+
+// the frame's counts and the ticket back to zero
+__global__ __launch_bounds__(128) void k_ing_hist_zero(int* counts) {
+  if (threadIdx.x < ING_HIST_WORDS) counts[threadIdx.x] = 0;
+}
+// H1 per point into the block's LDS bins, the block's non-empty bins into counts; the block that draws the last ticket adds the finished
+// counts to the running sum and counts the frame.  Integer atomics only: the result does not depend on the order of the blocks.
+__global__ __launch_bounds__(ING_BLK) void k_ing_hist(const char* pts, int n, long long stride /* bytes */, int* counts, long long* sum) {
+  __shared__ int bins[ING_HIST_BINS];
+  __shared__ int last;
+  if (threadIdx.x < ING_HIST_BINS) bins[threadIdx.x] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * ING_BLK + threadIdx.x;
+  if (i < n) {
+    const float* p = (const float*)(pts + (size_t)i * stride);
+    const float x = p[0], y = p[1], z = p[2];
+    const float d = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(x, x), __fmul_rn(y, y)), __fmul_rn(z, z)));  // the range gate's norm (k_flt_gate)
+    if (d < (float)ING_HIST_BINS) atomicAdd(&bins[(int)floorf(d)], 1);  // d >= 0 or NaN: finite and floorf(d) < 100
+  }
+  __syncthreads();
+  if (threadIdx.x < ING_HIST_BINS && bins[threadIdx.x]) atomicAdd(counts + threadIdx.x, bins[threadIdx.x]);
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) last = atomicAdd((unsigned*)(counts + ING_HIST_BINS), 1u) == gridDim.x - 1;
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  if (threadIdx.x < ING_HIST_BINS) sum[threadIdx.x] += atomicAdd(counts + threadIdx.x, 0);  // (read where the other blocks' atomics landed)
+  if (threadIdx.x == 0) sum[ING_HIST_BINS] += 1;
 }
 
 }  // namespace apd

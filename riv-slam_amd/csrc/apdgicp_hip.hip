@@ -612,7 +612,10 @@ struct apdgicp_scan_ingest {
   DevBuf stage_cloud, desk;                                           // deskew: the staged host cloud, the output
   PinnedBuf h_scal;                                                   // mirror of scal
   int64_t n_rows = 0, n_desk = 0;
-  int64_t launches = 0, waits = 0;  // of the last run / deskew (tests/measure/bench_scan_ingest.py)
+  int64_t launches = 0, waits = 0;  // of the last run / run_polar / deskew / histogram_add (tests/measure/bench_scan_ingest.py, bench_polar_ingest.py)
+  DevBuf stage_polar[5];            // run_polar: the staged lanes of a host message (one array of structures: [0] alone)
+  DevBuf stage_hist, hist, hist_sum;  // histogram: the staged host cloud; int counts[100] + ticket; int64 sum[100] + frames (H2)
+  bool hist_live = false;           // hist / hist_sum exist and hist_sum was zeroed on the stream
   ~apdgicp_scan_ingest() {
     if (stream) (void)hipStreamSynchronize(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
@@ -5932,6 +5935,60 @@ int apdgicp_scan_ingest_run(apdgicp_scan_ingest* h, const float* xyz, int64_t n,
   });
 }
 
+// PI1 .. PI5
+int apdgicp_scan_ingest_run_polar(apdgicp_scan_ingest* h, const float* range, int64_t range_stride_bytes, const float* azimuth, int64_t azimuth_stride_bytes,
+                                  const float* elevation, int64_t elevation_stride_bytes, const float* snr, int64_t snr_stride_bytes, const float* velocity,
+                                  int64_t velocity_stride_bytes, int64_t n, int on_device, int64_t* n_out) {
+  return guarded([&]() -> int {
+    if (!h || !n_out) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    *n_out = 0;
+    const char* base[5] = {(const char*)range, (const char*)azimuth, (const char*)elevation, (const char*)snr, (const char*)velocity};
+    const int64_t stride[5] = {range_stride_bytes, azimuth_stride_bytes, elevation_stride_bytes, snr_stride_bytes, velocity_stride_bytes};
+    // (nothing of the object is touched before the arguments are good: the rows of the last good run stay readable, PI4)
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative number of targets");
+    for (int k = 0; k < 5; k++) {
+      if (n > 0 && !base[k]) return fail(APDGICP_ERR_INVALID_ARG, "a lane of the message is null");
+      if (stride[k] < 4 || stride[k] % 4) return fail(APDGICP_ERR_INVALID_ARG, "a lane stride must be a multiple of 4 bytes and >= 4");
+    }
+    if (n > ING_MAX_N) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 targets");
+    h->n_rows = 0, h->launches = h->waits = 0;
+    if (n == 0) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    if (!on_device) {
+      // (no wait, as in run)
+      const char* lo = *std::min_element(base, base + 5);
+      const char* hi = *std::max_element(base, base + 5) + 4;
+      bool one = n >= 2 && hi - lo <= stride[0];
+      for (int k = 1; k < 5; k++) one = one && stride[k] == stride[0];
+      if (one) {
+        // one array of structures (RadarTargetExtended[]: stride 76, the fields at 0 / 4 / 8 / 16 / 12): [lo, last byte) is the caller's; one copy
+        const size_t bytes = (size_t)(n - 1) * stride[0] + (size_t)(hi - lo);
+        APD_TRY(h->stage_polar[0].ensure(bytes));
+        APD_HIP(hipMemcpyAsync(h->stage_polar[0].p, lo, bytes, hipMemcpyHostToDevice, h->stream));
+        for (int k = 0; k < 5; k++) base[k] = h->stage_polar[0].as<char>() + (base[k] - lo);
+      } else {
+        for (int k = 0; k < 5; k++) {
+          const size_t bytes = (size_t)(n - 1) * stride[k] + 4;
+          DevBuf& st = h->stage_polar[k];
+          APD_TRY(st.ensure(bytes));
+          APD_HIP(hipMemcpyAsync(st.p, base[k], bytes, hipMemcpyHostToDevice, h->stream));
+          base[k] = st.as<char>();
+        }
+      }
+    }
+    APD_TRY(h->rows.ensure((size_t)n * 32));
+    APD_TRY(h->index.ensure((size_t)n * 4));
+    const PolarLanes L{base[0], base[1], base[2], base[3], base[4], stride[0], stride[1], stride[2], stride[3], stride[4]};
+    const int ni = (int)n;
+    hipLaunchKernelGGL(k_ing_polar, dim3((ni + ING_BLK - 1) / ING_BLK), dim3(ING_BLK), 0, h->stream, L, ni, h->rows.as<float4>(), h->index.as<int>());
+    APD_HIP(hipGetLastError());
+    h->launches = 1, h->waits = 0;
+    h->n_rows = n;  // PI2: no gate, nothing to wait for
+    *n_out = n;
+    return 0;
+  });
+}
+
 int apdgicp_scan_ingest_points(apdgicp_scan_ingest* h, const float** device_rows, const int32_t** device_index, int64_t* n) {
   return guarded([&]() -> int {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
@@ -6021,6 +6078,83 @@ int apdgicp_scan_ingest_synchronize(apdgicp_scan_ingest* h) {
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     APD_HIP(hipSetDevice(h->device));
     APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+// H1 .. H4
+static int ingest_hist_ensure(apdgicp_scan_ingest* h) {
+  if (h->hist_live) return 0;
+  APD_TRY(h->hist.ensure(ING_HIST_WORDS * sizeof(int)));
+  APD_TRY(h->hist_sum.ensure(ING_HIST_WORDS * sizeof(long long)));
+  APD_HIP(hipMemsetAsync(h->hist.p, 0, ING_HIST_WORDS * sizeof(int), h->stream));
+  APD_HIP(hipMemsetAsync(h->hist_sum.p, 0, ING_HIST_WORDS * sizeof(long long), h->stream));  // (the reference's vector is never zeroed, H3)
+  h->hist_live = true;
+  return 0;
+}
+
+int apdgicp_scan_ingest_histogram_add(apdgicp_scan_ingest* h, const float* xyz, int64_t n, int64_t stride_bytes, int on_device) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (n < 0) return fail(APDGICP_ERR_INVALID_ARG, "negative number of points");
+    if (n > 0 && !xyz) return fail(APDGICP_ERR_INVALID_ARG, "the cloud is null");
+    if (stride_bytes < 12 || stride_bytes % 4) return fail(APDGICP_ERR_INVALID_ARG, "stride must be a multiple of 4 bytes and >= 12");
+    if (n > ING_MAX_N) return fail(APDGICP_ERR_UNSUPPORTED, "more than 2^24 points");
+    h->launches = h->waits = 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_TRY(ingest_hist_ensure(h));
+    const char* d_in = (const char*)xyz;
+    if (n > 0 && !on_device) {
+      // (no wait, as in run)
+      const size_t bytes = (size_t)(n - 1) * stride_bytes + 12;
+      APD_TRY(h->stage_hist.ensure(bytes));
+      APD_HIP(hipMemcpyAsync(h->stage_hist.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+      d_in = h->stage_hist.as<char>();
+    }
+    const int ni = (int)n, nb = std::max(1, (ni + ING_BLK - 1) / ING_BLK);  // n = 0: one block that counts nothing and adds the frame of zeros
+    hipLaunchKernelGGL(k_ing_hist_zero, dim3(1), dim3(128), 0, h->stream, h->hist.as<int>());
+    hipLaunchKernelGGL(k_ing_hist, dim3(nb), dim3(ING_BLK), 0, h->stream, d_in, ni, (long long)stride_bytes, h->hist.as<int>(), h->hist_sum.as<long long>());
+    APD_HIP(hipGetLastError());
+    h->launches = 2, h->waits = 0;
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_histogram_last(apdgicp_scan_ingest* h, int32_t counts[100]) {
+  return guarded([&]() -> int {
+    if (!h || !counts) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    memset(counts, 0, ING_HIST_BINS * sizeof(int32_t));
+    if (!h->hist_live) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipMemcpyAsync(counts, h->hist.p, ING_HIST_BINS * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    APD_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_histogram_read(apdgicp_scan_ingest* h, int64_t sum[100], int64_t* frames) {
+  return guarded([&]() -> int {
+    if (!h || (!sum && !frames)) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    long long host[ING_HIST_WORDS];
+    memset(host, 0, sizeof(host));
+    if (h->hist_live) {
+      APD_HIP(hipSetDevice(h->device));
+      APD_HIP(hipMemcpyAsync(host, h->hist_sum.p, sizeof(host), hipMemcpyDeviceToHost, h->stream));
+      APD_HIP(hipStreamSynchronize(h->stream));
+    }
+    for (int b = 0; b < ING_HIST_BINS && sum; b++) sum[b] = host[b];
+    if (frames) *frames = host[ING_HIST_BINS];
+    return 0;
+  });
+}
+
+int apdgicp_scan_ingest_histogram_reset(apdgicp_scan_ingest* h) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    if (!h->hist_live) return 0;
+    APD_HIP(hipSetDevice(h->device));
+    APD_HIP(hipMemsetAsync(h->hist.p, 0, ING_HIST_WORDS * sizeof(int), h->stream));
+    APD_HIP(hipMemsetAsync(h->hist_sum.p, 0, ING_HIST_WORDS * sizeof(long long), h->stream));
     return 0;
   });
 }

@@ -131,6 +131,8 @@ SYMBOLS = [
     "apdgicp_scan_ingest_default_params", "apdgicp_scan_ingest_create", "apdgicp_scan_ingest_destroy", "apdgicp_scan_ingest_set_params", "apdgicp_scan_ingest_run",
     "apdgicp_scan_ingest_points", "apdgicp_scan_ingest_copy", "apdgicp_scan_ingest_deskew", "apdgicp_scan_ingest_deskewed", "apdgicp_scan_ingest_deskewed_copy",
     "apdgicp_scan_ingest_synchronize", "apdgicp_scan_ingest_stats",
+    "apdgicp_scan_ingest_run_polar", "apdgicp_scan_ingest_histogram_add", "apdgicp_scan_ingest_histogram_last", "apdgicp_scan_ingest_histogram_read",
+    "apdgicp_scan_ingest_histogram_reset",
 ]
 
 _lib = None
@@ -391,6 +393,11 @@ def load_library(path: str | None = None):
     L.apdgicp_scan_ingest_deskewed_copy.argtypes = [vp, vp, i64]
     L.apdgicp_scan_ingest_synchronize.argtypes = [vp]
     L.apdgicp_scan_ingest_stats.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_scan_ingest_run_polar.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, i32, C.POINTER(i64)]
+    L.apdgicp_scan_ingest_histogram_add.argtypes = [vp, vp, i64, i64, i32]
+    L.apdgicp_scan_ingest_histogram_last.argtypes = [vp, vp]
+    L.apdgicp_scan_ingest_histogram_read.argtypes = [vp, vp, C.POINTER(i64)]
+    L.apdgicp_scan_ingest_histogram_reset.argtypes = [vp]
     if path is None:
         _lib = L
     return L

@@ -3,6 +3,8 @@
 {x, y, z, intensity, doppler} cloud the ego-velocity estimate reads (:667-697, :497-506), and the IMU deskew with the base-link
 transform between that estimate and distance_filter (:792-810, :914-975).  Host side of include/apdgicp_hip.h's apdgicp_scan_ingest_*
 entry points; the semantics are I1 .. I7 there.  preprocess_scan() is the whole callback with every per-point step on the device.
+run_polar() is the head of cloud_callback_scan (:324-340, PI1 .. PI5: a RadarScanExtended of range / azimuth / elevation targets),
+preprocess_polar_scan() that callback, and histogram_*() the distance histogram that ends all three (:451-461, H1 .. H4).
 """
 from __future__ import annotations
 
@@ -14,6 +16,9 @@ from .registration import DevicePoints, _check, _cloud_arg, _ptr, load_library
 
 FLAG_XF_LINEAR_CHAIN = 2
 MAX_POINTS = 1 << 24
+HISTOGRAM_BINS = 100
+POLAR_LANES = ("range", "azimuth", "elevation", "snr", "velocity")                      # the order of apdgicp_scan_ingest_run_polar's lanes
+TARGET_COLUMN = dict(range=0, azimuth=1, elevation=2, velocity=3, snr=4)                # their places among the 19 floats of a RadarTargetExtended
 
 
 class ScanIngestParams(C.Structure):
@@ -125,6 +130,77 @@ class ScanIngest:
         self.n = n_out.value
         return self.n
 
+    def run_polar(self, targets=None, **lanes) -> int:
+        """One msgs_radar/RadarScanExtended (PI1 .. PI5).  targets: the RadarTargetExtended[] as [n, 19] float32 (numpy, a torch CPU / CUDA
+        tensor; any [n, >= 5] array with range, azimuth, elevation, velocity, snr in columns 0 .. 4 is read in place), a numpy structured
+        array with those five float32 fields, or DevicePoints of such records -- or, instead of `targets`, the five lanes by keyword
+        (range=, azimuth=, elevation=, snr=, velocity=: numpy / tensor [n], strided views likewise, or (device pointer, stride_bytes)
+        together with n=).  Every target becomes a row; does not wait.  Returns the number of rows (= n)."""
+        n = lanes.pop("n", None)
+        if targets is not None:
+            if lanes:
+                raise TypeError("either `targets` or the five lanes by keyword")
+            if isinstance(targets, DevicePoints):
+                n = targets.n
+                lanes = {k: (targets.ptr + 4 * TARGET_COLUMN[k], targets.stride_bytes) for k in POLAR_LANES}
+            elif getattr(getattr(targets, "dtype", None), "names", None):
+                lanes = {k: targets[k] for k in POLAR_LANES}
+            else:
+                if not hasattr(targets, "data_ptr"):
+                    targets = np.asarray(targets)
+                    if targets.dtype != np.float32:
+                        targets = np.ascontiguousarray(targets, dtype=np.float32)
+                if len(targets.shape) != 2 or targets.shape[1] < 5:
+                    raise ValueError("targets must be [n, >= 5]")
+                lanes = {k: targets[:, TARGET_COLUMN[k]] for k in POLAR_LANES}
+        if sorted(lanes) != sorted(POLAR_LANES):
+            raise TypeError("run_polar needs range, azimuth, elevation, snr and velocity")
+        if n is None:
+            n = next(int(v.shape[0]) for v in lanes.values() if not isinstance(v, tuple))
+        args = [_lane_arg(lanes[k], n) for k in POLAR_LANES]
+        if n and len({a[2] for a in args}) != 1:
+            raise ValueError("the five lanes must all be on the device or all on the host")
+        dev = args[0][2]
+        if dev:
+            _wait_for_producer(*(a[3] for a in args))
+        flat = []
+        for ptr, stride, _, _ in args:
+            flat += [ptr, stride if n else 4]
+        n_out = C.c_int64()
+        _check(self.L.apdgicp_scan_ingest_run_polar(self.h, *flat, n, dev, C.byref(n_out)))
+        self.n = n_out.value
+        return self.n
+
+    def histogram_add(self, cloud) -> int:
+        """one frame of the distance histogram (H1 .. H4) from a cloud ([n, >= 3] float32: numpy, a torch CPU / CUDA tensor, DevicePoints such
+        as ScanFilter.points()); an empty cloud is a frame of zeros.  Does not wait; returns n."""
+        ptr, n, stride, dev, keep = _cloud_arg(_empty_as_numpy(cloud, 3))
+        if dev:
+            _wait_for_producer(keep)
+        _check(self.L.apdgicp_scan_ingest_histogram_add(self.h, ptr, n, stride if n else 12, dev))
+        return n
+
+    def histogram_last(self):
+        """the [100] int32 counts of the last histogram_add (bin b: floor(distance) == b); waits"""
+        out = np.zeros(HISTOGRAM_BINS, dtype=np.int32)
+        _check(self.L.apdgicp_scan_ingest_histogram_last(self.h, _ptr(out)))
+        return out
+
+    def histogram_read(self):
+        """(the [100] int64 sum of every frame since the last reset, the number of frames); waits"""
+        out, frames = np.zeros(HISTOGRAM_BINS, dtype=np.int64), C.c_int64()
+        _check(self.L.apdgicp_scan_ingest_histogram_read(self.h, _ptr(out), C.byref(frames)))
+        return out, frames.value
+
+    def histogram_reset(self):
+        _check(self.L.apdgicp_scan_ingest_histogram_reset(self.h))
+
+    def point_distribution(self):
+        """the point_distribution command (preprocessing_nodelet.cpp:1009-1021): the sum of the frames divided by their number, element-wise,
+        as integer division; zeros without a frame"""
+        total, frames = self.histogram_read()
+        return total // frames if frames else total
+
     def points(self) -> DevicePoints:
         """the rows of the last run in device memory ({x, y, z, intensity, doppler, 0, 0, 0}, 32-byte stride), valid until the next run:
         what EgoVelocityEstimator.run, ScanFilter.run, DBSCAN.run and setInputSource accept"""
@@ -183,7 +259,7 @@ class ScanIngest:
         return out
 
     def stats(self) -> dict:
-        """kernel launches and host waits of the last run or deskew"""
+        """kernel launches and host waits of the last run, run_polar, deskew or histogram_add"""
         a, b = C.c_int64(), C.c_int64()
         _check(self.L.apdgicp_scan_ingest_stats(self.h, C.byref(a), C.byref(b)))
         return dict(launches=a.value, waits=b.value)
@@ -203,12 +279,13 @@ def select_imu(stamps, scan_stamp) -> tuple[int, int]:
 
 
 def preprocess_scan(ingest: ScanIngest, estimator, scan_filter, xyz, intensity, doppler, registration=None, enable_dynamic_object_removal: bool = False,
-                    ang_vel=None, scan_period: float = 0.1, T=None, pre_transform=None, words=None, seed: int = 0) -> dict:
+                    ang_vel=None, scan_period: float = 0.1, T=None, pre_transform=None, words=None, seed: int = 0, histogram: bool = False) -> dict:
     """cloud_callback from the message to the published cloud (preprocessing_nodelet.cpp:667-830) and, with `registration`, the odometry's
     setInputSource: ingest -> EgoVelocityEstimator.run on the rows -> its inlier cloud (enable_dynamic_object_removal, :775-786) or the
     rows -> deskew + base-link transform -> ScanFilter.run -> setInputSource.  The message crosses to the device once (or is there
     already); no cloud visits the host before the filtered scan.  An empty source cloud returns before the deskew (:788-790).
-    Returns dict(n_ingest, ego = the estimate, n_source, n_filtered); nothing is set when the filtered scan is empty."""
+    Returns dict(n_ingest, ego = the estimate, n_source, n_filtered); nothing is set when the filtered scan is empty.  histogram = True:
+    the filtered scan also becomes a frame of the distance histogram (:818-828) on `ingest`."""
     n_in = ingest.run(xyz, intensity, doppler, pre_transform=pre_transform)
     rows = ingest.points()
     ego = estimator.run(rows if n_in else np.zeros((0, 5), dtype=np.float32), words=words, seed=seed)
@@ -216,9 +293,38 @@ def preprocess_scan(ingest: ScanIngest, estimator, scan_filter, xyz, intensity, 
     out = dict(n_ingest=n_in, ego=ego, n_source=source.n, n_filtered=0)
     if source.n == 0:
         return out
+    _callback_tail(ingest, scan_filter, source, registration, ang_vel, scan_period, T, histogram, out)
+    return out
+
+
+def _callback_tail(ingest, scan_filter, source, registration, ang_vel, scan_period, T, histogram, out):
+    """what the three callbacks share behind their source cloud: deskew + base-link transform, the scan filter, the distance histogram of
+    the filtered scan (empty or not, as the reference pushes one), setInputSource"""
     ingest.deskew(source, ang_vel=ang_vel, scan_period=scan_period, T=T)
     ingest.synchronize()  # the scan filter runs on a stream of its own
     out["n_filtered"] = scan_filter.run(ingest.deskewed())
+    if histogram:
+        ingest.histogram_add(scan_filter.points() if out["n_filtered"] else np.zeros((0, 3), dtype=np.float32))
     if out["n_filtered"] and registration is not None:
         registration.setInputSource(scan_filter.points())
+
+
+def preprocess_polar_scan(ingest: ScanIngest, estimator, scan_filter, targets, registration=None, ang_vel=None, scan_period: float = 0.1, T=None, words=None,
+                          seed: int = 0, histogram: bool = True) -> dict:
+    """cloud_callback_scan from the message to the published cloud (preprocessing_nodelet.cpp:324-464) and, with `registration`, the
+    odometry's setInputSource: run_polar -> EgoVelocityEstimator.run on the rows -> ALWAYS its inlier cloud (:416-420) -> deskew +
+    base-link transform -> ScanFilter.run -> the distance histogram of the filtered scan (:451-461) -> setInputSource.  `targets`: what
+    ScanIngest.run_polar accepts.  A failed estimate or an empty inlier cloud returns before the deskew (:423-425).  The outlier cloud
+    stays where EgoVelocityEstimator.outliers() leaves it for the RADIUS filter and DBSCAN.  Returns the dict of preprocess_scan plus
+    histogram: whether a frame was added."""
+    n_in = ingest.run_polar(targets)
+    rows = ingest.points()
+    ingest.synchronize()  # run_polar does not wait (PI2), and the estimator runs on a stream of its own
+    ego = estimator.run(rows if n_in else np.zeros((0, 5), dtype=np.float32), words=words, seed=seed)
+    source = estimator.inliers()
+    out = dict(n_ingest=n_in, ego=ego, n_source=source.n, n_filtered=0, histogram=False)
+    if not ego.success or source.n == 0:
+        return out
+    _callback_tail(ingest, scan_filter, source, registration, ang_vel, scan_period, T, histogram, out)
+    out["histogram"] = bool(histogram)
     return out
