@@ -22,6 +22,7 @@
 #include "apd_ndt_batch.hpp"
 #include "apd_icp.hpp"
 #include "apd_icp_batch.hpp"
+#include "apd_gicp_mp.hpp"
 #include "apd_dbscan.hpp"
 #include "apd_ingest.hpp"
 #include "apd_approx_voxel.hpp"
@@ -256,9 +257,35 @@ struct IcState {
   PinnedBuf h_rec;             // mirror of rec: one IcpRecord
 };
 
+// apdgicp_set_gicp_mp: the queries, the rows of the last linearize (counts, offsets and keys in buffers of its OWN, so that a Q call between two
+// linearizes changes nothing here), the fused distributions, the block rows and the trace of the last align (include/apdgicp_hip.h,
+// MP1 .. MP11).  The Hessian of the last linearize is the handle's (apdgicp_handle::final_H).
+struct MpState {
+  apdgicp_gicp_mp_params prm{1, 0, 0.5};
+  bool have = false;           // cnt / pos / bsum / keys / fused describe source points have_src_gen (n_have of them) against target points have_tgt_gen
+  uint64_t have_src_gen = 0, have_tgt_gen = 0;
+  int n_have = 0;
+  int64_t total = 0;           // entries of all rows of that linearize
+  uint64_t inv_tgt_gen = 0;    // inv_t: the inverse of the permutation of target points inv_tgt_gen, inv_n entries
+  int inv_n = 0;
+  int state = APDGICP_GICP_MP_NOT_CONVERGED;
+  int64_t launches = 0, waits = 0;  // of the last align
+  std::vector<double> tr_pose, tr_cost, tr_delta;  // the trace of the last align: 16 / 1 / 6 doubles per iteration
+  std::vector<int64_t> tr_n;
+  DevBuf q, cnt, pos, bsum, visit, keys, inv_t, fused, part, out, T, tot;
+  // apdgicp_gicp_mp_set_profiling: events at the phase boundaries of a linearize (tests/measure/bench_gicp_mp.py), read behind its last wait
+  bool profiling = false;
+  hipEvent_t ev[8] = {};
+  double phase_ms[6] = {0, 0, 0, 0, 0, 0};  // transform, count (+ mask, total), scan, fill, row sort, per-point kernel (+ sums)
+  ~MpState() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 // Which pipeline a handle runs: its own APD-GICP / plain GICP kernels, or one of the modes switched on through apdgicp_[batch_]set_*.
 // One value per handle, written by set_mode() alone ("Mode transitions").
-enum class Mode { APD, VGICP, VGICP_CUDA, NDT, ICP };
+enum class Mode { APD, VGICP, VGICP_CUDA, NDT, ICP, GICP_MP };
 
 struct apdgicp_handle {
   Engine eng;   // declared first, so destroyed last: its stream still exists while the members below free their buffers
@@ -266,9 +293,10 @@ struct apdgicp_handle {
   VcState vc;   // (likewise)
   NdState nd;   // (likewise)
   IcState ic;   // (likewise)
+  MpState mp;   // (likewise)
   VoxSortScratch sort;  // (likewise) the scratch of a voxel-map build of whichever voxel mode is on
   FrozenLin lin;        // (likewise) the frozen state of the last linearize of whichever voxel mode is on
-  double final_H[36];   // FAST_VGICP_CUDA and NDT: the Hessian of the last align in the mode, on the host (identity until then, and again when either is entered)
+  double final_H[36];   // FAST_VGICP_CUDA and NDT: the Hessian of the last align in the mode, on the host (identity until then, and again when either is entered); FastGICPMultiPoints: of the last linearize
   Mode mode = Mode::APD;
   apdgicp_handle() { reset_final_H(); }
   void reset_final_H() {
@@ -631,7 +659,7 @@ const char* cloud_name(int which) { return which == kSrc ? "source" : "target"; 
 struct ModeText {
   const char *name, *setter;
 };
-constexpr ModeText kModeText[] = {{"APD-GICP", ""}, {"voxelized GICP", "set_vgicp"}, {"FAST_VGICP_CUDA", "set_vgicp_cuda"}, {"NDT", "set_ndt"}, {"point-to-point ICP", "set_icp"}};
+constexpr ModeText kModeText[] = {{"APD-GICP", ""}, {"voxelized GICP", "set_vgicp"}, {"FAST_VGICP_CUDA", "set_vgicp_cuda"}, {"NDT", "set_ndt"}, {"point-to-point ICP", "set_icp"}, {"FastGICPMultiPoints", "set_gicp_mp"}};
 // a getter of mode m on a handle that is in another one: "NDT is off (apdgicp_batch_set_ndt)"
 int mode_is_off(Mode m, bool batch) {
   const ModeText& t = kModeText[(int)m];
@@ -1533,10 +1561,212 @@ int ic_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   return 0;
 }
 
+// ---- FastGICPMultiPoints (include/apdgicp_hip.h MP1 .. MP11; kernels: apd_gicp_mp.hpp over apd_search.hpp)
+int check_gicp_mp_params(const apdgicp_gicp_mp_params* p) {
+  if (!p) return 0;
+  if (!std::isfinite(p->neighbor_search_radius) || !(p->neighbor_search_radius > 0.0))
+    return fail(APDGICP_ERR_INVALID_ARG, "FastGICPMultiPoints: neighbor_search_radius must be finite and positive");
+  return 0;
+}
+
+// MP1: the regularisations whose result does not depend on the scale of the scatter matrix
+int mp_check_regularization(const apdgicp_handle* h) {
+  const int r = h->eng.params.regularization;
+  if (r != APDGICP_REG_PLANE && r != APDGICP_REG_NORMALIZED_MIN_EIG)
+    return fail(APDGICP_ERR_UNSUPPORTED, "FastGICPMultiPoints: only PLANE and NORMALIZED_MIN_EIG are offered (MIN_EIG and FROBENIUS act on the undivided scatter matrix there, NONE aborts)");
+  return 0;
+}
+
+// both clouds sorted, both covariances there, the target's inverse permutation
+int mp_prepare(apdgicp_handle* h) {
+  Engine& e = h->eng;
+  MpState& v = h->mp;
+  APD_TRY(mp_check_regularization(h));
+  if (e.clouds.size() < 2 || e.clouds[kSrc].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "source cloud is not set");
+  if (e.clouds[kTgt].n <= 0) return fail(APDGICP_ERR_NO_INPUT, "target cloud is not set");
+  for (int which : {kSrc, kTgt})
+    if (e.clouds[which].n < e.params.k_correspondences)
+      return fail(APDGICP_ERR_TOO_FEW_POINTS, std::string("FastGICPMultiPoints: the ") + cloud_name(which) + " cloud has fewer points than k_correspondences");
+  APD_TRY(ensure_pair(h));
+  APD_HIP(hipSetDevice(e.device));
+  const Engine::Cloud& t = e.clouds[kTgt];
+  if (!v.inv_t.p || v.inv_tgt_gen != h->cloud_gen[kTgt] || v.inv_n != t.n || (size_t)t.n * 4 > v.inv_t.cap) {
+    v.inv_n = 0;
+    APD_TRY(v.inv_t.ensure((size_t)t.n * 4));
+    hipLaunchKernelGGL(k_vg_inverse_perm, dim3((unsigned)((t.n + 255) / 256)), dim3(256), 0, e.stream, t.perm.as<int>(), t.n, v.inv_t.as<int>());
+    APD_HIP(hipGetLastError());
+    v.inv_tgt_gen = h->cloud_gen[kTgt], v.inv_n = t.n;
+    v.launches += 1;
+  }
+  return 0;
+}
+
+// linearize (MP2 .. MP5) at T (column-major 4x4): two waits, one behind the total that sizes the rows, one behind the sums
+int mp_linearize(apdgicp_handle* h, const double* T16, double* H, double* b, double* cost, int* matched) {
+  APD_TRY(mp_prepare(h));
+  Engine& e = h->eng;
+  MpState& v = h->mp;
+  roctx_range rr("apdgicp:gicp_mp_linearize");
+  const Engine::Cloud &s = e.clouds[kSrc], &t = e.clouds[kTgt];
+  const int n = s.n, nqb = (n + SQ_BLK - 1) / SQ_BLK, nsb = (n + SCAN_BLK - 1) / SCAN_BLK, npb = (n + MP_BLK - 1) / MP_BLK;
+  const int xf = (e.params.flags & APDGICP_FLAG_XF_LINEAR_CHAIN) ? 1 : 0;
+  const double radius = v.prm.neighbor_search_radius;
+  const float r2 = (float)(radius * radius);  // Q4
+  v.have = false;
+  APD_TRY(v.q.ensure((size_t)n * sizeof(float4)));
+  APD_TRY(v.cnt.ensure((size_t)n * sizeof(int)));
+  APD_TRY(v.pos.ensure((size_t)n * sizeof(int)));
+  APD_TRY(v.bsum.ensure(((size_t)nsb + 1) * sizeof(int)));
+  APD_TRY(v.visit.ensure((size_t)nqb * sizeof(int)));
+  APD_TRY(v.fused.ensure((size_t)n * MP_FUSED * sizeof(double)));
+  APD_TRY(v.part.ensure((size_t)npb * MP_R * sizeof(double)));
+  APD_TRY(v.out.ensure(64 * sizeof(double)));
+  APD_TRY(v.T.ensure(12 * sizeof(double)));
+  APD_TRY(v.tot.ensure(sizeof(long long)));
+  double T12[12];
+  colmajor_to_rows12(T16, T12);
+  APD_HIP(hipMemcpyAsync(v.T.p, T12, sizeof(T12), hipMemcpyHostToDevice, e.stream));
+  const SearchTarget tg{t.pts.as<float4>(), t.perm.as<int>(), t.cbox.as<Box>(), t.gbox.as<Box>(), t.n, 0};
+  auto mark = [&](int k) -> int {  // (profiling only: an event behind what has been enqueued so far)
+    if (!v.profiling) return 0;
+    if (!v.ev[k]) APD_HIP(hipEventCreate(&v.ev[k]));
+    APD_HIP(hipEventRecord(v.ev[k], e.stream));
+    return 0;
+  };
+  APD_TRY(mark(0));
+  hipLaunchKernelGGL(k_mp_transform, dim3((unsigned)npb), dim3(MP_BLK), 0, e.stream, s.pts.as<float4>(), n, v.T.as<double>(), xf, v.q.as<float4>());
+  APD_TRY(mark(1));
+  hipLaunchKernelGGL(k_radius_count, dim3((unsigned)nqb), dim3(SQ_BLK), 0, e.stream, tg, v.q.as<float4>(), s.perm.as<int>(), n, r2, v.cnt.as<int>(), v.visit.as<int>());
+  hipLaunchKernelGGL(k_mp_mask, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e.stream, v.q.as<float4>(), s.perm.as<int>(), n, v.cnt.as<int>());
+  hipLaunchKernelGGL(k_mp_total, dim3(1), dim3(MP_BLK), 0, e.stream, v.cnt.as<int>(), n, v.tot.as<long long>());
+  APD_TRY(mark(2));
+  hipLaunchKernelGGL(k_radius_scan, dim3((unsigned)nsb), dim3(SCAN_BLK), 0, e.stream, v.cnt.as<int>(), n, v.pos.as<int>(), v.bsum.as<int>());
+  hipLaunchKernelGGL(k_scan_bsum, dim3(1), dim3(SCAN_BLK), 0, e.stream, v.bsum.as<int>(), nsb, v.bsum.as<int>() + nsb);
+  APD_HIP(hipGetLastError());
+  APD_TRY(mark(3));
+  APD_HIP(hipMemcpyAsync(e.h_probe.p, v.tot.p, sizeof(long long), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  v.launches += 6, v.waits += 1;
+  const long long total = *e.h_probe.as<long long>();
+  if (total < 0 || total > 0x7fffffffll) return fail(APDGICP_ERR_UNSUPPORTED, "FastGICPMultiPoints: more than 2^31 - 1 hits in all (" + std::to_string(total) + ")");
+  if (total > 0) APD_TRY(v.keys.ensure((size_t)total * sizeof(unsigned long long)));
+  APD_TRY(mark(4));
+  if (total > 0) {
+    hipLaunchKernelGGL(k_radius_fill, dim3((unsigned)nqb), dim3(SQ_BLK), 0, e.stream, tg, v.q.as<float4>(), s.perm.as<int>(), n, r2, v.cnt.as<int>(), v.pos.as<int>(),
+                       v.bsum.as<int>(), v.keys.as<unsigned long long>());
+    APD_TRY(mark(5));
+    hipLaunchKernelGGL(k_radius_sort_rows, dim3((unsigned)n), dim3(SQ_SORT_BLK), 0, e.stream, v.cnt.as<int>(), v.pos.as<int>(), v.bsum.as<int>(),
+                       v.keys.as<unsigned long long>());
+    v.launches += 2;
+  } else {
+    APD_TRY(mark(5));
+  }
+  APD_TRY(mark(6));
+  const MpCloud S{s.pts.as<float4>(), s.cov.as<double>(), s.perm.as<int>(), n, 0}, Tg{t.opts.as<float4>(), t.cov.as<double>(), v.inv_t.as<int>(), t.n, 0};
+  hipLaunchKernelGGL(k_mp_point, dim3((unsigned)npb), dim3(MP_BLK), 0, e.stream, S, Tg, v.keys.as<unsigned long long>(), v.cnt.as<int>(), v.pos.as<int>(), v.bsum.as<int>(),
+                     v.T.as<double>(), radius, v.fused.as<double>(), v.part.as<double>());
+  hipLaunchKernelGGL(k_icp_sums, dim3(1), dim3(64), 0, e.stream, v.part.as<double>(), npb, (int)MP_R, v.out.as<double>());
+  APD_HIP(hipGetLastError());
+  APD_TRY(mark(7));
+  APD_HIP(hipMemcpyAsync(e.h_probe.p, v.out.p, MP_R * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+  APD_HIP(hipStreamSynchronize(e.stream));
+  v.launches += 2, v.waits += 1;
+  if (v.profiling) {
+    const int from[6] = {0, 1, 2, 4, 5, 6}, to[6] = {1, 2, 3, 5, 6, 7};
+    for (int k = 0; k < 6; k++) {
+      float ms = 0.f;
+      APD_HIP(hipEventElapsedTime(&ms, v.ev[from[k]], v.ev[to[k]]));
+      v.phase_ms[k] = (double)ms;
+    }
+  }
+  const double* o = e.h_probe.as<double>();
+  int at = 0;
+  for (int a = 0; a < 6; a++)
+    for (int c = a; c < 6; c++, at++) h->final_H[a + 6 * c] = h->final_H[c + 6 * a] = o[at];  // MP9: the last H
+  if (H && b) {
+    memcpy(H, h->final_H, 36 * sizeof(double));
+    memcpy(b, o + 21, 6 * sizeof(double));
+  }
+  if (cost) *cost = o[27];
+  if (matched) *matched = (int)std::min(o[28], 2147483647.0);
+  v.have = true, v.have_src_gen = h->cloud_gen[kSrc], v.have_tgt_gen = h->cloud_gen[kTgt], v.n_have = n, v.total = total;
+  return 0;
+}
+
+// MP6 / MP7: plain Gauss-Newton on the host over mp_linearize
+int mp_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
+  Engine& e = h->eng;
+  MpState& v = h->mp;
+  const apdgicp_params& p = e.params;
+  v.launches = v.waits = 0;
+  APD_TRY(mp_prepare(h));
+  float g[16];
+  if (guess) memcpy(g, guess, sizeof(g));
+  else identity16(g);
+  Rigid x;  // MP6: the guess's blocks, widened
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) x.m[4 * i + j] = (double)g[i + 4 * j];
+  v.tr_pose.clear(), v.tr_cost.clear(), v.tr_delta.clear(), v.tr_n.clear();
+  v.state = APDGICP_GICP_MP_NOT_CONVERGED;
+  bool converged = false;
+  int iterations = 0, n_lin = 0, matched = 0;
+  double cost = 0.0;
+  for (int it = 0; it < p.max_iterations; it++) {  // MPI:92
+    iterations = it;
+    double T16[16], H[36], gr[6], ng[6], d[6] = {0, 0, 0, 0, 0, 0};
+    rigid_to_colmajor(x, T16);
+    APD_TRY(mp_linearize(h, T16, H, gr, &cost, &matched));
+    n_lin++;
+    v.tr_pose.insert(v.tr_pose.end(), T16, T16 + 16), v.tr_cost.push_back(cost), v.tr_n.push_back(matched);
+    if (matched < 2) {  // MP7: H has rank <= 3 per row
+      v.state = APDGICP_GICP_MP_TOO_FEW_ROWS;
+      v.tr_delta.insert(v.tr_delta.end(), d, d + 6);
+      break;
+    }
+    for (int q = 0; q < 6; q++) ng[q] = -gr[q];
+    solve6_spd(H, 0.0, ng, d);  // H d = g (MPI:99)
+    v.tr_delta.insert(v.tr_delta.end(), d, d + 6);
+    bool finite = true;
+    for (int q = 0; q < 6; q++) finite = finite && std::isfinite(d[q]);
+    if (!finite) {
+      v.state = APDGICP_GICP_MP_SINGULAR;
+      break;
+    }
+    const double nr[6] = {-d[0], -d[1], -d[2], 0.0, 0.0, 0.0};
+    const Rigid E = make_delta(nr);  // MPI:101-102: R <- exp(-d_r) R, t <- t - d_t (the translation is not rotated)
+    Rigid y = x;
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) y.m[4 * i + j] = (E.m[4 * i] * x.m[j] + E.m[4 * i + 1] * x.m[4 + j]) + E.m[4 * i + 2] * x.m[8 + j];
+      y.m[4 * i + 3] = x.m[4 * i + 3] - d[3 + i];
+    }
+    x = y;
+    if (is_converged(make_delta(d), p.rotation_epsilon, p.transformation_epsilon)) {  // MPI:104, 118-127
+      converged = true;
+      v.state = APDGICP_GICP_MP_CONVERGED;
+      break;
+    }
+  }
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 4; j++) out->T[i + 4 * j] = (float)x.m[4 * i + j];
+  out->T[3] = out->T[7] = out->T[11] = 0.f;
+  out->T[15] = 1.f;
+  out->final_cost = cost;
+  out->converged = converged;
+  out->iterations = iterations;
+  out->n_linearize = n_lin;
+  out->n_compute_error = 0;
+  out->lm_failed = 0;
+  out->n_matched = matched;
+  h->trace_from_host_loop = true;  // (apdgicp_get_trace: this align left no optimiser trace)
+  h->tr_lambda.clear(), h->tr_rho.clear(), h->tr_y0.clear(), h->tr_yi.clear(), h->tr_dnorm.clear(), h->tr_poses.clear();
+  return 0;
+}
+
 // the align of the mode that is on (APD has two loops of its own: apdgicp_align, apdgicp_align_host_loop)
 int mode_align(apdgicp_handle* h, const float guess[16], apdgicp_result* out) {
   switch (h->mode) {
     case Mode::ICP: return ic_align(h, guess, out);
+    case Mode::GICP_MP: return mp_align(h, guess, out);
     case Mode::NDT: return nd_align(h, guess, out);
     case Mode::VGICP: return vg_align(h, guess, out);
     case Mode::VGICP_CUDA: return vc_align(h, guess, out);
@@ -2247,7 +2477,12 @@ void set_mode(apdgicp_handle* h, Mode to) {
   h->have_corr = false;  // (the APD kernels' correspondences are those of their own last linearize, and none is left)
   if (from == Mode::ICP || to == Mode::ICP) h->pair_ready = false;  // (the pair of the other side was set up with / without covariances)
   h->lin.have = false;  // (the one frozen state is the mode's that made it)
-  if (to == Mode::VGICP_CUDA || to == Mode::NDT) h->reset_final_H();
+  if (to == Mode::VGICP_CUDA || to == Mode::NDT || to == Mode::GICP_MP) h->reset_final_H();
+  if (from == Mode::GICP_MP || to == Mode::GICP_MP) {  // (what the mode's getters read is one visit's)
+    MpState& v = h->mp;
+    v.have = false, v.state = APDGICP_GICP_MP_NOT_CONVERGED, v.launches = v.waits = 0;
+    v.tr_pose.clear(), v.tr_cost.clear(), v.tr_delta.clear(), v.tr_n.clear();
+  }
   h->mode = to;  // (apdgicp_set_icp forgets the last estimate with every enabling call, entering or not)
 }
 
@@ -2479,6 +2714,7 @@ int apdgicp_linearize(apdgicp_handle* h, const double T[16], double H[36], doubl
     if (!h || !T) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     switch (h->mode) {
       case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
+      case Mode::GICP_MP: return mp_linearize(h, T, H, b, cost, nullptr);
       case Mode::NDT: return nd_linearize(h, T, H, b, cost, nullptr);
       case Mode::VGICP: return vg_linearize(h, T, H, b, cost, nullptr);
       case Mode::VGICP_CUDA: return vc_linearize(h, T, H, b, cost, nullptr);
@@ -2496,6 +2732,7 @@ int apdgicp_compute_error(apdgicp_handle* h, const double T[16], double* cost) {
     if (!h || !T || !cost) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
     switch (h->mode) {
       case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, kIcNoLinearize);
+      case Mode::GICP_MP: return fail(APDGICP_ERR_UNSUPPORTED, "FastGICPMultiPoints has no compute_error: its loop is plain Gauss-Newton (MP7)");
       case Mode::NDT: return nd_error(h, T, cost);
       case Mode::VGICP: return vg_error(h, T, cost);
       case Mode::VGICP_CUDA: return vc_error(h, T, cost);
@@ -2511,6 +2748,7 @@ int apdgicp_get_correspondences(apdgicp_handle* h, int32_t* corr, float* sq, int
     if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
     switch (h->mode) {
       case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP keeps its own correspondences: apdgicp_icp_get_correspondences");
+      case Mode::GICP_MP: return fail(APDGICP_ERR_UNSUPPORTED, "FastGICPMultiPoints has a row of correspondences per point: apdgicp_gicp_mp_get_rows");
       case Mode::NDT: return fail(APDGICP_ERR_UNSUPPORTED, "NDT has no point correspondences: apdgicp_ndt_get_correspondences");
       case Mode::VGICP: return fail(APDGICP_ERR_UNSUPPORTED, "voxelized GICP has no point correspondences: apdgicp_vgicp_get_correspondences");
       case Mode::VGICP_CUDA: return fail(APDGICP_ERR_UNSUPPORTED, "FAST_VGICP_CUDA has no point correspondences: apdgicp_vgicp_cuda_get_correspondences");
@@ -2904,6 +3142,152 @@ int apdgicp_icp_debug_counts(apdgicp_handle* h, int64_t* launches, int64_t* wait
   return 0;
 }
 
+// ------------------------------------------------------------------------------------ FastGICPMultiPoints
+void apdgicp_gicp_mp_default_params(apdgicp_gicp_mp_params* p) {
+  if (!p) return;
+  p->enable = 1;
+  p->reserved = 0;
+  p->neighbor_search_radius = 0.5;  // MPI:35
+}
+
+int apdgicp_set_gicp_mp(apdgicp_handle* h, const apdgicp_gicp_mp_params* p) {
+  APD_TRY(check_gicp_mp_params(p));  // (before the handle: what can be said about the parameters alone)
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  MpState& v = h->mp;
+  if (!p || !p->enable) {  // (a no-op while another mode is on)
+    if (p) v.prm = *p;
+    if (h->mode == Mode::GICP_MP) set_mode(h, Mode::APD);
+    return 0;
+  }
+  APD_TRY(mp_check_regularization(h));  // MP1: refused with nothing changed
+  if (p->neighbor_search_radius != v.prm.neighbor_search_radius) v.have = false;
+  v.prm = *p;
+  set_mode(h, Mode::GICP_MP);
+  return 0;
+}
+
+int apdgicp_get_gicp_mp(const apdgicp_handle* h, apdgicp_gicp_mp_params* p, int* enabled) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (p) {
+    *p = h->mp.prm;
+    p->enable = h->mode == Mode::GICP_MP ? 1 : 0;
+  }
+  if (enabled) *enabled = h->mode == Mode::GICP_MP ? 1 : 0;
+  return 0;
+}
+
+// the last linearize must still describe the clouds the handle holds
+static int mp_check_have(apdgicp_handle* h, int64_t n) {
+  const MpState& v = h->mp;
+  if (h->mode != Mode::GICP_MP) return mode_is_off(Mode::GICP_MP, false);
+  if (!v.have || v.have_src_gen != h->cloud_gen[kSrc] || v.have_tgt_gen != h->cloud_gen[kTgt] || h->eng.clouds[kSrc].n != v.n_have)
+    return fail(APDGICP_ERR_NO_INPUT, "no linearize of the clouds the handle holds now");
+  if (n != v.n_have) return fail(APDGICP_ERR_INVALID_ARG, "n does not match the source size");
+  return 0;
+}
+
+int apdgicp_gicp_mp_get_rows(apdgicp_handle* h, int64_t* row_start, int64_t n, int64_t* total) {
+  return guarded([&]() -> int {
+    if (!h || !row_start || !total) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    APD_TRY(mp_check_have(h, n));
+    Engine& e = h->eng;
+    std::vector<int> cnt((size_t)n);
+    APD_HIP(hipSetDevice(e.device));
+    APD_HIP(hipMemcpyAsync(cnt.data(), h->mp.cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    int64_t sum = 0;
+    for (int64_t i = 0; i < n; i++) row_start[i] = sum, sum += cnt[(size_t)i];
+    row_start[n] = sum;
+    if (sum != h->mp.total) return fail(APDGICP_ERR_INTERNAL, "FastGICPMultiPoints: inconsistent row lengths");
+    *total = sum;
+    return 0;
+  });
+}
+
+int apdgicp_gicp_mp_get_row_entries(apdgicp_handle* h, int32_t* index, float* sq_dist) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    APD_TRY(mp_check_have(h, h->mp.n_have));
+    const MpState& v = h->mp;
+    if (v.total == 0) return 0;
+    if (!index || !sq_dist) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+    Engine& e = h->eng;
+    APD_HIP(hipSetDevice(e.device));
+    std::vector<unsigned long long> keys((size_t)v.total);  // (the rows lie one behind the other in the caller's source order)
+    APD_HIP(hipMemcpyAsync(keys.data(), v.keys.p, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (size_t i = 0; i < keys.size(); i++) {
+      const uint32_t bits = (uint32_t)(keys[i] >> 32);
+      index[i] = (int32_t)(uint32_t)keys[i];
+      memcpy(&sq_dist[i], &bits, 4);
+    }
+    return 0;
+  });
+}
+
+int apdgicp_gicp_mp_get_fused(apdgicp_handle* h, double* sum_w, double* mean_B, double* cov_B, int64_t n) {
+  return guarded([&]() -> int {
+    if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+    APD_TRY(mp_check_have(h, n));
+    Engine& e = h->eng;
+    APD_HIP(hipSetDevice(e.device));
+    std::vector<double> f((size_t)n * MP_FUSED);
+    APD_HIP(hipMemcpyAsync(f.data(), h->mp.fused.p, f.size() * sizeof(double), hipMemcpyDeviceToHost, e.stream));
+    APD_HIP(hipStreamSynchronize(e.stream));
+    for (int64_t i = 0; i < n; i++) {
+      const double* r = &f[(size_t)i * MP_FUSED];
+      if (sum_w) sum_w[i] = r[0];
+      if (mean_B) memcpy(mean_B + 3 * i, r + 1, 3 * sizeof(double));
+      if (cov_B) memcpy(cov_B + 6 * i, r + 4, 6 * sizeof(double));
+    }
+    return 0;
+  });
+}
+
+int apdgicp_gicp_mp_get_trace(apdgicp_handle* h, int64_t capacity, double* pose16, double* cost, int64_t* n_matched, double* delta6, int64_t* n_iterations) {
+  return guarded([&]() -> int {
+    if (!h || !n_iterations || capacity < 0) return fail(APDGICP_ERR_INVALID_ARG, "bad argument");
+    if (h->mode != Mode::GICP_MP) return mode_is_off(Mode::GICP_MP, false);
+    const MpState& v = h->mp;
+    *n_iterations = (int64_t)v.tr_n.size();
+    const int64_t m = std::min<int64_t>(*n_iterations, capacity);
+    if (m && pose16) memcpy(pose16, v.tr_pose.data(), m * 16 * sizeof(double));
+    if (m && cost) memcpy(cost, v.tr_cost.data(), m * sizeof(double));
+    if (m && n_matched) memcpy(n_matched, v.tr_n.data(), m * sizeof(int64_t));
+    if (m && delta6) memcpy(delta6, v.tr_delta.data(), m * 6 * sizeof(double));
+    return 0;
+  });
+}
+
+int apdgicp_gicp_mp_state(apdgicp_handle* h, int32_t* state) {
+  if (!h || !state) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  if (h->mode != Mode::GICP_MP) return mode_is_off(Mode::GICP_MP, false);
+  *state = h->mp.state;
+  return 0;
+}
+
+int apdgicp_gicp_mp_debug_counts(apdgicp_handle* h, int64_t* launches, int64_t* waits) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  if (h->mode != Mode::GICP_MP) return mode_is_off(Mode::GICP_MP, false);
+  if (launches) *launches = h->mp.launches;
+  if (waits) *waits = h->mp.waits;
+  return 0;
+}
+
+int apdgicp_gicp_mp_set_profiling(apdgicp_handle* h, int enable) {
+  if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
+  h->mp.profiling = enable != 0;
+  return 0;
+}
+
+int apdgicp_gicp_mp_last_phases(apdgicp_handle* h, double ms[6]) {
+  if (!h || !ms) return fail(APDGICP_ERR_INVALID_ARG, "null argument");
+  if (h->mode != Mode::GICP_MP) return mode_is_off(Mode::GICP_MP, false);
+  if (!h->mp.profiling || !h->mp.have) return fail(APDGICP_ERR_NO_INPUT, "no profiled linearize (apdgicp_gicp_mp_set_profiling)");
+  memcpy(ms, h->mp.phase_ms, sizeof(h->mp.phase_ms));
+  return 0;
+}
+
 int apdgicp_get_ndt(const apdgicp_handle* h, apdgicp_ndt_params* p, int* enabled) {
   if (!h) return fail(APDGICP_ERR_INVALID_ARG, "handle is null");
   if (p) *p = h->nd.prm;
@@ -3224,6 +3608,7 @@ int apdgicp_get_final_hessian(apdgicp_handle* h, double H[36]) {
       case Mode::ICP: return fail(APDGICP_ERR_UNSUPPORTED, "point-to-point ICP has no Hessian");
       case Mode::NDT:  // NDT and FAST_VGICP_CUDA keep the Hessian of their last align on the host (identity until then)
       case Mode::VGICP_CUDA:
+      case Mode::GICP_MP:  // (of its last linearize: MP9)
         memcpy(H, h->final_H, 36 * sizeof(double));
         return 0;
       case Mode::VGICP:
@@ -3681,6 +4066,7 @@ int apdgicp_batch_align_async(apdgicp_batch* b, const apdgicp_pair* pairs, int64
         case Mode::NDT: APD_TRY(ndb_align(b, pairs, n_pairs)); break;
         case Mode::ICP: APD_TRY(icb_align(b, pairs, n_pairs)); break;
         case Mode::VGICP_CUDA: APD_TRY(vcb_align(b, pairs, n_pairs)); break;
+        case Mode::GICP_MP:  // (single handles only: no setter of a batch handle names it)
         case Mode::APD: break;
       }
       if (d_results) *d_results = b->eng.d_results.p;

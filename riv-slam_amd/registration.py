@@ -123,6 +123,9 @@ SYMBOLS = [
     "apdgicp_icp_get_working_cloud", "apdgicp_icp_get_trace", "apdgicp_icp_convergence_state", "apdgicp_icp_debug_counts",
     "apdgicp_batch_set_icp", "apdgicp_batch_get_icp", "apdgicp_batch_icp_states", "apdgicp_batch_icp_get_correspondences", "apdgicp_batch_icp_get_working_cloud",
     "apdgicp_batch_icp_get_trace", "apdgicp_batch_icp_debug_counts",
+    "apdgicp_gicp_mp_default_params", "apdgicp_set_gicp_mp", "apdgicp_get_gicp_mp", "apdgicp_gicp_mp_get_rows", "apdgicp_gicp_mp_get_row_entries",
+    "apdgicp_gicp_mp_get_fused", "apdgicp_gicp_mp_get_trace", "apdgicp_gicp_mp_state", "apdgicp_gicp_mp_debug_counts",
+    "apdgicp_gicp_mp_set_profiling", "apdgicp_gicp_mp_last_phases",
     "apdgicp_batch_set_vgicp_cuda", "apdgicp_batch_get_vgicp_cuda", "apdgicp_batch_vgicp_cuda_kept", "apdgicp_batch_vgicp_cuda_get_covariances",
     "apdgicp_batch_vgicp_cuda_voxel_count", "apdgicp_batch_vgicp_cuda_get_voxels", "apdgicp_batch_vgicp_cuda_get_correspondences",
     "apdgicp_batch_vgicp_cuda_build_count", "apdgicp_batch_vgicp_cuda_debug_counts", "apdgicp_batch_vgicp_cuda_last_phases",
@@ -345,6 +348,18 @@ def load_library(path: str | None = None):
     L.apdgicp_icp_get_trace.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
     L.apdgicp_icp_convergence_state.argtypes = [vp, C.POINTER(C.c_int32)]
     L.apdgicp_icp_debug_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_gicp_mp_default_params.argtypes = [vp]
+    L.apdgicp_gicp_mp_default_params.restype = None
+    L.apdgicp_set_gicp_mp.argtypes = [vp, vp]
+    L.apdgicp_get_gicp_mp.argtypes = [vp, vp, C.POINTER(i32)]
+    L.apdgicp_gicp_mp_get_rows.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.apdgicp_gicp_mp_get_row_entries.argtypes = [vp, vp, vp]
+    L.apdgicp_gicp_mp_get_fused.argtypes = [vp, vp, vp, vp, i64]
+    L.apdgicp_gicp_mp_get_trace.argtypes = [vp, i64, vp, vp, vp, vp, C.POINTER(i64)]
+    L.apdgicp_gicp_mp_state.argtypes = [vp, C.POINTER(C.c_int32)]
+    L.apdgicp_gicp_mp_debug_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+    L.apdgicp_gicp_mp_set_profiling.argtypes = [vp, i32]
+    L.apdgicp_gicp_mp_last_phases.argtypes = [vp, vp]
     L.apdgicp_batch_set_icp.argtypes = [vp, vp]
     L.apdgicp_batch_get_icp.argtypes = [vp, vp, C.POINTER(i32)]
     L.apdgicp_batch_icp_states.argtypes = [vp, vp, i64]
